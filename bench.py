@@ -16,7 +16,13 @@ Further legs of the same line (reported, never `value`): `config4` = on-the-fly 
 `inference` = BASELINE config 5 at its real size, --infer-clips (1024) distinct 60-s clips sharded over the ranks through
 SALSA-FOA + CRNN forward + DCASE rows on the host, with per-clip latency percentiles (bench_crnn.infer_bench).
 
+A plain run does only what the headline needs: synthesise the clips, warm up (at least --warmup steps and 0.5 s), time ONE
+block of --steps feature steps, write the outputs if --dump-outputs is given, print the line.  Everything else -- the median
+of several blocks, per-kernel attribution and roofline, SALSA-Lite, the CRNN-side legs, the stock-PyTorch and CPU baselines,
+--pcie / --streams / --infer-torch-baseline -- runs only with --full (the line's fields for them are null otherwise).
+
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full --dump-outputs out/
   python bench.py --gpus 8            # no launcher needed: re-executes itself under torch.distributed.run, one rank per GPU
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
@@ -34,6 +40,9 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md; ~6.3 TB/s achievable)
 F64_VALU_PEAK_TFLOPS = 78.6  # float64 vector peak, same guide (256 CUs x 4 SIMDs x 16 lanes x 2 flop x 2.4 GHz)
+WARMUP_MIN_S = 0.5           # the warm-up lasts at least this long, whatever --warmup says (main())
+DUMP_BYTES = 64 << 20        # --dump-outputs: an output up to this size is written whole ...
+DUMP_SAMPLE = 8 << 20        # ... a larger one as this many seeded draws of its elements (32 MB of float32)
 
 
 def _clip(args):
@@ -160,6 +169,22 @@ def harness_bench(fmt, fmax, batch, n_samples, host):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def dump_outputs(out, out_dir):
+    """--dump-outputs: the feature array the last timed step handed back (this rank's [batch][C][T][F] float32) as .npy files in
+    out_dir.  Up to DUMP_BYTES it is written whole (features.npy); a larger one (the default 32 x 60-s batch: 860 MB) as a fixed
+    sample -- DUMP_SAMPLE flat indices drawn by np.random.default_rng(0), sorted and de-duplicated -- in features_sample.npy, the
+    same elements on every run with the same arguments."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = out.numel()
+    if n * out.element_size() <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, 'features.npy'), out.cpu().numpy())
+        return
+    idx = np.unique(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))
+    sample = out.reshape(-1)[torch.from_numpy(idx).to(out.device)]
+    np.save(os.path.join(out_dir, 'features_sample.npy'), sample.cpu().numpy())
+
+
 def _flush_c_stdio():
     """push out whatever native libraries (RCCL's version banner) left in libc's stdout buffer -- every rank, as soon as its
     process group is gone, so that nothing of it can land after rank 0's result line"""
@@ -220,8 +245,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--blocks', type=int, default=5, help='timed blocks of --steps steps; the median block is reported')
+    ap.add_argument('--warmup', type=int, default=3, help='untimed steps before the timed ones (at least this many, and at least 0.5 s of them)')
+    ap.add_argument('--blocks', type=int, default=None, help='timed blocks of --steps steps; the median block is reported (default: 1, with --full 5)')
+    ap.add_argument('--full', action='store_true', help='also run every leg beyond the headline figure: per-kernel attribution, roofline, SALSA-Lite, '
+                                                        'CRNN training / config 4 / inference, the stock-PyTorch and CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last one computed as DIR/*.npy '
+                                                                         '(rank 0\'s features: whole up to 64 MB, else a fixed seeded sample)')
     ap.add_argument('--batch', type=int, default=32, help='clips per GPU per step')
     ap.add_argument('--seconds', type=float, default=60.0)
     ap.add_argument('--feature', default='salsa', choices=['salsa', 'salsa_lite', 'salsa_ipd'])
@@ -244,6 +273,10 @@ def main():
     ap.add_argument('--fused', type=int, default=0, help='measurement: salsa_plan_set_fused mode (1 = STFT -> tracker -> fused STFT + '
                                                          'covariance / eigen kernel; bit-identical, measured slower: DESIGN section 6)')
     args = ap.parse_args()
+    if not args.full and (args.pcie or args.streams > 1 or args.infer_torch_baseline):
+        ap.error('--pcie, --streams and --infer-torch-baseline are legs of --full')
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
 
     from bench_crnn import infer_bench, self_spawn, train_bench
     self_spawn(args.gpus, __file__)           # `--gpus N` without a launcher: become N ranks (does not return then)
@@ -293,13 +326,19 @@ def main():
             dist.barrier()
 
     power = None
-    if rank == 0:                                       # package power / shader clock over the timed regions (bench_crnn.PowerSampler)
+    if rank == 0 and args.full:                         # package power / shader clock over the timed regions (bench_crnn.PowerSampler)
         from bench_crnn import PowerSampler
         power = PowerSampler(dev)
         import atexit
         atexit.register(power.close)
-    for _ in range(args.warmup):
-        ex.extract(audio, out=out)
+    # warm-up: at least --warmup steps AND at least WARMUP_MIN_S of them -- a block timed after only a few steps reads ~8 % slow (the
+    # part's clocks are still ramping up: it is the first of five 20-step blocks after three warm-up steps, the other four agree)
+    warm, t_w = 0, time.perf_counter()
+    while warm < args.warmup or time.perf_counter() - t_w < WARMUP_MIN_S:
+        for _ in range(max(args.warmup - warm, 10)):
+            ex.extract(audio, out=out)
+            warm += 1
+        torch.cuda.synchronize()
     block_s = []
     for _ in range(max(1, args.blocks)):
         torch.cuda.synchronize()
@@ -318,6 +357,8 @@ def main():
             el = float(tt.item())
         block_s.append(el)
     elapsed = float(np.median(block_s))             # the median K-step block (max over ranks within each block)
+    if args.dump_outputs and rank == 0:             # (before any --full pass below reuses `out`)
+        dump_outputs(out, args.dump_outputs)
 
     # per-kernel durations: HIP events recorded by the library on the launch stream, separate pass (not in `value`)
     kernels = []
@@ -325,7 +366,7 @@ def main():
     cpu = None
     pcie = None
     pipelined = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # Per-kernel attribution, two ways (tools/timing_probe.py, profiles/r3_timing_schemes.json):
         #  (1) `ms_per_launch` = PREFIX DIFFERENCES of the real launch sequence, wall clock, no events: K issues of [STFT],
         #      of [STFT, tracker] and of the whole path on the buffers a full call left behind (every kernel is idempotent on
@@ -525,7 +566,7 @@ def main():
                 pcie['harness'] = harness_bench(fmt, fmax, args.batch, n_samples, host)
 
     lite_leg = None
-    if world == 1 and args.feature == 'salsa':
+    if world == 1 and args.feature == 'salsa' and args.full:
         # ---- SURVEY 8(a8) / BASELINE config 1's feature on the GPU (reported, never `value`): SALSA-Lite MIC on the same 32 x 60-s batch --
         # one launch of the STFT kernel's Lite STD instantiation per step; algorithmic bytes 48 715 748 per clip
         try:
@@ -567,6 +608,8 @@ def main():
             'rccl_ranks': rccl_ranks,
             'steps': args.steps,
             'warmup': args.warmup,
+            'warmup_steps_run': warm,
+            'full': args.full,              # (without --full the legs below the config are null: not run)
             'ms_per_step': round(1e3 * elapsed / args.steps, 4),
             'blocks_ms': [round(1e3 * b / args.steps, 4) for b in block_s],
             'blocks_note': 'ms per step of each timed %d-step block (max over ranks); value / ms_per_step = the median block' % args.steps,
@@ -611,7 +654,8 @@ def main():
         os._exit(3)
 
     watchdog, disarm_term = None, None
-    if world > 1 and not args.no_crnn and args.feature == 'salsa':
+    run_crnn = args.full and not args.no_crnn and args.feature == 'salsa'
+    if world > 1 and run_crnn:
         import threading
         limit = float(os.environ.get('SALSA_BENCH_LEG_TIMEOUT', '600'))
         watchdog = threading.Timer(limit, bail, args=('the CRNN-side legs did not finish within %.0f s at N = %d' % (limit, world),))
@@ -637,7 +681,7 @@ def main():
         return done[name]
 
     crnn = config4 = infer = None
-    if not args.no_crnn and args.feature == 'salsa':
+    if run_crnn:
         crnn = leg('crnn', lambda: train_bench(rank, world, dev, batch=32, steps=args.crnn_steps, warmup=args.crnn_warmup, power=power))
         # ---- BASELINE config 4: raw 8-s MIC chunks -> SALSA-MIC on device -> the reference's augmentation -> training step
         if not args.no_config4:
@@ -682,7 +726,7 @@ def main():
             done['inference']['speedup_vs_torch_baseline'] = round(done['inference']['value'] / tb['value'], 3)
     # CPU baseline: rank 0 only, for every N (after the process group is gone, so the other ranks are not kept waiting on a
     # collective); the same bounded sample at every N
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.feature, fmt, fmax, n_samples)
 
     line = make_line(cpu)

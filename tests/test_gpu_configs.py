@@ -340,7 +340,7 @@ def test_bench_eight_ranks_on_one_gpu_with_the_drivers_command():
     env.update(SALSA_BENCH_SHARE_GPU='1', OMP_NUM_THREADS='2')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '3', '--warmup', '1',
-           '--blocks', '2', '--crnn-steps', '2', '--crnn-warmup', '1', '--infer-steps', '1']
+           '--full', '--blocks', '2', '--crnn-steps', '2', '--crnn-warmup', '1', '--infer-steps', '1']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out_lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
@@ -360,6 +360,29 @@ def test_bench_eight_ranks_on_one_gpu_with_the_drivers_command():
     assert cpu is not None and cpu['value'] > 0 and 1 <= cpu['cores'] <= effective_cpus()['effective_cores']
     assert all(c['cores'] <= effective_cpus()['effective_cores'] for c in cpu.get('configs', []))
     assert 'status' not in line
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(dev, tmp_path):
+    """A plain `bench.py` run (no --full): ONE block of exactly --steps steps, none of the extra legs, and --dump-outputs writes
+    the features of the last timed step -- its seeded sample equals the same elements of an extraction of the same seeded batch here."""
+    import json
+    import subprocess
+
+    from bench import DUMP_SAMPLE, make_batch
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1', '--batch', '8',
+                        '--seconds', '20', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line['steps'] == 4 and len(line['blocks_ms']) == 1 and line['full'] is False and line['ms_per_step'] > 0
+    assert abs(line['value'] * line['ms_per_step'] / 1e3 - 8 * 20) < 1e-2 * 8 * 20
+    for k in ('roofline', 'cpu_baseline', 'crnn', 'config4', 'inference', 'salsa_lite'):
+        assert line[k] is None, k
+    got = np.load(tmp_path / 'features_sample.npy')                        # 8 x 7 x 1601 x 200 float32 = 72 MB: sampled
+    assert got.dtype == np.float32 and got.nbytes <= 64 << 20
+    out = _extractor(audio_format='foa', feature_type='salsa', fmax_doa=9000).extract(torch.from_numpy(make_batch(2021, 8, 20 * 24000)).to(dev))
+    idx = np.unique(np.random.default_rng(0).integers(0, out.numel(), DUMP_SAMPLE))
+    np.testing.assert_array_equal(got, out.reshape(-1)[torch.from_numpy(idx).to(dev)].cpu().numpy())
 
 
 def _free_port():
@@ -409,7 +432,7 @@ def test_bench_self_spawns_two_ranks():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--blocks', '1', '--seconds', '10', '--crnn-steps', '2', '--crnn-warmup', '1'],
+                        '--full', '--blocks', '1', '--seconds', '10', '--crnn-steps', '2', '--crnn-warmup', '1'],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
@@ -465,7 +488,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env['SALSA_BENCH_SHARE_GPU'] = '1'
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--blocks', '1', '--crnn-steps', '2', '--crnn-warmup', '1', '--infer-steps', '2', '--infer-clips', '128', '--no-cpu-baseline'],
+                        '--full', '--blocks', '1', '--crnn-steps', '2', '--crnn-warmup', '1', '--infer-steps', '2', '--infer-clips', '128', '--no-cpu-baseline'],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     last = r.stdout.strip().splitlines()[-1]
@@ -531,7 +554,7 @@ def test_bench_n2_failure_in_a_crnn_leg_still_prints_the_feature_half():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(SALSA_BENCH_SHARE_GPU='1', SALSA_BENCH_FAIL_LEG='config4', SALSA_BENCH_LEG_TIMEOUT='45')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--blocks', '1', '--crnn-steps', '2', '--crnn-warmup', '1', '--infer-steps', '1', '--infer-clips', '64', '--no-cpu-baseline'],
+                        '--full', '--blocks', '1', '--crnn-steps', '2', '--crnn-warmup', '1', '--infer-steps', '1', '--infer-clips', '64', '--no-cpu-baseline'],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode != 0
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

@@ -211,6 +211,25 @@ def test_power_sampler_degrades_to_none_without_hwmon_files(tmp_path):
     assert st['mean_w'] == 1390.0 and st['sclk_mhz_mean'] == 2000.0 and st['cap_w'] == 1400.0 and st['samples'] == 10
 
 
+def test_bench_dump_outputs_whole_or_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: an output up to 64 MB is written whole; a larger one as the same seeded sample of its elements on
+    every run, within 64 MB."""
+    import torch
+
+    import bench
+    small = torch.arange(2 * 7 * 5 * 3, dtype=torch.float32).reshape(2, 7, 5, 3)
+    bench.dump_outputs(small, str(tmp_path / 'small'))
+    assert sorted(os.listdir(tmp_path / 'small')) == ['features.npy']
+    np.testing.assert_array_equal(np.load(tmp_path / 'small' / 'features.npy'), small.numpy())
+    big = torch.arange(9 << 20, dtype=torch.float64).reshape(4, 9, -1, 16)            # 72 MB: the values are their flat indices
+    for d in ('big1', 'big2'):
+        bench.dump_outputs(big, str(tmp_path / d))
+        assert sorted(os.listdir(tmp_path / d)) == ['features_sample.npy']
+    a, b = np.load(tmp_path / 'big1' / 'features_sample.npy'), np.load(tmp_path / 'big2' / 'features_sample.npy')
+    assert a.dtype == np.float64 and a.nbytes <= 64 << 20 and np.array_equal(a, b)
+    assert bench.DUMP_SAMPLE // 2 < a.size <= bench.DUMP_SAMPLE and np.all(np.diff(a) > 0) and a[-1] < big.numel()
+
+
 def test_clip_readers_shape_from_header_and_read_into_place(tmp_path):
     """the file pipeline's reader primitives (round 6): audio_shape reads only the header; load_audio_into fills a caller's
     (pinned) slot -- straight from the file for a float32 .npy in the slot's layout, through load_audio otherwise -- and the raw

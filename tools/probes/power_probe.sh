@@ -21,4 +21,4 @@ echo "== idle"; sample 3
 echo "== c64 forward, real loads"; python /tmp/c64_loop.py 6 & sleep 2.5; sample 12; wait
 if [ -n "${SALSA_ZERO_LIB:-}" ]; then echo "== c64 forward, zero-source probe build"; SALSA_HIP_LIB=$SALSA_ZERO_LIB python /tmp/c64_loop.py 6 & sleep 2.5; sample 12; wait; fi
 echo "== feature bench in a loop"; (for i in 1 2 3; do python bench.py --no-cpu-baseline --no-crnn --no-config4 --no-infer --blocks 20 > /dev/null 2>&1; done) & sleep 4; sample 12; wait
-echo "== CRNN training bench"; python bench.py --no-cpu-baseline --no-config4 --no-infer --crnn-steps 400 --blocks 1 > /dev/null 2>&1 & sleep 8; sample 12; wait
+echo "== CRNN training bench"; python bench.py --full --no-cpu-baseline --no-config4 --no-infer --crnn-steps 400 --blocks 1 > /dev/null 2>&1 & sleep 8; sample 12; wait
