@@ -75,7 +75,12 @@ typedef struct salsa_params {
     int fs;                    /* 24000 */
     int n_fft;                 /* 512 | 256 */
     int hop_len;               /* 300 */
-    int win_len;               /* <= n_fft */
+    int win_len;               /* <= n_fft: the Hann window of the SALSA log-spectrogram channels only (centre-padded to n_fft, as
+                                * librosa's pad_center).  The DOA spectra of SALSA and every SALSA-Lite / IPD channel use the n_fft
+                                * Hann window, as in the reference (salsa_feature_extraction.py:186-192 vs :360-361; the Lite script
+                                * reads win_len and never uses it).  A SALSA plan with win_len < n_fft runs the STFT kernel twice
+                                * (DOA window, then spectrogram window) and always the three-kernel schedule: the fused kernel and
+                                * the pipelined schedules fall back to it, with the same results. */
     int fmin_doa;              /* Hz */
     int fmax_doa;              /* Hz (clamped to fs/2 like the reference) */
     double cond_num;           /* coherence threshold, default 5 */

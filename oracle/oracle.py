@@ -132,7 +132,8 @@ def extract_normalized_eigenvector(X, condition_number=5.0, n_hopframes=3, is_tr
 
 def extract_salsa(audio, fs=24000, n_fft=512, hop=300, win=None, fmin_doa=50, fmax_doa=9000, cond_num=5.0,
                   n_hopframes=3, is_tracking=True, is_compress_high_freq=True, audio_format='foa', return_aux=False):
-    """audio (4, N) float32 -> (7, T, F) float32: the per-file body of salsa_feature_extraction.py:353-377."""
+    """audio (4, N) float32 -> (7, T, F) float32: the per-file body of salsa_feature_extraction.py:353-377.
+    win (win_len) windows the log-spectrogram channels only (:186-192); the DOA STFT (:360-361) uses the n_fft Hann window."""
     if audio_format not in ('foa', 'mic'):
         raise ValueError('Unknown audio format {}'.format(audio_format))
     audio = np.ascontiguousarray(audio, np.float32)
@@ -156,7 +157,8 @@ def extract_salsa(audio, fs=24000, n_fft=512, hop=300, win=None, fmin_doa=50, fm
 
 def extract_lite(audio, fs=24000, n_fft=512, hop=300, win=None, fmin_doa=50, fmax_doa=2000,
                  feature_type='salsa_lite'):
-    """audio (4, N) float32 -> (7, T, cutoff-lower) float32: salsa_lite_feature_extraction.py:94-123."""
+    """audio (4, N) float32 -> (7, T, cutoff-lower) float32: salsa_lite_feature_extraction.py:94-123.
+    win is accepted and ignored, as the reference reads win_len (:44) and never uses it: both STFTs use the n_fft window."""
     assert feature_type in ['salsa_lite', 'salsa_ipd'], 'Invalid feature type {}'.format(feature_type)
     audio = np.ascontiguousarray(audio, np.float32)
     win = n_fft if win is None else win

@@ -404,17 +404,22 @@ int salsa_oracle_extract_salsa(const float *audio, long N, int fs, int n_fft, in
     long T = salsa_oracle_n_frames(N, hop);
     int nb = n_fft / 2 + 1, nd = upper - lower;
     if (nd < 0 || nd > F) return -3;
+    /* the log-spectrogram STFT is windowed with win_length (:186-192); the DOA STFT (:360-361) passes no win_length,
+     * so librosa uses a Hann window of n_fft samples.  When win == n_fft they are one STFT. */
     float *st = (float *)malloc(sizeof(float) * 2 * (size_t)nb * T);
+    float *sd = win == n_fft ? st : (float *)malloc(sizeof(float) * 2 * (size_t)nb * T);
     float *X = (float *)malloc(sizeof(float) * 2 * (size_t)(nd > 0 ? nd : 1) * T * C);
     for (int c = 0; c < C; c++) {
-        salsa_oracle_stft(audio + (size_t)c * N, N, n_fft, hop, win, st);          /* :186 and :360 (same STFT) */
+        salsa_oracle_stft(audio + (size_t)c * N, N, n_fft, hop, win, st);          /* :186 */
         logspec_from_stft(st, T, n_fft, compress, out + (size_t)c * T * F);        /* :194-195 */
+        if (sd != st) salsa_oracle_stft(audio + (size_t)c * N, N, n_fft, hop, n_fft, sd);   /* :360-361 */
         for (int b = 0; b < nd; b++)                                                /* :365-366 */
             for (long t = 0; t < T; t++) {
-                X[(((size_t)b * T + t) * C + c) * 2] = st[((size_t)(b + lower) * T + t) * 2];
-                X[(((size_t)b * T + t) * C + c) * 2 + 1] = st[((size_t)(b + lower) * T + t) * 2 + 1];
+                X[(((size_t)b * T + t) * C + c) * 2] = sd[((size_t)(b + lower) * T + t) * 2];
+                X[(((size_t)b * T + t) * C + c) * 2 + 1] = sd[((size_t)(b + lower) * T + t) * 2 + 1];
             }
     }
+    if (sd != st) free(sd);
     double *ev = (double *)malloc(sizeof(double) * 3 * (size_t)(nd > 0 ? nd : 1) * T);
     salsa_oracle_eigvec(X, nd, T, cond, n_hop, tracking, format, fs, n_fft, lower, ev, NULL, aux_rank, aux_margin);
     /* :372-377  transpose (0,2,1) into zeros (3,T,F) and stack under the 4 log-spec channels */
@@ -429,7 +434,7 @@ int salsa_oracle_extract_salsa(const float *audio, long N, int fs, int n_fft, in
 }
 
 /* ------------------------------------------------------------------------------------------------ SALSA-Lite / IPD
- * salsa_lite_feature_extraction.py:94-123.  audio [4][N] -> out [7][T][cutoff-lower] float32.
+ * salsa_lite_feature_extraction.py:94-123.  audio [4][N] -> out [7][T][cutoff-lower] float32.  win is ignored (:44).
  * ipd = 0: 'salsa_lite' (divide by delta*k, :115) ; ipd = 1: 'salsa_ipd' (divide by pi, :113).
  * Note :120 zeroes CROPPED indices >= upper_bin (i.e. absolute bins >= upper_bin+lower_bin) -- reproduced as is. */
 int salsa_oracle_extract_lite(const float *audio, long N, int fs, int n_fft, int hop, int win, int fmin_doa,
@@ -444,7 +449,9 @@ int salsa_oracle_extract_lite(const float *audio, long N, int fs, int n_fft, int
     if (F <= 0) return -3;
     const double delta = 2.0 * M_PI * fs / (n_fft * 343.0); /* :62-63 */
     float *st = (float *)malloc(sizeof(float) * 2 * (size_t)nb * T * C);
-    for (int c = 0; c < C; c++) salsa_oracle_stft(audio + (size_t)c * N, N, n_fft, hop, win, st + (size_t)c * 2 * nb * T);
+    /* :44 reads win_len but never uses it: both STFTs (:97-98) take the default n_fft Hann window */
+    (void)win;
+    for (int c = 0; c < C; c++) salsa_oracle_stft(audio + (size_t)c * N, N, n_fft, hop, n_fft, st + (size_t)c * 2 * nb * T);
 #pragma omp parallel for schedule(static) num_threads(g_threads)
     for (long t = 0; t < T; t++) {
         for (int f = 0; f < F; f++) {

@@ -2218,7 +2218,8 @@ struct salsa_plan {
     int lower, upper, cutoff, nd, F, ident;
     int spec_lo, spec_hi, flex;
     double delta, snr_ratio;
-    double *d_window;
+    double *d_window;     // the log-spectrogram window: win_len Hann centre-padded to n_fft (SALSA); n_fft Hann (SALSA-Lite / IPD, contrib)
+    double *d_window_doa; // the DOA spectra's window, n_fft Hann: the same table as d_window unless a SALSA plan has win_len < n_fft
     cplx<double> *d_tw;
     const float *sc_mean, *sc_std; // caller-owned device arrays set by salsa_plan_set_scaler (or NULL)
     unsigned long long *stats;     // caller-owned device counters set by salsa_plan_set_stats (or NULL)
@@ -2253,7 +2254,7 @@ struct salsa_plan {
 // whose ring fits the LDS; everything else keeps the three-kernel path
 static bool fused_eligible(const salsa_plan *pl, const KParams &kp)
 {
-    return SALSA_PK && pl->p.n_fft == 512 && kp.feature == SALSA_FEATURE_SALSA && kp.nch == 4 && kp.n_hop == 3 && kp.tracking &&
+    return SALSA_PK && pl->d_window == pl->d_window_doa && pl->p.n_fft == 512 && kp.feature == SALSA_FEATURE_SALSA && kp.nch == 4 && kp.n_hop == 3 && kp.tracking &&
            !kp.flex && kp.cond >= SALSA_PK_COND_MIN && kp.cond < 1e6 && !kp.force_f64 && kp.nd >= 1 && kp.T >= 4 * FZ_S && kp.F <= 256 &&
            fused_lds_bytes(kp.nd, kp.F, kp.sc_mean != nullptr) <= 160 * 1024;
 }
@@ -2433,20 +2434,26 @@ int salsa_plan_create(const salsa_params *params, salsa_plan **out_plan)
         delete pl;
         return fail(SALSA_EHIP, "hipGetDevice failed (no HIP device?)%s");
     }
-    // window: scipy.signal.get_window('hann', win, fftbins=True), centre-padded to n_fft ; twiddles W_N^m
-    double *hw = new double[p.n_fft];
+    // windows: scipy.signal.get_window('hann', win, fftbins=True), centre-padded to n_fft (librosa pad_center: (n_fft - win) // 2
+    // zeros on the left) ; twiddles W_N^m.  Only the SALSA log-spectrogram honours win_len (salsa_feature_extraction.py:186-192); its
+    // DOA STFT (:360-361) and both SALSA-Lite STFTs (salsa_lite_feature_extraction.py:97-98, win_len read at :44 and unused) pass no
+    // win_length, i.e. the n_fft window.  Equal lengths: one table.
+    const int spec_win = (p.feature_type == SALSA_FEATURE_SALSA && !pl->flex) ? p.win_len : p.n_fft;
+    const int nwin = spec_win == p.n_fft ? 1 : 2;
+    double *hw = new double[2 * p.n_fft];
     cplx<double> *htw = new cplx<double>[p.n_fft];
-    const int lpad = (p.n_fft - p.win_len) / 2;
-    for (int i = 0; i < p.n_fft; i++) hw[i] = 0.0;
-    for (int n = 0; n < p.win_len; n++) hw[lpad + n] = 0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * n / p.win_len);
+    for (int i = 0; i < 2 * p.n_fft; i++) hw[i] = 0.0;
+    for (int n = 0; n < spec_win; n++) hw[(p.n_fft - spec_win) / 2 + n] = 0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * n / spec_win);
+    for (int n = 0; n < p.n_fft; n++) hw[p.n_fft + n] = 0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * n / p.n_fft);
     for (int m = 0; m < p.n_fft; m++)
         htw[m] = {cos(-2.0 * 3.14159265358979323846 * m / p.n_fft), sin(-2.0 * 3.14159265358979323846 * m / p.n_fft)};
-    hipError_t e1 = hipMalloc((void **)&pl->d_window, sizeof(double) * p.n_fft);
+    hipError_t e1 = hipMalloc((void **)&pl->d_window, sizeof(double) * p.n_fft * nwin);
     hipError_t e2 = hipMalloc((void **)&pl->d_tw, sizeof(cplx<double>) * p.n_fft);
     if (e1 == hipSuccess && e2 == hipSuccess) {
-        e1 = hipMemcpy(pl->d_window, hw, sizeof(double) * p.n_fft, hipMemcpyHostToDevice);
+        e1 = hipMemcpy(pl->d_window, hw, sizeof(double) * p.n_fft * nwin, hipMemcpyHostToDevice);
         e2 = hipMemcpy(pl->d_tw, htw, sizeof(cplx<double>) * p.n_fft, hipMemcpyHostToDevice);
     }
+    if (e1 == hipSuccess) pl->d_window_doa = nwin == 2 ? pl->d_window + p.n_fft : pl->d_window;
     delete[] hw;
     delete[] htw;
     if (e1 != hipSuccess || e2 != hipSuccess) {
@@ -2560,7 +2567,8 @@ static void mark_end(salsa_plan *pl, hipStream_t s, int i)
     if (i >= 0) (void)hipEventRecord(pl->ev1[i], s);
 }
 
-static int launch_stft(salsa_plan *pl, const KParams &kp, const float *d_audio, float *d_out, float4 *Xs, hipStream_t s)
+// one K1 launch with the window `win` (one of the plan's two tables)
+static int launch_stft(salsa_plan *pl, const KParams &kp, const double *win, const float *d_audio, float *d_out, float4 *Xs, hipStream_t s)
 {
     const bool lite = kp.feature == SALSA_FEATURE_LITE || kp.feature == SALSA_FEATURE_IPD;
     const bool single = !lite && kp.pair_sel >= 0; // one channel pair per launch: twice the frames per wave, same work per wave
@@ -2572,32 +2580,48 @@ static int launch_stft(salsa_plan *pl, const KParams &kp, const float *d_audio, 
     // contrib plan with SALSA_FLAG_NO_CLIP_FREQS and a lite band from bin 0 have F = 257: they take the plain kernel, whose
     // store path reads the tables from global memory at any F)
     // the dataset scripts' layout as a compile-time fact (stft_kernel's STD instantiations; K1_STD 0: the general kernel, for A/B)
-    const bool std_layout = K1_STD && pl->p.n_fft == 512 && !lite && !single && kp.feature == SALSA_FEATURE_SALSA && kp.compress &&
+    // (STD instantiations: plans with one window only -- a SALSA plan with win_len < n_fft takes the general kernel, twice)
+    const bool one_window = pl->d_window == pl->d_window_doa;
+    const bool std_layout = K1_STD && one_window && pl->p.n_fft == 512 && !lite && !single && kp.feature == SALSA_FEATURE_SALSA && kp.compress &&
                             kp.spec_lo == 1 && kp.spec_hi == 193 && kp.ident == 192 && kp.F == 200 && kp.nch == 4 &&
                             kp.layout == SALSA_LAYOUT_PLANAR && kp.pair_sel < 0;
-    const bool lite_std = K1_LITE_STD && pl->p.n_fft == 512 && lite && kp.nch == 4 && kp.layout == SALSA_LAYOUT_PLANAR && !kp.sc_mean &&
+    const bool lite_std = K1_LITE_STD && one_window && pl->p.n_fft == 512 && lite && kp.nch == 4 && kp.layout == SALSA_LAYOUT_PLANAR && !kp.sc_mean &&
                           kp.cutoff <= 256 && kp.pair_sel < 0;
     if (lite_std) {
-        hipLaunchKernelGGL((stft_kernel<512, double, true, NF_LITE, 2, false, true>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
+        hipLaunchKernelGGL((stft_kernel<512, double, true, NF_LITE, 2, false, true>), grid, dim3(256), 0, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
     } else if (std_layout) {
         constexpr size_t SCT_BYTES = 2 * 4 * 256 * sizeof(float);
-        if (kp.sc_mean) hipLaunchKernelGGL((stft_kernel<512, double, false, NF_FULL, 2, true, true>), grid, dim3(256), SCT_BYTES, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
-        else hipLaunchKernelGGL((stft_kernel<512, double, false, NF_FULL, 2, false, true>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
+        if (kp.sc_mean) hipLaunchKernelGGL((stft_kernel<512, double, false, NF_FULL, 2, true, true>), grid, dim3(256), SCT_BYTES, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
+        else hipLaunchKernelGGL((stft_kernel<512, double, false, NF_FULL, 2, false, true>), grid, dim3(256), 0, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
     } else if (pl->p.n_fft == 512 && kp.sc_mean && !single && kp.F <= 256) {
         constexpr size_t SCT_BYTES = 2 * 4 * 256 * sizeof(float);
-        if (lite) hipLaunchKernelGGL((stft_kernel<512, double, true, NF_LITE, 2, true>), grid, dim3(256), SCT_BYTES, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
-        else hipLaunchKernelGGL((stft_kernel<512, double, false, NF_FULL, 2, true>), grid, dim3(256), SCT_BYTES, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
+        if (lite) hipLaunchKernelGGL((stft_kernel<512, double, true, NF_LITE, 2, true>), grid, dim3(256), SCT_BYTES, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
+        else hipLaunchKernelGGL((stft_kernel<512, double, false, NF_FULL, 2, true>), grid, dim3(256), SCT_BYTES, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
     } else if (pl->p.n_fft == 512) {
-        if (lite) hipLaunchKernelGGL((stft_kernel<512, double, true, NF_LITE>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
-        else if (single) hipLaunchKernelGGL((stft_kernel<512, double, false, NF_PAIR>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
-        else hipLaunchKernelGGL((stft_kernel<512, double, false, NF_FULL>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
+        if (lite) hipLaunchKernelGGL((stft_kernel<512, double, true, NF_LITE>), grid, dim3(256), 0, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
+        else if (single) hipLaunchKernelGGL((stft_kernel<512, double, false, NF_PAIR>), grid, dim3(256), 0, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
+        else hipLaunchKernelGGL((stft_kernel<512, double, false, NF_FULL>), grid, dim3(256), 0, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
     } else {
-        if (lite) hipLaunchKernelGGL((stft_kernel<256, double, true, NF_LITE>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
-        else if (single) hipLaunchKernelGGL((stft_kernel<256, double, false, NF_PAIR>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
-        else hipLaunchKernelGGL((stft_kernel<256, double, false, NF_FULL>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
+        if (lite) hipLaunchKernelGGL((stft_kernel<256, double, true, NF_LITE>), grid, dim3(256), 0, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
+        else if (single) hipLaunchKernelGGL((stft_kernel<256, double, false, NF_PAIR>), grid, dim3(256), 0, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
+        else hipLaunchKernelGGL((stft_kernel<256, double, false, NF_FULL>), grid, dim3(256), 0, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
     }
     HIP_TRY(hipGetLastError());
     return SALSA_OK;
+}
+
+// K1 of salsa_extract_batch.  One window: one launch.  Full SALSA with win_len < n_fft: the spill (DOA spectra) comes from the
+// n_fft window and the log-spectrogram channels from the win_len window, so the general kernel runs twice: with the DOA window
+// (spill + provisional channels 0-3), then log-spec only (no spill store) with the spectrogram window, overwriting channels 0-3 of
+// the 7-channel output (fused scaler included).  Same stream: the second launch's stores land last.
+static int launch_k1(salsa_plan *pl, const KParams &kp, const float *d_audio, float *d_out, float4 *Xs, hipStream_t s)
+{
+    if (pl->d_window == pl->d_window_doa || kp.feature != SALSA_FEATURE_SALSA) return launch_stft(pl, kp, pl->d_window, d_audio, d_out, Xs, s);
+    const int rc = launch_stft(pl, kp, pl->d_window_doa, d_audio, d_out, Xs, s);
+    if (rc) return rc;
+    KParams lp = kp;
+    lp.feature = FEATURE_LOGSPEC_ONLY; // (OC stays 7)
+    return launch_stft(pl, lp, pl->d_window, d_audio, d_out, nullptr, s);
 }
 
 int salsa_extract_batch(salsa_plan *pl, const float *d_audio, int batch, int64_t n_samples, float *d_out,
@@ -2655,7 +2679,7 @@ int salsa_extract_batch(salsa_plan *pl, const float *d_audio, int batch, int64_t
         const int reps = pl->timing > 1 ? pl->timing : 1;
         int m = mark_begin(pl, s1, "stft_logspec");
         int rc = SALSA_OK;
-        for (int r = 0; r < reps && !rc; r++) rc = launch_stft(pl, gp, a, o, xs, s1);
+        for (int r = 0; r < reps && !rc; r++) rc = launch_k1(pl, gp, a, o, xs, s1);
         mark_end(pl, s1, m);
         if (rc || !full) return rc;
         if (pl->stop_after == 1) return SALSA_PARTIAL; // (measurement mode: the caller is told the outputs are NOT complete)
@@ -2670,7 +2694,7 @@ int salsa_extract_batch(salsa_plan *pl, const float *d_audio, int batch, int64_t
         if (two) { // channels 2/3 (the tracker below only needs channel 0 and may run beside this launch)
             gp.pair_sel = 1;
             m = mark_begin(pl, s1, "stft_logspec");
-            rc = launch_stft(pl, gp, a, o, xs, s1);
+            rc = launch_stft(pl, gp, pl->d_window, a, o, xs, s1);
             mark_end(pl, s1, m);
             if (rc) return rc;
             gp.pair_sel = -1;
@@ -2707,7 +2731,9 @@ int salsa_extract_batch(salsa_plan *pl, const float *d_audio, int batch, int64_t
         }
         return SALSA_OK;
     };
-    const bool piped = full && !pl->timing && !pl->stop_after && kp.nd > 0 && (pl->n_groups > 1 || (pl->pipe_flags & SALSA_PIPE_SPLIT_PAIRS));
+    // (a plan with two windows keeps the plain in-order schedule: the pipelined one launches K1 per channel pair with one window)
+    const bool piped = full && !pl->timing && !pl->stop_after && kp.nd > 0 && pl->d_window == pl->d_window_doa &&
+                       (pl->n_groups > 1 || (pl->pipe_flags & SALSA_PIPE_SPLIT_PAIRS));
     if (!piped) return run_group(0, batch, s, s, nullptr, nullptr, false);
     const int G = batch < pl->n_groups ? batch : pl->n_groups;
     const bool split = (pl->pipe_flags & SALSA_PIPE_SPLIT_PAIRS) != 0;
@@ -2846,7 +2872,7 @@ int salsa_logspec_batch(salsa_plan *pl, const float *d_audio, int batch, int n_c
     kp.compress = pl->p.is_compress_high_freq;
     kp.spec_lo = 1;
     kp.spec_hi = kp.ident + 1;
-    return launch_stft(pl, kp, d_audio, d_out, nullptr, (hipStream_t)hip_stream);
+    return launch_stft(pl, kp, pl->d_window, d_audio, d_out, nullptr, (hipStream_t)hip_stream); // (the spectrogram window: win_len)
 }
 
 int salsa_eigvec_batch(salsa_plan *pl, const float *d_X, int batch, int n_bins, int64_t n_frames, int lower_bin,

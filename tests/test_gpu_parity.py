@@ -49,19 +49,21 @@ def _check(out, ref, margin=None, n_spec=4):
         assert bad.sum() <= max(2, int(2e-5 * bad.size))
 
 
-def _check_lite(out, ref, ftype='salsa_lite', lower=1):
+def _check_lite(out, ref, ftype='salsa_lite', lower=1, n_spec=4, period=None):
     """SALSA-Lite / IPD (7,T,F).  Mirror-symmetric frames (frame 0; the last frame when (N-1) % hop == 0) have a
     REAL spectrum up to 1e-14 round-off, so an inter-channel phase of +-pi has a sign decided by that round-off in the
-    reference too: phases are compared modulo one turn, and at most a handful of elements may use the wrap."""
+    reference too: phases are compared modulo one turn, and at most a handful of elements may use the wrap.
+    period: one turn per feature row (default: fs 24000, n_fft 512); n_spec = 0: out / ref are the phase channels alone."""
     assert out.shape == ref.shape and out.dtype == np.float32
-    np.testing.assert_allclose(out[:4], ref[:4], rtol=RTOL, atol=ATOL_DB)
+    np.testing.assert_allclose(out[:n_spec], ref[:n_spec], rtol=RTOL, atol=ATOL_DB)
     F = out.shape[2]
     k = np.arange(lower, lower + F, dtype=np.float64)
-    period = 2.0 * np.ones(F) if ftype == 'salsa_ipd' else 2 * np.pi / (2 * np.pi * 24000 / (512 * 343.0) * k)
-    d = out[4:].astype(np.float64) - ref[4:]
+    if period is None:
+        period = 2.0 * np.ones(F) if ftype == 'salsa_ipd' else 2 * np.pi / (2 * np.pi * 24000 / (512 * 343.0) * k)
+    d = out[n_spec:].astype(np.float64) - ref[n_spec:]
     wraps = np.round(d / period)
     d = d - period * wraps
-    assert np.all(np.abs(d) <= ATOL_SP + RTOL * np.abs(ref[4:]))
+    assert np.all(np.abs(d) <= ATOL_SP + RTOL * np.abs(ref[n_spec:]))
     wrapped_frames = np.unique(np.nonzero(wraps)[1])
     assert len(wrapped_frames) <= 2, 'phase wraps outside the mirror-symmetric frames: %s' % wrapped_frames
 
@@ -395,7 +397,7 @@ def test_clip_group_pipeline_is_bit_identical(dev):
 
 
 # ----------------------------------------------------------------------------------------------- reference surface
-def _make_tree(tmp, fmt, clips, fmax, n_fft=512, hop=300):
+def _make_tree(tmp, fmt, clips, fmax, n_fft=512, hop=300, win=None):
     import yaml
     from scipy.io import wavfile
     data_dir, feat_dir = os.path.join(tmp, 'data'), os.path.join(tmp, 'feat')
@@ -406,7 +408,7 @@ def _make_tree(tmp, fmt, clips, fmax, n_fft=512, hop=300):
         wavfile.write(os.path.join(d, name + '.wav'), 24000, y.T)          # float32 WAV: samples survive exactly
     os.makedirs(os.path.join(data_dir, fmt + '_eval'), exist_ok=True)
     cfg = {'data_dir': data_dir, 'feature_dir': feat_dir,
-           'data': {'format': fmt, 'fs': 24000, 'n_fft': n_fft, 'win_len': n_fft, 'hop_len': hop, 'fmin_doa': 50,
+           'data': {'format': fmt, 'fs': 24000, 'n_fft': n_fft, 'win_len': win or n_fft, 'hop_len': hop, 'fmin_doa': 50,
                     'fmax_doa': fmax}}
     path = os.path.join(tmp, 'cfg.yml')
     with open(path, 'w') as f:
@@ -859,3 +861,200 @@ def test_timing_modes_leave_results_untouched(dev):
     ex.L.salsa_plan_set_timing(ex._plan, 0)
     ex.extract(a, out=out)
     assert torch.equal(out, ref) and torch.equal(out[:, 4:], spatial)
+
+
+# ----------------------------------------------------------------------------------------------- win_len < n_fft (g19), off-default settings (g20)
+G19 = ['foa_w400', 'foa_w401', 'mic_w400', 'mic_w401', 'foa_nfft256_w200', 'lite_w400', 'ipd_w400']
+G20 = ['foa_fmin200', 'foa_fmin300', 'foa_hop240', 'foa_hop512', 'foa_fs48000', 'foa_cond1p5', 'foa_cond2', 'foa_nhop2',
+       'mic_fmin300', 'foa_nfft256_fmin0', 'lite_nfft256', 'ipd_fmax4000']
+
+
+def _check_case_clip(oracle, c, out, y, spatial, logspec):
+    """one clip of a g19 / g20 case on the device: against the reference's file (spectrogram channels at the stored frames,
+    spatial channels whole) and against the oracle at every frame"""
+    from golden_cases import lite_period, oracle_features
+    ref, margin = oracle_features(oracle, c, y)
+    np.testing.assert_allclose(out[:4, ::c['stride']], logspec, rtol=RTOL, atol=ATOL_DB)
+    if c['kind'] == 'salsa':
+        _check(out[4:], spatial, margin, n_spec=0)
+        _check(out, ref, margin)
+    else:
+        lo = oracle.bin_limits(c['fs'], c['n_fft'], c['fmin_doa'], c['fmax_doa'])[0]
+        period = lite_period(c, lo, out.shape[2])
+        _check_lite(out[4:], spatial, c['kind'], n_spec=0, period=period)
+        _check_lite(out, ref, c['kind'], period=period)
+
+
+def _golden_case_on_device(dev, oracle, fixture, case, **kw):
+    """every clip of a case through SalsaExtractor; clips of equal length go in ONE launch (a batch)"""
+    from golden_cases import case_clips, extractor_kwargs
+    meta, a = load_golden(fixture)
+    c = meta['cases'][case]
+    clips = case_clips(c)
+    ex = _extractor(device=dev, **dict(extractor_kwargs(c), **kw))
+    for n in sorted({y.shape[1] for y in clips.values()}):
+        names = [k for k in clips if clips[k].shape[1] == n]
+        ys = np.stack([clips[k] for k in names])
+        x = torch.from_numpy(ys).to(dev)
+        if kw.get('audio_layout') == 'interleaved':
+            x = x.transpose(1, 2).contiguous()
+        out = ex.extract(x).cpu().numpy()
+        for i, k in enumerate(names):
+            _check_case_clip(oracle, c, out[i], clips[k], a['%s|%s|spatial' % (case, k)], a['%s|%s|logspec' % (case, k)])
+    return c, clips
+
+
+@pytest.mark.parametrize('case', G19)
+def test_win_len_golden_on_device(dev, oracle, case):
+    """win_len < n_fft: only the SALSA log-spectrogram channels take the win_len window; the DOA spectra and SALSA-Lite / IPD use the
+    n_fft window, as in the reference (fixture g19; foa_w400 holds two clips of equal length, extracted as one batch)."""
+    c, clips = _golden_case_on_device(dev, oracle, 'g19_win_len', case)
+    if case == 'foa_w400':
+        assert len(clips) == 2 and len({y.shape for y in clips.values()}) == 1
+
+
+def test_win_len_golden_interleaved_layout(dev, oracle):
+    _golden_case_on_device(dev, oracle, 'g19_win_len', 'foa_w400', audio_layout='interleaved')
+
+
+@pytest.mark.parametrize('case', G20)
+def test_off_default_golden_on_device(dev, oracle, case):
+    """off-default fmin_doa, hop_len, fs, cond_num, n_hopframes, n_fft 256, Lite at n_fft 256, IPD at fmax_doa 4000 (fixture g20)"""
+    _golden_case_on_device(dev, oracle, 'g20_off_default', case)
+
+
+def test_win_len_logspec_entry_point_on_device(dev):
+    """features.MagStftExtractor(win_length=400).extract (salsa_logspec_batch) against the reference's MagStftExtractor (g19)"""
+    from salsa_amd.features import MagStftExtractor
+    meta, a = load_golden('g19_win_len')
+    m = meta['magstft']
+    seed, n, fs, sha = m['clip']
+    y = synth_clip(seed, n, fs=fs)
+    assert sha256_of(y) == sha
+    out = MagStftExtractor(n_fft=m['n_fft'], hop_length=m['hop'], win_length=m['win']).extract(y)
+    assert out.shape == a['magstft_w400'].shape
+    np.testing.assert_allclose(out, a['magstft_w400'], rtol=RTOL, atol=ATOL_DB)
+
+
+def _case_tree(tmp, c, fmt):
+    from golden_cases import case_clips
+    clips = {'dev|' + k: y for k, y in case_clips(c).items()}
+    return clips, _make_tree(tmp, fmt, clips, c['fmax_doa'], n_fft=c['n_fft'], hop=c['hop'], win=c['win'])
+
+
+@pytest.mark.parametrize('case', ['foa_w400', 'mic_w400'])
+def test_win_len_harness_reproduces_reference_tree(dev, oracle, tmp_path, case):
+    """features.extract_features on a tree whose YAML has win_len: 400: file names, feature files and scaler as the reference's
+    run (g19)"""
+    from golden_cases import oracle_features
+    from salsa_amd import io as sio
+    from salsa_amd.features import extract_features
+    meta, a = load_golden('g19_win_len')
+    c = meta['cases'][case]
+    clips, (cfg, feat_dir) = _case_tree(str(tmp_path), c, c['format'])
+    extract_features(data_config=cfg, batch_size=2, task='feature_scaler')
+    for k, y in clips.items():
+        name = k.split('|')[1]
+        got = sio.load_arrays(os.path.join(feat_dir, *c['files'][name].split('|')))['feature']
+        np.testing.assert_allclose(got[:4, ::c['stride']], a['%s|%s|logspec' % (case, name)], rtol=RTOL, atol=ATOL_DB)
+        _check(got[4:], a['%s|%s|spatial' % (case, name)], oracle_features(oracle, c, y)[1], n_spec=0)
+    sc = sio.load_arrays(os.path.join(feat_dir, *c['files']['scaler'].split('|')))
+    for k in ('mean', 'std'):
+        np.testing.assert_allclose(sc[k], a['%s|%s' % (case, k)], rtol=1e-5, atol=1e-5)
+
+
+@pytest.mark.parametrize('case', ['lite_w400', 'ipd_w400'])
+def test_win_len_lite_harness(dev, oracle, tmp_path, case):
+    """lite_features.extract_features with win_len: 400 in the YAML: the reference reads it and leaves it unused (g19)"""
+    from golden_cases import lite_period
+    from salsa_amd import io as sio
+    from salsa_amd import lite_features
+    meta, a = load_golden('g19_win_len')
+    c = meta['cases'][case]
+    clips, (cfg, feat_dir) = _case_tree(str(tmp_path), c, 'mic')
+    lite_features.extract_features(data_config=cfg, feature_type=c['kind'], batch_size=2)
+    for k in clips:
+        name = k.split('|')[1]
+        got = sio.load_arrays(os.path.join(feat_dir, *c['files'][name].split('|')))['feature']
+        np.testing.assert_allclose(got[:4, ::c['stride']], a['%s|%s|logspec' % (case, name)], rtol=RTOL, atol=ATOL_DB)
+        period = lite_period(c, oracle.bin_limits(24000, 512, c['fmin_doa'], c['fmax_doa'])[0], got.shape[2])
+        _check_lite(got[4:], a['%s|%s|spatial' % (case, name)], c['kind'], n_spec=0, period=period)
+    sc = sio.load_arrays(os.path.join(feat_dir, *c['files']['scaler'].split('|')))
+    for k in ('mean', 'std'):
+        np.testing.assert_allclose(sc[k], a['%s|%s' % (case, k)], rtol=1e-5, atol=1e-5)
+
+
+def test_win_len_device_invariants(dev):
+    """bit-identities of the window split: win_len moves the SALSA log-spectrogram channels and nothing else, an explicit
+    win_len = n_fft is the default plan, and the fused scaler on a two-window plan equals separate normalisation"""
+    from salsa_amd.extractor import normalize_
+    ys = np.stack([synth_clip(1960 + i, 3 * 24000) for i in range(2)])
+    a = torch.from_numpy(ys).to(dev)
+    for fmt, fmax in (('foa', 9000), ('mic', 4000)):
+        full = _extractor(audio_format=fmt, fmax_doa=fmax).extract(a).clone()
+        assert torch.equal(_extractor(audio_format=fmt, fmax_doa=fmax, win_len=512).extract(a), full)
+        for win in (400, 401):
+            w = _extractor(audio_format=fmt, fmax_doa=fmax, win_len=win).extract(a)
+            assert torch.equal(w[:, 4:], full[:, 4:]), (fmt, win)
+            assert not torch.equal(w[:, :4], full[:, :4])
+    for ftype in ('salsa_lite', 'salsa_ipd'):
+        ref = _extractor(audio_format='mic', feature_type=ftype, fmax_doa=2000).extract(a).clone()
+        assert torch.equal(_extractor(audio_format='mic', feature_type=ftype, fmax_doa=2000, win_len=400).extract(a), ref)
+    rng = np.random.RandomState(19)
+    mean = (rng.randn(4, 1, 200) * 5 - 50).astype(np.float32)
+    std = (rng.rand(4, 1, 200) * 10 + 5).astype(np.float32)
+    ex = _extractor(win_len=400)
+    raw = ex.extract(a).clone()
+    ref = normalize_(raw.clone(), torch.from_numpy(mean), torch.from_numpy(std))
+    ex.set_scaler(mean, std)
+    assert torch.equal(ex.extract(a), ref)
+    ex.set_scaler(None)
+    assert torch.equal(ex.extract(a), raw)
+
+
+@pytest.mark.parametrize('fmt', ['foa', 'mic'])
+def test_win_len_large_batch_against_oracle(dev, oracle, fmt):
+    """win_len 400 on 8 clips x 10 s in one launch: many frames and tiles of every kernel, against the oracle"""
+    fmax = 9000 if fmt == 'foa' else 4000
+    ys = np.stack([synth_clip(1970 + i, 10 * 24000) for i in range(8)])
+    out = _extractor(audio_format=fmt, fmax_doa=fmax, win_len=400).extract(torch.from_numpy(ys).to(dev)).cpu().numpy()
+    for i in range(8):
+        ref, aux = oracle.extract_salsa(ys[i], win=400, fmax_doa=fmax, audio_format=fmt, return_aux=True)
+        _check(out[i], ref, aux['margin'])
+
+
+def test_win_len_alternative_schedules(dev):
+    """every other schedule of salsa_extract_batch on a win_len 400 plan -- fused kernel, clip-group pipeline, split pairs,
+    graph replay, timing modes, the STFT-prefix issue, streamed bulk -- gives the three-kernel result bit for bit"""
+    from salsa_amd.extractor import StreamedExtractor
+    ys = np.stack([synth_clip(1980 + i, 4 * 24000) for i in range(4)])
+    a = torch.from_numpy(ys).to(dev)
+    for fmt, fmax in (('foa', 9000), ('mic', 4000)):
+        ex = _extractor(audio_format=fmt, fmax_doa=fmax, win_len=400)
+        ref = ex.extract(a).clone()
+        for mode in (1, 2):
+            ex.set_fused(mode)
+            assert torch.equal(ex.extract(a), ref), (fmt, 'fused', mode)
+        ex.set_fused(0)
+        for groups, split, graph in ((2, False, False), (3, True, False), (2, True, True)):
+            ex.set_pipeline(groups, split_pairs=split, graph=graph)
+            for _ in range(2):
+                assert torch.equal(ex.extract(a), ref), (fmt, groups, split, graph)
+        ex.set_pipeline(1)
+        ex.set_groups(2)
+        assert torch.equal(ex.extract(a), ref)
+        ex.set_groups(1)
+        out = torch.empty_like(ref)
+        for mode in (1, 3):
+            ex.set_timing(mode)
+            ex.extract(a, out=out)
+            assert [n for n, _ in ex.read_timing()] == ['stft_logspec', 'noise_floor_tracker', 'cov_eig']
+            assert torch.equal(out, ref), (fmt, 'timing', mode)
+        ex.set_timing(0)
+        out[:, :4] = 0.0
+        with ex.issue_prefix(1):
+            ex.extract(a, out=out)
+        assert torch.equal(out[:, :4], ref[:, :4])                 # the STFT stage alone leaves the win_len spectrogram
+        batches = [a[:2].contiguous(), a[2:].contiguous()]
+        got = [o.clone() for o in StreamedExtractor(n_streams=2, audio_format=fmt, fmax_doa=fmax, win_len=400).extract_many(batches)]
+        assert torch.equal(torch.cat(got), ref)

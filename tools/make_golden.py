@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Generate tests/golden/*.npz by running the UPSTREAM reference (imported from /root/reference, unmodified) in the
-build container.  Run:  python tools/make_golden.py          (needs /root/reference; never runs on the GPU box)
+build container.  Run:  python tools/make_golden.py [g19 g20 ...]   (all generators, or only the named ones; needs the reference
+checkout; never runs on the GPU box)
 
 The reference has no tests, golden vectors or fixtures of its own, so these vectors ARE the pin:
 every array below is an output of the reference's own functions
@@ -135,7 +136,7 @@ def g2_adversarial():
 
 
 # ----------------------------------------------------------------------------------------------- harness runs
-def make_tree(tmp, fmt, dev_clips, eval_clips, fs=24000, n_fft=512, hop=300, fmin=50, fmax=9000):
+def make_tree(tmp, fmt, dev_clips, eval_clips, fs=24000, n_fft=512, hop=300, fmin=50, fmax=9000, win=None):
     data_dir = os.path.join(tmp, 'data')
     feat_dir = os.path.join(tmp, 'feat')
     for split, clips in ((fmt + '_dev', dev_clips), (fmt + '_eval', eval_clips)):
@@ -146,7 +147,7 @@ def make_tree(tmp, fmt, dev_clips, eval_clips, fs=24000, n_fft=512, hop=300, fmi
             open(p, 'wb').close()
             ref_shims.register_audio(p, audio)
     cfg = {'data_dir': data_dir, 'feature_dir': feat_dir,
-           'data': {'format': fmt, 'fs': fs, 'n_fft': n_fft, 'win_len': n_fft, 'hop_len': hop,
+           'data': {'format': fmt, 'fs': fs, 'n_fft': n_fft, 'win_len': win or n_fft, 'hop_len': hop,
                     'fmin_doa': fmin, 'fmax_doa': fmax}}
     cfg_path = os.path.join(tmp, 'cfg.yml')
     with open(cfg_path, 'w') as f:
@@ -506,17 +507,112 @@ def g18_feature_tree():
     shutil.rmtree(tmp)
 
 
+# ----------------------------------------------------------------------------------------------- G19/G20: off-default YAML settings
+def ref_case(name, kind, fmt, clips, fs=24000, n_fft=512, hop=300, win=None, fmin=50, fmax=9000, cond=5, n_hop=3,
+             task='feature', stride=1):
+    """One parameter set through the reference's own extract_features (a synthetic tree, as in g3/g4): dev clips only (so the
+    scaler, when task='feature_scaler', covers all of them).  -> (meta, arrays): per clip the spatial channels whole and the
+    spectrogram channels every `stride`-th frame; the scaler's mean / std when one was written."""
+    tmp = tempfile.mkdtemp()
+    ref_shims.H5_STORE.clear()
+    audio = {k: synth_clip(s, n, fs=fs) for k, (s, n) in clips.items()}
+    cfg_path, feat_dir = make_tree(tmp, fmt, audio, {}, fs=fs, n_fft=n_fft, hop=hop, fmin=fmin, fmax=fmax, win=win)
+    with np.errstate(all='ignore'):
+        if kind == 'salsa':
+            ref_salsa.extract_features(data_config=cfg_path, cond_num=cond, n_hopframes=n_hop, is_tracking=True,
+                                       is_compress_high_freq=True, task=task)
+        else:
+            ref_lite.extract_features(data_config=cfg_path, feature_type=kind, task=task)
+    got = collect(feat_dir)
+    shutil.rmtree(tmp)
+    arrays, files = {}, {}
+    for key, v in got.items():
+        parts = key.split('|')
+        if parts[-1] == 'feature':
+            clip = parts[-2][:-3]
+            arrays['%s|%s|spatial' % (name, clip)] = v[4:]
+            arrays['%s|%s|logspec' % (name, clip)] = v[:4, ::stride]
+            files[clip] = '|'.join(parts[:-1])                       # the file's path in the feature tree
+        else:
+            arrays['%s|%s' % (name, parts[-1])] = v                   # *_feature_scaler.h5: mean, std
+            files['scaler'] = '|'.join(parts[:-1])
+    assert len([k for k in arrays if k.endswith('|spatial')]) == len(clips), sorted(got)
+    meta = {'kind': kind, 'format': fmt, 'fs': fs, 'n_fft': n_fft, 'hop': hop, 'win': win or n_fft, 'fmin_doa': fmin,
+            'fmax_doa': fmax, 'cond_num': cond, 'n_hopframes': n_hop, 'stride': stride, 'files': files,
+            'clips': {k: [s, n, fs, sha256_of(audio[k])] for k, (s, n) in clips.items()}}
+    return meta, arrays
+
+
+def ref_cases(fixture, what, cases, extra=None):
+    meta, arrays = {'what': what, 'cases': {}}, {}
+    for name, kw in cases:
+        meta['cases'][name], a = ref_case(name, **kw)
+        arrays.update(a)
+    if extra:
+        extra(meta, arrays)
+    save(fixture, meta, **arrays)
+
+
+def g19_win_len():
+    """win_len != n_fft.  The reference windows ONLY the log-spectrogram STFT with win_len (MagStftExtractor.extract,
+    salsa_feature_extraction.py:186-192, librosa pad_center: (n_fft - win_len) // 2 zeros on the left); its DOA STFT (:360-361)
+    and both SALSA-Lite / IPD STFTs (salsa_lite_feature_extraction.py:97-98; win_len read at :44, unused) use the n_fft window.
+    win_len 401 pins the centring of an odd window.  Spatial channels whole, spectrogram channels every 2nd frame (the
+    MagStftExtractor output whole)."""
+    two = {'fold1_room1_mix001': (1901, 9600), 'fold2_room1_mix002': (1902, 9600)}   # (equal lengths: one batch on the device)
+    one = lambda seed: {'fold1_room1_mix%03d' % (seed % 1000): (seed, 9600)}           # noqa: E731
+    sp = dict(kind='salsa', stride=2, task='feature_scaler')
+    cases = [
+        ('foa_w400', dict(sp, fmt='foa', clips=two, win=400)),
+        ('foa_w401', dict(sp, fmt='foa', clips=one(1903), win=401)),
+        ('mic_w400', dict(sp, fmt='mic', clips=one(1904), win=400, fmax=4000)),
+        ('mic_w401', dict(sp, fmt='mic', clips=one(1905), win=401, fmax=4000)),
+        ('foa_nfft256_w200', dict(sp, fmt='foa', clips=one(1906), n_fft=256, hop=150, win=200)),
+        ('lite_w400', dict(sp, kind='salsa_lite', fmt='mic', clips=one(1907), win=400, fmax=2000)),
+        ('ipd_w400', dict(sp, kind='salsa_ipd', fmt='mic', clips=one(1908), win=400, fmax=2000)),
+    ]
+
+    def magstft(meta, arrays):
+        # the log-spectrogram-only entry point: MagStftExtractor(win_length=400).extract on one clip
+        y = synth_clip(1909, 9600)
+        ex = ref_salsa.MagStftExtractor(n_fft=512, hop_length=300, win_length=400, is_compress_high_freq=True)
+        arrays['magstft_w400'] = ex.extract(y)
+        meta['magstft'] = {'n_fft': 512, 'hop': 300, 'win': 400, 'clip': [1909, 9600, 24000, sha256_of(y)]}
+
+    ref_cases('g19_win_len', 'win_len != n_fft through the reference extract_features / MagStftExtractor', cases, magstft)
+
+
+def g20_off_default():
+    """Off-default parameter sets the C ABI accepts, through the reference's extract_features (one clip each, spatial channels
+    whole, spectrogram channels every 4th frame).  Clip lengths: 9601 = 32 * 300 + 1 (the last frame is mirror-symmetric
+    about the reflect point), 9700 (not a multiple of the hop), 12000 (0.5 s); the fs 48000 clip is synthesised at that
+    rate (the shim loader does not resample)."""
+    one = lambda seed, n=9600: {'fold1_room1_mix%03d' % (seed % 1000): (seed, n)}       # noqa: E731
+    sp = dict(kind='salsa', fmt='foa', stride=4)
+    cases = [
+        ('foa_fmin200', dict(sp, clips=one(2001, 9601), fmin=200)),
+        ('foa_fmin300', dict(sp, clips=one(2002, 9700), fmin=300)),
+        ('foa_hop240', dict(sp, clips=one(2003, 9600), hop=240)),
+        ('foa_hop512', dict(sp, clips=one(2004, 12000), hop=512)),
+        ('foa_fs48000', dict(sp, clips=one(2005, 19200), fs=48000)),
+        ('foa_cond1p5', dict(sp, clips=one(2006, 9600), cond=1.5)),
+        ('foa_cond2', dict(sp, clips=one(2007, 9700), cond=2)),
+        ('foa_nhop2', dict(sp, clips=one(2008, 9601), n_hop=2)),
+        ('mic_fmin300', dict(sp, fmt='mic', clips=one(2009, 9600), fmin=300, fmax=4000)),
+        ('foa_nfft256_fmin0', dict(sp, clips=one(2010, 9601), n_fft=256, hop=150, fmin=0)),
+        ('lite_nfft256', dict(kind='salsa_lite', fmt='mic', stride=4, clips=one(2011, 9700), n_fft=256, hop=150, fmax=2000)),
+        ('ipd_fmax4000', dict(kind='salsa_ipd', fmt='mic', stride=4, clips=one(2012, 9601), fmax=4000)),
+    ]
+    ref_cases('g20_off_default', 'off-default YAML / extract_features settings through the reference', cases)
+
+
+GENERATORS = [g5_w_and_bins, g1_eigvec, g2_adversarial, g3_end_to_end, g4_lite, g8_stft, g10_flexible, g13_flexible_multi,
+              g15_flexible_many, g11_augment, g12_metrics, g17_labels, g18_feature_tree, g19_win_len, g20_off_default]
+
+
 if __name__ == '__main__':
-    g5_w_and_bins()
-    g1_eigvec()
-    g2_adversarial()
-    g3_end_to_end()
-    g4_lite()
-    g8_stft()
-    g10_flexible()
-    g13_flexible_multi()
-    g15_flexible_many()
-    g11_augment()
-    g12_metrics()
-    g17_labels()
-    g18_feature_tree()
+    # python tools/make_golden.py [g19 g20 ...]: only the named generators (by fixture prefix); no argument: all of them
+    picked = [g for g in GENERATORS if not sys.argv[1:] or g.__name__.split('_')[0] in sys.argv[1:]]
+    assert picked, 'no generator named %s' % sys.argv[1:]
+    for gen in picked:
+        gen()
