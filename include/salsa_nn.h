@@ -59,6 +59,10 @@ int salsa_nn_conv3x3_stem(const float *x, int64_t x_batch_stride, int64_t x_chan
  * salsa_nn_conv3x3_wide_supported: 1 if the shape is taken (the padded input chunk of a 512-pixel tile must fit its LDS buffer). */
 int salsa_nn_conv3x3_wide_supported(int64_t N, int H, int W, int Cin, int Cout);
 int salsa_nn_conv3x3_wide(const void *x, const void *w, void *y, int64_t N, int H, int W, int Cin, int Cout, void *hip_stream);
+/* the kernel instantiation the two calls above and salsa_nn_conv3x3_wide_stats / _bias_act launch for an output [N][H][W][Cout]:
+ * returns the pixels per tile (512 | 256) and sets *tn to the output channels per tile (128 | 64); -1 for a NULL tn or a Cout
+ * that is not a positive multiple of 64.  Host only (no device call): lets a test prove which instantiation a shape reaches. */
+int salsa_nn_conv3x3_wide_config(int64_t N, int H, int W, int Cout, int *tn);
 /* inference: y = [relu](conv(x, w) + shift[co] [+ residual]) with the BatchNorm that follows folded in (w pre-scaled per output
  * channel, shift float32 [Cout], residual bf16 like y or NULL), applied to the float32 sums before the single rounding */
 int salsa_nn_conv3x3_wide_bias_act(const void *x, const void *w, const float *shift, const void *residual, void *y, int relu,

@@ -437,13 +437,22 @@ static int wide_tile(int64_t N, int H, int W, int Cout, int *tn)
     return (big_ok && (P + 511) / 512 * (Cout / 64) >= 192) ? 512 : 256;
 }
 
+/* the instantiation wide_dispatch launches for an (N, H, W, Cout) output: returns the pixels per tile (512 | 256) and sets *tn to
+ * the output channels per tile (128 | 64); -1 if tn is NULL or the shape is not one a supported convolution can have.  Host only:
+ * the tests read it to prove which kernel a shape reaches. */
+extern "C" int salsa_nn_conv3x3_wide_config(int64_t N, int H, int W, int Cout, int *tn)
+{
+    if (!tn || N <= 0 || H <= 0 || W <= 0 || Cout < 64 || Cout % 64) return -1;
+    return wide_tile(N, H, W, Cout, tn);
+}
+
 static int wide_dispatch(const void *x, const void *w, void *y, int64_t N, int H, int W, int Cin, int Cout, void *hip_stream,
                          const float *shift, const void *residual, int relu, double *stats_part = nullptr)
 {
     if (!x || !w || !y || x == y || !salsa_nn_conv3x3_wide_supported(N, H, W, Cin, Cout)) return -1;
     hipStream_t st = (hipStream_t)hip_stream;
     int tn;
-    const int tm = wide_tile(N, H, W, Cout, &tn);
+    const int tm = salsa_nn_conv3x3_wide_config(N, H, W, Cout, &tn);
     if (tn == 128 && tm == 512) return wide_launch<128, 8>(x, w, y, N, H, W, Cin, Cout, st, shift, residual, relu, stats_part);
     if (tn == 128) return wide_launch<128, 4>(x, w, y, N, H, W, Cin, Cout, st, shift, residual, relu, stats_part);
     if (tm == 512) return wide_launch<64, 8>(x, w, y, N, H, W, Cin, Cout, st, shift, residual, relu, stats_part);
@@ -455,7 +464,7 @@ extern "C" int salsa_nn_conv3x3_wide_stats_blocks(int64_t N, int H, int W, int C
 {
     if (!salsa_nn_conv3x3_wide_supported(N, H, W, Cin, Cout)) return 0;
     int tn;
-    const int tm = wide_tile(N, H, W, Cout, &tn);
+    const int tm = salsa_nn_conv3x3_wide_config(N, H, W, Cout, &tn);
     return (int)(((long)N * H * W + tm - 1) / tm);
 }
 

@@ -1,0 +1,219 @@
+"""Float64 references for the CRNN kernels (conv_wide.hip, conv_mfma.hip, conv_1x1.hip, nn_ops.hip, gru_scan.hip) and the
+per-element error bounds the tests hold them to.
+
+Every reference takes the operands the kernel saw (bf16 values cast up exactly) and evaluates in float64 on their device,
+so its own error is ~2^-53 relative and negligible.  A bound is never a multiple of max|ref|: it is built per element from
+the magnitudes that enter that element's floating-point chain, so a kernel that drops one term where the terms are large,
+or shifts every element by a small relative amount, still fails.
+
+Unit roundoff u = 2^-24 (float32).  The standard result for a sum of n terms added one after another in float32 is
+|computed - exact| <= (n - 1) u sum|term| (first order; Higham, Accuracy and Stability of Numerical Algorithms, 4.2), and a
+tree of depth d gives d u sum|term|.  The constants below are those chain lengths, counted from the kernels' code.
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+U32 = 2.0 ** -24            # float32 unit roundoff
+BF16_REL = 2.0 ** -8        # bf16 unit roundoff: rounding to bf16 moves a value by at most 2^-8 of itself (8-bit significand)
+_CHUNK_PIX = 1 << 15        # pixels per unfold chunk (memory stays ~ 32 Ki x 9 Cin doubles)
+
+
+def _chunks(n, hw):
+    step = max(1, _CHUNK_PIX // hw)
+    return [(i, min(n, i + step)) for i in range(0, n, step)]
+
+
+def conv_fwd_ref(x, w, shift=None, residual=None, relu=False):
+    """(ref, absum) float64 (N, Cout, H, W): ref = [relu](conv(x, w) + shift + residual) with 'same' padding (k = 1 or 3),
+    absum = sum |w x| over the products + |shift| + |residual| (the magnitudes in the element's float32 chain)."""
+    k = w.shape[-1]
+    N, _, H, W = x.shape
+    wd = w.double().reshape(w.shape[0], -1)
+    wa = wd.abs()
+    ref = torch.empty((N, w.shape[0], H, W), dtype=torch.float64, device=x.device)
+    absum = torch.empty_like(ref)
+    for a, b in _chunks(N, H * W):
+        xc = x[a:b].double()
+        cols = F.unfold(xc, k, padding=k // 2) if k > 1 else xc.reshape(b - a, xc.shape[1], H * W)   # (n, Cin k k, HW)
+        ref[a:b] = torch.matmul(wd, cols).view(b - a, -1, H, W)
+        absum[a:b] = torch.matmul(wa, cols.abs()).view(b - a, -1, H, W)
+    if shift is not None:
+        ref += shift.double().view(1, -1, 1, 1)
+        absum += shift.double().abs().view(1, -1, 1, 1)
+    if residual is not None:
+        ref += residual.double()
+        absum += residual.double().abs()
+    if relu:
+        ref.clamp_(min=0)
+    return ref, absum
+
+
+def conv_wgrad_ref(x, gy, k=3):
+    """(ref, absum) float64 (Cout, Cin, k, k): ref = sum over pixels of gy * x(shifted), absum = the same of |gy| |x|."""
+    N, Cin, H, W = x.shape
+    Cout = gy.shape[1]
+    ref = torch.zeros((Cout, Cin * k * k), dtype=torch.float64, device=x.device)
+    absum = torch.zeros_like(ref)
+    for a, b in _chunks(N, H * W):
+        xc = x[a:b].double()
+        cols = F.unfold(xc, k, padding=k // 2) if k > 1 else xc.reshape(b - a, Cin, H * W)          # (n, Cin k k, HW)
+        g = gy[a:b].double().reshape(b - a, Cout, H * W)
+        ref += torch.einsum('npq,ncq->pc', g, cols)
+        absum += torch.einsum('npq,ncq->pc', g.abs(), cols.abs())
+    return ref.view(Cout, Cin, k, k), absum.view(Cout, Cin, k, k)
+
+
+def flip_filter(w):
+    """the data gradient's filter: w'[ci][co][r][s] = w[co][ci][2-r][2-s] (a Cout -> Cin convolution on dy)"""
+    return w.flip(2, 3).transpose(0, 1)
+
+
+def bf16_bound(ref, absum, c):
+    """bound of a bf16 output whose float32 value v carries at most c * absum of accumulation error:
+    |y - ref| <= |fl(v) - v| + |v - ref| <= 2^-8 |v| + c absum <= 2^-8 |ref| + (1 + 2^-8) c absum; c holds that spare factor."""
+    return BF16_REL * ref.abs() + c * absum
+
+
+def conv_accum_c(n_terms):
+    """c for a float32 conv / GEMM output of n_terms products on the matrix cores: each MFMA step adds a 16-product dot
+    product to the accumulator (products of bf16 are exact in float32; the 16-term sum counts as a 16-deep chain), so
+    n_terms / 16 accumulator additions + 16, plus 2 for the epilogue's shift and residual adds."""
+    return (math.ceil(n_terms / 16) + 16 + 2) * U32
+
+
+def wide_wgrad_c(N, H, W, Cin, Cout):
+    """c for salsa_nn_conv3x3_wide_wrw's float32 dW at one (N, H, W, Cin, Cout), from its summation chain:
+    - the launch gives each of `shares` workgroups a contiguous run of ceil(tiles / shares) 128-pixel tiles, with
+      shares = min(tiles, ceil(256 / ((Cout / 128) (Cin / 32)))), tiles = ceil(N H W / 128);
+    - inside a workgroup the two wave groups (WG_KQ = 2) each take half of every tile's k-steps: an accumulator receives
+      tiles_per_share * 128 / 2 / 16 MFMA updates of 16 products each (+16 for the in-MFMA sum);
+    - the pair reduction adds the two halves (1);
+    - the shares meet in dW by float32 atomics or, deterministic, by a sequential sum of the slabs (shares).
+    Hence c = (tiles_per_share * 4 + 16 + 1 + shares) u.  At 32 x 160 x 50, 128 -> 128: shares 64, 32 tiles each, c = 209 u
+    = 1.2e-5; a sequential float32 sum over all 256 000 pixels would need c = 256 000 u = 1.5e-2 -- a bound that loose
+    would not see a missing 128-pixel tile (~sqrt(128) |gy x| against 1.5e-2 * 256 000 * E|gy x|)."""
+    tiles = math.ceil(N * H * W / 128)
+    pairs = (Cout // 128) * (Cin // 32)
+    shares = max(1, min(tiles, math.ceil(256 / pairs)))
+    per = math.ceil(tiles / shares)
+    return (per * 128 // 2 // 16 + 16 + 1 + shares) * U32
+
+
+def c64_wgrad_c(N, H, W):
+    """c for salsa_nn_conv3x3_c64_wrw (64 -> 64): nb persistent workgroups (128 / 256 / 512 from 128 / 4096 / 16384 tiles of
+    4 x 32 pixels up) each walk ceil(tiles / nb) tiles with an MFMA accumulator update per 16 pixels (8 per tile, + 16 for the
+    in-MFMA sum), then the nb partials are added: c = (ceil(tiles / nb) * 8 + 16 + nb) u.  Tiles are counted per image on a
+    grid rounded up to whole tiles."""
+    tiles = N * math.ceil(H / 4) * math.ceil(W / 32)
+    nb = 512 if tiles >= 16384 else 256 if tiles >= 4096 else 128 if tiles >= 128 else tiles
+    return (math.ceil(tiles / nb) * 8 + 16 + nb) * U32
+
+
+def conv1x1_wgrad_c(M, Cin, Cout):
+    """c for salsa_nn_conv1x1_wrw: 64-pixel tiles, split = min(ceil(tiles / 2), max(1, 512 / ((Cout / 128) (Cin / 64))))
+    workgroups along the pixels, each walking per = ceil(tiles / split) tiles with an MFMA step per 16 pixels, then the
+    workgroups' partials are added (split): c = (per * 4 + 16 + split) u."""
+    tiles = math.ceil(M / 64)
+    split = max(1, 512 // ((Cout // 128) * (Cin // 64)))
+    split = max(1, min(split, (tiles + 1) // 2))
+    per = math.ceil(tiles / split)
+    return (per * 4 + 16 + split) * U32
+
+
+def check(got, ref, bound, what):
+    """assert |got - ref| <= bound element-wise; returns max(|got - ref| / bound) for the report"""
+    err = (got.double() - ref).abs()
+    bad = ~(err <= bound)                                            # (a NaN fails)
+    ratio = float((err / bound.clamp(min=1e-300)).max())
+    if bool(bad.any()):
+        i = int(bad.flatten().nonzero()[0])
+        raise AssertionError('%s: %d of %d elements outside the bound; first at %d: got %r ref %r bound %r (max err / bound %.3g)'
+                             % (what, int(bad.sum()), bad.numel(), i, float(got.flatten()[i]), float(ref.flatten()[i]),
+                                float(bound.flatten()[i]), ratio))
+    return ratio
+
+
+# ------------------------------------------------------------------------------------------------------------ BatchNorm
+def bn_rows_per_thread(M, C, bf16):
+    """upper bound of the float32 chain of one thread in nn_ops.hip's reductions: a thread covers <= BN_RPT = 32 rows of a
+    chunk, and with the grid capped at BN_MAX_BLOCKS = 1024 blocks of rpi = 256 / (C / L) rows it walks several chunks"""
+    rpi = 256 // (C // (8 if bf16 else 4))
+    return max(32, math.ceil(M / (rpi * 1024))) + int(math.log2(rpi)) + 2
+
+
+def bn_train_ref(x, gamma, beta, eps, residual=None, relu=True, pool=False):
+    """training-mode BatchNorm2d [+ residual] [+ ReLU] [-> 2x2 average pool] in float64.  Returns a dict: y, pre (the
+    pre-activation), mean, var (biased), invstd, xhat, and fwd_abs: the magnitudes of y's float32 chain,
+    |gamma| invstd (|x| + |mean|) + |beta| + |residual| + |gamma xhat| (1 + mean^2 / var)  -- the last term for the variance,
+    whose float32 partial sums of squares carry BN_BATCH u (mean^2 + var) of error."""
+    xd = x.double()
+    M = xd.shape[0] * xd.shape[2] * xd.shape[3]
+    mean = xd.mean(dim=(0, 2, 3))
+    var = (xd * xd).mean(dim=(0, 2, 3)) - mean * mean
+    invstd = 1.0 / torch.sqrt(var + eps)
+    v = lambda t: t.view(1, -1, 1, 1)
+    xhat = (xd - v(mean)) * v(invstd)
+    g, b = gamma.double(), beta.double()
+    pre = xhat * v(g) + v(b)
+    fwd_abs = v(g.abs() * invstd) * (xd.abs() + v(mean.abs())) + v(b.abs()) + (xhat * v(g)).abs() * v(1 + mean * mean / var)
+    if residual is not None:
+        pre = pre + residual.double()
+        fwd_abs = fwd_abs + residual.double().abs()
+    y = pre.clamp(min=0) if relu else pre
+    if pool:
+        y = F.avg_pool2d(y, 2)
+    return dict(y=y, pre=pre, mean=mean, var=var, unbiased=var * M / (M - 1), invstd=invstd, xhat=xhat, fwd_abs=fwd_abs, M=M)
+
+
+def bn_bwd_ref(r, gamma, gy, relu=True, pool=False, fwd_c=16 * U32, bf16=False):
+    """float64 gradients of bn_train_ref's output for an upstream gradient gy, with bounds: returns dict dx, dres, dgamma,
+    dbeta and their bounds.  Elements whose pre-activation lies within the forward's error bound of 0 have an undecided
+    ReLU mask: they may count either way, so their |g| joins the bounds of the sums and their own dx / dres are exempt."""
+    pre, xhat, invstd, M = r['pre'], r['xhat'], r['invstd'], r['M']
+    N, C, H, W = pre.shape
+    g = gy.double()
+    if pool:
+        g = F.interpolate(g, scale_factor=2, mode='nearest') / 4
+        g = F.pad(g, (0, W - g.shape[3], 0, H - g.shape[2]))
+    amb = torch.zeros_like(pre, dtype=torch.bool)
+    ga_amb = torch.zeros_like(g)
+    if relu:
+        amb = pre.abs() <= fwd_c * r['fwd_abs']
+        ga_amb = g.abs() * amb                                    # (|g| before the mask: it may count there or not)
+        g = g * (pre > 0)
+    v = lambda t: t.view(1, -1, 1, 1)
+    dbeta = g.sum(dim=(0, 2, 3))
+    dgamma = (g * xhat).sum(dim=(0, 2, 3))
+    chain = bn_rows_per_thread(M, C, bf16) * U32
+    ga = g.abs()
+    xh_abs = xhat.abs() + v(invstd * r['mean'].abs())        # |xhat| and the float32 mean's rounding in it
+    b_dbeta = chain * ga.sum(dim=(0, 2, 3)) + ga_amb.sum(dim=(0, 2, 3))
+    b_dgamma = (chain + 4 * U32) * (ga * xh_abs).sum(dim=(0, 2, 3)) + (ga_amb * xhat.abs()).sum(dim=(0, 2, 3))
+    gd = gamma.double()
+    a = gd * invstd
+    dx = v(a) * (g - v(dbeta / M) - xhat * v(dgamma / M))
+    dx_abs = v(a.abs()) * (8 * U32 * (ga + v(dbeta.abs() / M) + xh_abs * v(dgamma.abs() / M))
+                           + v(b_dbeta / M) + xhat.abs() * v(b_dgamma / M))
+    out = dict(dx=dx, dres=g, dgamma=dgamma, dbeta=dbeta, b_dgamma=b_dgamma, b_dbeta=b_dbeta, exempt=amb)
+    out['b_dx'] = (BF16_REL * dx.abs() if bf16 else 0) + dx_abs
+    out['b_dres'] = (BF16_REL * g.abs() if bf16 else 0 * g) + 2 * U32 * ga
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ GRU
+def gru_ref(gru, x, gy, whh_round=None):
+    """outputs and gradients of a batch_first bidirectional nn.GRU evaluated in float64 on the CPU (a copy of `gru`; W_hh
+    optionally passed through whh_round first, e.g. a float16 rounding).  -> (y, [dx] + [grad of every parameter])"""
+    import copy
+    g64 = copy.deepcopy(gru).cpu().double()
+    if whh_round is not None:
+        with torch.no_grad():
+            for n, p in g64.named_parameters():
+                if n.startswith('weight_hh'):
+                    p.copy_(whh_round(p))
+    xr = x.detach().cpu().double().requires_grad_(True)
+    y, _ = g64(xr)
+    y.backward(gy.detach().cpu().double())
+    return y.detach(), [xr.grad] + [p.grad for p in g64.parameters()]
