@@ -11,6 +11,7 @@ NN_SRC_PATH = os.path.join(_HERE, 'csrc', 'nn_ops.hip')
 CONV_SRC_PATH = os.path.join(_HERE, 'csrc', 'conv_mfma.hip')
 CONV_WIDE_SRC_PATH = os.path.join(_HERE, 'csrc', 'conv_wide.hip')
 CONV_1X1_SRC_PATH = os.path.join(_HERE, 'csrc', 'conv_1x1.hip')
+BASELINE_SRC_PATH = os.path.join(_HERE, 'csrc', 'baseline_kernels.hip')
 
 FORMAT = {'foa': 0, 'mic': 1}
 FEATURE = {'salsa': 0, 'salsa_lite': 1, 'salsa_ipd': 2}
@@ -32,11 +33,22 @@ class SalsaParams(C.Structure):
                 ('floor_mask_ratio', C.c_double), ('fmax_spec', C.c_int), ('reserved', C.c_int)]
 
 
+# include/salsa_baseline.h
+BASELINE_FEATURE = {'melspec': 0, 'melspeciv': 1, 'melspecgcc': 2, 'linspeciv': 3, 'linspecgcc': 4}
+
+
+class BaselineParams(C.Structure):
+    _fields_ = [('fs', C.c_int), ('n_fft', C.c_int), ('hop_len', C.c_int), ('win_len', C.c_int), ('n_mels', C.c_int),
+                ('feature_type', C.c_int), ('fmin', C.c_double), ('fmax', C.c_double), ('is_compressed_freq', C.c_int),
+                ('reserved', C.c_int)]
+
+
 _lib = None
 
 
 def build_command():
-    return ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC', '-o', LIB_PATH, SRC_PATH, GRU_SRC_PATH, NN_SRC_PATH, CONV_SRC_PATH, CONV_WIDE_SRC_PATH, CONV_1X1_SRC_PATH]
+    return ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC', '-o', LIB_PATH, SRC_PATH, GRU_SRC_PATH, NN_SRC_PATH, CONV_SRC_PATH, CONV_WIDE_SRC_PATH, CONV_1X1_SRC_PATH,
+            BASELINE_SRC_PATH]
 
 
 def load():
@@ -148,6 +160,13 @@ def load():
     L.salsa_multichannel_workspace_bytes.restype = C.c_size_t
     L.salsa_multichannel_workspace_bytes.argtypes = [vp, C.c_int, C.c_int, C.c_int64]
     L.salsa_extract_multichannel.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int64, vp, vp, C.c_size_t, vp]
+    L.salsa_baseline_plan_create.argtypes = [C.POINTER(BaselineParams), C.POINTER(vp)]
+    L.salsa_baseline_plan_destroy.argtypes = [vp]
+    L.salsa_baseline_output_shape.argtypes = [vp, C.c_int64, ip, C.POINTER(C.c_int64), ip]
+    L.salsa_baseline_workspace_bytes.restype = C.c_size_t
+    L.salsa_baseline_workspace_bytes.argtypes = [vp, C.c_int, C.c_int64]
+    L.salsa_baseline_extract_batch.argtypes = [vp, vp, C.c_int, C.c_int64, vp, vp, C.c_size_t, vp]
+    L.salsa_baseline_mel_matrix.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, fp]
     flags = L.salsa_build_flags().decode()
     if flags:                                        # an A/B or probe library (SALSA_HIP_LIB / tools/dev_build.sh with -D...): say so, loudly
         import sys
@@ -177,3 +196,5 @@ NN_EXPORTS = ['salsa_nn_avgpool2x2_fwd', 'salsa_nn_avgpool2x2_bwd', 'salsa_nn_co
               'salsa_nn_bn_eval_fwd', 'salsa_nn_bn_bwd', 'salsa_nn_bn_train_fwd_pool', 'salsa_nn_bn_bwd_pool', 'salsa_nn_conv_filter_bank', 'salsa_nn_conv3x3_c64_stats_blocks', 'salsa_nn_conv3x3_c64_stats', 'salsa_nn_conv3x3_stem_wrw', 'salsa_nn_conv3x3_stem_stats_blocks', 'salsa_nn_conv3x3_stem_stats', 'salsa_nn_conv3x3_stem_wrw_bn', 'salsa_nn_conv1x1_supported', 'salsa_nn_conv1x1', 'salsa_nn_conv1x1_wrw_supported', 'salsa_nn_conv1x1_wrw', 'salsa_nn_seld_loss', 'salsa_nn_seld_loss_bwd', 'salsa_nn_freq_mean_fwd',
               'salsa_nn_freq_mean_bwd', 'salsa_nn_colsum2', 'salsa_nn_conv3x3_wide_stats', 'salsa_nn_conv3x3_wide_stats_blocks', 'salsa_nn_conv3x3_wide_config', 'salsa_nn_set_deterministic', 'salsa_nn_get_deterministic', 'salsa_nn_conv3x3_stem_wrw_bnf', 'salsa_nn_conv3x3_stem_wrw_bnf_ws_bytes', 'salsa_nn_bn_train_finalize', 'salsa_nn_conv3x3_c64_xform_stats', 'salsa_nn_conv3x3_c64_wrw_xform', 'salsa_nn_adam_step', 'salsa_nn_bn_train_fwd_bits',
               'salsa_nn_bn_train_fwd_pool_bits', 'salsa_nn_bn_bwd_pool_bits']
+BASELINE_EXPORTS = ['salsa_baseline_plan_create', 'salsa_baseline_plan_destroy', 'salsa_baseline_output_shape',
+                    'salsa_baseline_workspace_bytes', 'salsa_baseline_extract_batch', 'salsa_baseline_mel_matrix']

@@ -2312,6 +2312,8 @@ extern "C" {
 int salsa_abi_version(void) { return SALSA_ABI_VERSION; }
 const char *salsa_build_flags(void) { return SALSA_BUILD_FLAGS; }
 const char *salsa_last_error(void) { return g_err; }
+// the other translation units' failures (baseline_kernels.hip) land in the same per-thread message; not part of the public ABI
+__attribute__((visibility("hidden"))) void salsa_set_last_error_(const char *msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
 
 int salsa_bin_limits(int fs, int n_fft, int fmin_doa, int fmax_doa, int *lower_bin, int *upper_bin, int *cutoff_bin)
 {

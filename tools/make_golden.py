@@ -606,8 +606,82 @@ def g20_off_default():
     ref_cases('g20_off_default', 'off-default YAML / extract_features settings through the reference', cases)
 
 
+# ----------------------------------------------------------------------------------------------- G21: baseline features
+def g21_baseline():
+    """dataset/feature_extraction.py (the baseline features: log-mel / log-linear + IV or GCC-PHAT) through the reference's
+    select_extractor(...).extract and extract_features(...) + compute_scaler on a two-split tree.  The reference pins
+    numpy 1.19, whose np.fft.irfft evaluates a complex64 input in float64; numpy >= 2 evaluates it in float32, so the
+    reference's irfft calls are run on the complex128 upcast of their input (meta 'irfft').  GCC types return float64 from
+    .extract; the fixture stores every output as the float32 the reference writes to its feature files."""
+    from dataset import feature_extraction as ref_base  # noqa: E402  (the reference)
+    irfft = np.fft.irfft
+    np.fft.irfft = lambda a, *k, **kw: irfft(np.asarray(a).astype(np.complex128), *k, **kw)
+    try:
+        arrays, meta = {}, {'what': 'baseline features (dataset/feature_extraction.py)', 'irfft': 'complex128 upcast (numpy 1.19)',
+                            'cases': []}
+        # short clips keep the fixture small: 900 samples = 4 frames at hop 300 (7 at hop 150), more than the GCC types' reflect
+        # padding of n_fft samples; the silence cases take 1200 samples with frame 2 wholly inside the silent stretch
+        N, N_SIL, SIL = 900, 1200, (300, 900)
+
+        def silent(seed):
+            y = synth_clip(seed, N_SIL).copy()
+            y[:, SIL[0]:SIL[1]] = 0.0
+            return y
+        # FOA-labelled clips at the reference config's defaults; MIC-labelled clips at n_fft 256 / hop 150 (mel types: 64 bands)
+        cases = []
+        for i, ft in enumerate(('melspec', 'melspeciv', 'melspecgcc', 'linspeciv', 'linspecgcc')):
+            cases.append(('%s_foa' % ft, ft, 2100 + 2 * i, {}))
+            cases.append(('%s_mic_nfft256' % ft, ft, 2101 + 2 * i, dict(n_fft=256, hop=150, n_mels=64)))
+        cases += [('melspeciv_win400', 'melspeciv', 2123, dict(win=400)),
+                  ('linspecgcc_win400', 'linspecgcc', 2124, dict(win=400)),
+                  ('linspeciv_nocompress', 'linspeciv', 2125, dict(compress=False)),
+                  ('linspecgcc_nocompress', 'linspecgcc', 2126, dict(compress=False)),
+                  ('melspeciv_silence', 'melspeciv', 2127, dict(silence=True)),
+                  ('linspecgcc_silence', 'linspecgcc', 2128, dict(silence=True)),
+                  ('melspecgcc_silence', 'melspecgcc', 2129, dict(silence=True))]
+        for name, ft, seed, o in cases:
+            fs, n_fft, hop = 24000, o.get('n_fft', 512), o.get('hop', 300)
+            win, fmin, fmax = o.get('win', n_fft), 50, 12000
+            n_mels = o.get('n_mels', 128)
+            if ft.startswith('lin'):
+                n_mels = (200 if n_fft == 512 else 100) if o.get('compress', True) else n_fft // 2
+            n = N_SIL if o.get('silence') else N
+            y = silent(seed) if o.get('silence') else synth_clip(seed, n)
+            ex = ref_base.select_extractor(feature_type=ft, fs=fs, n_fft=n_fft, hop_length=hop, n_mels=n_mels, win_length=win,
+                                           fmin=fmin, fmax=fmax)
+            arrays[name] = np.asarray(ex.extract(y), np.float32)
+            meta['cases'].append(dict(name=name, feature_type=ft, seed=seed, n=n, sha=sha256_of(synth_clip(seed, n)),
+                                      silence=list(SIL) if o.get('silence') else None, fs=fs, n_fft=n_fft, hop=hop, win=win,
+                                      fmin=fmin, fmax=fmax, n_mels=n_mels, compress=bool(o.get('compress', True))))
+        for n_fft, n_mels in ((512, 128), (256, 64)):
+            arrays['melW_%d_%d' % (n_fft, n_mels)] = ref_base.FeatureExtractor(fs=24000, n_fft=n_fft, hop_length=300, n_mels=n_mels,
+                                                                               fmin=50, fmax=12000).melW
+        # a two-split tree through extract_features (+ compute_scaler): two dev clips of different lengths, one eval clip
+        meta['trees'] = []
+        for fmt, ft, seeds in (('mic', 'melspecgcc', (2143, 2144, 2145)),):
+            tmp = tempfile.mkdtemp()
+            clips = {s: synth_clip(s, N + 300 * (s % 2)) for s in seeds}
+            cfg_path, feat_dir = make_tree(tmp, fmt, {'fold1_room1_mix%03d' % (s - 2139): clips[s] for s in seeds[:2]},
+                                           {'fold2_room1_mix%03d' % (s - 2139): clips[s] for s in seeds[2:]})
+            cfg = yaml.safe_load(open(cfg_path))
+            cfg['data'].update(fmin=50, fmax=12000, n_mels=128)
+            for k in ('fmin_doa', 'fmax_doa'):
+                cfg['data'].pop(k)
+            yaml.safe_dump(cfg, open(cfg_path, 'w'))
+            ref_base.extract_features(data_config=cfg_path, feature_type=ft, task='feature_scaler')
+            got = collect(feat_dir)
+            for k, v in got.items():
+                arrays['tree_%s|%s' % (fmt, k)] = v
+            meta['trees'].append(dict(format=fmt, feature_type=ft, seeds=list(seeds), lengths=[int(clips[s].shape[1]) for s in seeds],
+                                      shas=[sha256_of(clips[s]) for s in seeds], keys=sorted(got)))
+            shutil.rmtree(tmp)
+        save('g21_baseline', meta, **arrays)
+    finally:
+        np.fft.irfft = irfft
+
+
 GENERATORS = [g5_w_and_bins, g1_eigvec, g2_adversarial, g3_end_to_end, g4_lite, g8_stft, g10_flexible, g13_flexible_multi,
-              g15_flexible_many, g11_augment, g12_metrics, g17_labels, g18_feature_tree, g19_win_len, g20_off_default]
+              g15_flexible_many, g11_augment, g12_metrics, g17_labels, g18_feature_tree, g19_win_len, g20_off_default, g21_baseline]
 
 
 if __name__ == '__main__':

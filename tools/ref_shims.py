@@ -13,6 +13,11 @@ arithmetic is not under /root/reference, so it is restated below from the pinned
   float32 input) -- i.e. values are float64-accurate then rounded to float32.
 * ``librosa.power_to_db(S, ref=1.0, amin=1e-10, top_db=None)`` = 10*log10(max(amin,S)) - 10*log10(max(amin,ref)),
   evaluated in the dtype of S (float32 on this path).
+* ``librosa.filters.mel(sr, n_fft, n_mels=128, fmin=0.0, fmax=None, htk=False, norm='slaney', dtype=float32)``
+  (librosa 0.8.0 filters.py): Slaney mel scale (linear below 1 kHz, logarithmic above), triangles over
+  ``linspace(0, sr/2, 1 + n_fft//2)`` stored into a float32 matrix, then ``weights *= enorm`` with the float64
+  ``enorm = 2 / (mel_f[2:] - mel_f[:-2])`` (rounded back to float32).  ``check_mel_against_transformers`` holds it to
+  ``transformers.audio_utils.mel_filter_bank(norm='slaney', mel_scale='slaney')`` where that package is installed.
 * ``librosa.load(path, sr, mono=False, dtype=float32)`` on a native-rate file: samples as (C, N) float32; the shim
   serves arrays registered in-memory (or .npy payloads) instead of decoding WAV.
 * ``h5py.File(path,'w').create_dataset(name, data, dtype)`` / ``hf[name][:]``: an in-memory capture.
@@ -79,6 +84,68 @@ def _power_to_db(S, ref=1.0, amin=1e-10, top_db=80.0):
     return log_spec
 
 
+def _hz_to_mel(frequencies):
+    frequencies = np.asanyarray(frequencies)
+    f_min, f_sp = 0.0, 200.0 / 3
+    mels = (frequencies - f_min) / f_sp
+    min_log_hz = 1000.0
+    min_log_mel = (min_log_hz - f_min) / f_sp
+    logstep = np.log(6.4) / 27.0
+    if frequencies.ndim:
+        log_t = frequencies >= min_log_hz
+        mels[log_t] = min_log_mel + np.log(frequencies[log_t] / min_log_hz) / logstep
+    elif frequencies >= min_log_hz:
+        mels = min_log_mel + np.log(frequencies / min_log_hz) / logstep
+    return mels
+
+
+def _mel_to_hz(mels):
+    mels = np.asanyarray(mels)
+    f_min, f_sp = 0.0, 200.0 / 3
+    freqs = f_min + f_sp * mels
+    min_log_hz = 1000.0
+    min_log_mel = (min_log_hz - f_min) / f_sp
+    logstep = np.log(6.4) / 27.0
+    if mels.ndim:
+        log_t = mels >= min_log_mel
+        freqs[log_t] = min_log_hz * np.exp(logstep * (mels[log_t] - min_log_mel))
+    elif mels >= min_log_mel:
+        freqs = min_log_hz * np.exp(logstep * (mels - min_log_mel))
+    return freqs
+
+
+def _mel(sr, n_fft, n_mels=128, fmin=0.0, fmax=None, htk=False, norm='slaney', dtype=np.float32):
+    assert not htk and norm == 'slaney'
+    if fmax is None:
+        fmax = float(sr) / 2
+    n_mels = int(n_mels)
+    weights = np.zeros((n_mels, int(1 + n_fft // 2)), dtype=dtype)
+    fftfreqs = np.linspace(0, float(sr) / 2, int(1 + n_fft // 2), endpoint=True)
+    mel_f = _mel_to_hz(np.linspace(_hz_to_mel(fmin), _hz_to_mel(fmax), n_mels + 2))
+    fdiff = np.diff(mel_f)
+    ramps = np.subtract.outer(mel_f, fftfreqs)
+    for i in range(n_mels):
+        lower = -ramps[i] / fdiff[i]
+        upper = ramps[i + 2] / fdiff[i + 1]
+        weights[i] = np.maximum(0, np.minimum(lower, upper))
+    enorm = 2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels])
+    weights *= enorm[:, np.newaxis]
+    return weights
+
+
+def check_mel_against_transformers(sr=24000, n_fft=512, n_mels=128, fmin=50.0, fmax=12000.0):
+    """max |_mel - transformers' slaney filter bank| in float32 ulps of the weights (None when transformers is absent)"""
+    try:
+        from transformers.audio_utils import mel_filter_bank
+    except Exception:
+        return None
+    ref = mel_filter_bank(num_frequency_bins=1 + n_fft // 2, num_mel_filters=n_mels, min_frequency=fmin, max_frequency=fmax,
+                          sampling_rate=sr, norm='slaney', mel_scale='slaney').T
+    ours = _mel(sr, n_fft, n_mels, fmin, fmax)
+    ulp = np.spacing(np.maximum(np.abs(ref), 1e-30).astype(np.float32))
+    return float(np.max(np.abs(ours.astype(np.float64) - ref) / ulp))
+
+
 # ------------------------------------------------------------------------------------------------ h5py shim
 H5_STORE = {}
 
@@ -108,6 +175,7 @@ def install():
     """Insert the stub modules and numpy-1.19 aliases, put the reference on sys.path."""
     lib = types.ModuleType('librosa')
     lib.load, lib.stft, lib.power_to_db = _load, _stft, _power_to_db
+    lib.filters = types.SimpleNamespace(mel=_mel)
     h5 = types.ModuleType('h5py')
     h5.File = _H5File
     fire = types.ModuleType('fire')
