@@ -186,6 +186,13 @@ int salsa_to_freq_major(const float *d_feat, int64_t n_rows, int64_t n_frames, i
 int salsa_augment_batch(const float *d_in, int64_t in_batch_stride, int64_t in_channel_stride, float *d_out, int batch,
                         int64_t n_frames, int n_freq, int audio_format, int n_zero_channels, const int *d_params,
                         const float *d_uval, const float *d_minmax, void *hip_stream);
+/* The baseline GCC recipe (melspecgcc / linspecgcc, dataset/datamodule.py:83-100) in one pass: GccRandomSwapChannelMic
+ * (transforms.py:526-618; only the FIRST set bit of m0..m2 acts on the features, some GCC rows are flipped along the lag axis),
+ * RandomShiftUpDownNp(n_last_channels=6) on the four spectrogram rows, then the cutout rectangles with the last 6 rows zeroed.
+ * d_out: float32 [B][10][T][F]; d_in, d_params, d_uval, d_minmax as salsa_augment_batch (m3 unused). */
+int salsa_augment_gcc_batch(const float *d_in, int64_t in_batch_stride, int64_t in_channel_stride, float *d_out, int batch,
+                            int64_t n_frames, int n_freq, const int *d_params, const float *d_uval, const float *d_minmax,
+                            void *hip_stream);
 
 /* Per-kernel timing of salsa_extract_batch with HIP events recorded on the call's stream (for roofline reporting).
  * enable == 1 brackets each launch with an event pair.  enable = K > 1 launches every kernel of the call K times back to

@@ -46,9 +46,12 @@ int salsa_nn_conv3x3_c64_bias_act(const void *x, const void *w, const float *shi
  * y bf16 [N][H/2][W/2][64]; H and W even */
 int salsa_nn_conv3x3_c64_bias_act_pool(const void *x, const void *w, const float *shift, const void *residual, void *y, int relu,
                                        int64_t N, int H, int W, void *hip_stream);
-/* the network's first layer, Cin <= 8 -> 64 channels, on the extractor's output layout: x float32 planar [N][Cin][H][W] with
+/* the network's first layer, Cin <= 16 -> 64 channels, on the extractor's output layout: x float32 planar [N][Cin][H][W] with
  * contiguous rows and the given batch / channel strides (elements; a time-cropped view needs no copy);
- * wq bf16 [64 co][10 taps][8 ci] (taps row-major, tap 9 and ci >= Cin zero); y bf16 channels-last [N][H][W][64];
+ * wq bf16, two layouts by Cin:
+ *   Cin <= 8       (SALSA, 7 channels):          [64 co][10 taps][8 ci]  (taps row-major, tap 9 and ci >= Cin zero);
+ *   9 <= Cin <= 16 (baseline GCC, 10 channels): [64 co][9 taps][16 ci]  (taps row-major, ci >= Cin zero);
+ * y bf16 channels-last [N][H][W][64];
  * shift NULL: plain convolution, else y = [relu](conv + shift[co]) with the BatchNorm folded as above */
 int salsa_nn_conv3x3_stem(const float *x, int64_t x_batch_stride, int64_t x_channel_stride, const void *wq, const float *shift,
                           void *y, int relu, int64_t N, int Cin, int H, int W, void *hip_stream);
@@ -95,8 +98,10 @@ int salsa_nn_conv3x3_c64_stats(const void *x, const void *w, void *y, double *st
 int salsa_nn_conv3x3_stem_stats_blocks(int64_t N, int H, int W);
 int salsa_nn_conv3x3_stem_stats(const float *x, int64_t x_batch_stride, int64_t x_channel_stride, const void *wq, void *y,
                                 double *stats_part, int64_t N, int Cin, int H, int W, void *hip_stream);
-/* weight gradient of the (Cin <= 7) -> 64 first layer: dw float32 [64 co][Cin][3][3] contiguous += sum_pixels dy[p][co] *
- * x[ci][p + tap] (zero it first); x float32 planar as in salsa_nn_conv3x3_stem, dy bf16 channels-last [N][H][W][64] */
+/* weight gradient of the (Cin <= 14) -> 64 first layer: dw float32 [64 co][Cin][3][3] contiguous += sum_pixels dy[p][co] *
+ * x[ci][p + tap] (zero it first); x float32 planar as in salsa_nn_conv3x3_stem, dy bf16 channels-last [N][H][W][64].
+ * Cin <= 7 covers the Cin * 9 columns with one 64-column block, 8 <= Cin <= 14 with two (128 columns, the last one kept for
+ * the ones plane of _bnf).  This and the two calls below return -1 for Cin > 14. */
 int salsa_nn_conv3x3_stem_wrw(const float *x, int64_t x_batch_stride, int64_t x_channel_stride, const void *dy, float *dw, int64_t N,
                               int Cin, int H, int W, void *hip_stream);
 /* The same with the BatchNorm (+ ReLU) behind the first layer differentiated on the fly: g = gradient of the BatchNorm's OUTPUT,
@@ -113,6 +118,8 @@ int salsa_nn_conv3x3_stem_wrw_bn(const float *x, int64_t x_batch_stride, int64_t
  * forward's saved statistics; ws: salsa_nn_conv3x3_stem_wrw_bnf_ws_bytes(N, H, W) bytes of device scratch (-5 when smaller); dw is
  * ADDED to, dgamma / dbeta are written.  Always bit-reproducible (slabs added in a fixed order, float64). */
 size_t salsa_nn_conv3x3_stem_wrw_bnf_ws_bytes(int64_t N, int H, int W);
+/* the workspace of salsa_nn_conv3x3_stem_wrw_bnf for 8 <= Cin <= 14 (128-column slabs and a grid of its own) */
+size_t salsa_nn_conv3x3_stem16_wrw_bnf_ws_bytes(int64_t N, int H, int W);
 int salsa_nn_conv3x3_stem_wrw_bnf(const float *x, int64_t x_batch_stride, int64_t x_channel_stride, const void *g, const void *x1,
                                   const float *mean, const float *invstd, const float *gamma, const float *beta, int relu, float *dw,
                                   float *dgamma, float *dbeta, void *ws, size_t ws_bytes, int64_t N, int Cin, int H, int W,

@@ -9,6 +9,11 @@
   * CompositeCutout (:257-283) = one of RandomCutoutNp (:58-121), SpecAugmentNp (:124-194), RandomCutoutHoleNp (:197-254),
     all of which fill rectangles with a value drawn between the sample's min and max (zeros in the last
     ``n_zero_channels`` spatial rows): one core, ``fill_rects``.
+  * GccRandomSwapChannelMic (:526-618), for the baseline melspecgcc / linspecgcc features (M1..M4 | xc12 xc13 xc14 xc23
+    xc24 xc34): the same three swaps as a permutation of the ten rows, some GCC rows flipped along the lag axis.  Its feature
+    branches are ``if / elif / elif`` -- only the FIRST set bit acts on x -- while its target branches are independent ``if``s
+    like the MIC SALSA ones (every set bit acts on y_doa).  Reproduced as is: ``swap_channels_gcc`` + ``swap_targets(.., 'mic')``.
+Which of these a feature type gets is ``RECIPES`` (datamodule.py:44-100).
 The deterministic cores take the random draw as an argument; ``draw_*`` reproduce the reference's draws IN ITS CALL ORDER
 from a numpy RandomState-like source, so ``reference_train_transform`` under ``np.random.seed(s)`` equals the
 reference's SeldDataset augmentation under the same seed (golden g11); the ``random_*`` wrappers are the batched
@@ -16,6 +21,26 @@ on-device forms drawing per sample from a torch.Generator.  Pure index / sign / 
 as plumbing only."""
 import numpy as np
 import torch
+
+
+# (audio_format, feature_type) -> (swap, spectrogram rows the shift moves (None: all), cutout zero rows (None: no cutout),
+# aspect-ratio divisor of the cutout: train_chunk_len / 200 for the linear types, / 128 for the mel ones), datamodule.py:44-100
+RECIPES = {
+    ('foa', 'salsa'): ('foa', None, None, 200),
+    ('foa', 'linspeciv'): ('foa', None, 3, 200),
+    ('foa', 'melspeciv'): ('foa', None, 3, 128),
+    ('mic', 'salsa'): ('mic', None, 3, 200),
+    ('mic', 'linspecgcc'): ('gcc', 4, 6, 200),
+    ('mic', 'melspecgcc'): ('gcc', 4, 6, 128),
+}
+
+
+def recipe(audio_format, feature_type='salsa'):
+    """RECIPES[(audio_format, feature_type)]; NotImplementedError for any other pair, as the reference raises."""
+    try:
+        return RECIPES[(audio_format, feature_type)]
+    except KeyError:
+        raise NotImplementedError('aug not implemented for {} {}'.format(audio_format, feature_type)) from None
 
 
 def swap_channels_foa(x, y_doa, m, n_classes: int = 12):
@@ -100,6 +125,32 @@ def random_swap_channels_mic(x, y_sed, y_doa, gen=None, p: float = 0.5, n_classe
     m = torch.randint(0, 2, (B, 3), generator=gen) * apply[:, None]
     xn, yn = swap_channels_mic(x, y_doa, m.to(x.device), n_classes)
     return xn, y_sed, yn
+
+
+# ------------------------------------------------------------------------------------------------------- GCC swap
+# per case (0: none, 1: m0, 2: m1, 3: m2 -- the first set bit): output row c = input row GCC_SRC[case][c], lag-flipped where
+# GCC_FLIP[case][c] (transforms.py:568-602)
+GCC_SRC = torch.tensor([[0, 1, 2, 3, 4, 5, 6, 7, 8, 9], [0, 2, 1, 3, 5, 4, 6, 7, 9, 8],
+                        [3, 1, 2, 0, 8, 9, 6, 7, 4, 5], [1, 0, 3, 2, 4, 8, 7, 6, 5, 9]])
+GCC_FLIP = torch.tensor([[0, 0, 0, 0, 0, 0, 0, 0, 0, 0], [0, 0, 0, 0, 0, 0, 0, 1, 0, 0],
+                         [0, 0, 0, 0, 1, 1, 1, 0, 1, 1], [0, 0, 0, 0, 1, 0, 0, 0, 0, 1]], dtype=torch.bool)
+
+
+def swap_channels_gcc(x, m):
+    """x (B,10,T,F), m (B,>=3) in {0,1} -> the features of GccRandomSwapChannelMic (only the first set bit acts; the targets:
+    swap_targets(y_doa, m, 'mic'))."""
+    b = m[:, :3].to(torch.bool)
+    case = torch.where(b[:, 0], 1, torch.where(b[:, 1], 2, torch.where(b[:, 2], 3, 0))).to(x.device)
+    src, flip = GCC_SRC.to(x.device)[case], GCC_FLIP.to(x.device)[case]
+    xs = torch.gather(x, 1, src[:, :, None, None].expand(x.shape))
+    return torch.where(flip[:, :, None, None], xs.flip(-1), xs)
+
+
+def _shift_rows(x, shift_len, up, rows):
+    """shift_up_down on the first ``rows`` channels only (RandomShiftUpDownNp(n_last_channels=C - rows)); rows None: all."""
+    if rows is None:
+        return shift_up_down(x, shift_len, up)
+    return torch.cat([shift_up_down(x[:, :rows], shift_len, up), x[:, rows:]], dim=1)
 
 
 # ------------------------------------------------------------------------------------------------------- cutouts
@@ -195,32 +246,36 @@ def _rects_to_tensors(rect_lists, n_rects=8):
 
 
 def reference_train_transform(x, y_sed, y_doa, audio_format='foa', rng=np.random, image_aspect_ratio=None,
-                              n_classes: int = 12, freq_shift_range: int = 10, p: float = 0.5):
-    """One sample through the reference's training augmentation for SALSA features (datamodule.py:45-52 FOA, :73-82 MIC;
-    applied joint-then-plain, dataloader.py:56-60), drawing from ``rng`` exactly as the reference draws from np.random.
-    x (7,T,F), y_sed (T_lab,n_classes), y_doa (T_lab,3*n_classes) tensors (any device) -> same."""
+                              n_classes: int = 12, freq_shift_range: int = 10, p: float = 0.5, feature_type='salsa'):
+    """One sample through the reference's training augmentation for ``feature_type`` (RECIPES; datamodule.py:44-100; applied
+    joint-then-plain, dataloader.py:56-60), drawing from ``rng`` exactly as the reference draws from np.random.
+    x (C,T,F), y_sed (T_lab,n_classes), y_doa (T_lab,3*n_classes) tensors (any device) -> same."""
+    swap, rows, n_zero, div = recipe(audio_format, feature_type)
     xb, yb = x[None], y_doa[None]
     if rng.rand() < p:                                           # MapDataAugmentBase.__call__ :346-353
-        if audio_format == 'foa':
+        if swap == 'foa':
             m = rng.randint(2, size=(4,))                        # :409
             xb, yb = swap_channels_foa(xb, yb, torch.as_tensor(m)[None], n_classes)
-        else:
+        elif swap == 'mic':
             m = rng.randint(2, size=(3,))                        # :483
             xb, yb = swap_channels_mic(xb, yb, torch.as_tensor(m)[None], n_classes)
+        else:
+            m = torch.as_tensor(rng.randint(2, size=(3,)))[None]  # :567
+            xb, yb = swap_channels_gcc(xb, m), swap_targets(yb, m, 'mic', n_classes)
     if rng.rand() < p:                                           # RandomShiftUpDownNp :298-320
         shift = rng.randint(1, freq_shift_range, 1)[0]
         up = rng.choice(['up', 'down'], 1)[0] == 'up'
-        xb = shift_up_down(xb, torch.as_tensor([shift]), torch.as_tensor([bool(up)]))
-    if audio_format == 'mic' and rng.rand() < p:                 # CompositeCutout(n_zero_channels=3) is in the MIC recipe only
+        xb = _shift_rows(xb, torch.as_tensor([shift]), torch.as_tensor([bool(up)]), rows)
+    if n_zero is not None and rng.rand() < p:                    # CompositeCutout(n_zero_channels=n_zero)
         T, F = xb.shape[-2:]
-        ratio = T / 200 if image_aspect_ratio is None else image_aspect_ratio
+        ratio = T / div if image_aspect_ratio is None else image_aspect_ratio
         rects = draw_composite_cutout(rng, T, F, float(xb.min()), float(xb.max()), ratio)
-        xb = fill_rects(xb, *_rects_to_tensors([rects]), n_zero_channels=3)
+        xb = fill_rects(xb, *_rects_to_tensors([rects]), n_zero_channels=n_zero)
     return xb[0], y_sed, yb[0]
 
 
 def reference_draws(rng, T, F, audio_format='foa', minmax_after=None, image_aspect_ratio=None, freq_shift_range: int = 10,
-                    p: float = 0.5):
+                    p: float = 0.5, feature_type='salsa'):
     """The draws reference_train_transform makes, IN THE SAME ORDER from the same numpy source, as a parameter dict for ONE
     sample in apply_augment_hip's format -- so that the reference's own augmented samples (golden g11, np.random.seed(s)) can be
     demanded from the HIP kernel itself.  The cutout's fill value is drawn between the min and max of the sample AFTER swap and
@@ -231,15 +286,16 @@ def reference_draws(rng, T, F, audio_format='foa', minmax_after=None, image_aspe
              top=torch.zeros((1, 8), dtype=torch.long), h=torch.zeros((1, 8), dtype=torch.long),
              left=torch.zeros((1, 8), dtype=torch.long), w=torch.zeros((1, 8), dtype=torch.long),
              u=torch.zeros((1, 8), dtype=torch.float32), minmax=torch.tensor([[0.0, 1.0]]))
+    _, _, n_zero, div = recipe(audio_format, feature_type)
     if rng.rand() < p:
         nbits = 4 if audio_format == 'foa' else 3
         d['m'][0, :nbits] = torch.as_tensor(rng.randint(2, size=(nbits,)))
     if rng.rand() < p:
         d['shift'][0] = int(rng.randint(1, freq_shift_range, 1)[0])
         d['up'][0] = bool(rng.choice(['up', 'down'], 1)[0] == 'up')
-    if audio_format == 'mic' and rng.rand() < p:
+    if n_zero is not None and rng.rand() < p:
         vmin, vmax = minmax_after(d)
-        ratio = T / 200 if image_aspect_ratio is None else image_aspect_ratio
+        ratio = T / div if image_aspect_ratio is None else image_aspect_ratio
         rects = draw_composite_cutout(rng, T, F, float(vmin), float(vmax), ratio)
         top, h, left, w, val = _rects_to_tensors([rects])
         d['top'], d['h'], d['left'], d['w'] = top, h, left, w
@@ -314,47 +370,55 @@ def swap_targets(y_doa, m, audio_format='foa', n_classes: int = 12):
     return torch.cat([x, y, z], dim=2)
 
 
-def draw_augment(B, T, F, audio_format='foa', gen=None, p: float = 0.5, freq_shift_range: int = 10):
-    """All per-sample draws of the SALSA training recipe (datamodule.py:45-52 FOA, :73-82 MIC) for a batch, on the host:
+def draw_augment(B, T, F, audio_format='foa', gen=None, p: float = 0.5, freq_shift_range: int = 10, feature_type='salsa'):
+    """All per-sample draws of the training recipe of ``feature_type`` (RECIPES, datamodule.py:44-100) for a batch, on the host:
     dict(m (B,4) swap bits -- MIC uses the first three --, shift (B,) 0 = none, up (B,), top/h/left/w (B,8), u (B,8))."""
+    _, _, n_zero, div = recipe(audio_format, feature_type)
     nbits = 4 if audio_format == 'foa' else 3
     m = torch.zeros((B, 4), dtype=torch.long)
     m[:, :nbits] = torch.randint(0, 2, (B, nbits), generator=gen) * (torch.rand(B, generator=gen) < p)[:, None]
     shift = torch.randint(1, freq_shift_range, (B,), generator=gen) * (torch.rand(B, generator=gen) < p)
     up = torch.randint(0, 2, (B,), generator=gen).bool()
-    if audio_format == 'mic':
-        top, h, left, w, u = draw_composite_cutout_batch(B, T, F, gen, p, T / 200)
+    if n_zero is not None:
+        top, h, left, w, u = draw_composite_cutout_batch(B, T, F, gen, p, T / div)
     else:
         top, h, left, w, u = (torch.zeros((B, 8), dtype=torch.long),) * 4 + (torch.zeros((B, 8)),)
     return dict(m=m, shift=shift, up=up, top=top, h=h, left=left, w=w, u=u)
 
 
-def apply_augment_torch(x, y_doa, d, audio_format='foa', n_classes: int = 12):
+def apply_augment_torch(x, y_doa, d, audio_format='foa', n_classes: int = 12, feature_type='salsa'):
     """The drawn augmentation with torch operators (any device): swap -> shift -> cutout; the cutout's fill range is the
     min / max of the sample BEFORE augmentation.  Returns (x', y_doa')."""
+    swap, rows, n_zero, _ = recipe(audio_format, feature_type)
     lo, hi = sample_minmax(x)
-    if audio_format == 'foa':
+    if swap == 'foa':
         xn, yn = swap_channels_foa(x, y_doa, d['m'].to(x.device), n_classes)
-    else:
+    elif swap == 'mic':
         xn, yn = swap_channels_mic(x, y_doa, d['m'][:, :3].to(x.device), n_classes)
-    xn = shift_up_down(xn, d['shift'], d['up'])
-    if audio_format == 'mic':
+    else:
+        xn, yn = swap_channels_gcc(x, d['m']), swap_targets(y_doa, d['m'], 'mic', n_classes)
+    xn = _shift_rows(xn, d['shift'], d['up'], rows)
+    if n_zero is not None:
         value = lo[:, None] + (hi - lo)[:, None] * d['u'].to(x.device, x.dtype)
-        xn = fill_rects(xn, d['top'], d['h'], d['left'], d['w'], value, n_zero_channels=3)
+        xn = fill_rects(xn, d['top'], d['h'], d['left'], d['w'], value, n_zero_channels=n_zero)
     return xn, yn
 
 
 def _rows_contiguous(x):
-    """[B,7,T,F] whose (T,F) blocks are dense: contiguous tensors and time-cropped views of them."""
-    return x.stride(3) == 1 and x.stride(2) == x.shape[3] and x.stride(1) >= x.shape[2] * x.shape[3] and x.stride(0) >= 7 * x.stride(1)
+    """[B,C,T,F] whose (T,F) blocks are dense: contiguous tensors and time-cropped views of them."""
+    return (x.stride(3) == 1 and x.stride(2) == x.shape[3] and x.stride(1) >= x.shape[2] * x.shape[3]
+            and x.stride(0) >= x.shape[1] * x.stride(1))
 
 
-def apply_augment_hip(x, d, audio_format='foa'):
-    """The drawn augmentation of the FEATURES in one pass of libsalsa_hip.so (salsa_augment_batch): x float32 CUDA
-    [B,7,T,F] contiguous -> new tensor.  (The targets are a (B, T_lab, 36) sign / swap: apply_augment_torch's y.)"""
+def apply_augment_hip(x, d, audio_format='foa', feature_type='salsa'):
+    """The drawn augmentation of the FEATURES in one pass of libsalsa_hip.so (salsa_augment_batch; the GCC types:
+    salsa_augment_gcc_batch): x float32 CUDA [B,C,T,F] (C = 7, or 10 for GCC) with dense rows -> new tensor.  (The targets are a
+    (B, T_lab, 36) sign / swap: apply_augment_torch's y.)"""
     import ctypes as C
     from . import _lib
-    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 7 and _rows_contiguous(x)
+    swap, _, n_zero, _ = recipe(audio_format, feature_type)
+    nch = 10 if swap == 'gcc' else 7
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == nch and _rows_contiguous(x)
     B, _, T, F = x.shape
     par = torch.zeros((B, 40), dtype=torch.int32)
     par[:, 0:4] = d['m']
@@ -368,25 +432,30 @@ def apply_augment_hip(x, d, audio_format='foa'):
     else:
         minmax = torch.stack(sample_minmax(x), dim=1).contiguous()
     assert minmax.shape == (B, 2)
-    out = torch.empty((B, 7, T, F), dtype=torch.float32, device=x.device)
+    out = torch.empty((B, nch, T, F), dtype=torch.float32, device=x.device)
+    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
     with torch.cuda.device(x.device):
-        rc = _lib.load().salsa_augment_batch(C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), C.c_void_p(out.data_ptr()), B, T, F,
-                                             _lib.FORMAT[audio_format], 3 if audio_format == 'mic' else 0,
-                                             C.c_void_p(par.data_ptr()), C.c_void_p(u.data_ptr()), C.c_void_p(minmax.data_ptr()),
-                                             C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        if swap == 'gcc':
+            rc = _lib.load().salsa_augment_gcc_batch(C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), C.c_void_p(out.data_ptr()), B,
+                                                     T, F, C.c_void_p(par.data_ptr()), C.c_void_p(u.data_ptr()),
+                                                     C.c_void_p(minmax.data_ptr()), stream)
+        else:
+            rc = _lib.load().salsa_augment_batch(C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), C.c_void_p(out.data_ptr()), B, T,
+                                                 F, _lib.FORMAT[audio_format], n_zero or 0, C.c_void_p(par.data_ptr()),
+                                                 C.c_void_p(u.data_ptr()), C.c_void_p(minmax.data_ptr()), stream)
     if rc:
         raise RuntimeError('salsa_augment_batch failed: ' + _lib.last_error())
     return out
 
 
-def augment_batch(x, y_sed, y_doa, audio_format='foa', gen=None, n_classes: int = 12):
-    """The reference's SALSA training recipe on a batch: channel swap (format-specific, changes the targets), frequency
-    shift, and -- MIC only -- CompositeCutout(n_zero_channels=3) (datamodule.py:45-52, :73-82).  CUDA float32 features go
-    through the one-pass HIP kernel; the (tiny) target transform and everything on CPU use the torch operators."""
+def augment_batch(x, y_sed, y_doa, audio_format='foa', gen=None, n_classes: int = 12, feature_type='salsa'):
+    """The reference's training recipe of ``feature_type`` on a batch (RECIPES, datamodule.py:44-100): channel swap
+    (changes the targets), frequency shift, and CompositeCutout where the recipe has one.  CUDA float32 features go through
+    the one-pass HIP kernel; the (tiny) target transform and everything on CPU use the torch operators."""
     B, _, T, F = x.shape
-    d = draw_augment(B, T, F, audio_format, gen)
+    d = draw_augment(B, T, F, audio_format, gen, feature_type=feature_type)
     if x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and _rows_contiguous(x):
         m_dev = d['m'].pin_memory().to(x.device, non_blocking=True)
-        return apply_augment_hip(x, d, audio_format), y_sed, swap_targets(y_doa, m_dev, audio_format, n_classes)
-    xn, yn = apply_augment_torch(x, y_doa, d, audio_format, n_classes)
+        return apply_augment_hip(x, d, audio_format, feature_type), y_sed, swap_targets(y_doa, m_dev, audio_format, n_classes)
+    xn, yn = apply_augment_torch(x, y_doa, d, audio_format, n_classes, feature_type)
     return xn, y_sed, yn

@@ -639,13 +639,14 @@ def _planar_rows(x):
 
 
 def _stem_filter(weight, scale=None):
-    """(64, Cin <= 8, 3, 3) -> the stem kernel's bf16 [64][10 taps][8 channels] (zero-padded), optionally scaled per output
-    channel (folded BatchNorm)."""
+    """(64, Cin <= 8, 3, 3) -> the stem kernel's bf16 [64][10 taps][8 channels] (zero-padded); (64, 9 <= Cin <= 16, 3, 3) ->
+    [64][9 taps][16 channels] (include/salsa_nn.h); optionally scaled per output channel (folded BatchNorm)."""
     w = weight.detach().float()
     if scale is not None:
         w = w * scale[:, None, None, None]
-    wq = torch.zeros((64, 10, 8), dtype=torch.float32, device=w.device)
-    wq[:, :9, :w.shape[1]] = w.permute(0, 2, 3, 1).reshape(64, 9, w.shape[1])
+    cin = w.shape[1]
+    wq = torch.zeros((64, 10, 8) if cin <= 8 else (64, 9, 16), dtype=torch.float32, device=w.device)
+    wq[:, :9, :cin] = w.permute(0, 2, 3, 1).reshape(64, 9, cin)
     return wq.to(torch.bfloat16).contiguous()
 
 
@@ -662,11 +663,19 @@ def _conv_stem(x, wq, shift=None, relu=False):
 
 
 USE_HIP_STEM_WRW = os.environ.get('SALSA_HIP_STEM_WRW', '1') != '0'
+# the first layer for 9-16 input channels (the baseline GCC features' 10) on the 16-channel stem kernels; 0: MIOpen through torch
+USE_HIP_STEM16 = os.environ.get('SALSA_HIP_STEM16', '1') != '0'
+STEM16_WRW_MAX_CIN = 14   # the weight gradient's cap (128 columns; include/salsa_nn.h)
+
+
+def _stem_wrw_hip(cin):
+    """The stem weight-gradient kernels take this many input channels: <= 7, and 9..14 on the 16-channel path."""
+    return USE_HIP_STEM_WRW and (cin <= 7 or (USE_HIP_STEM16 and 9 <= cin <= STEM16_WRW_MAX_CIN))
 
 
 class _Conv3x3Stem(torch.autograd.Function):
-    """The first layer (7 -> 64) on the stem kernels: forward, and the weight gradient straight from the float32 planar input
-    (salsa_nn_conv3x3_stem_wrw; 8 input channels: MIOpen).  The input needs no gradient."""
+    """The first layer (7 or 10 -> 64) on the stem kernels: forward, and the weight gradient straight from the float32 planar input
+    (salsa_nn_conv3x3_stem_wrw; 8, 15 or 16 input channels: MIOpen).  The input needs no gradient."""
 
     @staticmethod
     def forward(ctx, x, weight):
@@ -679,7 +688,7 @@ class _Conv3x3Stem(torch.autograd.Function):
         gx = gw = None
         if ctx.needs_input_grad[0]:
             raise RuntimeError('the stem convolution does not differentiate its input')
-        if ctx.needs_input_grad[1] and USE_HIP_STEM_WRW and x.shape[1] <= 7:
+        if ctx.needs_input_grad[1] and _stem_wrw_hip(x.shape[1]):
             N, Cin, H, W = x.shape
             gy = gy.contiguous(memory_format=torch.channels_last)
             gw = _grad_zeros((64, Cin, 3, 3), x.device)
@@ -822,7 +831,7 @@ class _StemConvBnRelu(torch.autograd.Function):
         coef = torch.empty(7 * Cn, dtype=torch.float32, device=x.device)
         gw = _grad_zeros((64, Cin, 3, 3), x.device)
         if USE_STEM_BN_REDUCE_FUSED:   # the BatchNorm backward's reduction inside the weight-gradient pass as well (one read of g, x1)
-            nbytes = L.salsa_nn_conv3x3_stem_wrw_bnf_ws_bytes(N, H, W)
+            nbytes = (L.salsa_nn_conv3x3_stem_wrw_bnf_ws_bytes if Cin <= 7 else L.salsa_nn_conv3x3_stem16_wrw_bnf_ws_bytes)(N, H, W)
             slabs = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
             with torch.cuda.device(x.device):
                 rc = L.salsa_nn_conv3x3_stem_wrw_bnf(_ptr(x), x.stride(0), x.stride(1), _ptr(g), _ptr(x1), _ptr(save[0]), _ptr(save[1]),
@@ -953,7 +962,7 @@ class Conv3x3(torch.nn.Conv2d):
     def _stem_eligible(self, x):
         return (USE_HIP_CONV and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and _planar_rows(x)
                 and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16
-                and self.in_channels <= 8 and self.out_channels == 64 and self.kernel_size == (3, 3) and self.stride == (1, 1)
+                and (self.in_channels <= 8 or (USE_HIP_STEM16 and self.in_channels <= 16)) and self.out_channels == 64 and self.kernel_size == (3, 3) and self.stride == (1, 1)
                 and self.padding == (1, 1) and self.bias is None and self.dilation == (1, 1) and self.groups == 1
                 and not x.requires_grad and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31 // 64)
 
@@ -1136,7 +1145,7 @@ def _conv_bn_act(conv, bn, x, residual=None, relu=True, dropout_p=0.0, pool=Fals
         return avg_pool2x2(y) if pool else y
     if (USE_STEM_FUSED_BWD and USE_HIP_STEM_WRW and USE_HIP_BN and isinstance(conv, Conv3x3) and isinstance(bn, BatchNormAct2d)
             and bn.training and torch.is_grad_enabled() and relu and residual is None and dropout_p == 0.0 and not pool
-            and conv._stem_eligible(x) and x.shape[1] <= 7 and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and conv._stem_eligible(x) and _stem_wrw_hip(x.shape[1]) and bn.affine and bn.track_running_stats and bn.momentum is not None
             and conv.weight.requires_grad and _lib.load().salsa_nn_bn_supported(1, x.shape[0] * x.shape[2] * x.shape[3], 64)):
         bn._stats_serial = getattr(bn, '_stats_serial', 0) + 1
         with torch.autocast('cuda', enabled=False):

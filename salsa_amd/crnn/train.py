@@ -23,14 +23,16 @@ def lr_at(progress: float) -> float:
     return float(np.interp(min(max(progress, 0.0), 1.0), MILESTONES, LRS))
 
 
-def synthetic_batch(batch: int, device, seed: int = 0, n_frames: int = 640, n_freq: int = 200, n_classes: int = 12):
+def synthetic_batch(batch: int, device, seed: int = 0, n_frames: int = 640, n_freq: int = 200, n_classes: int = 12,
+                    n_channels: int = 7):
     """TNSSE2021-shaped synthetic training chunks: features N(0,1) on the 4 spectrogram
-    channels and U(-1,1)*Bernoulli(0.25) on the 3 spatial channels; SED Bernoulli(0.05); DOA unit vectors where active."""
+    channels and U(-1,1)*Bernoulli(0.25) on the n_channels - 4 spatial channels (3 for SALSA and IV, 6 for GCC; n_freq 128
+    for the mel types); SED Bernoulli(0.05); DOA unit vectors where active."""
     g = torch.Generator(device='cpu').manual_seed(seed)
-    x = torch.empty(batch, 7, n_frames, n_freq)
+    x = torch.empty(batch, n_channels, n_frames, n_freq)
     x[:, :4] = torch.randn(batch, 4, n_frames, n_freq, generator=g)
-    x[:, 4:] = (torch.rand(batch, 3, n_frames, n_freq, generator=g) * 2 - 1) * \
-        (torch.rand(batch, 3, n_frames, n_freq, generator=g) < 0.25)
+    x[:, 4:] = (torch.rand(batch, n_channels - 4, n_frames, n_freq, generator=g) * 2 - 1) * \
+        (torch.rand(batch, n_channels - 4, n_frames, n_freq, generator=g) < 0.25)
     n_lab = n_frames // 8                                          # 80 feature frames/s -> 10 labels/s
     sed = (torch.rand(batch, n_lab, n_classes, generator=g) < 0.05).float()
     v = torch.randn(batch, n_lab, 3, n_classes, generator=g)
@@ -41,7 +43,8 @@ def synthetic_batch(batch: int, device, seed: int = 0, n_frames: int = 640, n_fr
 
 class Trainer:
     def __init__(self, device, amp_dtype=torch.bfloat16, ddp: bool = None, total_steps: int = 1313 * 50,
-                 bf16_grad_allreduce: bool = True, seed: int = 2021):
+                 bf16_grad_allreduce: bool = True, seed: int = 2021, n_input_channels: int = 7):
+        """n_input_channels: 7 (SALSA, melspeciv, linspeciv) or 10 (melspecgcc, linspecgcc), experiments/configs/seld.yml."""
         torch.manual_seed(seed)
         self.device = torch.device(device)
         if self.device.type == 'cuda' and os.environ.get('SALSA_MIOPEN_FIND', '0') == '1':
@@ -49,7 +52,7 @@ class Trainer:
         self.amp_dtype = amp_dtype
         self.total_steps = total_steps
         self.step_idx = 0
-        model = SeldCRNN().to(self.device)
+        model = SeldCRNN(n_input_channels=n_input_channels).to(self.device)
         self.channels_last = self.device.type == 'cuda' and os.environ.get('SALSA_CHANNELS_LAST', '1') == '1'
         if self.channels_last:
             model = model.to(memory_format=torch.channels_last)
@@ -88,7 +91,7 @@ class Trainer:
         if not self.channels_last:
             return x
         if (nn_ops.USE_HIP_CONV and self.amp_dtype == torch.bfloat16 and x.dtype == torch.float32 and x.dim() == 4
-                and x.shape[1] <= 8 and nn_ops._planar_rows(x)):
+                and (x.shape[1] <= 8 or (nn_ops.USE_HIP_STEM16 and x.shape[1] <= 16)) and nn_ops._planar_rows(x)):
             return x
         return x.contiguous(memory_format=torch.channels_last)
 

@@ -1071,13 +1071,16 @@ constexpr int STH = 8, SHALO_H = STH + 2; // stem tile: 8 rows x TW pixels, wave
 #ifndef STEM_FWD_WPS
 #define STEM_FWD_WPS 2 // round 5: with (256, 1) the compiler parked the accumulators in 64 AGPRs next to 160 - 208 VGPRs: one (training) / two (inference) waves per SIMD; held to 256 / 2 registers they stay in VGPRs: two / three waves, 277 -> 210 us (training, with the statistics epilogue), 0.361 -> 0.313 ms (inference sub-batch)
 #endif
-template <bool STATS>
+// NG = 2 (9 <= Cin <= 16, the baseline GCC features' 10 channels): a halo pixel holds 16 bf16 channels (32 B), one K step is one
+// tap across all 16 (lanes 0-31 channels 0-7, lanes 32-63 channels 8-15): 9 steps, no padding tap; filter [64][9 taps][16].
+template <bool STATS, int NG = 1>
 __global__ __launch_bounds__(256, STEM_FWD_WPS) void conv3x3_stem_fwd_kernel(const float *__restrict__ x, const unsigned short *__restrict__ wq,
                                                                unsigned short *__restrict__ y, int N, int Cin, int H, int W, long x_batch_stride,
                                                                long x_channel_stride, const float *__restrict__ shift, int relu,
                                                                double *__restrict__ stats_part)
 {
-    __shared__ __attribute__((aligned(16))) unsigned short xs2[2][SHALO_H * HALO_W * 8]; // double-buffered halo tile (round 4)
+    constexpr int PCH = 8 * NG, KSTEPS = NG == 1 ? 5 : 9; // channels per halo pixel, K steps
+    __shared__ __attribute__((aligned(16))) unsigned short xs2[2][SHALO_H * HALO_W * PCH]; // double-buffered halo tile (round 4)
     __shared__ __attribute__((aligned(16))) unsigned short ys[4 * TW * ROW]; // per wave: one output row, [pixel][ROW]
     __shared__ __attribute__((aligned(16))) float shs[64]; // the folded-BatchNorm shift (inference), read from LDS in the epilogue: as
                                                            // global loads inside the tile loop they were 16 DEPENDENT round trips per
@@ -1085,11 +1088,13 @@ __global__ __launch_bounds__(256, STEM_FWD_WPS) void conv3x3_stem_fwd_kernel(con
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int px = lane & 31, khalf = lane >> 5;
     if (tid < 64) shs[tid] = shift ? shift[tid] : 0.f; // (the first barrier of the tile loop publishes it)
-    bf16x8 af[5][2]; // [K step][co half]: filter row co = 32*mt + (lane&31), tap 2*step + khalf, its 8 channels
+    bf16x8 af[KSTEPS][2]; // [K step][co half]: filter row co = 32*mt + (lane&31), tap 2*step + khalf, its 8 channels (NG = 2: tap step, channels 8*khalf..)
 #pragma unroll
-    for (int ks = 0; ks < 5; ks++)
+    for (int ks = 0; ks < KSTEPS; ks++)
 #pragma unroll
-        for (int mt = 0; mt < 2; mt++) af[ks][mt] = *(const bf16x8 *)(wq + ((mt * 32 + px) * 10 + 2 * ks + khalf) * 8);
+        for (int mt = 0; mt < 2; mt++)
+            af[ks][mt] = NG == 1 ? *(const bf16x8 *)(wq + ((mt * 32 + px) * 10 + 2 * ks + khalf) * 8)
+                                 : *(const bf16x8 *)(wq + ((mt * 32 + px) * 9 + ks) * 16 + 8 * khalf);
     const int tiles_w = (W + TW - 1) / TW, tiles_h = (H + STH - 1) / STH;
     const long n_tiles = (long)N * tiles_h * tiles_w;
     float rs[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, rq[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -1103,7 +1108,7 @@ __global__ __launch_bounds__(256, STEM_FWD_WPS) void conv3x3_stem_fwd_kernel(con
     // memory queue (the loads themselves, one tile old, and the stores of the tile before that) has long retired, so the
     // compiler's vmcnt(0) in front of the conversion costs nothing and no wait ever follows a store.
     constexpr int SPF = (SHALO_H * HALO_W + 255) / 256; // halo pixels per thread
-    float pv[SPF][8];
+    float pv[SPF][PCH];
     bool pin[SPF];
     // Round 5 (as in the weight gradient below, where the same three changes took 14 % off an issue-bound kernel): tile coordinates
     // from cursors stepped by the grid size with carries instead of 64-bit divisions (two decodes per tile), every address = a
@@ -1135,22 +1140,38 @@ __global__ __launch_bounds__(256, STEM_FWD_WPS) void conv3x3_stem_fwd_kernel(con
             pin[j] = (p < SHALO_H * HALO_W) & ((unsigned)h < (unsigned)H) & ((unsigned)wcol < (unsigned)W);
             const unsigned o = pin[j] ? (unsigned)(h * W + wcol) : 0u;
 #pragma unroll
-            for (int c = 0; c < 8; c++) { // unconditional (valid) loads.  NOT `c < Cin ? c * stride : 0`: the compiler then re-used the
+            for (int c = 0; c < PCH; c++) { // unconditional (valid) loads.  NOT `c < Cin ? c * stride : 0`: the compiler then re-used the
                 const int cc = c < Cin ? c : Cin - 1; // c = 0 load for the planes beyond Cin behind a `s_waitcnt vmcnt(0)` -- a full
                 pv[j][c] = xn[o + (unsigned)(cc * xcs32)]; // memory round trip in the middle of every prefetch
             }
         }
     };
-    auto convert = [&](int buf) { // registers -> bf16 [pixel][8 channels] in LDS: one 16-byte write packs a pixel
+    auto convert = [&](int buf) { // registers -> bf16 [pixel][PCH channels] in LDS: one 16-byte write per 8 channels of a pixel
 #pragma unroll
         for (int j = 0; j < SPF; j++) {
             const int p = tid + j * 256;
-            uint4 pk;
-            pk.x = pack_bf16((pin[j] && 0 < Cin) ? pv[j][0] : 0.f, (pin[j] && 1 < Cin) ? pv[j][1] : 0.f);
-            pk.y = pack_bf16((pin[j] && 2 < Cin) ? pv[j][2] : 0.f, (pin[j] && 3 < Cin) ? pv[j][3] : 0.f);
-            pk.z = pack_bf16((pin[j] && 4 < Cin) ? pv[j][4] : 0.f, (pin[j] && 5 < Cin) ? pv[j][5] : 0.f);
-            pk.w = pack_bf16((pin[j] && 6 < Cin) ? pv[j][6] : 0.f, (pin[j] && 7 < Cin) ? pv[j][7] : 0.f);
-            if (p < SHALO_H * HALO_W) *(uint4 *)(xs2[buf] + p * 8) = pk;
+            if constexpr (NG == 1) {
+                uint4 pk;
+                pk.x = pack_bf16((pin[j] && 0 < Cin) ? pv[j][0] : 0.f, (pin[j] && 1 < Cin) ? pv[j][1] : 0.f);
+                pk.y = pack_bf16((pin[j] && 2 < Cin) ? pv[j][2] : 0.f, (pin[j] && 3 < Cin) ? pv[j][3] : 0.f);
+                pk.z = pack_bf16((pin[j] && 4 < Cin) ? pv[j][4] : 0.f, (pin[j] && 5 < Cin) ? pv[j][5] : 0.f);
+                pk.w = pack_bf16((pin[j] && 6 < Cin) ? pv[j][6] : 0.f, (pin[j] && 7 < Cin) ? pv[j][7] : 0.f);
+                if (p < SHALO_H * HALO_W) *(uint4 *)(xs2[buf] + p * 8) = pk;
+            } else {
+                uint4 pk[NG];
+#pragma unroll
+                for (int g = 0; g < NG; g++) {
+                    const int c0 = 8 * g;
+                    pk[g].x = pack_bf16((pin[j] && c0 + 0 < Cin) ? pv[j][c0 + 0] : 0.f, (pin[j] && c0 + 1 < Cin) ? pv[j][c0 + 1] : 0.f);
+                    pk[g].y = pack_bf16((pin[j] && c0 + 2 < Cin) ? pv[j][c0 + 2] : 0.f, (pin[j] && c0 + 3 < Cin) ? pv[j][c0 + 3] : 0.f);
+                    pk[g].z = pack_bf16((pin[j] && c0 + 4 < Cin) ? pv[j][c0 + 4] : 0.f, (pin[j] && c0 + 5 < Cin) ? pv[j][c0 + 5] : 0.f);
+                    pk[g].w = pack_bf16((pin[j] && c0 + 6 < Cin) ? pv[j][c0 + 6] : 0.f, (pin[j] && c0 + 7 < Cin) ? pv[j][c0 + 7] : 0.f);
+                }
+                if (p < SHALO_H * HALO_W) {
+#pragma unroll
+                    for (int g = 0; g < NG; g++) *(uint4 *)(xs2[buf] + p * PCH + 8 * g) = pk[g];
+                }
+            }
         }
     };
 #define STEM_BARRIER()                                       \
@@ -1180,12 +1201,12 @@ __global__ __launch_bounds__(256, STEM_FWD_WPS) void conv3x3_stem_fwd_kernel(con
 #pragma unroll
         for (int mt = 0; mt < 2; mt++) acc[rr][mt] = f32x16{};
 #pragma unroll
-    for (int ks = 0; ks < 5; ks++) {
-        const int tap = 2 * ks + khalf < 9 ? 2 * ks + khalf : 8; // tap 9: any address, its weights are zero
+    for (int ks = 0; ks < KSTEPS; ks++) {
+        const int tap = NG == 2 ? ks : 2 * ks + khalf < 9 ? 2 * ks + khalf : 8; // tap 9: any address, its weights are zero
         const int r = tap / 3, sx = tap - 3 * r;
 #pragma unroll
         for (int rr = 0; rr < 2; rr++) {
-            const bf16x8 b = *(const bf16x8 *)(xs + ((wv * 2 + rr + r) * HALO_W + px + sx) * 8);
+            const bf16x8 b = *(const bf16x8 *)(xs + ((wv * 2 + rr + r) * HALO_W + px + sx) * PCH + (NG == 2 ? 8 * khalf : 0));
 #pragma unroll
             for (int mt = 0; mt < 2; mt++) acc[rr][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks][mt], b, acc[rr][mt], 0, 0, 0);
         }
@@ -1296,33 +1317,34 @@ extern "C" int salsa_nn_conv3x3_stem_stats_blocks(int64_t N, int H, int W)
 extern "C" int salsa_nn_conv3x3_stem_stats(const float *x, int64_t x_batch_stride, int64_t x_channel_stride, const void *wq, void *y,
                                            double *stats_part, int64_t N, int Cin, int H, int W, void *hip_stream)
 {
-    if (!x || !wq || !y || !stats_part || N <= 0 || Cin <= 0 || Cin > 8 || H <= 0 || W <= 0 || N * H * W >= INT32_MAX / CH ||
+    if (!x || !wq || !y || !stats_part || N <= 0 || Cin <= 0 || Cin > 16 || H <= 0 || W <= 0 || N * H * W >= INT32_MAX / CH ||
         x_channel_stride < (int64_t)H * W || x_batch_stride < x_channel_stride * Cin ||
         x_channel_stride * Cin >= INT32_MAX /* 32-bit element offsets inside an image */)
         return -1;
     const unsigned nb = (unsigned)salsa_nn_conv3x3_stem_stats_blocks(N, H, W);
-    hipLaunchKernelGGL(conv3x3_stem_fwd_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)hip_stream, x, (const unsigned short *)wq,
-                       (unsigned short *)y, (int)N, Cin, H, W, (long)x_batch_stride, (long)x_channel_stride, (const float *)nullptr, 0,
-                       stats_part);
+    hipLaunchKernelGGL((Cin <= 8 ? conv3x3_stem_fwd_kernel<true> : conv3x3_stem_fwd_kernel<true, 2>), dim3(nb), dim3(256), 0,
+                       (hipStream_t)hip_stream, x, (const unsigned short *)wq, (unsigned short *)y, (int)N, Cin, H, W, (long)x_batch_stride,
+                       (long)x_channel_stride, (const float *)nullptr, 0, stats_part);
     return hipGetLastError() == hipSuccess ? 0 : -6;
 }
 
-// x float32 planar [N][Cin][H][W] (Cin <= 8; rows contiguous, batch / channel strides in elements, so a time-cropped view of
-// the extractor's output needs no copy), wq bf16 [64][10][8] = w[co][tap][ci] zero-padded (tap 9 and ci >= Cin zero),
+// x float32 planar [N][Cin][H][W] (Cin <= 16; rows contiguous, batch / channel strides in elements, so a time-cropped view of
+// the extractor's output needs no copy), wq bf16 [64][10][8] = w[co][tap][ci] zero-padded (tap 9 and ci >= Cin zero) for
+// Cin <= 8, [64][9][16] = w[co][tap][ci] (ci >= Cin zero) for 9 <= Cin <= 16;
 // y bf16 channels-last [N][H][W][64]; shift NULL: plain convolution, else y = [relu](conv + shift[co]) (folded BatchNorm)
 extern "C" int salsa_nn_conv3x3_stem(const float *x, int64_t x_batch_stride, int64_t x_channel_stride, const void *wq,
                                      const float *shift, void *y, int relu, int64_t N, int Cin, int H, int W, void *hip_stream)
 {
-    if (!x || !wq || !y || N <= 0 || Cin <= 0 || Cin > 8 || H <= 0 || W <= 0 || N * H * W >= INT32_MAX / CH ||
+    if (!x || !wq || !y || N <= 0 || Cin <= 0 || Cin > 16 || H <= 0 || W <= 0 || N * H * W >= INT32_MAX / CH ||
         x_channel_stride < (int64_t)H * W || x_batch_stride < x_channel_stride * Cin ||
         x_channel_stride * Cin >= INT32_MAX /* 32-bit element offsets inside an image */)
         return -1;
     const long tiles = (long)N * ((H + STH - 1) / STH) * ((W + TW - 1) / TW);
     if (tiles >= INT32_MAX) return -1;
     const unsigned nb = (unsigned)(tiles >= STEM_FWD_GRID ? STEM_FWD_GRID : tiles); // persistent: six workgroups per CU
-    hipLaunchKernelGGL(conv3x3_stem_fwd_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)hip_stream, x,
-                       (const unsigned short *)wq, (unsigned short *)y, (int)N, Cin, H, W, (long)x_batch_stride, (long)x_channel_stride,
-                       shift, relu, (double *)nullptr);
+    hipLaunchKernelGGL((Cin <= 8 ? conv3x3_stem_fwd_kernel<false> : conv3x3_stem_fwd_kernel<false, 2>), dim3(nb), dim3(256), 0,
+                       (hipStream_t)hip_stream, x, (const unsigned short *)wq, (unsigned short *)y, (int)N, Cin, H, W, (long)x_batch_stride,
+                       (long)x_channel_stride, shift, relu, (double *)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -6;
 }
 
@@ -1634,22 +1656,28 @@ extern "C" int salsa_nn_conv3x3_c64_wrw_xform(const void *x1, const void *dy, fl
 // aligned 16-byte read.  33.5 GFLOP against 0.64 GB of input: HBM-bound; a wave owns one 32 x 32 block of dW.
 namespace {
 
+// CB = column blocks of 64: 1 for Cin <= 7 (the SALSA path), 2 for 8 <= Cin <= 14 (the baseline GCC features' 10 channels: 90 of
+// 128 columns).  With CB = 2 a wave owns two 32 x 32 blocks of dW (columns 32 nb + 64 cb) that share every A fragment.
 constexpr int SW_XROW = 40;                               // bf16 per (ci, halo row, shift) row: 32 + pad (80-byte pitch)
-constexpr int SW_XS = 8 * WHALO_H * 3 * SW_XROW;          // 8 channel planes (those >= Cin stay zero)
-constexpr int SW_XPF = (7 * WHALO_H * WHALO_W + 255) / 256; // float32 halo elements per thread
+template <int CB> constexpr int SW_XS = 8 * CB * WHALO_H * 3 * SW_XROW; // 8 CB channel planes (those >= Cin stay zero)
+template <int CB> constexpr int SW_XPF = (7 * CB * WHALO_H * WHALO_W + 255) / 256; // float32 halo elements per thread
 
-template <int KS>
-__device__ __forceinline__ void stem_wrw_steps(f32x16 &acc, const unsigned ga, const unsigned xa)
+template <int CB, int KS>
+__device__ __forceinline__ void stem_wrw_steps(f32x16 (&acc)[CB], const unsigned ga, const unsigned (&xa)[CB])
 {
     if constexpr (KS < 8) {
         constexpr int rr = KS >> 1, hw = KS & 1;
         tr_frag fa;
-        bf16x8 b;
+        bf16x8 b[CB];
         LDS_TR_ISSUE(fa, ga, 2 * ((rr * WT_W + 16 * hw) * ROW));
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(b) : "v"(xa), "n"(2 * (rr * 3 * SW_XROW + 16 * hw)));
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa.lo), "+v"(fa.hi), "+v"(b));
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_value(fa), b, acc, 0, 0, 0);
-        stem_wrw_steps<KS + 1>(acc, ga, xa);
+#pragma unroll
+        for (int cb = 0; cb < CB; cb++)
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(b[cb]) : "v"(xa[cb]), "n"(2 * (rr * 3 * SW_XROW + 16 * hw)));
+        if constexpr (CB == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa.lo), "+v"(fa.hi), "+v"(b[0]));
+        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa.lo), "+v"(fa.hi), "+v"(b[0]), "+v"(b[1]));
+#pragma unroll
+        for (int cb = 0; cb < CB; cb++) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_value(fa), b[cb], acc[cb], 0, 0, 0);
+        stem_wrw_steps<CB, KS + 1>(acc, ga, xa);
     }
 }
 
@@ -1659,36 +1687,46 @@ __device__ __forceinline__ void stem_wrw_steps(f32x16 &acc, const unsigned ga, c
 // S0 must leave out the OUTPUT pixels of a tile that hang over the image's right / bottom edge by itself (G and Xh see g = xh = 0
 // there, but those pixels' input patches next to the edge are real): om[hw][q] = the pair of ones for pixel pair q of the lane's eight
 // pixels in column half hw (zero where the pixel is outside), rows outside (rr >= h_left) are dropped per row.
-template <int KS>
-__device__ __forceinline__ void stem_wrw_steps2(f32x16 &acc_g, f32x16 &acc_x, float &s0, float &t, const unsigned ga, const unsigned ga2,
-                                                const unsigned xa, const unsigned (&om)[2][4], const int h_left)
+template <int CB, int KS>
+__device__ __forceinline__ void stem_wrw_steps2(f32x16 (&acc_g)[CB], f32x16 (&acc_x)[CB], float (&s0)[CB], float (&t)[CB], const unsigned ga,
+                                                const unsigned ga2, const unsigned (&xa)[CB], const unsigned (&om)[2][4], const int h_left)
 {
     if constexpr (KS < 8) {
         constexpr int rr = KS >> 1, hw = KS & 1;
         tr_frag fa, fx;
         typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-        u32x4_t b;
+        u32x4_t b[CB];
         LDS_TR_ISSUE(fa, ga, 2 * ((rr * WT_W + 16 * hw) * ROW));
         LDS_TR_ISSUE(fx, ga2, 2 * ((rr * WT_W + 16 * hw) * ROW));
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(b) : "v"(xa), "n"(2 * (rr * 3 * SW_XROW + 16 * hw)));
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa.lo), "+v"(fa.hi), "+v"(fx.lo), "+v"(fx.hi), "+v"(b));
-        const bf16x8 bv = __builtin_bit_cast(bf16x8, b);
-        acc_g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_value(fa), bv, acc_g, 0, 0, 0);
-        acc_x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_value(fx), bv, acc_x, 0, 0, 0);
+#pragma unroll
+        for (int cb = 0; cb < CB; cb++)
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(b[cb]) : "v"(xa[cb]), "n"(2 * (rr * 3 * SW_XROW + 16 * hw)));
+        if constexpr (CB == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa.lo), "+v"(fa.hi), "+v"(fx.lo), "+v"(fx.hi), "+v"(b[0]));
+        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa.lo), "+v"(fa.hi), "+v"(fx.lo), "+v"(fx.hi), "+v"(b[0]), "+v"(b[1]));
+#pragma unroll
+        for (int cb = 0; cb < CB; cb++) {
+            const bf16x8 bv = __builtin_bit_cast(bf16x8, b[cb]);
+            acc_g[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_value(fa), bv, acc_g[cb], 0, 0, 0);
+            acc_x[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_value(fx), bv, acc_x[cb], 0, 0, 0);
+        }
         // (one asm statement with its own trailing wait states: a dot product's result needs them before an ordinary vector
         // instruction may read it, and the compiler's hazard recognizer cannot see into asm statements -- four separate ones let the
         // add below read t too early; the builtin form was worse: the compiler then read the fragment's registers after re-using them)
-        if (hw == 0) t = 0.f;
-        asm volatile("v_dot2_f32_bf16 %0, %1, %5, %0\n\tv_dot2_f32_bf16 %0, %2, %6, %0\n\tv_dot2_f32_bf16 %0, %3, %7, %0\n\t"
-                     "v_dot2_f32_bf16 %0, %4, %8, %0\n\ts_nop 4"
-                     : "+v"(t)
-                     : "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w), "v"(om[hw][0]), "v"(om[hw][1]), "v"(om[hw][2]), "v"(om[hw][3]));
-        if (hw == 1) s0 += rr < h_left ? t : 0.f;
-        stem_wrw_steps2<KS + 1>(acc_g, acc_x, s0, t, ga, ga2, xa, om, h_left);
+#pragma unroll
+        for (int cb = 0; cb < CB; cb++) {
+            if (hw == 0) t[cb] = 0.f;
+            asm volatile("v_dot2_f32_bf16 %0, %1, %5, %0\n\tv_dot2_f32_bf16 %0, %2, %6, %0\n\tv_dot2_f32_bf16 %0, %3, %7, %0\n\t"
+                         "v_dot2_f32_bf16 %0, %4, %8, %0\n\ts_nop 4"
+                         : "+v"(t[cb])
+                         : "v"(b[cb].x), "v"(b[cb].y), "v"(b[cb].z), "v"(b[cb].w), "v"(om[hw][0]), "v"(om[hw][1]), "v"(om[hw][2]), "v"(om[hw][3]));
+            if (hw == 1) s0[cb] += rr < h_left ? t[cb] : 0.f;
+        }
+        stem_wrw_steps2<CB, KS + 1>(acc_g, acc_x, s0, t, ga, ga2, xa, om, h_left);
     }
 }
 struct StemBnf { const float *mean, *invstd, *gamma, *beta; }; // MODE 2: the forward's statistics and the affine parameters [64]
-constexpr int SW_SLAB = 2 * 64 * 64 + 3 * 64; // MODE 2: a workgroup's partial sums: G[64][64] (column 63 = dbeta), Xh[64][64], S0[2][64], dgamma[64]
+// MODE 2: a workgroup's partial sums: G[64][64 CB] (last column = dbeta), Xh[64][64 CB], S0[2][64 CB], dgamma[64]
+template <int CB> constexpr int SW_SLAB = 2 * 64 * 64 * CB + 2 * 64 * CB + 64;
 
 // BN: dy is not the gradient of the convolution's output but of the BatchNorm (+ ReLU) output behind it, and x1 that
 // BatchNorm's input (= this convolution's output): the tile's dx = a (g masked - b - (x1 - mean) k) -- the BatchNorm backward's
@@ -1704,11 +1742,12 @@ constexpr int SW_SLAB = 2 * 64 * 64 + 3 * 64; // MODE 2: a workgroup's partial s
 //     dW[co][c] = a[co] (G[co][c] - b[co] S0[c] - k'[co] Xh[co][c]),   a = gamma invstd.
 // The salsa_nn_bn_bwd(dx = NULL) launch (a second read of the 524-MB g and x1, ~145 us) disappears; the operands are g (exact in
 // bf16) and bf16(xh) where MODE 1 rounds dx to bf16: the same order of rounding error.
-template <int MODE>
+// CB = 2, MODE 2 holds four accumulator tiles per wave and the doubled halo loads: bound to one wave per SIMD (512 registers).
+template <int MODE, int CB = 1>
 #ifndef STEM_WRW_WPS
 #define STEM_WRW_WPS 1
 #endif
-__global__ __launch_bounds__(256, MODE == 2 ? 2 : STEM_WRW_WPS) void conv3x3_stem_wrw_kernel(const float *__restrict__ x, long xbs, long xcs,
+__global__ __launch_bounds__(256, MODE == 2 && CB == 1 ? 2 : STEM_WRW_WPS) void conv3x3_stem_wrw_kernel(const float *__restrict__ x, long xbs, long xcs,
                                                                const unsigned short *__restrict__ dy, float *__restrict__ dw,
                                                                int N, int Cin, int H, int W,
                                                                const unsigned short *__restrict__ x1, const float *__restrict__ coef,
@@ -1719,7 +1758,7 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : STEM_WRW_WPS) void conv3x3_ste
     // (8 spare elements in front: the halo conversion stores every element into all three shifted copies UNCONDITIONALLY -- columns
     // -2, -1, 32, 33 land in the 8 padding columns of this row or of the one before, which nothing reads; behind `0 <= col < 32`
     // each of the 18 stores was an EXEC-mask region of its own)
-    __shared__ __attribute__((aligned(16))) unsigned short xs_raw[SW_XS + 8];
+    __shared__ __attribute__((aligned(16))) unsigned short xs_raw[SW_XS<CB> + 8];
     unsigned short *const xs = xs_raw + 8;
     __shared__ __attribute__((aligned(16))) unsigned short gl[WT_H * WT_W * ROW];
     __shared__ __attribute__((aligned(16))) unsigned short gl2[MODE == 2 ? WT_H * WT_W * ROW : 8]; // MODE 2: the xh tile
@@ -1728,18 +1767,29 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : STEM_WRW_WPS) void conv3x3_ste
     const int mb = wv & 1, nb = wv >> 1; // this wave: co 32*mb.., columns 32*nb..
     const int i16 = lane & 15, cb = (lane >> 4) & 1, kh = lane >> 5;
     const unsigned a_lane = 2u * (unsigned)((8 * kh + (i16 >> 2)) * ROW + 32 * mb + 16 * cb + 4 * (i16 & 3));
-    const int c = 32 * nb + (lane & 31), ci = c / 9, tap = c - 9 * ci; // column 63: ci = 7, a zero plane (Cin <= 7)
-    const unsigned b_lane = 2u * (unsigned)(((ci * WHALO_H + tap / 3) * 3 + tap % 3) * SW_XROW + 8 * kh);
+    constexpr int NCOL = 64 * CB, ONES = (NCOL - 1) / 9; // columns; MODE 2: the spare plane of ones (7 / 14)
+    int c[CB];
+    unsigned xa[CB];
     const unsigned ga = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned short *)gl + a_lane;
-    const unsigned xa = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned short *)xs + b_lane;
-    const unsigned ga2 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned short *)gl2 + a_lane;
-    for (int i = tid; i < SW_XS / 8; i += 256) ((uint4 *)xs)[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (MODE == 2) { // the spare eighth input plane (column 63 = its tap 0) holds ONES: G[co][63] = sum_p g[p][co] = dbeta
-        __syncthreads();
-        for (int i = tid; i < WHALO_H * 3 * SW_XROW; i += 256) xs[7 * WHALO_H * 3 * SW_XROW + i] = 0x3F80;
+#pragma unroll
+    for (int cb = 0; cb < CB; cb++) { // last column: ci = ONES, a zero plane (Cin <= 7 / 14)
+        c[cb] = 32 * nb + 64 * cb + (lane & 31);
+        const int ci = c[cb] / 9, tap = c[cb] - 9 * ci;
+        const unsigned b_lane = 2u * (unsigned)(((ci * WHALO_H + tap / 3) * 3 + tap % 3) * SW_XROW + 8 * kh);
+        xa[cb] = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned short *)xs + b_lane;
     }
-    f32x16 acc = f32x16{}, acc_x = f32x16{};
-    float s0 = 0.f;  // MODE 2: this lane's share of S0[c] (its half of the k-steps' pixels)
+    const unsigned ga2 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned short *)gl2 + a_lane;
+    for (int i = tid; i < SW_XS<CB> / 8; i += 256) ((uint4 *)xs)[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (MODE == 2) { // the spare input plane ONES holds ones: G[co][NCOL - 1] = sum_p g[p][co] = dbeta
+        __syncthreads();
+        for (int i = tid; i < WHALO_H * 3 * SW_XROW; i += 256) xs[ONES * WHALO_H * 3 * SW_XROW + i] = 0x3F80;
+    }
+    f32x16 acc[CB], acc_x[CB];
+#pragma unroll
+    for (int cb = 0; cb < CB; cb++) { acc[cb] = f32x16{}; acc_x[cb] = f32x16{}; }
+    float s0[CB]; // MODE 2: this lane's share of S0[c] (its half of the k-steps' pixels)
+#pragma unroll
+    for (int cb = 0; cb < CB; cb++) s0[cb] = 0.f;
     float s_dg[8];   // MODE 2: this thread's share of dgamma (its pieces always cover the same 8 channels)
 #pragma unroll
     for (int e = 0; e < 8; e++) s_dg[e] = 0.f;
@@ -1754,7 +1804,7 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : STEM_WRW_WPS) void conv3x3_ste
     // occupancy.  Every load is unconditional (a clamped in-bounds address; validity bits applied at conversion), so that nothing
     // but loads sits between the loads of a set.
     struct TileRegs {
-        float px[SW_XPF];
+        float px[SW_XPF<CB>];
         uint4 pg[GP], pq[BN ? GP : 1];
         unsigned okx, okg; // validity bits of the halo elements / the tile pieces
         int th, tw;
@@ -1792,7 +1842,7 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : STEM_WRW_WPS) void conv3x3_ste
         const unsigned short *gb = dy + pix0, *qb = BN ? x1 + pix0 : nullptr;
         const int xcs32 = (int)xcs;
 #pragma unroll
-        for (int j = 0; j < SW_XPF; j++) {
+        for (int j = 0; j < SW_XPF<CB>; j++) {
             const int i = tid + j * 256, cc = i / (WHALO_H * WHALO_W), rr = i - cc * (WHALO_H * WHALO_W);
             const int hh = rr / WHALO_W, ww = rr - hh * WHALO_W;
             const int h = h0 + hh - 1, wc = w0 + ww - 1;
@@ -1867,7 +1917,7 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : STEM_WRW_WPS) void conv3x3_ste
     // registers -> LDS: the halo as three column-shifted bf16 copies per (ci, row); the (g [, x1]) tile as dx rows
     auto convert = [&](const TileRegs &r) {
 #pragma unroll
-        for (int j = 0; j < SW_XPF; j++) {
+        for (int j = 0; j < SW_XPF<CB>; j++) {
             const int i = tid + j * 256, cc = i / (WHALO_H * WHALO_W), rr = i - cc * (WHALO_H * WHALO_W);
             const int hh = rr / WHALO_W, ww = rr - hh * WHALO_W;
             if (i < n_x) {
@@ -1910,9 +1960,11 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : STEM_WRW_WPS) void conv3x3_ste
 #pragma unroll
                 for (int q = 0; q < 4; q++) om[hw][q] = (2 * q < nv ? 0x3F80u : 0u) | (2 * q + 1 < nv ? 0x3F800000u : 0u);
             }
-            float t = 0.f;
-            stem_wrw_steps2<0>(acc, acc_x, s0, t, ga, ga2, xa, om, h_left);
-        } else stem_wrw_steps<0>(acc, ga, xa);
+            float t[CB];
+#pragma unroll
+            for (int cb = 0; cb < CB; cb++) t[cb] = 0.f;
+            stem_wrw_steps2<CB, 0>(acc, acc_x, s0, t, ga, ga2, xa, om, h_left);
+        } else stem_wrw_steps<CB, 0>(acc, ga, xa);
     };
     TileRegs ra, rb;
     long tile = blockIdx.x; // (< n_tiles: the launch has at most one workgroup per tile)
@@ -1948,14 +2000,17 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : STEM_WRW_WPS) void conv3x3_ste
         multiply(ra.th, ra.tw);
     }
     if (MODE == 2) { // this workgroup's slab: G (column 63: dbeta), Xh, S0 (the two lane halves), dgamma
-        float *slab = part + (long)blockIdx.x * SW_SLAB;
+        float *slab = part + (long)blockIdx.x * SW_SLAB<CB>;
 #pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            const int co = 32 * mb + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-            slab[co * 64 + c] = acc[reg];
-            slab[64 * 64 + co * 64 + c] = acc_x[reg];
+        for (int cb = 0; cb < CB; cb++) {
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) {
+                const int co = 32 * mb + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+                slab[co * NCOL + c[cb]] = acc[cb][reg];
+                slab[64 * NCOL + co * NCOL + c[cb]] = acc_x[cb][reg];
+            }
+            if (mb == 0) slab[2 * 64 * NCOL + NCOL * kh + c[cb]] = s0[cb];
         }
-        if (mb == 0) slab[2 * 64 * 64 + 64 * kh + c] = s0;
         // dgamma: the 32 threads that share a channel group (tid & 7) through LDS, in a fixed order
         raw_barrier(); // (the last multiply's reads of gl are done)
         float *red = (float *)gl; // [8 values][256 threads]
@@ -1966,28 +2021,40 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : STEM_WRW_WPS) void conv3x3_ste
             const int grp = tid & 7, v = tid >> 3;
             float t = 0.f;
             for (int q = 0; q < 32; q++) t += red[v * 256 + grp + 8 * q];
-            slab[2 * 64 * 64 + 128 + grp * 8 + v] = t;
+            slab[2 * 64 * NCOL + 2 * NCOL + grp * 8 + v] = t;
         }
         return;
     }
     // D[m = co][n = column]: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-    if (c < Cin * 9 && (long)blockIdx.x < n_tiles) {
+    if constexpr (CB == 1) {
+        if (c[0] < Cin * 9 && (long)blockIdx.x < n_tiles) {
 #pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            const int co = 32 * mb + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-            salsa_nn_accumulate(dw, part, 64L * Cin * 9, (int)blockIdx.x, (long)co * (Cin * 9) + c, acc[reg]);
+            for (int reg = 0; reg < 16; reg++) {
+                const int co = 32 * mb + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+                salsa_nn_accumulate(dw, part, 64L * Cin * 9, (int)blockIdx.x, (long)co * (Cin * 9) + c[0], acc[0][reg]);
+            }
         }
+        return;
     }
+#pragma unroll
+    for (int cb = 0; cb < CB; cb++)
+        if (c[cb] < Cin * 9 && (long)blockIdx.x < n_tiles) {
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) {
+                const int co = 32 * mb + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+                salsa_nn_accumulate(dw, part, 64L * Cin * 9, (int)blockIdx.x, (long)co * (Cin * 9) + c[cb], acc[cb][reg]);
+            }
+        }
 }
 
 } // namespace
 
-// dw: float32 [64 co][Cin][3][3] contiguous, ADDED to (zero it first); x float32 planar [N][Cin <= 7][H][W] (strides in elements,
+// dw: float32 [64 co][Cin][3][3] contiguous, ADDED to (zero it first); x float32 planar [N][Cin <= 14][H][W] (strides in elements,
 // rows contiguous), dy bf16 channels-last [N][H][W][64]
 extern "C" int salsa_nn_conv3x3_stem_wrw(const float *x, int64_t x_batch_stride, int64_t x_channel_stride, const void *dy, float *dw,
                                          int64_t N, int Cin, int H, int W, void *hip_stream)
 {
-    if (!x || !dy || !dw || N <= 0 || Cin <= 0 || Cin > 7 || H <= 0 || W <= 0 || N * H * W >= INT32_MAX / CH ||
+    if (!x || !dy || !dw || N <= 0 || Cin <= 0 || Cin > 14 || H <= 0 || W <= 0 || N * H * W >= INT32_MAX / CH ||
         x_channel_stride < (int64_t)H * W || x_batch_stride < x_channel_stride * Cin ||
         x_channel_stride * Cin >= INT32_MAX /* 32-bit element offsets inside an image */)
         return -1;
@@ -1996,7 +2063,7 @@ extern "C" int salsa_nn_conv3x3_stem_wrw(const float *x, int64_t x_batch_stride,
     int rc = 0;
     float *part = salsa_nn_det_begin((int)nb, 64L * Cin * 9, (hipStream_t)hip_stream, &rc);
     if (rc) return rc;
-    hipLaunchKernelGGL(conv3x3_stem_wrw_kernel<0>, dim3(nb), dim3(256), 0, (hipStream_t)hip_stream, x, (long)x_batch_stride,
+    hipLaunchKernelGGL((Cin <= 7 ? conv3x3_stem_wrw_kernel<0> : conv3x3_stem_wrw_kernel<0, 2>), dim3(nb), dim3(256), 0, (hipStream_t)hip_stream, x, (long)x_batch_stride,
                        (long)x_channel_stride, (const unsigned short *)dy, dw, (int)N, Cin, H, W, (const unsigned short *)nullptr,
                        (const float *)nullptr, 0, part, StemBnf{});
     if (part) return salsa_nn_det_finish(part, (int)nb, 64L * Cin * 9, dw, (hipStream_t)hip_stream);
@@ -2010,28 +2077,31 @@ namespace {
 // MODE 2's second launch: workgroup co adds the slabs' partial sums of its output channel in float64 -- thread (column k = tid & 63,
 // slab lane tid >> 6) takes every 16th slab in ascending order, lane 0 then adds the 16 lanes' sums in lane order: a fixed order,
 // bit-reproducible -- and combines them: dW[co][k] += a (G - b S0[k] - k' Xh), dbeta = sum g, dgamma = sum g xh.
+// CB = 2: 128 columns, thread (k = tid & 127, slab lane tid >> 7), eight slab lanes.
+template <int CB = 1>
 __global__ __launch_bounds__(1024) void stem_wrw_bnf_finalize_kernel(const float *__restrict__ part, int nslab, double M, int ncol /* Cin * 9 */,
                                                                      const StemBnf bnf, float *__restrict__ dw, float *__restrict__ dgamma,
                                                                      float *__restrict__ dbeta)
 {
+    constexpr int NCOL = 64 * CB, NSL = 1024 / NCOL;
     __shared__ double red[5][1024];
-    const int co = blockIdx.x, k = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int co = blockIdx.x, k = threadIdx.x & (NCOL - 1), sl = threadIdx.x / NCOL;
     double sg = 0.0, sx = 0.0, s0 = 0.0, sb = 0.0, sd = 0.0;
-    for (int b0 = sl; b0 < nslab; b0 += 16 * 4) { // four slabs' loads in flight per thread; the additions keep their order
+    for (int b0 = sl; b0 < nslab; b0 += NSL * 4) { // four slabs' loads in flight per thread; the additions keep their order
         float v[4][5];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const int b = b0 + 16 * u;
-            const float *q = part + (long)(b < nslab ? b : b0) * SW_SLAB;
-            v[u][0] = q[co * 64 + k];
-            v[u][1] = q[64 * 64 + co * 64 + k];
-            v[u][2] = q[2 * 64 * 64 + k] + q[2 * 64 * 64 + 64 + k]; // S0: the two lane halves
-            v[u][3] = q[co * 64 + 63];                              // dbeta: G's column of ones
-            v[u][4] = q[2 * 64 * 64 + 128 + co];
+            const int b = b0 + NSL * u;
+            const float *q = part + (long)(b < nslab ? b : b0) * SW_SLAB<CB>;
+            v[u][0] = q[co * NCOL + k];
+            v[u][1] = q[64 * NCOL + co * NCOL + k];
+            v[u][2] = q[2 * 64 * NCOL + k] + q[2 * 64 * NCOL + NCOL + k]; // S0: the two lane halves
+            v[u][3] = q[co * NCOL + NCOL - 1];                              // dbeta: G's column of ones
+            v[u][4] = q[2 * 64 * NCOL + 2 * NCOL + co];
         }
 #pragma unroll
         for (int u = 0; u < 4; u++)
-            if (b0 + 16 * u < nslab) {
+            if (b0 + NSL * u < nslab) {
                 sg += (double)v[u][0]; sx += (double)v[u][1]; s0 += (double)v[u][2]; sb += (double)v[u][3]; sd += (double)v[u][4];
             }
     }
@@ -2039,9 +2109,9 @@ __global__ __launch_bounds__(1024) void stem_wrw_bnf_finalize_kernel(const float
     __syncthreads();
     if (sl != 0) return;
     double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int q = 0; q < 16; q++)
+    for (int q = 0; q < NSL; q++)
 #pragma unroll
-        for (int a = 0; a < 5; a++) t[a] += red[a][q * 64 + k];
+        for (int a = 0; a < 5; a++) t[a] += red[a][q * NCOL + k];
     const double a = (double)bnf.gamma[co] * (double)bnf.invstd[co], bb = t[3] / M, kk = t[4] / M;
     if (k < ncol) dw[(long)co * ncol + k] += (float)(a * (t[0] - bb * t[2] - kk * t[1]));
     if (k == 0) {
@@ -2056,7 +2126,17 @@ extern "C" size_t salsa_nn_conv3x3_stem_wrw_bnf_ws_bytes(int64_t N, int H, int W
 {
     if (N <= 0 || H <= 0 || W <= 0) return 0;
     const long tiles = (long)N * ((H + WT_H - 1) / WT_H) * ((W + WT_W - 1) / WT_W);
-    return sizeof(float) * SW_SLAB * (size_t)(tiles >= STEM_WRW_BN_GRID ? STEM_WRW_BN_GRID : tiles);
+    return sizeof(float) * SW_SLAB<1> * (size_t)(tiles >= STEM_WRW_BN_GRID ? STEM_WRW_BN_GRID : tiles);
+}
+
+// 8 <= Cin <= 14 (conv3x3_stem_wrw_kernel<2, 2>): one workgroup per CU is resident, so the grid is one round of 256
+constexpr long STEM16_WRW_BN_GRID = 256;
+/* the same for 8 <= Cin <= 14: larger slabs, a grid of its own */
+extern "C" size_t salsa_nn_conv3x3_stem16_wrw_bnf_ws_bytes(int64_t N, int H, int W)
+{
+    if (N <= 0 || H <= 0 || W <= 0) return 0;
+    const long tiles = (long)N * ((H + WT_H - 1) / WT_H) * ((W + WT_W - 1) / WT_W);
+    return sizeof(float) * SW_SLAB<2> * (size_t)(tiles >= STEM16_WRW_BN_GRID ? STEM16_WRW_BN_GRID : tiles);
 }
 
 /* The first layer's weight gradient with the WHOLE BatchNorm (+ ReLU) backward behind it folded in (conv3x3_stem_wrw_kernel<2>): g =
@@ -2068,19 +2148,29 @@ extern "C" int salsa_nn_conv3x3_stem_wrw_bnf(const float *x, int64_t x_batch_str
                                              const float *beta, int relu, float *dw, float *dgamma, float *dbeta, void *ws,
                                              size_t ws_bytes, int64_t N, int Cin, int H, int W, void *hip_stream)
 {
-    if (!x || !g || !x1 || !mean || !invstd || !gamma || !beta || !dw || !dgamma || !dbeta || !ws || N <= 0 || Cin <= 0 || Cin > 7 ||
+    if (!x || !g || !x1 || !mean || !invstd || !gamma || !beta || !dw || !dgamma || !dbeta || !ws || N <= 0 || Cin <= 0 || Cin > 14 ||
         H <= 0 || W <= 0 || N * H * W >= INT32_MAX / CH || x_channel_stride < (int64_t)H * W || x_batch_stride < x_channel_stride * Cin ||
         x_channel_stride * Cin >= INT32_MAX)
         return -1;
-    if (ws_bytes < salsa_nn_conv3x3_stem_wrw_bnf_ws_bytes(N, H, W)) return -5;
     const long tiles = (long)N * ((H + WT_H - 1) / WT_H) * ((W + WT_W - 1) / WT_W);
-    const unsigned nb = (unsigned)(tiles >= STEM_WRW_BN_GRID ? STEM_WRW_BN_GRID : tiles);
     const StemBnf bnf = {mean, invstd, gamma, beta};
     hipStream_t st = (hipStream_t)hip_stream;
+    if (Cin > 7) {
+        if (ws_bytes < salsa_nn_conv3x3_stem16_wrw_bnf_ws_bytes(N, H, W)) return -5;
+        const unsigned nb = (unsigned)(tiles >= STEM16_WRW_BN_GRID ? STEM16_WRW_BN_GRID : tiles);
+        hipLaunchKernelGGL((conv3x3_stem_wrw_kernel<2, 2>), dim3(nb), dim3(256), 0, st, x, (long)x_batch_stride, (long)x_channel_stride,
+                           (const unsigned short *)g, dw, (int)N, Cin, H, W, (const unsigned short *)x1, (const float *)nullptr, relu,
+                           (float *)ws, bnf);
+        hipLaunchKernelGGL(stem_wrw_bnf_finalize_kernel<2>, dim3(64), dim3(1024), 0, st, (const float *)ws, (int)nb, (double)(N * H * W),
+                           Cin * 9, bnf, dw, dgamma, dbeta);
+        return hipGetLastError() == hipSuccess ? 0 : -6;
+    }
+    if (ws_bytes < salsa_nn_conv3x3_stem_wrw_bnf_ws_bytes(N, H, W)) return -5;
+    const unsigned nb = (unsigned)(tiles >= STEM_WRW_BN_GRID ? STEM_WRW_BN_GRID : tiles);
     hipLaunchKernelGGL(conv3x3_stem_wrw_kernel<2>, dim3(nb), dim3(256), 0, st, x, (long)x_batch_stride, (long)x_channel_stride,
                        (const unsigned short *)g, dw, (int)N, Cin, H, W, (const unsigned short *)x1, (const float *)nullptr, relu,
                        (float *)ws, bnf);
-    hipLaunchKernelGGL(stem_wrw_bnf_finalize_kernel, dim3(64), dim3(1024), 0, st, (const float *)ws, (int)nb, (double)(N * H * W), Cin * 9,
+    hipLaunchKernelGGL(stem_wrw_bnf_finalize_kernel<1>, dim3(64), dim3(1024), 0, st, (const float *)ws, (int)nb, (double)(N * H * W), Cin * 9,
                        bnf, dw, dgamma, dbeta);
     return hipGetLastError() == hipSuccess ? 0 : -6;
 }
@@ -2092,7 +2182,7 @@ extern "C" int salsa_nn_conv3x3_stem_wrw_bn(const float *x, int64_t x_batch_stri
                                             const void *x1, const float *coef, int relu, float *dw, int64_t N, int Cin, int H, int W,
                                             void *hip_stream)
 {
-    if (!x || !g || !x1 || !coef || !dw || N <= 0 || Cin <= 0 || Cin > 7 || H <= 0 || W <= 0 || N * H * W >= INT32_MAX / CH ||
+    if (!x || !g || !x1 || !coef || !dw || N <= 0 || Cin <= 0 || Cin > 14 || H <= 0 || W <= 0 || N * H * W >= INT32_MAX / CH ||
         x_channel_stride < (int64_t)H * W || x_batch_stride < x_channel_stride * Cin ||
         x_channel_stride * Cin >= INT32_MAX /* 32-bit element offsets inside an image */)
         return -1;
@@ -2103,7 +2193,7 @@ extern "C" int salsa_nn_conv3x3_stem_wrw_bn(const float *x, int64_t x_batch_stri
     int rc = 0;
     float *part = salsa_nn_det_begin((int)nb, 64L * Cin * 9, (hipStream_t)hip_stream, &rc);
     if (rc) return rc;
-    hipLaunchKernelGGL(conv3x3_stem_wrw_kernel<1>, dim3(nb), dim3(256), 0, (hipStream_t)hip_stream, x, (long)x_batch_stride,
+    hipLaunchKernelGGL((Cin <= 7 ? conv3x3_stem_wrw_kernel<1> : conv3x3_stem_wrw_kernel<1, 2>), dim3(nb), dim3(256), 0, (hipStream_t)hip_stream, x, (long)x_batch_stride,
                        (long)x_channel_stride, (const unsigned short *)g, dw, (int)N, Cin, H, W, (const unsigned short *)x1, coef, relu, part, StemBnf{});
     if (part) return salsa_nn_det_finish(part, (int)nb, 64L * Cin * 9, dw, (hipStream_t)hip_stream);
     return hipGetLastError() == hipSuccess ? 0 : -6;

@@ -2201,6 +2201,62 @@ __global__ __launch_bounds__(256) void augment_kernel(const float *__restrict__ 
     for (int c = 0; c < 7; c++) dst[c * plane] = x[c];
 }
 
+// The baseline GCC recipe (dataset/datamodule.py:83-100) on [B][10][T][F] = M1..M4 | xc12 xc13 xc14 xc23 xc24 xc34: the
+// GccRandomSwapChannelMic permutation (transforms.py:568-602; its branches are if / elif / elif, so only the FIRST set bit of
+// m0..m2 acts on the features), some GCC rows also flipped along the lag axis (f -> F-1-f); RandomShiftUpDownNp with
+// n_last_channels = 6 (only the four spectrogram rows shift); the cutout rectangles with the last 6 rows zeroed.  Pure gathers:
+// every output value is an input value or the fill value.  One thread = all 10 channels of one (clip, frame, bin).
+__constant__ signed char gcc_src[4][10] = {{0, 1, 2, 3, 4, 5, 6, 7, 8, 9},  // no swap
+                                           {0, 2, 1, 3, 5, 4, 6, 7, 9, 8},  // m0: swap M2 / M3
+                                           {3, 1, 2, 0, 8, 9, 6, 7, 4, 5},  // m1: swap M1 / M4
+                                           {1, 0, 3, 2, 4, 8, 7, 6, 5, 9}}; // m2: swap M1 / M2 and M3 / M4
+__constant__ signed char gcc_flip[4][10] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                                            {0, 0, 0, 0, 0, 0, 0, 1, 0, 0},
+                                            {0, 0, 0, 0, 1, 1, 1, 0, 1, 1},
+                                            {0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+__global__ __launch_bounds__(256) void augment_gcc_kernel(const float *__restrict__ in, long in_batch, long in_chan,
+                                                          float *__restrict__ out, int T, int F, const int *__restrict__ par,
+                                                          const float *__restrict__ uval, const float *__restrict__ minmax)
+{
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= T * F) return;
+    const int t = i / F, f = i - t * F;
+    const int *p = par + b * AUG_NPAR;
+    const long plane = (long)T * F;
+    const float *src = in + (long)b * in_batch;
+    float *dst = out + (long)b * 10 * plane + i;
+    int hit = -1;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int top = p[8 + r], h = p[16 + r], left = p[24 + r], w = p[32 + r];
+        if (t >= top && t < top + h && f >= left && f < left + w) hit = r;
+    }
+    if (hit >= 0) {
+#pragma clang fp contract(off)
+        const float lo = minmax[2 * b], hi = minmax[2 * b + 1];
+        const float v = lo + (hi - lo) * uval[b * 8 + hit];
+#pragma unroll
+        for (int c = 0; c < 10; c++) dst[c * plane] = c < 4 ? v : 0.f;
+        return;
+    }
+    const int s = p[4];
+    int fs = f;
+    if (s > 0) {
+        if (p[5]) fs = f - s < 0 ? s - f : f - s;
+        else fs = f + s > F - 1 ? 2 * (F - 1) - (f + s) : f + s;
+    }
+    fs = fs < 0 ? 0 : fs > F - 1 ? F - 1 : fs;        // (a shift of F bins or more: stay inside the row)
+    const int k = p[0] ? 1 : p[1] ? 2 : p[2] ? 3 : 0;
+    const float *row = src + (long)t * F;
+#pragma unroll
+    for (int c = 0; c < 10; c++) {
+        const int g = c < 4 ? fs : f;                  // the shift moves the spectrogram rows only
+        const int gf = gcc_flip[k][c] ? F - 1 - g : g; // the swap's lag flip, taken before the shift
+        dst[c * plane] = row[gcc_src[k][c] * in_chan + gf];
+    }
+}
+
 __global__ __launch_bounds__(256) void db10_kernel(const float *__restrict__ p, float *__restrict__ o, long n)
 {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -3076,6 +3132,22 @@ int salsa_augment_batch(const float *d_in, int64_t in_batch_stride, int64_t in_c
     hipLaunchKernelGGL(augment_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, (hipStream_t)hip_stream,
                        d_in, (long)in_batch_stride, (long)in_channel_stride, d_out, (int)n_frames, n_freq, audio_format,
                        n_zero_channels, d_params, d_uval, d_minmax);
+    HIP_TRY(hipGetLastError());
+    return SALSA_OK;
+}
+
+int salsa_augment_gcc_batch(const float *d_in, int64_t in_batch_stride, int64_t in_channel_stride, float *d_out, int batch,
+                            int64_t n_frames, int n_freq, const int *d_params, const float *d_uval, const float *d_minmax,
+                            void *hip_stream)
+{
+    if (in_channel_stride < n_frames * n_freq || in_batch_stride < 10 * in_channel_stride)
+        return fail(SALSA_EINVAL, "salsa_augment_gcc_batch: input strides smaller than the [10][T][F] block%s");
+    if (!d_in || !d_out || d_in == d_out || !d_params || !d_uval || !d_minmax || batch <= 0 || batch > 65535 || n_frames <= 0 ||
+        n_freq <= 1 || n_frames * n_freq >= INT32_MAX)
+        return fail(SALSA_EINVAL, "salsa_augment_gcc_batch: bad argument%s");
+    const long n = (long)n_frames * n_freq;
+    hipLaunchKernelGGL(augment_gcc_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, (hipStream_t)hip_stream,
+                       d_in, (long)in_batch_stride, (long)in_channel_stride, d_out, (int)n_frames, n_freq, d_params, d_uval, d_minmax);
     HIP_TRY(hipGetLastError());
     return SALSA_OK;
 }

@@ -1,9 +1,10 @@
 """On-device counterpart of the reference's data layer (dataset/database.py + dataset/dataloader.py) for training
 straight from raw audio (BASELINE.json config 4) or from a tree of precomputed feature files (config 3; add_feature_files +
 load_feature_scaler = Database.load_chunk_data / load_feature_scaler): clips are extracted on the GPU, kept there in the reference's
-concatenated ``(C, sum T, F)`` layout (database.py:230-231), normalised on load with the scaler (first 4 channels only,
-:197-202) and sliced into chunks with the reference's segment index arithmetic (:98-119).  ``__getitem__`` returns the
-same 4-tuple contract as SeldDataset (dataloader.py:37-62) minus augmentation: (X (7,chunk,F), sed, doa, name).
+concatenated ``(C, sum T, F)`` layout (database.py:230-231), normalised on load with the scaler (the first 4 channels for
+SALSA, every channel for the baseline IV / GCC features, whose scaler holds all C: :197-202) and sliced into chunks with the
+reference's segment index arithmetic (:98-119).  ``__getitem__`` returns the same 4-tuple contract as SeldDataset
+(dataloader.py:37-62) minus augmentation: (X (C,chunk,F), sed, doa, name).
 
 Nothing here runs in DataLoader worker processes: HIP contexts do not survive fork, so extraction happens on the
 training process' stream (SURVEY.md section 7 'hard parts')."""
@@ -81,9 +82,15 @@ def load_classwise_gt(gt_meta_fn, n_frames: int, n_classes: int = 12, label_upsa
 
 
 class GpuFeatureBank(torch.utils.data.Dataset):
+    """extractor: a SalsaExtractor, a baseline_features.BaselineExtractor, or None (precomputed feature files).
+    n_scaler_channels: the channels fit_scaler() covers and finalize() normalises; None takes it from the data -- every channel
+    of a BaselineExtractor's output (the reference's baseline compute_scaler, feature_extraction.py:526-586), else 4 (SALSA).
+    A scaler given by load_feature_scaler / set_scaler normalises its own number of channels, (4 | C, 1, F)."""
+
     def __init__(self, extractor: SalsaExtractor = None, fs=24000, hop_len=300, label_rate=10, chunk_len_s=8.0,
-                 chunk_hop_len_s=0.5, n_classes=12, max_clip_s=60, device=None):
+                 chunk_hop_len_s=0.5, n_classes=12, max_clip_s=60, device=None, n_scaler_channels=None):
         self.ex = extractor                                                    # None: a bank of precomputed feature files (add_feature_files)
+        self.n_scaler_channels = n_scaler_channels
         self.device = extractor.device if extractor is not None else torch.device(device if device is not None else 'cuda')
         self.fs, self.hop_len, self.label_rate, self.n_classes = fs, hop_len, label_rate, n_classes
         self.chunk_len = second2frame(chunk_len_s, fs, hop_len)
@@ -126,7 +133,8 @@ class GpuFeatureBank(torch.utils.data.Dataset):
             i = j
 
     def load_feature_scaler(self, scaler_file):
-        """<fmt>_feature_scaler.h5 -> the bank's scaler: Database.load_feature_scaler (database.py:87-96: 'mean', 'std' of shape (4, 1, F))"""
+        """<fmt>_feature_scaler.h5 -> the bank's scaler: Database.load_feature_scaler (database.py:87-96: 'mean', 'std' of shape
+        (4, 1, F) for SALSA, (C, 1, F) for the baseline features -- then every channel is normalised, :197-202)"""
         from . import io as sio
         z = sio.load_arrays(scaler_file)
         self.set_scaler(z['mean'], z['std'])
@@ -137,7 +145,10 @@ class GpuFeatureBank(torch.utils.data.Dataset):
         n_frames = min(feats.shape[2], self.max_frames)
         n_frames -= n_frames % self.upsample
         feats = feats[:, :, :n_frames].contiguous()
-        self._sums = scaler_accumulate(feats, self._sums)
+        if self.n_scaler_channels is None:
+            from .baseline_features import BaselineExtractor
+            self.n_scaler_channels = feats.shape[1] if isinstance(self.ex, BaselineExtractor) else 4
+        self._sums = scaler_accumulate(feats, self._sums, self.n_scaler_channels)
         self._n += feats.shape[0] * n_frames
         if gt_meta is not None:
             assert len(gt_meta) == len(names)
@@ -170,9 +181,9 @@ class GpuFeatureBank(torch.utils.data.Dataset):
         self.mean, self.std = torch.as_tensor(np.asarray(mean, np.float32)), torch.as_tensor(np.asarray(std, np.float32))
 
     def finalize(self):
-        """concatenate along time (database.py:230) and normalise the spectrogram channels in place."""
+        """concatenate along time (database.py:230) and normalise the scaler's channels in place."""
         assert self.mean is not None, 'call fit_scaler() or set_scaler() first'
-        feats = torch.cat(self.blocks, dim=1).contiguous()                   # (7, sum T, F)
+        feats = torch.cat(self.blocks, dim=1).contiguous()                   # (C, sum T, F)
         normalize_(feats[None], self.mean, self.std)
         self.features = feats
         self.sed_all, self.doa_all = torch.cat(self.sed), torch.cat(self.doa)

@@ -359,6 +359,50 @@ def g11_augment():
     save('g11_augment', meta, **arrays)
 
 
+# ----------------------------------------------------------------------------------------------- G22: baseline recipes
+def g22_baseline_augment():
+    """The reference's training augmentation for the four baseline feature types (dataset/datamodule.py:53-100) applied the
+    way SeldDataset.__getitem__ does (dataloader.py:56-60), under np.random.seed(s): SHA-256 of the outputs for 48 seeds per
+    type + one full output per type.  GCC on a (10, 48, 64) input, IV on (7, 48, 64); aspect ratios T / 128 (mel) and
+    T / 200 (linear), as the reference derives them from train_chunk_len."""
+    import hashlib
+    from utilities import transforms as T
+    rng = np.random.RandomState(22)
+    x10 = rng.randn(10, 48, 64).astype(np.float32)
+    x7 = rng.randn(7, 48, 64).astype(np.float32)
+    y_sed = (rng.rand(6, 12) < 0.2).astype(np.float32)
+    y_doa = rng.randn(6, 36).astype(np.float32)
+    arrays = {'x10': x10, 'x7': x7, 'y_sed': y_sed, 'y_doa': y_doa}
+    meta = {'seeds': list(range(2200, 2248)), 'sha': {}, 'aspect': {}}
+    for ft in ('linspeciv', 'melspeciv', 'linspecgcc', 'melspecgcc'):
+        ratio = 48 / (128 if ft.startswith('mel') else 200)
+        meta['aspect'][ft] = ratio
+        if ft.endswith('iv'):
+            x = x7
+            joint = T.ComposeMapTransform([T.TfmapRandomSwapChannelFoa(n_classes=12)])
+            plain = T.ComposeTransformNp([T.RandomShiftUpDownNp(freq_shift_range=10),
+                                          T.CompositeCutout(image_aspect_ratio=ratio, n_zero_channels=3)])
+        else:
+            x = x10
+            joint = T.ComposeMapTransform([T.GccRandomSwapChannelMic(n_classes=12)])
+            plain = T.ComposeTransformNp([T.RandomShiftUpDownNp(freq_shift_range=10, n_last_channels=6),
+                                          T.CompositeCutout(image_aspect_ratio=ratio, n_zero_channels=6)])
+        hs = []
+        for s in meta['seeds']:
+            np.random.seed(s)
+            xo, so, do = joint(x, y_sed, y_doa)
+            xo = plain(xo)
+            assert xo.dtype == np.float32 and do.dtype == np.float32 and so is y_sed
+            hs.append([hashlib.sha256(np.ascontiguousarray(xo).tobytes()).hexdigest(),
+                       hashlib.sha256(np.ascontiguousarray(do).tobytes()).hexdigest()])
+            if s == meta["seeds"][0]:
+                arrays['%s_x_%d' % (ft, s)] = xo
+                arrays['%s_doa_%d' % (ft, s)] = do
+        meta['sha'][ft] = hs
+        print('    %s: %d distinct outputs of %d' % (ft, len({h[0] for h in hs}), len(hs)))
+    save('g22_baseline_augment', meta, **arrays)
+
+
 # ----------------------------------------------------------------------------------------------- G12: SELD metrics
 def g12_metrics():
     """metrics/SELD2021_evaluation_metrics.py + metrics/dcase_utils.py on synthetic DCASE-format rows (CSV round trip
@@ -681,7 +725,8 @@ def g21_baseline():
 
 
 GENERATORS = [g5_w_and_bins, g1_eigvec, g2_adversarial, g3_end_to_end, g4_lite, g8_stft, g10_flexible, g13_flexible_multi,
-              g15_flexible_many, g11_augment, g12_metrics, g17_labels, g18_feature_tree, g19_win_len, g20_off_default, g21_baseline]
+              g15_flexible_many, g11_augment, g12_metrics, g17_labels, g18_feature_tree, g19_win_len, g20_off_default, g21_baseline,
+              g22_baseline_augment]
 
 
 if __name__ == '__main__':
