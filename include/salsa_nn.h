@@ -93,6 +93,11 @@ int salsa_nn_conv3x3_wide_wrw(const void *x, const void *dy, float *dw, const in
  * BatchNorm that follows (salsa_nn_bn_train_fwd / _pool: stats_part, stats_blocks) then makes no statistics pass over y. */
 int salsa_nn_conv3x3_c64_stats_blocks(int64_t N, int H, int W);
 int salsa_nn_conv3x3_c64_stats(const void *x, const void *w, void *y, double *stats_part, int64_t N, int H, int W, void *hip_stream);
+/* the geometry the 64 -> 64 forward (salsa_nn_conv3x3_c64, _stats, _xform_stats, _bias_act[_pool]) runs for [N][H][W][64], and the
+ * weight gradient as well (its tiles are the same 4 x 32 pixels): returns the tile count and sets *transposed to 1 when the kernels
+ * take the map with its axes swapped, else 0; -1 for a NULL transposed or a bad shape.  Host only (no device call): lets a test
+ * prove which geometry a shape reaches. */
+int salsa_nn_conv3x3_c64_config(int64_t N, int H, int W, int *transposed);
 /* Training forward of the first layer from a persistent launch that also leaves the per-channel partial sums of its output
  * (see salsa_nn_conv3x3_c64_stats): stats_part[salsa_nn_conv3x3_stem_stats_blocks(N, H, W)][2][64] float64. */
 int salsa_nn_conv3x3_stem_stats_blocks(int64_t N, int H, int W);

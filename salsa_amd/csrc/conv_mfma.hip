@@ -962,6 +962,15 @@ extern "C" int salsa_nn_conv3x3_c64(const void *x, const void *w, void *y, int64
     return hipGetLastError() == hipSuccess ? 0 : -6;
 }
 
+/* the forward plan: its tile count (TH x TW output pixels each), *transposed = the geometry's tap_t (see struct Geo); host only */
+extern "C" int salsa_nn_conv3x3_c64_config(int64_t N, int H, int W, int *transposed)
+{
+    if (!transposed || N <= 0 || H <= 0 || W <= 0 || N * H * W >= INT32_MAX / CH) return -1;
+    const C64Plan pl = c64_plan(N, H, W, TH, TW);
+    *transposed = pl.geo.tap_t;
+    return (int)pl.tiles;
+}
+
 /* number of partial rows ([2][64] float64 each) salsa_nn_conv3x3_c64_stats writes = its workgroup count */
 extern "C" int salsa_nn_conv3x3_c64_stats_blocks(int64_t N, int H, int W)
 {

@@ -1,6 +1,7 @@
 """CPU checks behind tests/test_nn_kernels_at_scale_gpu.py: the wide convolution's dispatch (which instantiation every bench
-layer reaches), its weight-gradient index tables against a numpy restatement of the padded layout, and the power of the
-float64 checker in tests/nn_reference.py -- it must reject small, realistic kernel bugs.  No GPU calls."""
+layer reaches, at the SALSA / lin maps and at the mel maps), the 64 -> 64 convolution's geometry, its weight-gradient index
+tables against a numpy restatement of the padded layout, and the power of the float64 checker in tests/nn_reference.py -- it
+must reject small, realistic kernel bugs.  No GPU calls."""
 import ctypes as C
 import math
 import os
@@ -48,20 +49,52 @@ def config(lib, n, h, w, cout):
     return tm, tn.value
 
 
+def wrw3(h, w):
+    """conv_wide.hip's wrw3_supported restated: three tile buffers when a tile's x slots are few enough"""
+    rc, ic = (127 + w - 1) // w, (127 + h * w - 1) // (h * w)
+    xs = (127 + 2 * rc + (w + 2) * ic + 2 * (w + 2) + 3 + 15) & ~15
+    lds = 3 * (xs * 64 + 128 * 256) + 3 * ((xs + 63) // 64) * 256 + 5 * 512 + 256
+    return (xs + 63) // 64 + 2 <= 8 and xs // 16 <= 24 and lds <= 160 * 1024
+
+
+WRW_IMMEDIATE_W = (50, 25, 12)          # conv_wide.hip: widths with their own weight-gradient instantiation; others: W2C = 0
+
+
+def c64_plan(n, h, w, th=4, tw=32):
+    """conv_mfma.hip's c64_plan restated: (tiles, transposed) -- the map is handed over with its axes swapped when that needs
+    fewer than 95 % of the tiles (TH x TW = 4 x 32 for the forward and the weight gradient alike)"""
+    tn = n * -(-h // th) * -(-w // tw)
+    tt = n * -(-w // th) * -(-h // tw)
+    return (tt, 1) if tt * 100 < tn * 95 else (tn, 0)
+
+
+def c64_config(lib, n, h, w):
+    tr = C.c_int(-7)
+    tiles = lib.salsa_nn_conv3x3_c64_config(n, h, w, C.byref(tr))
+    return tiles, tr.value
+
+
 # the wide 3x3 layers of the CRNN (stages 2 - 4) at the bench's map sizes: (Cin, Cout, H, W); the data gradient of each is a
-# Cout -> Cin convolution at the same map
+# Cout -> Cin convolution at the same map.  BENCH_WIDE: 200 frequency bins in (SALSA, linspec*); MEL_WIDE: 128 (melspec*)
 BENCH_WIDE = [(64, 128, 160, 50), (128, 128, 160, 50), (128, 256, 80, 25), (256, 256, 80, 25), (256, 512, 40, 12), (512, 512, 40, 12)]
+MEL_WIDE = [(64, 128, 160, 32), (128, 128, 160, 32), (128, 256, 80, 16), (256, 256, 80, 16), (256, 512, 40, 8), (512, 512, 40, 8)]
+# (C, H, W) of the four residual stages' BatchNorms at the mel maps (the first: the 64 -> 64 stage after the stem's pool)
+MEL_STAGES = [(64, 320, 64), (128, 160, 32), (256, 80, 16), (512, 40, 8)]
 
 
-def test_wide_dispatch_at_every_bench_layer(lib):
+def _assert_wide_dispatch(lib, layers):
     for n in (8, 16, 32):
-        for cin, cout, h, w in BENCH_WIDE:
+        for cin, cout, h, w in layers:
             assert lib.salsa_nn_conv3x3_wide_supported(n, h, w, cin, cout)
             assert config(lib, n, h, w, cout) == wide_tile(n, h, w, cout), ('fwd', n, cin, cout, h, w)
             assert lib.salsa_nn_conv3x3_wide_supported(n, h, w, cout, cin)
             assert config(lib, n, h, w, cin) == wide_tile(n, h, w, cin), ('dgrad', n, cin, cout, h, w)
             tm, _ = config(lib, n, h, w, cout)
             assert lib.salsa_nn_conv3x3_wide_stats_blocks(n, h, w, cin, cout) == (n * h * w + tm - 1) // tm
+
+
+def test_wide_dispatch_at_every_bench_layer(lib):
+    _assert_wide_dispatch(lib, BENCH_WIDE)
     # what batch 32 runs: every one of the four instantiations is reached by a bench layer
     assert config(lib, 32, 160, 50, 128) == (512, 128)          # 64 -> 128, 128 -> 128 forward; 128 -> 128 data gradient
     assert config(lib, 32, 80, 25, 256) == (512, 128)           # 128 -> 256, 256 -> 256 forward; 256 -> 256 data gradient
@@ -73,6 +106,50 @@ def test_wide_dispatch_at_every_bench_layer(lib):
     assert wide_xl_bytes(512, 160, 50) == MAX_XL_BYTES
     assert config(lib, 0, 8, 8, 64)[0] == -1 and config(lib, 2, 8, 8, 96)[0] == -1
     assert lib.salsa_nn_conv3x3_wide_config(2, 8, 8, 64, None) == -1
+
+
+def test_wide_dispatch_at_every_mel_layer(lib):
+    """the 128-bin maps (160 x 32, 80 x 16, 40 x 8) reach instantiations the 200-bin maps do not reach with the same Cout"""
+    _assert_wide_dispatch(lib, MEL_WIDE)
+    assert config(lib, 32, 160, 32, 128) == (512, 128)          # 64 -> 128, 128 -> 128 forward; 128 -> 128 data gradient
+    assert config(lib, 32, 80, 16, 256) == (256, 128)           # 128 -> 256, 256 -> 256 forward (80 x 25: (512, 128))
+    assert config(lib, 32, 40, 8, 512) == (256, 64)             # 256 -> 512, 512 -> 512 forward: 8 column blocks of 64
+    assert config(lib, 32, 160, 32, 64) == (512, 64)            # data gradient of 64 -> 128
+    assert config(lib, 32, 80, 16, 128) == (256, 64)            # data gradient of 128 -> 256 (80 x 25: (256, 128))
+    assert config(lib, 32, 40, 8, 256) == (256, 64)             # data gradient of 256 -> 512; 512 -> 512's too (40 x 12: (256, 128))
+    # the weight gradients: every mel width takes the generic (W2C = 0) kernel on three tile buffers
+    for cin, cout, h, w in MEL_WIDE:
+        assert lib.salsa_nn_conv3x3_wide_wrw_supported(32, h, w, cin, cout), (cin, cout, h, w)
+        assert wrw3(h, w) and w not in WRW_IMMEDIATE_W, (h, w)
+    # the 1 x 1 shortcuts of the three stride-2 blocks: forward, data gradient, weight gradient
+    for cin, cout, h, w in (MEL_WIDE[0], MEL_WIDE[2], MEL_WIDE[4]):
+        M = 32 * h * w
+        assert lib.salsa_nn_conv1x1_supported(M, cin, cout) and lib.salsa_nn_conv1x1_supported(M, cout, cin)
+        assert lib.salsa_nn_conv1x1_wrw_supported(M, cin, cout)
+
+
+def test_batchnorm_takes_every_mel_stage(lib):
+    for n in (8, 16, 32):
+        for c, h, w in MEL_STAGES:
+            for dtype in (0, 1):
+                assert lib.salsa_nn_bn_supported(dtype, n * h * w, c), (n, c, h, w, dtype)
+
+
+def test_c64_geometry_query(lib):
+    """salsa_nn_conv3x3_c64_config against the restated plan: 320 x 100 (SALSA / lin) runs transposed, 320 x 64 (mel) does not
+    -- 5120 tiles either way, so the persistent loop walks ~10 tiles per workgroup in the untransposed geometry"""
+    assert c64_config(lib, 32, 320, 100) == (8000, 1) == c64_plan(32, 320, 100)
+    assert c64_config(lib, 32, 320, 64) == (5120, 0) == c64_plan(32, 320, 64)
+    assert c64_plan(32, 320, 64, tw=4, th=32) == (5120, 0)     # (both orientations tie: no transpose on a tie)
+    assert c64_config(lib, 32, 640, 200) == c64_plan(32, 640, 200)
+    for n in (1, 3, 32):
+        for h in (1, 2, 3, 4, 5, 7, 8, 31, 32, 33, 40, 64, 100, 127, 128, 160, 320, 640):
+            for w in (1, 3, 4, 5, 8, 12, 16, 25, 31, 32, 33, 50, 64, 65, 100, 128, 200):
+                assert c64_config(lib, n, h, w) == c64_plan(n, h, w), (n, h, w)
+    tr = C.c_int(-7)
+    for bad in ((0, 8, 8), (1, 0, 8), (1, 8, 0), (-1, 8, 8), (1 << 24, 64, 64)):
+        assert lib.salsa_nn_conv3x3_c64_config(*bad, C.byref(tr)) == -1, bad
+    assert lib.salsa_nn_conv3x3_c64_config(2, 8, 8, None) == -1
 
 
 def test_wide_supported_and_tile_size_at_the_lds_limit(lib):
