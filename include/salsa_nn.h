@@ -238,6 +238,18 @@ int salsa_nn_seld_loss_bwd(const float *a, int64_t na, const float *b, int64_t n
 int salsa_nn_freq_mean_fwd(const void *x, float *y, int64_t N, int H, int W, int C, int time_major, void *hip_stream);
 int salsa_nn_freq_mean_bwd(const float *g, void *dx, int64_t N, int H, int W, int C, int time_major, void *hip_stream);
 
+/* The decoder's freq_pool 'max' and 'avg_max' (reference models/decoders.py: torch.max(x, dim=3), and torch.mean + torch.max) in
+ * one pass, next to the mean above: x bf16 channels-last [N][H][W][C] -> float32 y and uint8 argmax, both [H][N][C] (time_major
+ * != 0) or [N][H][C]; C % 8 == 0, 1 <= W <= 255.  mode 1 (max): y = the maximum over w, exact (a bf16 value widened to float32).
+ * mode 2 (avg_max): y = mean + max, the mean accumulated in float32 in w order as salsa_nn_freq_mean_fwd does.
+ * Ties: argmax is the LOWEST w holding the maximum.  NaN: a NaN is greater than every number, so y is NaN and argmax the FIRST
+ * NaN's w.  _bwd: dx[n][h][w][c] = g[row][c] / W (mode 2 only) + g[row][c] * (w == argmax[row][c]), written as bf16.
+ * Both return 0, -1 for invalid arguments, -6 when the launch fails. */
+int salsa_nn_freq_pool_fwd(const void *x, float *y, uint8_t *argmax, int64_t N, int H, int W, int C, int mode, int time_major,
+                           void *hip_stream);
+int salsa_nn_freq_pool_bwd(const float *g, const uint8_t *argmax, void *dx, int64_t N, int H, int W, int C, int mode, int time_major,
+                           void *hip_stream);
+
 /* Column sums of one or two float32 row-major [M][C] matrices, ADDED to out_a / out_b (zero them first; b may be NULL): the GRU's
  * bias gradients db_ih = sum_(t,b) dgi, db_hh = sum_(t,b) dgh in one launch (torch's reduction / a ones-vector GEMV: ~17 us each). */
 int salsa_nn_colsum2(const float *a, const float *b, float *out_a, float *out_b, int64_t M, int C, void *hip_stream);

@@ -1,6 +1,7 @@
 """SELD CRNN with the reference's architecture and initialisation (models/encoders.py:26-56 PannResNet22,
 models/model_utils.py:187-228 ConvBlock, :312-367 basic block, :429-500 ResNet, models/decoders.py:13-154 SeldDecoder
-with decoder_type='bigru', freq_pool='avg', decoder_size=256 -- experiments/configs/seld.yml:25-32).
+with decoder_type='bigru', freq_pool='avg', decoder_size=256 -- experiments/configs/seld.yml:25-32 -- by default;
+decoder_type 'gru' | 'lstm' | 'bilstm' and freq_pool 'max' | 'avg_max' are built too, 'transformer' is refused).
 
 Shapes for an 8-s training chunk (7,640,200): stem (64,320,100) -> stage1 (64,320,100) -> stage2 (128,160,50) ->
 stage3 (256,80,25) -> stage4 (512,40,12) -> mean over frequency (40,512) -> BiGRU (40,512) -> SED logits (40,12) and
@@ -13,7 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .nn_ops import (BatchNormAct2d, Conv1x1, Conv3x3, ConvFilterBank, avg_pool2x2, conv1x1, conv_bn_act, folded_shortcut, freq_mean_sequence,
-                     invalidate_conv_caches, new_backward_generation, stack_groups)
+                     freq_pool_sequence, invalidate_conv_caches, new_backward_generation, stack_groups)
 
 
 GRU_FP32 = os.environ.get('SALSA_GRU_FP32', '1') == '1'
@@ -130,6 +131,26 @@ def _init_gru(rnn):
                     uni(blk)
 
 
+def _init_rnn_reference(rnn):
+    """the reference's init_gru (model_utils.py:159-184) restated for the gru / lstm / bilstm decoders, as it behaves: for every
+    layer's FORWARD-direction parameters only (``_l{i}``), W_ih and W_hh are split into three row blocks of rows // 3 (for an LSTM
+    341 of 1024 rows: the last row keeps torch's default), uniform(+-sqrt(3/fan_in)) per block but orthogonal for the third block of
+    W_hh, and both biases are zeroed; every ``_reverse`` parameter keeps torch's default U(+-1/sqrt(H)), biases included."""
+    def uni(t):
+        b = math.sqrt(3.0 / t.shape[1])
+        nn.init.uniform_(t, -b, b)
+
+    with torch.no_grad():
+        for i in range(rnn.num_layers):
+            for kind, inits in (('weight_ih', (uni, uni, uni)), ('weight_hh', (uni, uni, nn.init.orthogonal_))):
+                p = getattr(rnn, '%s_l%d' % (kind, i))
+                n = p.shape[0] // 3
+                for g, f in enumerate(inits):
+                    f(p[g * n:(g + 1) * n])
+            nn.init.zeros_(getattr(rnn, 'bias_ih_l%d' % i))
+            nn.init.zeros_(getattr(rnn, 'bias_hh_l%d' % i))
+
+
 class Head(nn.Module):
     def __init__(self, d, n_out):
         super().__init__()
@@ -140,35 +161,70 @@ class Head(nn.Module):
         return self.fc2(self.drop2(F.relu(self.fc1(self.drop1(x)), inplace=True)))
 
 
-class Decoder(nn.Module):
-    """mean over frequency -> 2-layer BiGRU(256) with dropout 0.3 -> SED head + x/y/z heads (decoders.py:13-154)."""
+DECODER_TYPES = ('gru', 'bigru', 'lstm', 'bilstm')
+FREQ_POOLS = ('avg', 'max', 'avg_max')
 
-    def __init__(self, n_in=512, n_classes=12, size=256):
+
+class Decoder(nn.Module):
+    """frequency pool -> 2-layer recurrent decoder (size 256) with dropout 0.3 -> SED head + x/y/z heads (decoders.py:13-154).
+    decoder_type 'bigru' (the default), 'gru', 'lstm' or 'bilstm'; freq_pool 'avg' (the default), 'max' or 'avg_max'.  The module
+    attribute is ``gru`` or ``lstm``, as in the reference's state dict."""
+
+    def __init__(self, n_in=512, n_classes=12, size=256, decoder_type='bigru', freq_pool='avg'):
         super().__init__()
-        self.n_classes = n_classes
-        self.gru = nn.GRU(n_in, size, num_layers=2, batch_first=True, bidirectional=True, dropout=0.3)
-        _init_gru(self.gru)
-        self.event = Head(2 * size, n_classes)
-        self.x, self.y, self.z = Head(2 * size, n_classes), Head(2 * size, n_classes), Head(2 * size, n_classes)
+        if decoder_type == 'transformer':
+            raise NotImplementedError("decoder_type 'transformer' is not implemented (supported: %s)" % ', '.join(DECODER_TYPES))
+        if decoder_type not in DECODER_TYPES:
+            raise ValueError('invalid decoder_type %r (supported: %s)' % (decoder_type, ', '.join(DECODER_TYPES)))
+        if freq_pool not in FREQ_POOLS:
+            raise NotImplementedError('freq pooling %r is not implemented (supported: %s)' % (freq_pool, ', '.join(FREQ_POOLS)))
+        self.n_classes, self.decoder_type, self.freq_pool = n_classes, decoder_type, freq_pool
+        bidirectional = decoder_type.startswith('bi')
+        if decoder_type == 'bigru':
+            self.gru = nn.GRU(n_in, size, num_layers=2, batch_first=True, bidirectional=True, dropout=0.3)
+            _init_gru(self.gru)
+        elif decoder_type == 'gru':
+            self.gru = nn.GRU(n_in, size, num_layers=2, batch_first=True, bidirectional=False, dropout=0.3)
+            _init_rnn_reference(self.gru)
+        else:
+            self.lstm = nn.LSTM(n_in, size, num_layers=2, batch_first=True, bidirectional=bidirectional, dropout=0.3)
+            _init_rnn_reference(self.lstm)
+        d = (2 if bidirectional else 1) * size
+        self.event = Head(d, n_classes)
+        self.x, self.y, self.z = Head(d, n_classes), Head(d, n_classes), Head(d, n_classes)
+
+    @property
+    def rnn(self):
+        return self.lstm if self.decoder_type in ('lstm', 'bilstm') else self.gru
 
     def forward(self, feat):
-        seq = freq_mean_sequence(feat)                          # (B, T', 512): mean over frequency
+        if self.freq_pool == 'avg':
+            seq = freq_mean_sequence(feat)                      # (B, T', 512): mean over frequency
+        else:
+            seq = freq_pool_sequence(feat, self.freq_pool)      # max / mean + max over frequency
         if seq.is_cuda and GRU_FP32:
             # 0.4 % of the FLOPs but, under bf16 autocast, ~6000 per-timestep cell kernels per forward (torch's native
             # fallback); in float32 the whole sequence goes through MIOpen's fused RNN
             amp = torch.is_autocast_enabled('cuda')
             with torch.autocast(device_type='cuda', enabled=False):
-                if FUSED_GRU:
-                    from .fused_gru import bigru_forward
-                    seq = bigru_forward(self.gru, seq.float(), self.training, half_weights=amp)   # one HIP launch per layer
+                if self.decoder_type == 'bigru':
+                    if FUSED_GRU:
+                        from .fused_gru import bigru_forward
+                        seq = bigru_forward(self.gru, seq.float(), self.training, half_weights=amp)   # one HIP launch per layer
+                    else:
+                        seq, _ = self.gru(seq.float())
                 else:
-                    seq, _ = self.gru(seq.float())
+                    from .fused_lstm import FUSED_LSTM, rnn_forward
+                    if FUSED_LSTM if self.decoder_type in ('lstm', 'bilstm') else FUSED_GRU:
+                        seq = rnn_forward(self.rnn, seq.float(), self.training, half_weights=amp)   # one HIP launch per layer
+                    else:
+                        seq, _ = self.rnn(seq.float())
             # the heads too (0.02 % of the FLOPs): under autocast their eight small linears cost 32 cast kernels per step
             # (weights and biases to bf16, their gradients back) around GEMMs of a few microseconds
             with torch.autocast(device_type='cuda', enabled=False):
                 return self._heads(seq.float())
         else:
-            seq, _ = self.gru(seq)
+            seq, _ = self.rnn(seq)
         return self._heads(seq)
 
     def _heads(self, seq):
@@ -218,12 +274,14 @@ def interpolate_tensor(t, ratio: float):
 
 class SeldCRNN(nn.Module):
     """forward(x (B,7,T,200)) -> dict at the LABEL rate (seld_models.py:39-66: encoder, decoder, then
-    interpolate by time_downsample_ratio * label_rate / feature_rate = 16 * 10 / 80 = 2)."""
+    interpolate by time_downsample_ratio * label_rate / feature_rate = 16 * 10 / 80 = 2).  decoder_type, freq_pool and
+    decoder_size are the reference's YAML keys of the same names (see Decoder)."""
 
-    def __init__(self, n_input_channels=7, n_classes=12, label_rate=10, feature_rate=80):
+    def __init__(self, n_input_channels=7, n_classes=12, label_rate=10, feature_rate=80, decoder_type='bigru', freq_pool='avg',
+                 decoder_size=256):
         super().__init__()
         self.encoder = Encoder(n_input_channels)
-        self.decoder = Decoder(self.encoder.n_output_channels, n_classes)
+        self.decoder = Decoder(self.encoder.n_output_channels, n_classes, decoder_size, decoder_type, freq_pool)
         self.ratio = self.encoder.time_downsample_ratio * label_rate / feature_rate
 
     def forward(self, x):
@@ -235,13 +293,14 @@ class SeldCRNN(nn.Module):
         stacked in memory, so that the stack is a view instead of a copy (nn_ops.pack_stacked_parameters).  Values, Parameter
         objects and state-dict keys are unchanged.  Call it after the last ``.to(device)`` (the Trainer does); returns self."""
         from .nn_ops import pack_stacked_parameters
-        gru, dec = self.decoder.gru, self.decoder
-        groups = [[getattr(gru, '%s_l%d%s' % (kind, layer, rev)) for rev in ('', '_reverse')]
+        gru, dec = self.decoder.rnn, self.decoder
+        directions = ('', '_reverse') if gru.bidirectional else ('',)
+        groups = [[getattr(gru, '%s_l%d%s' % (kind, layer, rev)) for rev in directions]
                   for layer in range(gru.num_layers) for kind in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')]
         heads = (dec.event, dec.x, dec.y, dec.z)
         groups += [[h.fc1.weight for h in heads], [h.fc1.bias for h in heads], [h.fc2.weight for h in heads], [h.fc2.bias for h in heads]]
         pack_stacked_parameters(groups)
-        if hasattr(gru, '_flat_weights'):      # nn.GRU caches references to its weights for the (unused here) MIOpen path
+        if hasattr(gru, '_flat_weights'):      # nn.GRU / nn.LSTM cache references to their weights for the (unused here) MIOpen path
             gru._flat_weights = [getattr(gru, n) if hasattr(gru, n) else None for n in gru._flat_weights_names]
         return self
 

@@ -378,6 +378,58 @@ def freq_mean_sequence(feat):
     return feat.mean(dim=3).transpose(1, 2)
 
 
+
+USE_HIP_FREQ_POOL = os.environ.get('SALSA_HIP_FREQ_POOL', '1') != '0'   # 0: the max / avg_max frequency pools on torch
+FREQ_POOL_MODE = {'max': 1, 'avg_max': 2}
+
+
+class _FreqPool(torch.autograd.Function):
+    """salsa_nn_freq_pool_fwd / _bwd: (N, C, T, F) bf16 channels-last -> float32 (T, N, C) time-major max (mode 1) or mean + max
+    (mode 2) over F; the argmax (uint8, lowest index on ties) is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, x, mode):
+        N, Cn, H, W = x.shape
+        y = torch.empty((H, N, Cn), dtype=torch.float32, device=x.device)
+        am = torch.empty((H, N, Cn), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            rc = _lib.load().salsa_nn_freq_pool_fwd(_ptr(x), _ptr(y), _ptr(am), N, H, W, Cn, mode, 1, _stream(x))
+        if rc:
+            raise RuntimeError('salsa_nn_freq_pool_fwd failed (%d)' % rc)
+        ctx.save_for_backward(am)
+        ctx.shape, ctx.mode = (N, Cn, H, W), mode
+        ctx.mark_non_differentiable(am)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        am, = ctx.saved_tensors
+        N, Cn, H, W = ctx.shape
+        g = g.contiguous().float()
+        dx = torch.empty((N, Cn, H, W), dtype=torch.bfloat16, device=g.device, memory_format=torch.channels_last)
+        with torch.cuda.device(g.device):
+            rc = _lib.load().salsa_nn_freq_pool_bwd(_ptr(g), _ptr(am), _ptr(dx), N, H, W, Cn, ctx.mode, 1, _stream(g))
+        if rc:
+            raise RuntimeError('salsa_nn_freq_pool_bwd failed (%d)' % rc)
+        return dx, None
+
+
+def freq_pool_sequence(feat, freq_pool: str):
+    """(B, C, T, F) encoder output -> (B, T, C): the decoder's frequency pool (models/decoders.py freq_pool 'avg' | 'max' |
+    'avg_max') and transpose.  'avg' is freq_mean_sequence; 'max' / 'avg_max' run salsa_nn_freq_pool for bf16 channels-last CUDA
+    maps with C % 8 == 0 and F <= 255 (float32, a view of a TIME-major buffer), the reference's torch expressions otherwise."""
+    if freq_pool == 'avg':
+        return freq_mean_sequence(feat)
+    if freq_pool not in FREQ_POOL_MODE:
+        raise NotImplementedError('freq pooling %s is not implemented' % freq_pool)
+    if (USE_HIP_FREQ_POOL and feat.is_cuda and feat.dtype == torch.bfloat16 and feat.dim() == 4 and feat.shape[1] % 8 == 0
+            and feat.shape[3] <= 255 and feat.is_contiguous(memory_format=torch.channels_last)):
+        return _FreqPool.apply(feat, FREQ_POOL_MODE[freq_pool]).transpose(0, 1)
+    x, _ = torch.max(feat, dim=3)
+    if freq_pool == 'avg_max':
+        x = torch.mean(feat, dim=3) + x
+    return x.transpose(1, 2)
+
 class _GradZeros:
     """Zero-initialised float32 weight-gradient buffers for the accumulating weight-gradient kernels, ONE allocation and ONE fill
     per backward pass instead of one ``torch.zeros`` per layer (25 fills of ~4 us in the training step).

@@ -31,7 +31,7 @@ import contextlib  # noqa: E402
 
 @contextlib.contextmanager
 def dropout_off(model):
-    """Every dropout of ``model`` switched off for the duration (F.dropout -> identity, nn.Dropout p = 0, GRU inter-layer
+    """Every dropout of ``model`` switched off for the duration (F.dropout -> identity, nn.Dropout p = 0, GRU / LSTM inter-layer
     dropout 0, the residual blocks' fused dropout 0): the deterministic training pass the g16 fixture was made with."""
     import torch.nn.functional as F
     saved = []
@@ -39,7 +39,7 @@ def dropout_off(model):
         if isinstance(m, torch.nn.Dropout):
             saved.append((m, 'p', m.p))
             m.p = 0.0
-        if isinstance(m, torch.nn.GRU):
+        if isinstance(m, torch.nn.RNNBase):                      # nn.GRU / nn.LSTM inter-layer dropout
             saved.append((m, 'dropout', m.dropout))
             m.dropout = 0.0
         if hasattr(m, 'dropout_p'):

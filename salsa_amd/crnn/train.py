@@ -43,8 +43,11 @@ def synthetic_batch(batch: int, device, seed: int = 0, n_frames: int = 640, n_fr
 
 class Trainer:
     def __init__(self, device, amp_dtype=torch.bfloat16, ddp: bool = None, total_steps: int = 1313 * 50,
-                 bf16_grad_allreduce: bool = True, seed: int = 2021, n_input_channels: int = 7):
-        """n_input_channels: 7 (SALSA, melspeciv, linspeciv) or 10 (melspecgcc, linspecgcc), experiments/configs/seld.yml."""
+                 bf16_grad_allreduce: bool = True, seed: int = 2021, n_input_channels: int = 7, decoder_type: str = 'bigru',
+                 freq_pool: str = 'avg', decoder_size: int = 256):
+        """n_input_channels: 7 (SALSA, melspeciv, linspeciv) or 10 (melspecgcc, linspecgcc), experiments/configs/seld.yml;
+        decoder_type ('bigru' | 'gru' | 'lstm' | 'bilstm'), freq_pool ('avg' | 'max' | 'avg_max') and decoder_size: the YAML's
+        model.decoder keys of the same names (SeldCRNN)."""
         torch.manual_seed(seed)
         self.device = torch.device(device)
         if self.device.type == 'cuda' and os.environ.get('SALSA_MIOPEN_FIND', '0') == '1':
@@ -52,7 +55,8 @@ class Trainer:
         self.amp_dtype = amp_dtype
         self.total_steps = total_steps
         self.step_idx = 0
-        model = SeldCRNN(n_input_channels=n_input_channels).to(self.device)
+        model = SeldCRNN(n_input_channels=n_input_channels, decoder_type=decoder_type, freq_pool=freq_pool,
+                         decoder_size=decoder_size).to(self.device)
         self.channels_last = self.device.type == 'cuda' and os.environ.get('SALSA_CHANNELS_LAST', '1') == '1'
         if self.channels_last:
             model = model.to(memory_format=torch.channels_last)

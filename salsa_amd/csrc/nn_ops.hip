@@ -759,6 +759,88 @@ __global__ __launch_bounds__(256) void freq_mean_bwd_kernel(const float *__restr
     *(uint4 *)(dx + rw * C + c8 * 8) = o;
 }
 
+// ------------------------------------------------------------------------------------------- frequency max / avg + max pool
+// The decoder's freq_pool 'max' and 'avg_max' (models/decoders.py: torch.max(x, dim=3), mean + max) in one pass, laid out like
+// freq_mean_fwd_kernel (8 channels per thread).  mode 1: y = max; mode 2: y = mean + max, the mean accumulated in w order as
+// freq_mean does.  argmax (uint8, W <= 255) is the LOWEST w holding the maximum; a NaN wins over every number and the first NaN
+// is kept, so NaN propagates with its own index.
+__global__ __launch_bounds__(256) void freq_pool_fwd_kernel(const unsigned short *__restrict__ x, float *__restrict__ y,
+                                                            uint8_t *__restrict__ argmax, long rows, int N, int H, int W, int C,
+                                                            int mode, int time_major)
+{
+    const int cv = C / 8;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * cv) return;
+    const long r = i / cv;
+    const int c8 = (int)(i - r * cv);
+    const uint4 *p = (const uint4 *)(x + (r * W) * C + c8 * 8);
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, mx[8];
+    int am[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int w = 0; w < W; w++) {
+        const uint4 v = p[(long)w * cv];
+        const unsigned u[4] = {v.x, v.y, v.z, v.w};
+        float e[8];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            e[2 * k] = __uint_as_float(u[k] << 16);
+            e[2 * k + 1] = __uint_as_float(u[k] & 0xFFFF0000u);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            acc[k] += e[k];
+            const bool take = w == 0 || e[k] > mx[k] || (e[k] != e[k] && mx[k] == mx[k]); // strictly greater, or the first NaN
+            mx[k] = take ? e[k] : mx[k];
+            am[k] = take ? w : am[k];
+        }
+    }
+    const float inv = 1.f / (float)W;
+    float out[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[k] = mode == 2 ? __fadd_rn(__fmul_rn(acc[k], inv), mx[k]) : mx[k]; // (mean rounded, then added: no fma)
+    const long n = r / H, h = r - n * H;
+    const long row = time_major ? h * N + n : r;
+    float *o = y + (row * C + c8 * 8);
+    *(float4 *)o = make_float4(out[0], out[1], out[2], out[3]);
+    *(float4 *)(o + 4) = make_float4(out[4], out[5], out[6], out[7]);
+    uint2 a;
+    a.x = (unsigned)am[0] | ((unsigned)am[1] << 8) | ((unsigned)am[2] << 16) | ((unsigned)am[3] << 24);
+    a.y = (unsigned)am[4] | ((unsigned)am[5] << 8) | ((unsigned)am[6] << 16) | ((unsigned)am[7] << 24);
+    *(uint2 *)(argmax + row * C + c8 * 8) = a;
+}
+
+// dx[n][h][w][c] = g[row][c] / W (mode 2 only) + g[row][c] * (w == argmax[row][c]), bf16 channels-last
+__global__ __launch_bounds__(256) void freq_pool_bwd_kernel(const float *__restrict__ g, const uint8_t *__restrict__ argmax,
+                                                            unsigned short *__restrict__ dx, long rows, int N, int H, int W, int C,
+                                                            int mode, int time_major)
+{
+    const int cv = C / 8;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * W * cv) return;
+    const long rw = i / cv;
+    const int c8 = (int)(i - rw * cv);
+    const long r = rw / W;
+    const int w = (int)(rw - r * W);
+    const long n = r / H, h = r - n * H;
+    const long row = time_major ? h * N + n : r;
+    const float *src = g + (row * C + c8 * 8);
+    const float4 a = *(const float4 *)src, b = *(const float4 *)(src + 4);
+    const uint2 am = *(const uint2 *)(argmax + row * C + c8 * 8);
+    const float gv[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const float inv = mode == 2 ? 1.f / (float)W : 0.f;
+    float d[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int idx = (int)(((k < 4 ? am.x : am.y) >> (8 * (k & 3))) & 0xFFu);
+        d[k] = __fadd_rn(__fmul_rn(gv[k], inv), idx == w ? gv[k] : 0.f);
+    }
+    uint4 o;
+    o.x = pack_bf16(d[0], d[1]);
+    o.y = pack_bf16(d[2], d[3]);
+    o.z = pack_bf16(d[4], d[5]);
+    o.w = pack_bf16(d[6], d[7]);
+    *(uint4 *)(dx + rw * C + c8 * 8) = o;
+}
+
 // ------------------------------------------------------------------------------------------------ deterministic reductions
 // dw[i] += sum over the slabs of ws[slab][i], in a FIXED order (what makes the result reproducible; it need not be slab order): a
 // workgroup owns 4 * 256 / SL consecutive elements and its SL slab lanes each add every SL-th slab in ascending order, then the SL
@@ -1339,6 +1421,28 @@ int salsa_nn_freq_mean_bwd(const float *g, void *dx, int64_t N, int H, int W, in
     const long rows = (long)N * H, n = rows * W * (C / 8);
     hipLaunchKernelGGL(freq_mean_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, g,
                        (unsigned short *)dx, rows, (int)N, H, W, C, time_major);
+    return hipGetLastError() == hipSuccess ? 0 : -6;
+}
+
+/* frequency max (mode 1) / mean + max (mode 2) of a bf16 channels-last map x [N][H][W][C] -> float32 y and uint8 argmax, both
+ * [H][N][C] when time_major else [N][H][C]; C % 8 == 0, W <= 255.  _bwd: dx = g / W (mode 2) + g at w == argmax, bf16 channels-last. */
+int salsa_nn_freq_pool_fwd(const void *x, float *y, uint8_t *argmax, int64_t N, int H, int W, int C, int mode, int time_major,
+                           void *hip_stream)
+{
+    if (!x || !y || !argmax || N <= 0 || H <= 0 || W <= 0 || W > 255 || C <= 0 || C % 8 || (mode != 1 && mode != 2)) return -1;
+    const long rows = (long)N * H, n = rows * (C / 8);
+    hipLaunchKernelGGL(freq_pool_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream,
+                       (const unsigned short *)x, y, argmax, rows, (int)N, H, W, C, mode, time_major);
+    return hipGetLastError() == hipSuccess ? 0 : -6;
+}
+
+int salsa_nn_freq_pool_bwd(const float *g, const uint8_t *argmax, void *dx, int64_t N, int H, int W, int C, int mode, int time_major,
+                           void *hip_stream)
+{
+    if (!g || !argmax || !dx || N <= 0 || H <= 0 || W <= 0 || W > 255 || C <= 0 || C % 8 || (mode != 1 && mode != 2)) return -1;
+    const long rows = (long)N * H, n = rows * W * (C / 8);
+    hipLaunchKernelGGL(freq_pool_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, g, argmax,
+                       (unsigned short *)dx, rows, (int)N, H, W, C, mode, time_major);
     return hipGetLastError() == hipSuccess ? 0 : -6;
 }
 
