@@ -232,6 +232,19 @@ int salsa_nn_seld_loss(const float *logit, const float *doa, const float *sed_gt
 int salsa_nn_seld_loss_bwd(const float *a, int64_t na, const float *b, int64_t nb, const float *g_loss, const float *g_sed,
                            const float *g_doa, float w_sed, float w_doa, float *out_a, float *out_b, void *hip_stream);
 
+/* The ACCDOA training loss (output_format 'accdoa'; reference models/interfaces.py:273-302, compute_classwise_accdoa_loss) and
+ * its gradient in one call: doa loss = sum over (row, class) of ((p_x - t_x)^2 + (p_y - t_y)^2 + (p_z - t_z)^2) sed_gt / rows;
+ * sed_gt [rows][nc], doa, doa_gt [rows][3 nc] (blocks x | y | z), float32 contiguous.  out3 = {loss = doa loss, 0, doa loss} (the
+ * reference discards its sed term); g_doa = 2 (p - t) sed_gt / rows; g_logit, when not NULL, [rows][nc] filled with zeros (the
+ * event logits get an exact-zero gradient).  Float64 partial sums per workgroup added in a fixed order: bit-reproducible.  The
+ * backward is salsa_nn_seld_loss_bwd with a = g_logit, b = g_doa, w_sed = 0, w_doa = 1. */
+#define SALSA_ACCDOA_LOSS_WS 64 /* float64 values of scratch (partial_ws) salsa_nn_accdoa_loss needs: one per workgroup */
+int salsa_nn_accdoa_loss(const float *doa, const float *sed_gt, const float *doa_gt, int64_t rows, int nc, float *out3, float *g_logit,
+                         float *g_doa, double *partial_ws, void *hip_stream);
+/* The SED decision of the ACCDOA output (reference models/interfaces.py:260-268): sed [rows][nc] = sqrt(x^2 + y^2 + z^2) of
+ * xyz [rows][3 nc], float32, bit-equal to numpy's float32 expression (no fma, correctly rounded square root). */
+int salsa_nn_accdoa_sed(const float *xyz, float *sed, int64_t rows, int nc, void *hip_stream);
+
 /* The decoder's frequency mean (reference models/decoders.py: x.mean(dim=3) then (B, C, T) -> (B, T, C)) in one pass:
  * x bf16 channels-last [N][H][W][C] -> float32 y [H][N][C] (time_major != 0: the GRU scans' order) or [N][H][C]; C % 8 == 0.
  * _bwd: dx[n][h][w][c] = g[row(n, h)][c] / W, bf16 channels-last. */

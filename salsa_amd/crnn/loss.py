@@ -1,5 +1,5 @@
-"""SELD training loss (models/interfaces.py:304-355): 0.3 * BCE-with-logits(SED) + 0.7 * sum over x,y,z of the
-activity-masked mean absolute error."""
+"""SELD training losses.  reg_xyz (models/interfaces.py:304-355): 0.3 * BCE-with-logits(SED) + 0.7 * sum over x,y,z of the
+activity-masked mean absolute error.  accdoa (:273-302): the activity-masked squared error of the xyz output over all rows."""
 import os
 
 import torch
@@ -69,3 +69,67 @@ class _SeldLoss(torch.autograd.Function):
         if rc:
             raise RuntimeError('salsa_nn_seld_loss_bwd failed (%d)' % rc)
         return oa, ob, None, None, None, None
+
+
+def accdoa_loss(pred, sed_gt, doa_gt):
+    """output_format 'accdoa' (compute_loss :273-282, compute_classwise_accdoa_loss :284-302): pred: dict from SeldCRNN; sed_gt
+    (B,T,C); doa_gt (B,T,3C) -> (loss, sed_loss, doa_loss) with doa_loss = sum(((p - t)^2 summed over x, y, z) * sed_gt) / (B T),
+    loss = doa_loss and sed_loss = 0 (the reference computes a sed term and discards it; loss_weight is not used).  The event
+    logits are not part of the loss, but they get an exact-zero gradient: with every parameter holding a gradient the bucketed
+    all-reduce and DDP see the same parameters as under reg_xyz, and Adam (weight_decay 0) leaves the event head unchanged, as
+    the reference's grad = None does."""
+    nc = sed_gt.shape[-1]
+    logit, doa = pred.get('event_frame_logit'), pred['doa_frame_output'].float()
+    if (FUSED_LOSS and doa.is_cuda and sed_gt.dtype == torch.float32 and doa_gt.dtype == torch.float32 and logit is not None
+            and logit.shape == sed_gt.shape and doa.shape == doa_gt.shape and doa.shape[-1] == 3 * nc):
+        out = _AccdoaLoss.apply(logit.float(), doa, sed_gt, doa_gt)
+        return out[0], out[1], out[2]
+    n = sed_gt.shape[0] * sed_gt.shape[1]
+    e = (doa - doa_gt) ** 2
+    d = torch.sum((e[..., :nc] + e[..., nc:2 * nc] + e[..., 2 * nc:]) * sed_gt) / n
+    if logit is not None and logit.requires_grad:
+        d = _ZeroGradTo.apply(d, logit)
+    return d, torch.zeros((), dtype=d.dtype, device=d.device), d
+
+
+class _ZeroGradTo(torch.autograd.Function):
+    """y = x, and an exact-zero gradient for `other` (value untouched, whatever `other` holds: no 0 * other arithmetic)"""
+
+    @staticmethod
+    def forward(ctx, x, other):
+        ctx.other = (other.shape, other.dtype, other.device)
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        shape, dtype, device = ctx.other
+        return g, torch.zeros(shape, dtype=dtype, device=device)
+
+
+class _AccdoaLoss(torch.autograd.Function):
+    """salsa_nn_accdoa_loss: the accdoa loss, its gradient and the event logits' zero gradient in one call; the backward is
+    salsa_nn_seld_loss_bwd with the weights (0, 1): g_logit stays zero, g_doa is scaled by g_loss + g_doa_loss."""
+
+    @staticmethod
+    def forward(ctx, logit, doa, sed_gt, doa_gt):
+        from .. import _lib
+        from .nn_ops import _ptr, _stream
+        doa, sed_gt, doa_gt = doa.contiguous(), sed_gt.contiguous(), doa_gt.contiguous()
+        nc = sed_gt.shape[-1]
+        rows = sed_gt.numel() // nc
+        out = torch.empty(3, dtype=torch.float32, device=doa.device)
+        ws = torch.empty(64, dtype=torch.float64, device=doa.device)         # include/salsa_nn.h SALSA_ACCDOA_LOSS_WS
+        ga, gb = torch.empty(logit.shape, dtype=torch.float32, device=doa.device), torch.empty_like(doa)
+        with torch.cuda.device(doa.device):
+            rc = _lib.load().salsa_nn_accdoa_loss(_ptr(doa), _ptr(sed_gt), _ptr(doa_gt), rows, nc, _ptr(out), _ptr(ga), _ptr(gb),
+                                                  _ptr(ws), _stream(doa))
+        if rc:
+            raise RuntimeError('salsa_nn_accdoa_loss failed (%d)' % rc)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(ga, gb)
+        ctx.w = (0.0, 1.0)
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    def backward(ctx, g_loss, g_sed, g_doa):
+        return _SeldLoss.backward(ctx, g_loss, g_sed, g_doa)[:4]

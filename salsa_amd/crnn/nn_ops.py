@@ -430,6 +430,32 @@ def freq_pool_sequence(feat, freq_pool: str):
         x = torch.mean(feat, dim=3) + x
     return x.transpose(1, 2)
 
+
+USE_HIP_ACCDOA_SED = os.environ.get('SALSA_HIP_ACCDOA_SED', '1') != '0'   # 0: the ACCDOA SED decision on torch
+
+
+def accdoa_sed(xyz, n_classes: int):
+    """(..., 3 n_classes) float32 ACCDOA output -> (..., n_classes) sqrt(x^2 + y^2 + z^2) per class (the reference's
+    get_sed_from_accdoa_output, crnn/postprocess.sed_from_accdoa): salsa_nn_accdoa_sed on CUDA tensors, bit-equal to numpy's
+    float32 expression; numpy's expression itself on CPU tensors (torch's CPU sqrt is not always correctly rounded); the torch
+    expression on CUDA tensors under SALSA_HIP_ACCDOA_SED=0."""
+    if xyz.shape[-1] != 3 * n_classes:
+        raise ValueError('accdoa_sed: last axis %d is not 3 x %d classes' % (xyz.shape[-1], n_classes))
+    if USE_HIP_ACCDOA_SED and xyz.is_cuda and xyz.dtype == torch.float32 and xyz.numel() > 0:
+        xyz = xyz.contiguous()
+        rows = xyz.numel() // xyz.shape[-1]
+        sed = torch.empty(xyz.shape[:-1] + (n_classes,), dtype=torch.float32, device=xyz.device)
+        with torch.cuda.device(xyz.device):
+            rc = _lib.load().salsa_nn_accdoa_sed(_ptr(xyz), _ptr(sed), rows, n_classes, _stream(xyz))
+        if rc:
+            raise RuntimeError('salsa_nn_accdoa_sed failed (%d)' % rc)
+        return sed
+    if not xyz.is_cuda:
+        from .postprocess import sed_from_accdoa
+        return torch.from_numpy(sed_from_accdoa(xyz.detach().numpy(), n_classes))
+    x, y, z = xyz[..., :n_classes], xyz[..., n_classes:2 * n_classes], xyz[..., 2 * n_classes:]
+    return torch.sqrt(x * x + y * y + z * z)
+
 class _GradZeros:
     """Zero-initialised float32 weight-gradient buffers for the accumulating weight-gradient kernels, ONE allocation and ONE fill
     per backward pass instead of one ``torch.zeros`` per layer (25 fills of ~4 us in the training step).

@@ -31,6 +31,16 @@ def combine_chunks(frame_output_pred: np.ndarray, chunk_len: int, chunk_hop_len:
     return out
 
 
+def sed_from_accdoa(doa: np.ndarray, n_classes: int = 12) -> np.ndarray:
+    """(..., 3 n_classes) ACCDOA xyz output -> (..., n_classes) SED activity: the length of each class's vector, in the input's
+    precision (models/interfaces.py:260-268, get_sed_from_accdoa_output; float32 on the reference's inference path).  It is
+    applied to the label-rate output of each chunk, before combine_chunks, as the reference does."""
+    x = doa[..., :n_classes]
+    y = doa[..., n_classes:2 * n_classes]
+    z = doa[..., 2 * n_classes:]
+    return np.sqrt(x ** 2 + y ** 2 + z ** 2)
+
+
 def to_dcase_rows(event_prob: np.ndarray, doa_xyz: np.ndarray, sed_threshold: float = 0.3, n_classes: int = 12,
                   max_nframes_per_file: int = 600, eval_version: str = '2021', as_array: bool = False):
     """event_prob (T, 12) sigmoid outputs, doa_xyz (T, 36) -> list of [frame, class, (0,) azimuth, elevation] rows, in the

@@ -11,11 +11,12 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .loss import seld_loss
+from .loss import accdoa_loss, seld_loss
 from .model import SeldCRNN
 
 MILESTONES = (0.0, 0.1, 0.7, 1.0)
 LRS = (3e-4, 3e-4, 3e-4, 1e-4)
+OUTPUT_FORMATS = ('reg_xyz', 'accdoa')
 
 
 def lr_at(progress: float) -> float:
@@ -44,10 +45,14 @@ def synthetic_batch(batch: int, device, seed: int = 0, n_frames: int = 640, n_fr
 class Trainer:
     def __init__(self, device, amp_dtype=torch.bfloat16, ddp: bool = None, total_steps: int = 1313 * 50,
                  bf16_grad_allreduce: bool = True, seed: int = 2021, n_input_channels: int = 7, decoder_type: str = 'bigru',
-                 freq_pool: str = 'avg', decoder_size: int = 256):
+                 freq_pool: str = 'avg', decoder_size: int = 256, output_format: str = 'reg_xyz'):
         """n_input_channels: 7 (SALSA, melspeciv, linspeciv) or 10 (melspecgcc, linspecgcc), experiments/configs/seld.yml;
         decoder_type ('bigru' | 'gru' | 'lstm' | 'bilstm'), freq_pool ('avg' | 'max' | 'avg_max') and decoder_size: the YAML's
-        model.decoder keys of the same names (SeldCRNN)."""
+        model.decoder keys of the same names (SeldCRNN); output_format: the YAML's data.output_format, 'reg_xyz' (SED from the
+        event head, loss.seld_loss) or 'accdoa' (SED = length of each class's xyz vector, loss.accdoa_loss)."""
+        if output_format not in OUTPUT_FORMATS:
+            raise ValueError('invalid output_format %r (supported: %s)' % (output_format, ', '.join(OUTPUT_FORMATS)))
+        self.output_format = output_format
         torch.manual_seed(seed)
         self.device = torch.device(device)
         if self.device.type == 'cuda' and os.environ.get('SALSA_MIOPEN_FIND', '0') == '1':
@@ -110,7 +115,7 @@ class Trainer:
             self.grad_sync.begin()
         with torch.autocast(device_type=self.device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None):
             pred = self.model(x)
-        loss, sed_l, doa_l = seld_loss(pred, sed, doa)
+        loss, sed_l, doa_l = (accdoa_loss if self.output_format == 'accdoa' else seld_loss)(pred, sed, doa)
         loss.backward()
         if self.grad_sync is not None:
             self.grad_sync.finish()                # averaged gradients are in place
@@ -120,9 +125,14 @@ class Trainer:
 
     @torch.no_grad()
     def infer(self, x):
-        """eval forward (bf16 autocast): sigmoid SED probabilities and xyz at label rate (inference path, config 5)."""
+        """eval forward (bf16 autocast): SED activities and xyz at label rate (inference path, config 5).  The activities are the
+        sigmoid of the event logits (reg_xyz) or the length of each class's xyz vector (accdoa, salsa_nn_accdoa_sed)."""
         self.model.eval()
         x = self._input_layout(x)
         with torch.autocast(device_type=self.device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None):
             out = self.raw_model(x)
+        if self.output_format == 'accdoa':
+            from .nn_ops import accdoa_sed
+            xyz = out['doa_frame_output'].float()
+            return accdoa_sed(xyz, self.raw_model.decoder.n_classes), xyz
         return torch.sigmoid(out['event_frame_logit'].float()), out['doa_frame_output'].float()

@@ -1017,6 +1017,71 @@ __global__ __launch_bounds__(256) void seld_loss_scale_kernel(const float *__res
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------ ACCDOA loss
+// models/interfaces.py:284-302 (compute_classwise_accdoa_loss, output_format 'accdoa'): doa = sum over (rows, class) of
+// ((p_x - t_x)^2 + (p_y - t_y)^2 + (p_z - t_z)^2) m / rows with m = sed_gt; loss = doa (the reference's "sed" term is discarded).
+// The gradient 2 (p - t) m / rows needs no sum: the first launch writes it (and zeros for the event logits, which the loss does
+// not read) next to a float64 partial sum per workgroup; the second, one wavefront, adds the partials in a fixed order.
+constexpr int ACCDOA_BLOCKS = 64;
+__global__ __launch_bounds__(256) void accdoa_loss_partial_kernel(const float *__restrict__ doa, const float *__restrict__ sed_gt,
+                                                                  const float *__restrict__ doa_gt, long rows, int nc,
+                                                                  float *__restrict__ g_logit, float *__restrict__ g_doa,
+                                                                  double *__restrict__ partial /* [ACCDOA_BLOCKS] */)
+{
+    __shared__ double red[256];
+    const long n = rows * nc;
+    const float scale = 2.f / (float)rows;
+    double s = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)ACCDOA_BLOCKS * 256) {
+        const long r = i / nc;
+        const int c = (int)(i - r * nc);
+        const float z = sed_gt[i];
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const long j = r * 3 * nc + k * nc + c;
+            const float e = doa[j] - doa_gt[j];
+            a += e * e;
+            g_doa[j] = e * z * scale;
+        }
+        s += (double)(a * z);
+        if (g_logit) g_logit[i] = 0.f;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(64) void accdoa_loss_finish_kernel(const double *__restrict__ partial, long rows, float *__restrict__ out3)
+{
+    if (threadIdx.x != 0) return;
+    double t = 0.0;
+    for (int b = 0; b < ACCDOA_BLOCKS; b++) t += partial[b];
+    const float d = (float)(t / (double)rows);
+    out3[0] = d;
+    out3[1] = 0.f;
+    out3[2] = d;
+}
+
+// SED of the ACCDOA output (models/interfaces.py:260-268): sed[r][c] = sqrt(x^2 + y^2 + z^2) of the class's (x, y, z) in
+// float32, rounded as numpy rounds it: each square, (x^2 + y^2) + z^2 and the square root correctly rounded, no fma
+__global__ __launch_bounds__(256) void accdoa_sed_kernel(const float *__restrict__ xyz, float *__restrict__ sed, long rows, int nc)
+{
+#pragma clang fp contract(off)
+    const long n = rows * nc;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long r = i / nc;
+        const int c = (int)(i - r * nc);
+        const float *p = xyz + r * 3 * nc + c;
+        const float x = p[0], y = p[nc], z = p[2 * nc];
+        sed[i] = sqrtf((x * x + y * y) + z * z); // (HIP's sqrtf is the correctly rounded one; __fsqrt_rn is native_sqrt here)
+    }
+}
+
 } // namespace
 
 // One workspace PER DEVICE (round-4 advice: a single process-global pointer, re-pointed by whichever device ran a forward last,
@@ -1401,6 +1466,30 @@ int salsa_nn_seld_loss_bwd(const float *a, int64_t na, const float *b, int64_t n
     const long blocks = (na + nb + 255) / 256;
     hipLaunchKernelGGL(seld_loss_scale_kernel, dim3((unsigned)(blocks < 512 ? blocks : 512)), dim3(256), 0, (hipStream_t)hip_stream, a,
                        (long)na, b, (long)nb, g_loss, g_sed, g_doa, w_sed, w_doa, out_a, out_b);
+    return hipGetLastError() == hipSuccess ? 0 : -6;
+}
+
+/* ACCDOA training loss and its gradient (reference models/interfaces.py:273-302): sed_gt [rows][nc]; doa, doa_gt [rows][3 nc]
+ * float32 contiguous.  out3 = {loss, 0, doa loss}; g_doa = d doa / d prediction; g_logit (NULL: none) [rows][nc] zero-filled;
+ * partial_ws: SALSA_ACCDOA_LOSS_WS float64 values of scratch. */
+int salsa_nn_accdoa_loss(const float *doa, const float *sed_gt, const float *doa_gt, int64_t rows, int nc, float *out3, float *g_logit,
+                         float *g_doa, double *partial_ws, void *hip_stream)
+{
+    if (!doa || !sed_gt || !doa_gt || !out3 || !g_doa || !partial_ws || rows <= 0 || nc <= 0) return -1;
+    hipLaunchKernelGGL(accdoa_loss_partial_kernel, dim3(ACCDOA_BLOCKS), dim3(256), 0, (hipStream_t)hip_stream, doa, sed_gt, doa_gt,
+                       (long)rows, nc, g_logit, g_doa, partial_ws);
+    hipLaunchKernelGGL(accdoa_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, (const double *)partial_ws, (long)rows,
+                       out3);
+    return hipGetLastError() == hipSuccess ? 0 : -6;
+}
+
+/* sed [rows][nc] = sqrt(x^2 + y^2 + z^2) of xyz [rows][3 nc] (blocks x | y | z), float32, bit-equal to numpy's float32 */
+int salsa_nn_accdoa_sed(const float *xyz, float *sed, int64_t rows, int nc, void *hip_stream)
+{
+    if (!xyz || !sed || rows <= 0 || nc <= 0) return -1;
+    const long blocks = (rows * nc + 255) / 256;
+    hipLaunchKernelGGL(accdoa_sed_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)hip_stream, xyz,
+                       sed, (long)rows, nc);
     return hipGetLastError() == hipSuccess ? 0 : -6;
 }
 

@@ -7,9 +7,11 @@ JSON line per (decoder_type, freq_pool, LSTM path): median / 10th / 90th percent
 The LSTM path is the one selected by SALSA_FUSED_LSTM when the process starts (1: the HIP scans, 0: nn.LSTM on MIOpen).  With
 --unfused-leg the tool runs the lstm / bilstm decoders once more in a CHILD process started with SALSA_FUSED_LSTM=0 and a time
 limit (--child-timeout): a step that does not finish in time is recorded as such ("trains": false) instead of stopping the bench.
+--output-format accdoa trains with the ACCDOA loss and infers its SED decision (the default, reg_xyz, writes the records as before;
+other values add an "output_format" key).
 
     python tools/bench_crnn_decoders.py [--steps 20] [--warmup 3] [--decoders gru,bigru,lstm,bilstm] [--pools avg,max,avg_max]
-                                        [--out profiles/crnn_decoders_bench.jsonl] [--unfused-leg]"""
+                                        [--out profiles/crnn_decoders_bench.jsonl] [--unfused-leg] [--output-format accdoa]"""
 import argparse
 import json
 import os
@@ -43,7 +45,7 @@ def run(args):
     clips = torch.randn((args.batch, 7, 4800, 200), device=dev, generator=g)          # 60-s clips at 80 frames/s
     for dt in args.decoders.split(','):
         for fp in args.pools.split(','):
-            tr = Trainer(dev, total_steps=10 ** 6, decoder_type=dt, freq_pool=fp)
+            tr = Trainer(dev, total_steps=10 ** 6, decoder_type=dt, freq_pool=fp, output_format=args.output_format)
             for _ in range(args.warmup):
                 tr.train_step(x, sed, doa)
             torch.cuda.synchronize()
@@ -69,6 +71,8 @@ def run(args):
                        train_steps=len(train), **_stats('train_step', train), train_chunks_per_s=round(args.batch / (sorted(train)[len(train) // 2]), 1),
                        infer_calls=len(infer), **_stats('infer_60s_batch', infer), loss=round(float(loss), 5), trains=True,
                        gpu=torch.cuda.get_device_name(0))
+            if args.output_format != 'reg_xyz':
+                rec['output_format'] = args.output_format
             lines.append(json.dumps(rec))
             print(lines[-1], flush=True)
             del tr
@@ -82,7 +86,8 @@ def unfused_leg(args):
     """the lstm / bilstm decoders with SALSA_FUSED_LSTM=0, in a child process under a time limit"""
     for dt in [d for d in args.decoders.split(',') if 'lstm' in d]:
         cmd = [sys.executable, os.path.abspath(__file__), '--steps', str(args.steps), '--warmup', str(args.warmup), '--infer-steps',
-               str(args.infer_steps), '--batch', str(args.batch), '--decoders', dt, '--pools', 'avg'] + (['--out', args.out] if args.out else [])
+               str(args.infer_steps), '--batch', str(args.batch), '--decoders', dt, '--pools', 'avg',
+               '--output-format', args.output_format] + (['--out', args.out] if args.out else [])
         env = dict(os.environ, SALSA_FUSED_LSTM='0')
         try:
             rc = subprocess.run(cmd, env=env, timeout=args.child_timeout).returncode
@@ -110,6 +115,7 @@ def main():
     ap.add_argument('--out', default=None, help='append the JSON lines to this file too')
     ap.add_argument('--unfused-leg', action='store_true', help='only the SALSA_FUSED_LSTM=0 leg (child processes)')
     ap.add_argument('--child-timeout', type=int, default=240)
+    ap.add_argument('--output-format', default='reg_xyz', choices=('reg_xyz', 'accdoa'), help="the YAML's data.output_format")
     args = ap.parse_args()
     if args.unfused_leg:
         sys.exit(0 if unfused_leg(args) == 0 else 1)
