@@ -2,6 +2,7 @@
 The CPU / non-channels-last / odd-channel cases fall through to the torch operator of the same name -- the CRNN is the
 consumer of the feature path, its CPU tests run the model on CPU tensors."""
 import ctypes as C
+import functools
 import os
 
 import torch
@@ -1032,6 +1033,14 @@ C64_STATS_MIN_PIX = int(os.environ.get('SALSA_C64_STATS_MIN_PIX', '0'))   # ... 
 USE_WIDE_CONV_STATS = os.environ.get('SALSA_WIDE_CONV_STATS', '1') != '0'   # the same in the wide kernels' epilogue
 
 
+@functools.lru_cache(maxsize=256)
+def _c64_map_ok(N, H, W):
+    """The 64 -> 64 and first-layer kernels take a map of N x H x W pixels (32-bit element offsets at 64 channels: every entry
+    point refuses N H W >= INT32_MAX / 64).  The library is asked (its host-only plan query applies the entry points' own
+    test), as _wide_eligible asks salsa_nn_conv3x3_wide_supported: a rule restated here accepted one map the kernels refuse."""
+    return _lib.load().salsa_nn_conv3x3_c64_config(N, H, W, C.byref(C.c_int(0))) != -1
+
+
 class Conv3x3(torch.nn.Conv2d):
     """nn.Conv2d(cin, cout, 3, padding=1, bias=False) whose 64 -> 64 instances run the MFMA kernel for bf16 channels-last
     CUDA inputs (i.e. under the trainer's autocast) and whose (Cin <= 8) -> 64 instance -- the network's first layer -- runs
@@ -1042,14 +1051,14 @@ class Conv3x3(torch.nn.Conv2d):
                 and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16
                 and (self.in_channels <= 8 or (USE_HIP_STEM16 and self.in_channels <= 16)) and self.out_channels == 64 and self.kernel_size == (3, 3) and self.stride == (1, 1)
                 and self.padding == (1, 1) and self.bias is None and self.dilation == (1, 1) and self.groups == 1
-                and not x.requires_grad and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31 // 64)
+                and not x.requires_grad and _c64_map_ok(x.shape[0], x.shape[2], x.shape[3]))
 
     def _hip_eligible(self, x):
         bf16 = x.dtype == torch.bfloat16 or (x.is_cuda and torch.is_autocast_enabled('cuda') and
                                              torch.get_autocast_dtype('cuda') == torch.bfloat16)
         return (USE_HIP_CONV and x.is_cuda and bf16 and self.in_channels == 64 and self.out_channels == 64 and x.dim() == 4
                 and self.kernel_size == (3, 3) and self.stride == (1, 1) and self.padding == (1, 1) and self.bias is None
-                and self.dilation == (1, 1) and self.groups == 1 and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31 // 64)
+                and self.dilation == (1, 1) and self.groups == 1 and _c64_map_ok(x.shape[0], x.shape[2], x.shape[3]))
 
     def _wide_eligible(self, x):
         bf16 = x.dtype == torch.bfloat16 or (x.is_cuda and torch.is_autocast_enabled('cuda') and

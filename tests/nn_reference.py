@@ -50,6 +50,71 @@ def conv_fwd_ref(x, w, shift=None, residual=None, relu=False):
     return ref, absum
 
 
+_STREAM_PIX = 1 << 17       # pixels per piece of conv_fwd_ref_stream (its unfold: 128 Ki x 9 Cin doubles, twice)
+
+
+def conv_fwd_ref_stream(x, w, shift=None, residual=None, relu=False, pool=False, max_pix=_STREAM_PIX):
+    """conv_fwd_ref piece by piece, for maps whose whole-batch float64 tensors must never exist (32 x 64 x 4800 x 200: 2 x 15.7
+    GB).  Yields ((n, h0, h1), ref, absum): clip n, OUTPUT rows h0 .. h1 - 1, ref / absum float64 (1, Cout, h1 - h0, Wout).  A
+    piece is a band of at most max_pix input pixels of ONE clip; its one-row halo comes from the neighbouring rows of the same
+    clip and is zero only at the clip's true top and bottom border, never the row of another clip or of a band's edge.
+    pool=True (H and W even, bands of whole row pairs): ref = avgpool2x2([relu](conv + shift + residual)), absum = the 2x2 mean
+    of the per-pixel absum; the bound of such an output is bf16_bound(ref, absum, pooled_conv_c(n_terms))."""
+    k = w.shape[-1]
+    p = k // 2
+    N, _, H, W = x.shape
+    assert not pool or (H % 2 == 0 and W % 2 == 0)
+    wd = w.double().reshape(w.shape[0], -1)
+    wa = wd.abs()
+    step = max(1, max_pix // W)
+    if pool:
+        step = max(2, step - step % 2)
+    sh = None if shift is None else shift.double().view(1, -1, 1, 1)
+    for n in range(N):
+        for h0 in range(0, H, step):
+            h1 = min(H, h0 + step)
+            lo, hi = max(0, h0 - p), min(H, h1 + p)
+            xs = F.pad(x[n:n + 1, :, lo:hi].double(), (0, 0, lo - (h0 - p), (h1 + p) - hi))   # zero rows at the clip's border only
+            cols = F.unfold(xs, k, padding=(0, p))                                            # (1, Cin k k, (h1 - h0) W)
+            ref = torch.matmul(wd, cols).view(1, -1, h1 - h0, W)
+            absum = torch.matmul(wa, cols.abs_()).view(1, -1, h1 - h0, W)
+            del cols, xs
+            if sh is not None:
+                ref += sh
+                absum += sh.abs()
+            if residual is not None:
+                r = residual[n:n + 1, :, h0:h1].double()
+                ref += r
+                absum += r.abs()
+            if relu:
+                ref.clamp_(min=0)
+            if pool:
+                yield (n, h0 // 2, h1 // 2), F.avg_pool2d(ref, 2), F.avg_pool2d(absum, 2)
+            else:
+                yield (n, h0, h1), ref, absum
+
+
+def pooled_conv_c(n_terms):
+    """c for salsa_nn_conv3x3_c64_bias_act_pool's output against conv_fwd_ref_stream(pool=True).  After the accumulator, the
+    shift and the residual (conv_accum_c), conv64_epilogue<true> in conv_mfma.hip forms a pooled value from the four float32
+    v = [relu](acc + shift + residual) as
+        s = 0 + v(row 0); s += v(row 1)           one float32 addition (the first adds to 0: exact)
+        s = 0.25 * (s + shfl_xor(s, 1))           one float32 addition; the product with 2^-2 is exact
+    and rounds once to bf16: k = 2 additions, each within u of a partial sum of the four |v|, so 2 u sum|v| / 4 <= 2 u mean(absum)
+    (|v| <= absum; ReLU is 1-Lipschitz and only shrinks |v|).  The four v's own accumulation errors, c absum each, average to
+    c mean(absum).  Hence c = conv_accum_c(n_terms) + 2 u on the 2x2 mean of absum."""
+    return conv_accum_c(n_terms) + 2 * U32
+
+
+def avgpool_bound(x):
+    """(ref, bound) of salsa_nn_avgpool2x2_fwd on bf16 input: avgpool2x2_fwd_kernel in nn_ops.hip forms (((a + b) + c) + d) / 4
+    in float32 -- three additions, each within u of a partial sum <= sum|x|, an exact division by 4 -- and rounds once to
+    bf16: |y - ref| <= 2^-8 |ref| + (1 + 2^-8) 3 u mean|x|."""
+    xd = x.double()
+    ref = F.avg_pool2d(xd, 2)
+    return ref, BF16_REL * ref.abs() + (1 + BF16_REL) * 3 * U32 * F.avg_pool2d(xd.abs(), 2)
+
+
 def conv_wgrad_ref(x, gy, k=3):
     """(ref, absum) float64 (Cout, Cin, k, k): ref = sum over pixels of gy * x(shifted), absum = the same of |gy| |x|."""
     N, Cin, H, W = x.shape

@@ -15,6 +15,10 @@ Two families of maps.  SALSA and the lin baseline features have 200 frequency bi
   wide weight gradient        W = 50 / 25 / 12: own instantiation  W = 32 / 16 / 8: the generic (W2C = 0) one, three buffers
   BatchNorm, 1 x 1 rows M     1 024 000 ... 15 360                 655 360 ... 10 240
   frequency mean              12 bins                              8 bins
+
+The stem's 640-row maps in training and the maps of 60-s inference (4800 x 200 down to 300 x 12; the 1024-workgroup grid of the
+64 -> 64 kernels, the fused pool, the 512-pixel wide tile at W = 12 / 8) are in tests/test_nn_kernels_full_res_gpu.py, with a
+streamed float64 reference; only the frequency mean at 300 rows is a parameter here.
 """
 import pytest
 import torch
@@ -286,7 +290,7 @@ def test_batchnorm_train_forward_backward_at_bench_size(stage, pool, dtype):
 
 
 # --------------------------------------------------------------------------------------------- frequency mean
-@pytest.mark.parametrize('shape', [(32, 512, 40, 12), (32, 512, 40, 8)])
+@pytest.mark.parametrize('shape', [(32, 512, 40, 12), (32, 512, 40, 8), (32, 512, 300, 12), (32, 512, 300, 8)])    # (300 rows: 60-s inference)
 def test_frequency_mean_forward_and_backward_at_bench_size(shape):
     """salsa_nn_freq_mean_fwd / _bwd as freq_mean_sequence calls them (time-major float32 buffer) against float64.  Forward: a
     sequential float32 sum of W terms ((W - 1) u of the sum of |x|), times fl(1 / W) (u of the mean for fl(1 / W), u for the

@@ -303,3 +303,146 @@ def test_batchnorm_reference_matches_torch_batch_norm():
         assert torch.allclose(r['y'], y.detach())
         for k, t in (('dx', xa), ('dres', ra), ('dgamma', ga), ('dbeta', ba)):
             assert torch.allclose(b[k], t.grad, atol=1e-10), k
+
+
+# ------------------------------------------------------------------------------------------------ the streamed reference
+def _stream_case(seed, n=3, cin=16, cout=8, h=10, w=6):
+    g = torch.Generator().manual_seed(seed)
+    x = _bf16(torch.randn(n, cin, h, w, generator=g) + torch.linspace(-1, 2, cin).view(1, -1, 1, 1))
+    wt = _bf16(torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5)
+    shift = torch.randn(cout, generator=g)
+    res = _bf16(torch.randn(n, cout, h, w, generator=g))
+    return x, wt, shift, res
+
+
+def _stream_check(y, x, wt, cin, pool=False, max_pix=24, **kw):
+    """nr.check of y piece by piece against the streamed reference, as the GPU tests call it -> the maximum ratio"""
+    c = nr.pooled_conv_c(9 * cin) if pool else nr.conv_accum_c(9 * cin)
+    worst, rows = 0.0, 0
+    for (n, a, b), ref, absum in nr.conv_fwd_ref_stream(x, wt, pool=pool, max_pix=max_pix, **kw):
+        worst = max(worst, nr.check(y[n:n + 1, :, a:b], ref, nr.bf16_bound(ref, absum, c), 'clip %d rows %d:%d' % (n, a, b)))
+        rows += b - a
+    assert rows == y.shape[0] * y.shape[2]                            # every row of every clip exactly once
+    return worst
+
+
+def test_streamed_reference_equals_the_whole_batch_one_piece_by_piece():
+    """bands of 4 (pooled: 4) rows cut through every clip of a ragged 3 x 9 x 11 map (and a 3 x 10 x 6 one, pooled): each
+    piece equals conv_fwd_ref (+ F.avg_pool2d) on the same rows, with and without shift / residual / ReLU, and 1x1 filters"""
+    g = torch.Generator().manual_seed(6)
+    x = _bf16(torch.randn(3, 16, 9, 11, generator=g) + 0.5)
+    wt = _bf16(torch.randn(8, 16, 3, 3, generator=g) * 0.1)
+    shift, res = torch.randn(8, generator=g), _bf16(torch.randn(3, 8, 9, 11, generator=g))
+    for kw in (dict(), dict(shift=shift, relu=True), dict(shift=shift, residual=res, relu=True), dict(residual=res)):
+        ref, absum = nr.conv_fwd_ref(x, wt, **kw)
+        pieces = list(nr.conv_fwd_ref_stream(x, wt, max_pix=44, **kw))
+        assert [p[0] for p in pieces] == [(n, a, min(9, a + 4)) for n in range(3) for a in (0, 4, 8)]
+        for (n, a, b), r, s in pieces:
+            assert torch.allclose(r, ref[n:n + 1, :, a:b], rtol=1e-13, atol=1e-13) and torch.allclose(s, absum[n:n + 1, :, a:b], rtol=1e-13)
+    w1 = _bf16(torch.randn(8, 16, 1, 1, generator=g))
+    ref, absum = nr.conv_fwd_ref(x, w1, shift=shift)
+    for (n, a, b), r, s in nr.conv_fwd_ref_stream(x, w1, shift=shift, max_pix=30):
+        assert torch.allclose(r, ref[n:n + 1, :, a:b], rtol=1e-13, atol=1e-13) and torch.allclose(s, absum[n:n + 1, :, a:b], rtol=1e-13)
+    x, wt, shift, res = _stream_case(7)
+    ref, absum = nr.conv_fwd_ref(x, wt, shift=shift, residual=res, relu=True)
+    ref, absum = torch.nn.functional.avg_pool2d(ref, 2), torch.nn.functional.avg_pool2d(absum, 2)
+    pieces = list(nr.conv_fwd_ref_stream(x, wt, shift=shift, residual=res, relu=True, pool=True, max_pix=24))
+    assert [p[0] for p in pieces] == [(n, a, min(5, a + 2)) for n in range(3) for a in (0, 2, 4)]      # 4 input rows = 2 pooled
+    for (n, a, b), r, s in pieces:
+        assert torch.allclose(r, ref[n:n + 1, :, a:b], rtol=1e-13, atol=1e-13) and torch.allclose(s, absum[n:n + 1, :, a:b], rtol=1e-13)
+    assert nr.pooled_conv_c(576) == nr.conv_accum_c(576) + 2 * nr.U32
+
+
+def test_streamed_checker_accepts_float32_evaluations():
+    x, wt, shift, res = _stream_case(8)
+    v = nr.conv_fwd_ref(x, wt, shift=shift, residual=res, relu=True)[0].float()        # the float32 value before the rounding
+    assert _stream_check(_bf16(v), x, wt, 16, shift=shift, residual=res, relu=True) <= 1
+    pooled = 0.25 * ((v[:, :, 0::2, 0::2] + v[:, :, 1::2, 0::2]) + (v[:, :, 0::2, 1::2] + v[:, :, 1::2, 1::2]))   # the kernel's order
+    assert _stream_check(_bf16(pooled), x, wt, 16, pool=True, shift=shift, residual=res, relu=True) <= 1
+
+
+def test_streamed_checker_rejects_a_tap_lost_or_bled_at_the_first_row_of_clip_1():
+    x, wt, shift, res = _stream_case(9)
+    ref, _ = nr.conv_fwd_ref(x, wt)
+    assert _stream_check(_bf16(ref.float()), x, wt, 16) <= 1
+    # (i) pixel (clip 1, row 0, column 2) loses the tap below-left
+    bad = ref.clone()
+    bad[1, :, 0, 2] -= (wt[:, :, 2, 0] * x[1, :, 1, 1][None]).sum(1)
+    with pytest.raises(AssertionError):
+        _stream_check(_bf16(bad.float()), x, wt, 16)
+    # (ii) the batch walked as one tall image: clip 1's first row takes clip 0's last row for its upper halo instead of zeros
+    bleed = ref.clone()
+    up = torch.nn.functional.pad(x[0, :, -1], (1, 1))                                  # (Cin, W + 2)
+    for s in range(3):
+        bleed[1, :, 0, :] += wt[:, :, 0, s] @ up[:, s:s + x.shape[3]]
+    with pytest.raises(AssertionError):
+        _stream_check(_bf16(bleed.float()), x, wt, 16)
+
+
+def test_streamed_checker_rejects_a_pool_of_bf16_rounded_pixels_on_five_percent():
+    """the fused pool must average the float32 values and round once; rounding the four pixels first is what an unfused
+    convolution + pool does, and on 5 % of the outputs it must not pass"""
+    x, wt, shift, res = _stream_case(10, n=4, cin=64, cout=32, h=12, w=16)
+    kw = dict(shift=shift, residual=res, relu=True)
+    v = nr.conv_fwd_ref(x, wt, **kw)[0].float()
+    pool = lambda t: 0.25 * ((t[:, :, 0::2, 0::2] + t[:, :, 1::2, 0::2]) + (t[:, :, 0::2, 1::2] + t[:, :, 1::2, 1::2]))
+    good, early = _bf16(pool(v)), _bf16(pool(v.to(torch.bfloat16).float()))
+    assert _stream_check(good, x, wt, 64, pool=True, max_pix=64, **kw) <= 1
+    pick = torch.rand(good.shape, generator=torch.Generator().manual_seed(10)) < 0.05
+    with pytest.raises(AssertionError):
+        _stream_check(torch.where(pick, early, good), x, wt, 64, pool=True, max_pix=64, **kw)
+
+
+def test_streamed_checker_rejects_a_residual_shifted_by_one_pixel():
+    x, wt, shift, res = _stream_case(11)
+    moved = torch.roll(res, 1, dims=3)                                                   # the residual of the pixel to the left
+    for pool in (False, True):
+        y = nr.conv_fwd_ref(x, wt, shift=shift, residual=moved, relu=True)[0].float()
+        if pool:
+            y = torch.nn.functional.avg_pool2d(y, 2)
+        with pytest.raises(AssertionError):
+            _stream_check(_bf16(y), x, wt, 16, pool=pool, shift=shift, residual=res, relu=True)
+
+
+# ------------------------------------------------------------------------------------------------ the full-resolution maps
+# (N, H, W) -> (tiles, transposed) of the largest 64 -> 64 launches: the stem's second convolution in training and the
+# inference path of a 60-s clip; every one has >= 16384 tiles, i.e. the 1024-workgroup persistent grid
+C64_FULL_RES = [((32, 640, 200), (32000, 1)), ((32, 640, 128), (20480, 0)),
+                ((32, 4800, 200), (240000, 1)), ((32, 2400, 100), (60000, 1)),
+                ((32, 4800, 128), (153600, 0)), ((32, 2400, 64), (38400, 0))]
+# (N, H, W, Cout) of the wide layers at inference (200-bin and 128-bin features): all take 512-pixel tiles
+WIDE_FULL_RES = [(32, 1200, 50, 128), (32, 600, 25, 256), (32, 300, 12, 512), (32, 1200, 32, 128), (32, 600, 16, 256), (32, 300, 8, 512)]
+
+
+def test_c64_geometry_and_grid_at_the_full_resolution_maps(lib):
+    for (n, h, w), geo in C64_FULL_RES:
+        assert c64_config(lib, n, h, w) == geo == c64_plan(n, h, w), (n, h, w)
+        assert geo[0] >= 16384 and lib.salsa_nn_conv3x3_c64_stats_blocks(n, h, w) == 1024, (n, h, w)
+    # the residual stage of an 8-s chunk, where the kernel tests stopped: the 512-workgroup grid
+    assert lib.salsa_nn_conv3x3_c64_stats_blocks(32, 320, 100) == 512 and lib.salsa_nn_conv3x3_c64_stats_blocks(32, 320, 64) == 512
+    # the weight gradient plans with the same 4 x 32 tiles: 512 workgroups (tiles >= 16384) of 63 / 40 tiles each; c64_wgrad_c
+    # counts the untransposed grid (70 at 640 x 200), an upper bound of the chain
+    assert -(-c64_plan(32, 640, 200)[0] // 512) == 63 and -(-c64_plan(32, 640, 128)[0] // 512) == 40
+    assert nr.c64_wgrad_c(32, 640, 200) == (70 * 8 + 16 + 512) * nr.U32 and nr.c64_wgrad_c(32, 640, 128) == (40 * 8 + 16 + 512) * nr.U32
+
+
+def test_wide_dispatch_at_the_inference_maps(lib):
+    for n, h, w, cout in WIDE_FULL_RES:
+        assert config(lib, n, h, w, cout) == wide_tile(n, h, w, cout) == (512, 128), (n, h, w, cout)
+        for cin in (cout // 2, cout):                                # the first and the second convolution of a block
+            assert lib.salsa_nn_conv3x3_wide_supported(n, h, w, cin, cout), (n, h, w, cin, cout)
+    assert config(lib, 32, 40, 12, 512) == (256, 128)                # (training's 40 x 12 does not reach 512-pixel tiles at W = 12)
+
+
+def test_python_eligibility_agrees_with_the_library_at_the_pixel_limit(lib):
+    """Conv3x3._hip_eligible / _stem_eligible take their size condition from nn_ops._c64_map_ok; the kernels refuse
+    N H W >= INT32_MAX / 64 = 33 554 431 pixels.  Both sides of the limit, host only (nothing is allocated)."""
+    from salsa_amd.crnn import nn_ops
+    tr = C.c_int(0)
+    for shape, ok in (((1, 33554430, 1), True), ((1, 33554431, 1), False), ((1, 33554432, 1), False), ((33554430, 1, 1), True),
+                      ((31, 1801, 601), False), ((32, 4800, 200), True), ((35, 4800, 200), False), ((2, 8, 8), True), ((0, 8, 8), False)):
+        n, h, w = shape
+        assert (lib.salsa_nn_conv3x3_c64_config(n, h, w, C.byref(tr)) != -1) == ok, shape
+        assert bool(nn_ops._c64_map_ok(n, h, w)) == ok, shape
+        assert (lib.salsa_nn_conv3x3_c64_stats_blocks(n, h, w) > 0) == ok, shape
+    assert 31 * 1801 * 601 == 33554431
