@@ -63,7 +63,9 @@ enum {
     SALSA_PARTIAL = 1,     /* measurement mode only (salsa_plan_set_timing(plan, -1 | -2)): a PREFIX of the path was issued, the
                             * output planes hold whatever an earlier full call left there -- never returned by a plain call */
     SALSA_EINVAL = -1,     /* bad argument (NULL pointer, negative size, ...) */
-    SALSA_ENFFT = -2,      /* n_fft not in {256, 512}: the reference's assert, salsa_feature_extraction.py:152,306 */
+    SALSA_ENFFT = -2,      /* full SALSA: n_fft not in {256, 512}, the reference's assert, salsa_feature_extraction.py:152,306.
+                            * SALSA-Lite / SALSA-IPD (whose script has no such assert): n_fft not in {256, 512, 1024} -- a restriction of
+                            * this library; 1024 is not taken with SALSA_FLAG_FLEX, nor by salsa_logspec_batch / salsa_compress_matrix */
     SALSA_EFORMAT = -3,    /* unknown audio format: the reference's ValueError, :125,:332 ; lite requires MIC, lite :72 */
     SALSA_EBINS = -4,      /* upper_bin > cutoff_bin (lite :59) or an empty / oversized DOA band */
     SALSA_EWORKSPACE = -5, /* workspace smaller than salsa_workspace_bytes() */
@@ -158,7 +160,7 @@ int salsa_plan_set_stats(salsa_plan *plan, unsigned long long *d_counters);
 
 /* compute_scaler (salsa_feature_extraction.py:204-262) on device: accumulate float64 sum / sum-of-squares over time of
  * the first n_scaler_channels channels per frequency into d_sums [2][n_scaler_channels][n_freq] (zeroed by the caller
- * once; mean = sum/n, std = sqrt(sumsq/n - mean^2), population variance like sklearn's StandardScaler).  n_freq <= 256. */
+ * once; mean = sum/n, std = sqrt(sumsq/n - mean^2), population variance like sklearn's StandardScaler). */
 int salsa_scaler_accumulate(const float *d_feat, int batch, int n_channels, int64_t n_frames, int n_freq,
                             int n_scaler_channels, double *d_sums, void *hip_stream);
 /* normalise-on-load (dataset/database.py:197-202): d_feat[:, :n_scaler_channels] = (x - mean) / std in place;

@@ -101,9 +101,19 @@ constexpr int FEATURE_LOGSPEC_ONLY = 3;
 // from registers: 10*log10 of the power into output channels c0, c1 and the DOA band of both channels as ONE float4
 // per bin into the spill.  A wave walks K1_NF consecutive frames x 2 pairs (no software prefetch: the registers it would
 // need cost a wave per SIMD, measured slower); the first twiddle of each pass lives in registers, the window in LDS.
+//
+// N = 1024 (SALSA-Lite / IPD only): 64 lanes x 16 points.  Rather than a 16 KB wave-private buffer and a radix-16 (or a fifth
+// radix-4) pass, the wave runs the 512-point plan TWICE -- on the even and on the odd samples, through the same 8 KB buffer -- and
+// joins the halves in registers with one decimation-in-time radix-2 step: Z[k] = E[k] + W_1024^k O[k], Z[k + 512] = E[k] - W_1024^k O[k].
+// Lane L holds E[L + 64 r] and O[L + 64 r] after the sub-transforms, so the join needs no exchange and leaves Z[L + 64 r], r < 16, in
+// the lane: the ownership the unpack wants.  W_1024^(L + 64 r) = W_1024^L (one register pair) times W_16^r (compile-time constants).
+// Same LDS round trips per point as a 16 x 16 x 4 plan (two), and the LDS per workgroup stays that of the 512-point kernel plus
+// the longer window table.
 template <int N> struct fft_cfg {
-    static constexpr int R = (N == 512) ? 8 : 4;                 // points per lane; 64 lanes per transform either way
-    static constexpr int NP = (N == 512) ? 2 : 3;                // twiddled passes (p = R, R^2, ...)
+    static constexpr int NSUB = (N == 1024) ? 2 : 1;             // sub-transforms per item (even / odd samples), joined in registers
+    static constexpr int NS = N / NSUB;                          // length of one Stockham transform
+    static constexpr int R = (NS == 512) ? 8 : 4;                // points per lane of one transform; 64 lanes per transform either way
+    static constexpr int NP = (NS == 512) ? 2 : 3;               // twiddled passes (p = R, R^2, ...)
 };
 
 __device__ __forceinline__ int swz(int e) { return e ^ ((e >> 3) & 7); }
@@ -228,6 +238,9 @@ template <> struct k1_x0_store<false> {
 #ifndef K1_LITE_WAVES
 #define K1_LITE_WAVES 1 // workgroups per CU the SALSA-Lite / IPD instantiations are compiled for (1: no register cap -> 184 VGPRs, 2 waves per SIMD)
 #endif
+#ifndef K1_LITE_1024_WAVES
+#define K1_LITE_1024_WAVES 1 // waves per SIMD the n_fft 1024 SALSA-Lite / IPD instantiation is compiled for (sixteen float64 points per lane: 256 VGPRs + 39 AGPRs, no scratch; capped at 2 waves = 256 registers the compiler spills 52 registers to scratch)
+#endif
 #ifndef K1_NF_LITE
 #define K1_NF_LITE 8 // frames per wave of the SALSA-Lite / IPD instantiations
 #endif
@@ -247,7 +260,7 @@ template <bool LITE> struct k1_cfg {
 // arithmetic in the same order: outputs are bit-identical (tests: goldens, fused-vs-three-kernel identity).  The DOA band stays a
 // run-time range (FOA 1..192, MIC 1..85, any fmin / fmax).
 template <int N, typename T, bool LITE, int NF, int NPAIRS = 2, bool SC = false, bool STD = false>
-__global__ __launch_bounds__(256, LITE ? (STD ? K1_LITE_STD_WAVES : K1_LITE_WAVES) : SC ? 3 : 1) void stft_kernel(const KParams kp, const float *__restrict__ audio,
+__global__ __launch_bounds__(256, LITE ? (STD ? K1_LITE_STD_WAVES : N == 1024 ? K1_LITE_1024_WAVES : K1_LITE_WAVES) : SC ? 3 : 1) void stft_kernel(const KParams kp, const float *__restrict__ audio,
                                                    const double *__restrict__ window,
                                                    const cplx<double> *__restrict__ tw, float *__restrict__ out,
                                                    float4 *__restrict__ Xs)
@@ -255,7 +268,10 @@ __global__ __launch_bounds__(256, LITE ? (STD ? K1_LITE_STD_WAVES : K1_LITE_WAVE
     constexpr int R = fft_cfg<N>::R;
     constexpr int NP = fft_cfg<N>::NP;
     constexpr int NB = N / 2 + 1;
-    __shared__ cplx<T> buf[4][N];
+    constexpr int NS = fft_cfg<N>::NS, NSUB = fft_cfg<N>::NSUB; // N = 1024: two NS-point transforms per item (even / odd samples)
+    constexpr int RL = R * NSUB;                                 // points per lane of the N-point transform
+    static_assert(NSUB == 1 || (LITE && !SC && !STD && NPAIRS == 2), "n_fft 1024 is a SALSA-Lite / IPD size only");
+    __shared__ cplx<T> buf[4][NS];
     __shared__ __attribute__((aligned(16))) float pw[4][2][64]; // powers of the compressed band (<= 63 bins) of the wave's two channels (STD reads them 16 bytes at a time)
 
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -287,10 +303,12 @@ __global__ __launch_bounds__(256, LITE ? (STD ? K1_LITE_STD_WAVES : K1_LITE_WAVE
         int p = R;
 #pragma unroll
         for (int q = 0; q < NP; q++, p *= R) {
-            const cplx<double> wd = tw[salsa::stockham_tw(lane, 1, p, N, R)];
+            const cplx<double> wd = tw[NSUB * salsa::stockham_tw(lane, 1, p, NS, R)]; // (the table holds W_N^m)
             w1[q] = {(T)wd.re, (T)wd.im};
         }
     }
+    cplx<T> wj = {(T)1, (T)0}; // N = 1024: W_N^lane, the lane's part of the twiddles that join the two half transforms
+    if constexpr (NSUB == 2) wj = {(T)tw[lane].re, (T)tw[lane].im};
     if (t_begin >= Tn) return; // wave-uniform; nothing below uses a workgroup barrier
     // channel pairs per clip: 2 (the dataset scripts), 3 / 4 on the contrib surface; NPAIRS == 0: any count, read from kp.nch
     // (9 - 16 microphones: one instantiation, the index arithmetic below is all that depends on it)
@@ -336,7 +354,9 @@ __global__ __launch_bounds__(256, LITE ? (STD ? K1_LITE_STD_WAVES : K1_LITE_WAVE
         const unsigned ch0 = 4u * (unsigned)(planar ? c0 * Ns : c0), ch1 = ch0 + 4u * (unsigned)(planar ? Ns : 1); // byte offsets
         const unsigned step = 4u * (unsigned)sstride;
         if (base >= 0 && base + N <= Ns) {
-            const unsigned q = (unsigned)(base + lane) * step;
+            const unsigned q = (unsigned)(base + NSUB * lane) * step;
+#pragma unroll
+            for (int u = 0; u < NSUB; u++)
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 if (STD) { // planar, 4-byte stride: the eight strided points of a channel are one address + immediates r * 256 (tried for every
@@ -344,24 +364,26 @@ __global__ __launch_bounds__(256, LITE ? (STD ? K1_LITE_STD_WAVES : K1_LITE_WAVE
                     y0[r] = ld_off_c(clip, ch0 + q, r * (N / R) * 4);
                     y1[r] = ld_off_c(clip, ch1 + q, r * (N / R) * 4);
                 } else {
-                    y0[r] = ld_off(clip, ch0 + q + (unsigned)(r * (N / R)) * step);
-                    y1[r] = ld_off(clip, ch1 + q + (unsigned)(r * (N / R)) * step);
+                    y0[u * R + r] = ld_off(clip, ch0 + q + (unsigned)(NSUB * r * (NS / R) + u) * step); // (sub-transform u: samples u, u + NSUB, ...)
+                    y1[u * R + r] = ld_off(clip, ch1 + q + (unsigned)(NSUB * r * (NS / R) + u) * step);
                 }
             }
         } else {
 #pragma unroll
+            for (int u = 0; u < NSUB; u++)
+#pragma unroll
             for (int r = 0; r < R; r++) {
-                int s = base + salsa::stockham_in(lane, r, N, R);
+                int s = base + NSUB * salsa::stockham_in(lane, r, NS, R) + u;
                 s = s < 0 ? -s : s;
                 s = s >= Ns ? 2 * (Ns - 1) - s : s;
-                y0[r] = ld_off(clip, ch0 + (unsigned)s * step);
-                y1[r] = ld_off(clip, ch1 + (unsigned)s * step);
+                y0[u * R + r] = ld_off(clip, ch0 + (unsigned)s * step);
+                y1[u * R + r] = ld_off(clip, ch1 + (unsigned)s * step);
             }
         }
     };
 
     const int nitems = psel >= 0 ? nfr_ : nfr_ * npairs;
-    float y0[R], y1[R];
+    float y0[RL], y1[RL];
     float *o = out + (long)b * kp.OC * Tn * kp.F; // [OC][T][F] of this clip (int offsets below)
     float4 *xs = Xs + (long)b * Tn * npairs * kp.nd;
     const int mlane = (64 - lane) & 63;           // lane holding the mirror bins N-k of this lane's bins
@@ -377,49 +399,71 @@ __global__ __launch_bounds__(256, LITE ? (STD ? K1_LITE_STD_WAVES : K1_LITE_WAVE
         return kp.sc_mean ? (v - ld_off(kp.sc_mean, off)) / ld_off(kp.sc_std, off) : v;
     };
     const unsigned plane = 4u * (unsigned)(Tn * kp.F); // bytes of one output channel of a clip
-    float2 x0keep[(LITE && STD) ? 1 : R / 2 + 1]; // SALSA-Lite: channel-0 spectrum of this lane's bins, kept from pair 0 for pair 1 (Lite STD: in LDS)
+    float2 x0keep[(LITE && STD) ? 1 : RL / 2 + 1]; // SALSA-Lite: channel-0 spectrum of this lane's bins, kept from pair 0 for pair 1 (Lite STD: in LDS)
     float2 *const x0s = k1_x0_store<LITE && STD>::get() + (LITE && STD ? w * K1_LITE_X0_SLOTS * 64 + lane : 0);
 
     for (int item = 0; item < nitems; item++) {
         const int t = t_begin + K1_TSTEP * item_frame(item);
         const int pr = item_pair(item);
         load_item(item, y0, y1);
-        cplx<T> v[R];
+        cplx<T> v[RL];
+#pragma unroll
+        for (int u = 0; u < NSUB; u++)
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            const T wn = wins[salsa::stockham_in(lane, r, N, R)];
-            v[r] = {wn * (T)y0[r], wn * (T)y1[r]};
+            const T wn = wins[NSUB * salsa::stockham_in(lane, r, NS, R) + u];
+            v[u * R + r] = {wn * (T)y0[u * R + r], wn * (T)y1[u * R + r]};
         }
-        // ---- Stockham passes, in place in the wave-private buffer
-        salsa::dftR<R>(v); // pass p = 1 (no twiddles)
+        // ---- Stockham passes, in place in the wave-private buffer (N = 1024: the even samples' transform, then the odd samples')
 #pragma unroll
-        for (int r = 0; r < R; r++) z[swz(salsa::stockham_out(lane, r, 1, R))] = v[r];
-        {
-            int p = R;
+        for (int u = 0; u < NSUB; u++) {
+            cplx<T> *const vs = v + u * R;
+            salsa::dftR<R>(vs); // pass p = 1 (no twiddles)
 #pragma unroll
-            for (int q = 0; q < NP; q++, p *= R) {
-                wave_lds_fence();
+            for (int r = 0; r < R; r++) z[swz(salsa::stockham_out(lane, r, 1, R))] = vs[r];
+            {
+                int p = R;
 #pragma unroll
-                for (int r = 0; r < R; r++) v[r] = z[swz(salsa::stockham_in(lane, r, N, R))];
-                wave_lds_fence();
-                {
-                    const cplx<T> a1 = w1[q], a2 = salsa::cmul(a1, a1), a3 = salsa::cmul(a2, a1);
-                    v[1] = salsa::cmul(v[1], a1);
-                    v[2] = salsa::cmul(v[2], a2);
-                    v[3] = salsa::cmul(v[3], a3);
-                    if (R == 8) {
-                        const cplx<T> a4 = salsa::cmul(a2, a2);
-                        v[4 % R] = salsa::cmul(v[4 % R], a4);
-                        v[5 % R] = salsa::cmul(v[5 % R], salsa::cmul(a4, a1));
-                        v[6 % R] = salsa::cmul(v[6 % R], salsa::cmul(a3, a3));
-                        v[7 % R] = salsa::cmul(v[7 % R], salsa::cmul(a4, a3));
+                for (int q = 0; q < NP; q++, p *= R) {
+                    wave_lds_fence();
+#pragma unroll
+                    for (int r = 0; r < R; r++) vs[r] = z[swz(salsa::stockham_in(lane, r, NS, R))];
+                    wave_lds_fence();
+                    {
+                        const cplx<T> a1 = w1[q], a2 = salsa::cmul(a1, a1), a3 = salsa::cmul(a2, a1);
+                        vs[1] = salsa::cmul(vs[1], a1);
+                        vs[2] = salsa::cmul(vs[2], a2);
+                        vs[3] = salsa::cmul(vs[3], a3);
+                        if (R == 8) {
+                            const cplx<T> a4 = salsa::cmul(a2, a2);
+                            vs[4 % R] = salsa::cmul(vs[4 % R], a4);
+                            vs[5 % R] = salsa::cmul(vs[5 % R], salsa::cmul(a4, a1));
+                            vs[6 % R] = salsa::cmul(vs[6 % R], salsa::cmul(a3, a3));
+                            vs[7 % R] = salsa::cmul(vs[7 % R], salsa::cmul(a4, a3));
+                        }
+                    }
+                    salsa::dftR<R>(vs);
+                    if (q + 1 < NP) {
+#pragma unroll
+                        for (int r = 0; r < R; r++) z[swz(salsa::stockham_out(lane, r, p, R))] = vs[r];
                     }
                 }
-                salsa::dftR<R>(v);
-                if (q + 1 < NP) {
+            }
+        }
+        if constexpr (NSUB == 2) {
+            // join: lane holds E[lane + 64 r] in v[r] and O[lane + 64 r] in v[R + r]; Z[k] = E[k] + W_N^k O[k], Z[k + N/2] = E[k] - W_N^k O[k]
+            // with W_N^(lane + 64 r) = W_N^lane * W_16^r
+            static_assert(R == 8, "the join's constants are W_16^r");
+            constexpr double c16[8] = {1.0, 0.92387953251128675613, 0.70710678118654752440, 0.38268343236508977173,
+                                       0.0, -0.38268343236508977173, -0.70710678118654752440, -0.92387953251128675613};
+            constexpr double s16[8] = {0.0, -0.38268343236508977173, -0.70710678118654752440, -0.92387953251128675613,
+                                       -1.0, -0.92387953251128675613, -0.70710678118654752440, -0.38268343236508977173};
 #pragma unroll
-                    for (int r = 0; r < R; r++) z[swz(salsa::stockham_out(lane, r, p, R))] = v[r];
-                }
+            for (int r = 0; r < R; r++) {
+                const cplx<T> wk = r == 0 ? wj : salsa::cmul(wj, cplx<T>{(T)c16[r], (T)s16[r]});
+                const cplx<T> e = v[r], ow = salsa::cmul(v[R + r], wk);
+                v[r] = salsa::cadd(e, ow);
+                v[R + r] = salsa::csub(e, ow);
             }
         }
         // lane now holds Z[lane + 64 r] in v[r] (the last pass writes y[i + r*64])
@@ -537,11 +581,14 @@ __global__ __launch_bounds__(256, LITE ? (STD ? K1_LITE_STD_WAVES : K1_LITE_WAVE
             }
         };
 #pragma unroll
-        for (int r = 0; r < R / 2; r++) {
-            // mirror of k = lane + 64 r is N-k = (64-lane) + 64 (R-1-r): register R-1-r of lane 64-lane;
-            // lane 0: N - 64 r = 64 (R-r), its own register (R-r) mod R
-            cplx<T> bm = {__shfl(v[R - 1 - r].re, mlane), __shfl(v[R - 1 - r].im, mlane)};
-            if (lane == 0) bm = v[(R - r) & (R - 1)];
+        for (int r = 0; r < RL / 2; r++) {
+            // mirror of k = lane + 64 r is N-k = (64-lane) + 64 (RL-1-r): register RL-1-r of lane 64-lane;
+            // lane 0: N - 64 r = 64 (RL-r), its own register (RL-r) mod RL
+            if constexpr (NSUB == 2) {
+                if (64 * r >= kp.cutoff) continue; // wave-uniform: no bin of this register is written (nor its X0 read: emit_bin)
+            }
+            cplx<T> bm = {__shfl(v[RL - 1 - r].re, mlane), __shfl(v[RL - 1 - r].im, mlane)};
+            if (lane == 0) bm = v[(RL - r) & (RL - 1)];
             if constexpr (STD && LITE) {
                 if (r == 0) emit_lite_std(std::integral_constant<int, 0>{}, v[r], bm);
                 else if (r == 1) emit_lite_std(std::integral_constant<int, 1>{}, v[r], bm);
@@ -557,7 +604,7 @@ __global__ __launch_bounds__(256, LITE ? (STD ? K1_LITE_STD_WAVES : K1_LITE_WAVE
             }
             __builtin_amdgcn_sched_barrier(0); // one bin at a time: keeps the live set (and the VGPR count) small
         }
-        if (!STD && lane == 0) emit_bin(N / 2, v[R / 2], v[R / 2], x0keep[(LITE && STD) ? 0 : R / 2]); // (STD: bin 256 is in no DOA band, row or compressed row)
+        if (!STD && lane == 0) emit_bin(N / 2, v[RL / 2], v[RL / 2], x0keep[(LITE && STD) ? 0 : RL / 2]); // (STD: bin 256 is in no DOA band, row or compressed row)
         // ---- compressed high-frequency rows of W: sum of 8 (last row 7) bins times 1/8
         if constexpr (STD && !LITE) {
             // eight groups x two channels = lanes 0..15: two 16-byte LDS reads and a fixed chain of eight additions in the order of
@@ -1977,24 +2024,24 @@ __global__ void relayout_kernel(const float4 *__restrict__ X, float4 *__restrict
 
 // ------------------------------------------------------------------------------------------------------------ scaler
 // compute_scaler (:204-262) on device: float64 sum and sum of squares over time of the first n_sc channels, per
-// frequency.  One block per (clip, channel, tile of 64 frames); lane = frequency (coalesced rows); one float64 atomic
-// pair per lane per block.  sums: [2][n_sc][F] (sum, sumsq), accumulated into (caller zeroes it once).
+// frequency.  One block per (clip, channel, tile of 64 frames); lane = frequency (coalesced rows; frequencies beyond 256 in further
+// trips); one float64 atomic pair per frequency per block.  sums: [2][n_sc][F] (sum, sumsq), accumulated into (caller zeroes it once).
 __global__ __launch_bounds__(256) void scaler_accumulate_kernel(const float *__restrict__ feat, int C, int T, int F,
                                                                 int n_sc, double *__restrict__ sums)
 {
-    const int f = threadIdx.x;
     const int c = blockIdx.y, b = blockIdx.z;
     const int t0 = blockIdx.x * 64, t1 = t0 + 64 < T ? t0 + 64 : T;
-    if (f >= F) return;
-    const float *p = feat + (((long)b * C + c) * T) * F + f;
-    double s = 0.0, ss = 0.0;
-    for (int t = t0; t < t1; t++) {
-        const double v = (double)p[(long)t * F];
-        s += v;
-        ss += v * v;
+    for (int f = threadIdx.x; f < F; f += 256) { // (one trip while F <= 256; SALSA-Lite at n_fft 1024 has F = 382)
+        const float *p = feat + (((long)b * C + c) * T) * F + f;
+        double s = 0.0, ss = 0.0;
+        for (int t = t0; t < t1; t++) {
+            const double v = (double)p[(long)t * F];
+            s += v;
+            ss += v * v;
+        }
+        atomicAdd(&sums[(long)c * F + f], s);
+        atomicAdd(&sums[((long)n_sc + c) * F + f], ss);
     }
-    atomicAdd(&sums[(long)c * F + f], s);
-    atomicAdd(&sums[((long)n_sc + c) * F + f], ss);
 }
 
 // normalise-on-load (dataset/database.py:197-202): feature[:n_sc] = (feature[:n_sc] - mean) / std, in place;
@@ -2412,7 +2459,14 @@ int salsa_plan_create(const salsa_params *params, salsa_plan **out_plan)
 {
     if (!params || !out_plan) return fail(SALSA_EINVAL, "salsa_plan_create: NULL argument%s");
     const salsa_params &p = *params;
-    if (p.n_fft != 512 && p.n_fft != 256) return fail(SALSA_ENFFT, "only 256 or 512 fft is supported%s");
+    // full SALSA: the reference's own assert (salsa_feature_extraction.py:152, :306).  Its SALSA-Lite / IPD script has none; here those
+    // two features also take 1024 (stft_kernel<1024, ...>), on the dataset scripts' surface (not contrib's SALSA_FLAG_FLEX); every other size is refused
+    const bool lite_1024 = p.n_fft == 1024 && (p.feature_type == SALSA_FEATURE_LITE || p.feature_type == SALSA_FEATURE_IPD) && !(p.flags & SALSA_FLAG_FLEX);
+    if (p.n_fft != 512 && p.n_fft != 256 && !lite_1024) {
+        if (p.feature_type == SALSA_FEATURE_LITE || p.feature_type == SALSA_FEATURE_IPD)
+            return fail(SALSA_ENFFT, "only 256, 512 or 1024 fft is supported for SALSA-Lite and SALSA-IPD (256 or 512 with the contrib flags)%s");
+        return fail(SALSA_ENFFT, "only 256 or 512 fft is supported%s");
+    }
     if (p.fs <= 0 || p.hop_len <= 0 || p.win_len <= 0 || p.win_len > p.n_fft)
         return fail(SALSA_EINVAL, "bad fs / hop_len / win_len (window length must be <= nfft)%s");
     if (p.audio_format != SALSA_FORMAT_FOA && p.audio_format != SALSA_FORMAT_MIC)
@@ -2651,6 +2705,11 @@ static int launch_stft(salsa_plan *pl, const KParams &kp, const double *win, con
         constexpr size_t SCT_BYTES = 2 * 4 * 256 * sizeof(float);
         if (kp.sc_mean) hipLaunchKernelGGL((stft_kernel<512, double, false, NF_FULL, 2, true, true>), grid, dim3(256), SCT_BYTES, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
         else hipLaunchKernelGGL((stft_kernel<512, double, false, NF_FULL, 2, false, true>), grid, dim3(256), 0, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
+    } else if (pl->p.n_fft == 1024) {
+        // SALSA-Lite / IPD only (salsa_plan_create).  One instantiation for every layout; an attached scaler is read from global memory
+        // in the store path (F = 382 at the defaults: the LDS tables of the SC instantiations hold 256 bins)
+        if (!lite) return fail(SALSA_ENFFT, "n_fft 1024 is a SALSA-Lite / SALSA-IPD size%s");
+        hipLaunchKernelGGL((stft_kernel<1024, double, true, NF_LITE>), grid, dim3(256), 0, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
     } else if (pl->p.n_fft == 512 && kp.sc_mean && !single && kp.F <= 256) {
         constexpr size_t SCT_BYTES = 2 * 4 * 256 * sizeof(float);
         if (lite) hipLaunchKernelGGL((stft_kernel<512, double, true, NF_LITE, 2, true>), grid, dim3(256), SCT_BYTES, s, kp, d_audio, win, pl->d_tw, d_out, Xs);
@@ -2917,6 +2976,7 @@ int salsa_logspec_batch(salsa_plan *pl, const float *d_audio, int batch, int n_c
 {
     if (!pl || !d_audio || !d_out || batch <= 0 || n_samples <= 0) return fail(SALSA_EINVAL, "salsa_logspec_batch: bad argument%s");
     if (n_channels != 4) return fail(SALSA_EINVAL, "salsa_logspec_batch: n_channels must be 4 (pad with silent channels)%s");
+    if (freq_dim(pl->p.n_fft, pl->p.is_compress_high_freq) < 0) return fail(SALSA_ENFFT, "nfft is not 512 or 256%s"); // (MagStftExtractor, :152)
     if (n_samples <= pl->p.n_fft / 2) return fail(SALSA_EINVAL, "clip shorter than n_fft/2 samples cannot be reflect-padded%s");
     if (n_samples * 16 >= INT32_MAX || (1 + n_samples / pl->p.hop_len) * 7 * 256 >= INT32_MAX / 2)
         return fail(SALSA_EINVAL, "clip too long for 32-bit per-clip indexing (split it)%s");
@@ -3050,7 +3110,7 @@ int salsa_plan_read_timing(salsa_plan *pl, float *ms, const char **names, int *n
 int salsa_scaler_accumulate(const float *d_feat, int batch, int n_channels, int64_t n_frames, int n_freq,
                             int n_scaler_channels, double *d_sums, void *hip_stream)
 {
-    if (!d_feat || !d_sums || batch <= 0 || n_channels <= 0 || n_frames <= 0 || n_freq <= 0 || n_freq > 256 ||
+    if (!d_feat || !d_sums || batch <= 0 || n_channels <= 0 || n_frames <= 0 || n_freq <= 0 ||
         n_scaler_channels <= 0 || n_scaler_channels > n_channels || n_frames >= INT32_MAX)
         return fail(SALSA_EINVAL, "salsa_scaler_accumulate: bad argument%s");
     dim3 grid((unsigned)((n_frames + 63) / 64), (unsigned)n_scaler_channels, (unsigned)batch);

@@ -14,7 +14,7 @@ from . import _lib
 def _raise(rc):
     msg = _lib.last_error()
     if rc == _lib.E_NFFT:
-        raise AssertionError(msg)            # the reference asserts n_fft in (256, 512)
+        raise AssertionError(msg)            # the reference asserts n_fft in (256, 512) for full SALSA; SALSA-Lite / IPD also take 1024 here
     if rc == _lib.E_FORMAT:
         if 'only for MIC' in msg:
             raise AssertionError(msg)        # salsa_lite_feature_extraction.py:72

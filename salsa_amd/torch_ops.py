@@ -25,8 +25,8 @@ def _plan(device, audio_format, feature_type, fs, n_fft, hop_len, fmin_doa, fmax
 def output_shape(n_samples, audio_format='foa', feature_type='salsa', fs=24000, n_fft=512, hop_len=300, fmin_doa=50,
                  fmax_doa=9000, is_compress_high_freq=True):
     """(7, T, F) of the feature array, host arithmetic only (salsa_feature_extraction.py:298-313, lite :50-59)."""
-    if n_fft not in (256, 512):
-        raise AssertionError('only 256 or 512 fft is supported')
+    if n_fft not in (256, 512) and not (n_fft == 1024 and feature_type in ('salsa_lite', 'salsa_ipd')):
+        raise AssertionError('only 256 or 512 fft is supported' + (' (SALSA-Lite and SALSA-IPD: also 1024)' if feature_type != 'salsa' else ''))
     T = 1 + n_samples // hop_len
     if feature_type == 'salsa':
         F = ((200 if n_fft == 512 else 100) if is_compress_high_freq else n_fft // 2)
