@@ -91,6 +91,8 @@ def test_eigvec_matches_reference_golden(dev, seed):
 
 
 def test_eigvec_adversarial_golden(dev, oracle):
+    """Goldens g2: exact rank-1 windows, eigenvalue ratios around cond_num, u[0] ~ 0, silence, constant magnitude, level steps, in
+    blocks of 10 bins x 40 frames.  The tracker's chunk (64-frame) and 32-bin group boundaries are in tests/test_tracker_gpu.py."""
     meta, a = load_golden('g2_adversarial')
     for case in meta['cases']:
         X = a['X_' + case]

@@ -724,9 +724,24 @@ def g21_baseline():
         np.fft.irfft = irfft
 
 
+def g27_tracker():
+    """The reference's indicator_sig (made as g1's sig_mask is: cond = 0, the non-zero pattern of the output) on the small aimed blocks
+    of tests/tracker_reference.py: clamp, slow rise at chunk boundaries, one-ulp knife edges and exact ties, wrap, T < 3.  Bit-packed."""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import tracker_reference as tr
+    arrays, meta = {}, {'cases': list(tr.GOLDEN_CASES), 'sha': {}, 'shape': {}, 'cond': 0.0, 'lower_bin': 1}
+    for name in tr.GOLDEN_CASES:
+        X, _ = tr.build_case(name)
+        assert X.shape[1] <= 70 and X.shape[2] <= 200
+        mask = np.stack([np.abs(run_eig(x, 'foa', True, cond=0.0)).sum(axis=0) > 0 for x in X])
+        meta['sha'][name], meta['shape'][name] = sha256_of(X), list(mask.shape)
+        arrays[name] = np.packbits(mask)
+    save('g27_tracker', meta, **arrays)
+
+
 GENERATORS = [g5_w_and_bins, g1_eigvec, g2_adversarial, g3_end_to_end, g4_lite, g8_stft, g10_flexible, g13_flexible_multi,
               g15_flexible_many, g11_augment, g12_metrics, g17_labels, g18_feature_tree, g19_win_len, g20_off_default, g21_baseline,
-              g22_baseline_augment]
+              g22_baseline_augment, g27_tracker]
 
 
 if __name__ == '__main__':
