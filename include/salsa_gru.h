@@ -10,6 +10,9 @@
  *   bhh   [D][3H]
  *   hs    [T][B][D][H]   hidden state AFTER step t (direction 1 scans t = T-1..0 and still stores at index t)
  *   saved [T][B][D][4H]  r, z, n, (W_hn h + b_hn) per step, for the backward scan (may be NULL for inference)
+ *
+ * Every entry point checks its arguments on the host before any launch and returns -1 for T <= 0, B outside 1..65535, D outside
+ * {1, 2}, an H it has no instantiation for (64, 128, 256; the register-resident pair: 256) or a NULL among the required pointers.
  */
 #ifndef SALSA_GRU_H
 #define SALSA_GRU_H

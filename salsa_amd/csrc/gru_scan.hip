@@ -368,6 +368,13 @@ __global__ __launch_bounds__(1024) void gru_bwd_regw_kernel(const float *__restr
     }
 }
 
+// the shapes every entry point accepts, checked on the host before any launch: one workgroup per (sample, direction), the
+// same limits as the LSTM scans (lstm_scan.hip); W_hh, b_hh and every [T][B][D][..] tensor hold exactly D directions
+bool gru_args_ok(int T, int B, int D, int H)
+{
+    return T > 0 && B > 0 && B <= 65535 && (D == 1 || D == 2) && (H == 256 || H == 128 || H == 64);
+}
+
 } // namespace
 
 extern "C" {
@@ -375,7 +382,7 @@ extern "C" {
 int salsa_gru_scan_fwd(const float *gi, const float *whh_t, const float *bhh, float *hs, float *saved, int T, int B, int D,
                        int H, void *hip_stream)
 {
-    if (!gi || !whh_t || !bhh || !hs || T <= 0 || B <= 0 || D <= 0 || (H != 256 && H != 128 && H != 64)) return -1;
+    if (!gi || !whh_t || !bhh || !hs || !gru_args_ok(T, B, D, H)) return -1;
     hipStream_t s = (hipStream_t)hip_stream;
     dim3 grid((unsigned)B, (unsigned)D);
     if (H == 256) hipLaunchKernelGGL((gru_fwd_kernel<256>), grid, dim3(256), 0, s, gi, whh_t, bhh, hs, saved, T, B, D);
@@ -387,7 +394,7 @@ int salsa_gru_scan_fwd(const float *gi, const float *whh_t, const float *bhh, fl
 int salsa_gru_scan_fwd_regw(const float *gi, const float *whh, const float *bhh, float *hs, float *saved, int T, int B, int D,
                             int H, void *hip_stream)
 {
-    if (!gi || !whh || !bhh || !hs || T <= 0 || B <= 0 || D <= 0 || H != 256) return -1;
+    if (!gi || !whh || !bhh || !hs || !gru_args_ok(T, B, D, H) || H != 256) return -1;
     hipLaunchKernelGGL((gru_fwd_regw_kernel<256>), dim3((unsigned)B, (unsigned)D), dim3(1024), 0, (hipStream_t)hip_stream, gi, whh,
                        bhh, hs, saved, T, B, D);
     return hipGetLastError() == hipSuccess ? 0 : -6;
@@ -396,7 +403,7 @@ int salsa_gru_scan_fwd_regw(const float *gi, const float *whh, const float *bhh,
 int salsa_gru_scan_bwd_regw(const float *dhs, const float *whh, const float *hs, const float *saved, float *dgi, float *dgh,
                             int T, int B, int D, int H, void *hip_stream)
 {
-    if (!dhs || !whh || !hs || !saved || !dgi || !dgh || T <= 0 || B <= 0 || D <= 0 || H != 256) return -1;
+    if (!dhs || !whh || !hs || !saved || !dgi || !dgh || !gru_args_ok(T, B, D, H) || H != 256) return -1;
     hipLaunchKernelGGL((gru_bwd_regw_kernel<256>), dim3((unsigned)B, (unsigned)D), dim3(1024), 0, (hipStream_t)hip_stream, dhs, whh,
                        hs, saved, dgi, dgh, T, B, D);
     return hipGetLastError() == hipSuccess ? 0 : -6;
@@ -405,7 +412,7 @@ int salsa_gru_scan_bwd_regw(const float *dhs, const float *whh, const float *hs,
 int salsa_gru_scan_bwd(const float *dhs, const float *whh, const float *hs, const float *saved, float *dgi, float *dgh,
                        int T, int B, int D, int H, void *hip_stream)
 {
-    if (!dhs || !whh || !hs || !saved || !dgi || !dgh || T <= 0 || B <= 0 || D <= 0 || (H != 256 && H != 128 && H != 64)) return -1;
+    if (!dhs || !whh || !hs || !saved || !dgi || !dgh || !gru_args_ok(T, B, D, H)) return -1;
     hipStream_t s = (hipStream_t)hip_stream;
     dim3 grid((unsigned)B, (unsigned)D);
     if (H == 256) hipLaunchKernelGGL((gru_bwd_kernel<256>), grid, dim3(256), 0, s, dhs, whh, hs, saved, dgi, dgh, T, B, D);

@@ -268,11 +268,12 @@ def bn_bwd_ref(r, gamma, gy, relu=True, pool=False, fwd_c=16 * U32, bf16=False):
 
 
 # ------------------------------------------------------------------------------------------------------------ GRU
-def gru_ref(gru, x, gy, whh_round=None):
-    """outputs and gradients of a batch_first bidirectional nn.GRU evaluated in float64 on the CPU (a copy of `gru`; W_hh
-    optionally passed through whh_round first, e.g. a float16 rounding).  -> (y, [dx] + [grad of every parameter])"""
+def rnn_ref(rnn, x, gy, whh_round=None):
+    """outputs and gradients of a batch_first nn.RNNBase (nn.GRU or nn.LSTM, one or two directions) evaluated in float64 on the
+    CPU (a copy of `rnn`; W_hh optionally passed through whh_round first, e.g. a float16 rounding).
+    -> (y, [dx] + [grad of every parameter])"""
     import copy
-    g64 = copy.deepcopy(gru).cpu().double()
+    g64 = copy.deepcopy(rnn).cpu().double()
     if whh_round is not None:
         with torch.no_grad():
             for n, p in g64.named_parameters():
@@ -282,3 +283,22 @@ def gru_ref(gru, x, gy, whh_round=None):
     y, _ = g64(xr)
     y.backward(gy.detach().cpu().double())
     return y.detach(), [xr.grad] + [p.grad for p in g64.parameters()]
+
+
+gru_ref = rnn_ref
+
+
+def _pool_input(N, Cn, H, W, g, kind):
+    """bf16 channels-last input of the frequency max / mean + max pool tests, drawn on g's device: 'plain', 'ties' (exact zeros,
+    repeated quarter values, all-zero columns, the w = 0 value repeated later on) or 'nan'"""
+    DEV = g.device
+    x = torch.randn((N, Cn, H, W), device=DEV, generator=g)
+    if kind == 'ties':
+        x = torch.relu(x).mul(4).round().div(4)                             # exact zeros and repeated quarter values
+        x[:, ::5, :, :] = 0.0                                               # all-zero frequency columns
+        x[:, 1::7, :, W // 2:] = x[:, 1::7, :, :1].expand(-1, -1, -1, W - W // 2)   # the w = 0 value repeated later on
+    elif kind == 'nan':
+        x[0, 3, 1, W - 2] = float('nan')
+        x[0, 3, 1, W - 1] = float('nan')
+        x[1 % N, 9, 0, 0] = float('nan')
+    return x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)

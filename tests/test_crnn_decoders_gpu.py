@@ -10,6 +10,7 @@ import torch
 
 import rnn_reference as rr
 from conftest import load_golden
+from nn_reference import _pool_input
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda:0')
@@ -103,19 +104,6 @@ def test_unidirectional_gru_register_resident_scans():
     torch.testing.assert_close(xa.grad, xb.grad, rtol=1e-2, atol=2e-3)
     for (n, p), (_, q) in zip(gru.named_parameters(), ref_m.named_parameters()):
         torch.testing.assert_close(p.grad, q.grad, rtol=1e-2, atol=1e-2 * float(q.grad.abs().max()), msg=n)
-
-
-def _pool_input(N, Cn, H, W, g, kind):
-    x = torch.randn((N, Cn, H, W), device=DEV, generator=g)
-    if kind == 'ties':
-        x = torch.relu(x).mul(4).round().div(4)                             # exact zeros and repeated quarter values
-        x[:, ::5, :, :] = 0.0                                               # all-zero frequency columns
-        x[:, 1::7, :, W // 2:] = x[:, 1::7, :, :1].expand(-1, -1, -1, W - W // 2)   # the w = 0 value repeated later on
-    elif kind == 'nan':
-        x[0, 3, 1, W - 2] = float('nan')
-        x[0, 3, 1, W - 1] = float('nan')
-        x[1 % N, 9, 0, 0] = float('nan')
-    return x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
 
 
 @pytest.mark.parametrize('mode', ['max', 'avg_max'])
