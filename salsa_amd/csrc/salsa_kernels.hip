@@ -1864,51 +1864,11 @@ __global__ __launch_bounds__(FZ_NT, 1) void fused_kernel(const KParams kp, const
 // the 2*n_hop+1 frames in float64, cyclic complex Jacobi with the rotations accumulated (eigenvalues = the diagonal, eigen-
 // vectors = the accumulated columns), gate "largest > second largest * ew_thresh" (:353), feature angle(conj(u_0) u_c) / f
 // (:360-362).  A completeness path, not a tuned one: the 2 x NCH^2 float64 matrices spill to scratch.
-// NCH > 0: compile-time size, fully unrolled (6 | 8).  NCH == 0: any even count up to MAXN = 16 read from kp.nch -- the same code
+// NCH > 0: compile-time size, fully unrolled (6 | 8).  NCH == 0: any even count up to HERMN_MAX = 16 read from kp.nch -- the same code
 // with run-time loop bounds and dynamically indexed scratch arrays (9 - 16 microphones: slower still, and as rare).
-constexpr int HERMN_MAX = SALSA_MAX_MICS;
-template <int NCH> struct hermn {
-    static constexpr int S = NCH > 0 ? NCH : HERMN_MAX;
-    double ar[S][S], ai[S][S];
-};
-
-template <int NCH>
-__device__ __forceinline__ void hermn_rotate(hermn<NCH> &A, hermn<NCH> &V, const int p, const int q, const int n)
-{
-    const double xr = A.ar[p][q], xi = A.ai[p][q];
-    const double r2 = xr * xr + xi * xi;
-    if (r2 == 0.0) return;
-    const double r = sqrt(r2);
-    // a_pq = r e^{i phi}.  U = D G: D_qq = e^{-i phi} makes the pivot real, G is the real Jacobi rotation that zeroes it.
-    const double er = xr / r, ei = xi / r;
-    const double tau = (A.ar[q][q] - A.ar[p][p]) / (2.0 * r);
-    const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-    const double c = 1.0 / sqrt(1.0 + t * t), sn = t * c;
-    // U_pp = c, U_qp = -sn e^{-i phi}, U_pq = sn, U_qq = c e^{-i phi}
-    const double uqp_r = -sn * er, uqp_i = sn * ei, uqq_r = c * er, uqq_i = -c * ei;
-    auto cols = [&](hermn<NCH> &M) { // M <- M U (columns p and q)
-#pragma unroll
-        for (int i = 0; i < n; i++) {
-            const double pr = M.ar[i][p], pi = M.ai[i][p], qr = M.ar[i][q], qi = M.ai[i][q];
-            M.ar[i][p] = pr * c + (qr * uqp_r - qi * uqp_i);
-            M.ai[i][p] = pi * c + (qr * uqp_i + qi * uqp_r);
-            M.ar[i][q] = pr * sn + (qr * uqq_r - qi * uqq_i);
-            M.ai[i][q] = pi * sn + (qr * uqq_i + qi * uqq_r);
-        }
-    };
-    cols(A);
-#pragma unroll
-    for (int j = 0; j < n; j++) { // A <- U^H A (rows p and q): conj(U_pp) = c, conj(U_qp), conj(U_pq) = sn, conj(U_qq)
-        const double pr = A.ar[p][j], pi = A.ai[p][j], qr = A.ar[q][j], qi = A.ai[q][j];
-        A.ar[p][j] = c * pr + (uqp_r * qr + uqp_i * qi);
-        A.ai[p][j] = c * pi + (uqp_r * qi - uqp_i * qr);
-        A.ar[q][j] = sn * pr + (uqq_r * qr + uqq_i * qi);
-        A.ai[q][j] = sn * pi + (uqq_r * qi - uqq_i * qr);
-    }
-    A.ar[p][q] = A.ai[p][q] = A.ar[q][p] = A.ai[q][p] = 0.0; // exactly, as the algebra says
-    A.ai[p][p] = A.ai[q][q] = 0.0;
-    cols(V);
-}
+// The solver itself (hermn, hermn_rotate, hermn_gate_eigvec) is in salsa_math.h, where the host emulation reaches it.
+using salsa::hermn;
+static_assert(salsa::HERMN_MAX == SALSA_MAX_MICS, "the run-time-sized solver holds SALSA_MAX_MICS channels");
 
 template <int NCH>
 __global__ __launch_bounds__(64) void cov_eig_n_kernel(const KParams kp, const float4 *__restrict__ Xs,
@@ -1955,49 +1915,16 @@ __global__ __launch_bounds__(64) void cov_eig_n_kernel(const KParams kp, const f
                         A.ai[i][j] += xi[i] * xr[j] - xr[i] * xi[j];
                     }
             }
-            double tr = 0.0;
+            double ur[S], ui[S];
+            int sweeps;
+            const bool good = salsa::hermn_gate_eigvec<NCH>(A, V, n, kp.cond, ur, ui, sweeps);
+            if (good) {
+                const int kb = bin + kp.lower;
+                const double den = (double)((float)(kb == 0 ? 1 : kb) * (float)kp.delta); // float32 norm_freq (:188-190)
 #pragma unroll
-            for (int i = 0; i < n; i++) tr += A.ar[i][i];
-            bool good = false;
-            if (tr > 0.0) {
-                for (int sweep = 0; sweep < 16; sweep++) {
-                    double off = 0.0;
-#pragma unroll
-                    for (int p = 0; p < n; p++)
-#pragma unroll
-                        for (int q = p + 1; q < n; q++) off += A.ar[p][q] * A.ar[p][q] + A.ai[p][q] * A.ai[p][q];
-                    if (off <= 1e-34 * tr * tr) break;
-#pragma unroll
-                    for (int p = 0; p < n; p++)
-#pragma unroll
-                        for (int q = p + 1; q < n; q++) hermn_rotate<NCH>(A, V, p, q, n);
-                }
-                int i1 = 0;
-                double l1 = A.ar[0][0];
-#pragma unroll
-                for (int i = 1; i < n; i++)
-                    if (A.ar[i][i] > l1) { l1 = A.ar[i][i]; i1 = i; }
-                double l2 = -1e300;
-#pragma unroll
-                for (int i = 0; i < n; i++)
-                    if (i != i1 && A.ar[i][i] > l2) l2 = A.ar[i][i];
-                good = l1 > l2 * kp.cond; // ews[:, -1] > ews[:, -2] * ew_thresh (:353)
-                if (good) {
-                    double ur[S], ui[S];
-#pragma unroll
-                    for (int i = 0; i < n; i++) {
-                        ur[i] = ui[i] = 0.0;
-#pragma unroll
-                        for (int j = 0; j < n; j++)
-                            if (j == i1) { ur[i] = V.ar[i][j]; ui[i] = V.ai[i][j]; }
-                    }
-                    const int kb = bin + kp.lower;
-                    const double den = (double)((float)(kb == 0 ? 1 : kb) * (float)kp.delta); // float32 norm_freq (:188-190)
-#pragma unroll
-                    for (int c = 1; c < n; c++) { // angle(conj(u_0) u_c) / f   (:360-362)
-                        const double wr = ur[0] * ur[c] + ui[0] * ui[c], wi = ur[0] * ui[c] - ui[0] * ur[c];
-                        e[c - 1] = (float)(atan2(wi, wr) / den);
-                    }
+                for (int c = 1; c < n; c++) { // angle(conj(u_0) u_c) / f   (:360-362)
+                    const double wr = ur[0] * ur[c] + ui[0] * ui[c], wi = ur[0] * ui[c] - ui[0] * ur[c];
+                    e[c - 1] = (float)(atan2(wi, wr) / den);
                 }
             }
             if (!good && !kp.tracking) e[0] = __builtin_nanf(""); // marks "failed the test" for flex_allpass_kernel

@@ -919,4 +919,104 @@ SALSA_HD bool tracker_step(double &floor, int &countdown, double mag, double snr
     return mag > snr_ratio * floor; // :87 (snr_ratio = 1.5 there; contrib's floor_mask_ratio kwarg)
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// N x N Hermitian eigen-solver of the contrib surface at 5 - 16 microphones (cov_eig_n_kernel; contrib/salsa_flexible.py
+// stacked_covmat_eigh :52-77 + the coherence test :353): cyclic complex Jacobi in float64 with the rotations accumulated
+// (eigenvalues = the diagonal, eigenvectors = the accumulated columns).
+// NCH > 0: compile-time size, fully unrolled (6 | 8).  NCH == 0: any even count up to HERMN_MAX read at run time -- the same code
+// with run-time loop bounds and dynamically indexed arrays.
+constexpr int HERMN_MAX = 16; // include/salsa_hip.h SALSA_MAX_MICS
+constexpr int HERMN_SWEEPS = 16;
+template <int NCH> struct hermn {
+    static constexpr int S = NCH > 0 ? NCH : HERMN_MAX;
+    double ar[S][S], ai[S][S];
+};
+
+template <int NCH>
+SALSA_HD void hermn_rotate(hermn<NCH> &A, hermn<NCH> &V, const int p, const int q, const int n)
+{
+    const double xr = A.ar[p][q], xi = A.ai[p][q];
+    const double r2 = xr * xr + xi * xi;
+    if (r2 == 0.0) return;
+    const double r = sqrt(r2);
+    // a_pq = r e^{i phi}.  U = D G: D_qq = e^{-i phi} makes the pivot real, G is the real Jacobi rotation that zeroes it.
+    const double er = xr / r, ei = xi / r;
+    const double tau = (A.ar[q][q] - A.ar[p][p]) / (2.0 * r);
+    const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+    const double c = 1.0 / sqrt(1.0 + t * t), sn = t * c;
+    // U_pp = c, U_qp = -sn e^{-i phi}, U_pq = sn, U_qq = c e^{-i phi}
+    const double uqp_r = -sn * er, uqp_i = sn * ei, uqq_r = c * er, uqq_i = -c * ei;
+    auto cols = [&](hermn<NCH> &M) { // M <- M U (columns p and q)
+#pragma unroll
+        for (int i = 0; i < n; i++) {
+            const double pr = M.ar[i][p], pi = M.ai[i][p], qr = M.ar[i][q], qi = M.ai[i][q];
+            M.ar[i][p] = pr * c + (qr * uqp_r - qi * uqp_i);
+            M.ai[i][p] = pi * c + (qr * uqp_i + qi * uqp_r);
+            M.ar[i][q] = pr * sn + (qr * uqq_r - qi * uqq_i);
+            M.ai[i][q] = pi * sn + (qr * uqq_i + qi * uqq_r);
+        }
+    };
+    cols(A);
+#pragma unroll
+    for (int j = 0; j < n; j++) { // A <- U^H A (rows p and q): conj(U_pp) = c, conj(U_qp), conj(U_pq) = sn, conj(U_qq)
+        const double pr = A.ar[p][j], pi = A.ai[p][j], qr = A.ar[q][j], qi = A.ai[q][j];
+        A.ar[p][j] = c * pr + (uqp_r * qr + uqp_i * qi);
+        A.ai[p][j] = c * pi + (uqp_r * qi - uqp_i * qr);
+        A.ar[q][j] = sn * pr + (uqq_r * qr + uqq_i * qi);
+        A.ai[q][j] = sn * pi + (uqq_r * qi - uqq_i * qr);
+    }
+    A.ar[p][q] = A.ai[p][q] = A.ar[q][p] = A.ai[q][p] = 0.0; // exactly, as the algebra says
+    A.ai[p][p] = A.ai[q][q] = 0.0;
+    cols(V);
+}
+
+// The per-bin solve of cov_eig_n_kernel on the summed covariance A (V = I on entry; both are left as the sweeps leave them:
+// diag(A) = the eigenvalues, unsorted): the sweeps, the pick of the two largest eigenvalues, the gate
+// "largest > second largest * ew_thresh" (:353) and, where it passes, the top eigenvector (ur, ui).  Returns the gate decision;
+// `sweeps` = the number of sweeps run (HERMN_SWEEPS: left by the cap, not by the stop rule).
+template <int NCH>
+SALSA_HD bool hermn_gate_eigvec(hermn<NCH> &A, hermn<NCH> &V, const int n, const double cond, double *ur, double *ui, int &sweeps)
+{
+    double tr = 0.0;
+#pragma unroll
+    for (int i = 0; i < n; i++) tr += A.ar[i][i];
+    bool good = false;
+    sweeps = 0;
+    if (tr > 0.0) {
+        for (int sweep = 0; sweep < HERMN_SWEEPS; sweep++) {
+            double off = 0.0;
+#pragma unroll
+            for (int p = 0; p < n; p++)
+#pragma unroll
+                for (int q = p + 1; q < n; q++) off += A.ar[p][q] * A.ar[p][q] + A.ai[p][q] * A.ai[p][q];
+            if (off <= 1e-34 * tr * tr) break;
+#pragma unroll
+            for (int p = 0; p < n; p++)
+#pragma unroll
+                for (int q = p + 1; q < n; q++) hermn_rotate<NCH>(A, V, p, q, n);
+            sweeps = sweep + 1;
+        }
+        int i1 = 0;
+        double l1 = A.ar[0][0];
+#pragma unroll
+        for (int i = 1; i < n; i++)
+            if (A.ar[i][i] > l1) { l1 = A.ar[i][i]; i1 = i; }
+        double l2 = -1e300;
+#pragma unroll
+        for (int i = 0; i < n; i++)
+            if (i != i1 && A.ar[i][i] > l2) l2 = A.ar[i][i];
+        good = l1 > l2 * cond; // ews[:, -1] > ews[:, -2] * ew_thresh (:353)
+        if (good) {
+#pragma unroll
+            for (int i = 0; i < n; i++) {
+                ur[i] = ui[i] = 0.0;
+#pragma unroll
+                for (int j = 0; j < n; j++)
+                    if (j == i1) { ur[i] = V.ar[i][j]; ui[i] = V.ai[i][j]; }
+            }
+        }
+    }
+    return good;
+}
+
 } // namespace salsa

@@ -302,3 +302,59 @@ int hostemu_pk_coeffs(const float *X, long n, double cond, double *t32, double *
     return 0;
 }
 }
+
+// The N x N solve of cov_eig_n_kernel (salsa_math.h hermn_gate_eigvec: cyclic complex Jacobi, gate, top column) on a batch of
+// Hermitian matrices.  A [m][n][n] complex128, row-major, both triangles given (the kernel accumulates both).  unrolled != 0: the
+// fully unrolled instantiation (n = 6 | 8); else the run-time-sized one (even n, 6..16).  Out, per matrix: lam [n] the diagonal at
+// exit, ascending; u [n] complex128 the top eigenvector (zeros where the gate fails); good = the gate decision; sweeps = sweeps run
+// (HERMN_SWEEPS: left by the cap); off = the off-diagonal sum of squares (upper triangle) at exit; tr = the trace before the sweeps.
+template <int NCH>
+static void hermn_batch(const double *Ain, long m, int n, double cond, double *lam, double *u, int *good, int *sweeps, double *off,
+                        double *tr)
+{
+    for (long k = 0; k < m; k++) {
+        hermn<NCH> A, V;
+        const double *a = Ain + (size_t)k * n * n * 2;
+        for (int i = 0; i < n; i++)
+            for (int j = 0; j < n; j++) {
+                A.ar[i][j] = a[(i * n + j) * 2];
+                A.ai[i][j] = a[(i * n + j) * 2 + 1];
+                V.ar[i][j] = i == j ? 1.0 : 0.0;
+                V.ai[i][j] = 0.0;
+            }
+        double t = 0.0;
+        for (int i = 0; i < n; i++) t += A.ar[i][i];
+        tr[k] = t;
+        double ur[hermn<NCH>::S], ui[hermn<NCH>::S];
+        for (int i = 0; i < n; i++) ur[i] = ui[i] = 0.0;
+        int sw = 0;
+        good[k] = hermn_gate_eigvec<NCH>(A, V, n, cond, ur, ui, sw) ? 1 : 0;
+        sweeps[k] = sw;
+        double o = 0.0;
+        for (int p = 0; p < n; p++)
+            for (int q = p + 1; q < n; q++) o += A.ar[p][q] * A.ar[p][q] + A.ai[p][q] * A.ai[p][q];
+        off[k] = o;
+        double *l = lam + (size_t)k * n;
+        for (int i = 0; i < n; i++) l[i] = A.ar[i][i];
+        for (int i = 1; i < n; i++) // insertion sort, ascending
+            for (int j = i; j > 0 && l[j] < l[j - 1]; j--) { const double s = l[j]; l[j] = l[j - 1]; l[j - 1] = s; }
+        for (int i = 0; i < n; i++) { u[((size_t)k * n + i) * 2] = ur[i]; u[((size_t)k * n + i) * 2 + 1] = ui[i]; }
+    }
+}
+
+extern "C" {
+int hostemu_hermn(const double *A, long m, int n, double cond, int unrolled, double *lam, double *u, int *good, int *sweeps,
+                  double *off, double *tr)
+{
+    if (unrolled) {
+        if (n == 6) hermn_batch<6>(A, m, n, cond, lam, u, good, sweeps, off, tr);
+        else if (n == 8) hermn_batch<8>(A, m, n, cond, lam, u, good, sweeps, off, tr);
+        else return -1;
+        return 0;
+    }
+    if (n < 6 || n > HERMN_MAX || (n & 1)) return -1;
+    hermn_batch<0>(A, m, n, cond, lam, u, good, sweeps, off, tr);
+    return 0;
+}
+int hostemu_hermn_sweep_cap(void) { return HERMN_SWEEPS; }
+}
