@@ -245,6 +245,25 @@ int salsa_nn_accdoa_loss(const float *doa, const float *sed_gt, const float *doa
  * xyz [rows][3 nc], float32, bit-equal to numpy's float32 expression (no fma, correctly rounded square root). */
 int salsa_nn_accdoa_sed(const float *xyz, float *sed, int64_t rows, int nc, void *hip_stream);
 
+/* Test-time chunk combination and DCASE row decoding in one launch (reference models/interfaces.py:97-139 combine_chunks, then
+ * :232-256 of write_classwise_output_to_file; salsa_amd/csrc/seld_decode.hip): sed [n_files][n_chunks][chunk_len][nc] ACTIVITIES (not
+ * logits) and xyz [..][3 nc] (blocks x | y | z), float32 contiguous at the label rate; chunk_len and chunk_hop in label frames.
+ * Chunk starts are arange(0, n_frames - chunk_len + 1, chunk_hop) plus the leftover start n_frames - chunk_len; chunk 0 is copied,
+ * the first chunk_len - chunk_hop frames of every later chunk become (old + new) / 2 (combine 0) or sqrtf(old * new) (combine 1) and
+ * its other frames overwrite -- the reference's running pairwise average, float32 without fma: bit-equal to numpy.  n_chunks == 1
+ * is plain placement of a chunk of chunk_len >= n_frames frames, trimmed.  A pair (frame, class) is active when its combined sed
+ * >= sed_threshold in float32 (NaN: inactive); rows [n_files][n_frames * nc][4] int16 (8-byte aligned) receives (frame, class,
+ * azimuth, elevation) of file f's active pairs, frame ascending and class ascending within a frame, in its first counts[f] rows;
+ * the rows behind them are not written.  The angles are round-half-even of atan2(y, x) and atan2(z, sqrt(x^2 + y^2)) in degrees,
+ * computed in float64 from the combined xyz; azimuth 180 is written as -180.  file_sed [n_files][n_frames][nc] and file_xyz
+ * [..][3 nc], when not NULL, receive the combined arrays.  Bit-reproducible (no atomics).  Returns 0; -1, before any device call,
+ * for a NULL required pointer, n_frames or nc outside 1 .. 32767, chunk_len or chunk_hop < 1, n_chunks different from the number
+ * of starts, chunk_hop > chunk_len or chunk_len > n_frames with more than one chunk, or combine not 0 / 1; -6 when the launch
+ * fails. */
+int salsa_nn_seld_decode(const float *sed, const float *xyz, int n_files, int n_chunks, int chunk_len, int chunk_hop, int n_frames,
+                         int nc, float sed_threshold, int combine, int16_t *rows, int *counts, float *file_sed, float *file_xyz,
+                         void *hip_stream);
+
 /* The decoder's frequency mean (reference models/decoders.py: x.mean(dim=3) then (B, C, T) -> (B, T, C)) in one pass:
  * x bf16 channels-last [N][H][W][C] -> float32 y [H][N][C] (time_major != 0: the GRU scans' order) or [N][H][C]; C % 8 == 0.
  * _bwd: dx[n][h][w][c] = g[row(n, h)][c] / W, bf16 channels-last. */

@@ -1,0 +1,112 @@
+"""Test-time chunks (reference data.test_chunk_len_s / test_chunk_hop_len_s: dataset/database.py:27, :98-119) and the DCASE row
+decoding of a batch of files on the device (salsa_nn_seld_decode, include/salsa_nn.h): the reference cuts every test clip into
+overlapping chunks, runs the model on each, averages the label-rate chunk outputs back into one file prediction
+(models/interfaces.py:97-139) and writes one row per active (frame, class) pair (:210-258).  `split_test_chunks` is the cut,
+`decode_dcase_rows` everything behind the model in one launch, `rows_to_list` the host's view of its result -- exactly what
+crnn/postprocess.py's combine_chunks + to_dcase_rows give, which stay the host path and the yardstick."""
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib
+from ..dataset import get_segment_idxes, second2frame
+
+COMBINE = {'mean': 0, 'gmean': 1}
+
+
+def test_chunk_frames(test_chunk_len_s: float, test_chunk_hop_len_s: float, fs: int = 24000, hop_len: int = 300, label_rate: float = 10):
+    """The YAML keys in frames -> ((chunk_len, chunk_hop_len) in feature frames, (chunk_len, chunk_hop) in label frames): the first
+    as Database.second2frame gives them (dataset/database.py:56-57), the second as combine_chunks derives them from the first
+    (models/interfaces.py:107-108).  (4.0, 2.0) -> ((320, 160), (40, 20)); seld.yml's (60.0, 60.1) -> ((4800, 4808), (600, 601)): a
+    hop beyond the chunk length is the reference's way of asking for the whole clip in one chunk."""
+    feature_rate = fs / hop_len
+    feat = (second2frame(test_chunk_len_s, fs, hop_len), second2frame(test_chunk_hop_len_s, fs, hop_len))
+    return feat, tuple(int(f * label_rate / feature_rate) for f in feat)
+
+
+test_chunk_frames.__test__ = False       # (a product function whose name a test collector would take for a test)
+
+
+def chunk_starts(n_frames: int, chunk_len: int, chunk_hop: int) -> list:
+    """combine_chunks' chunk starts (models/interfaces.py:116-119); one chunk at least as long as the file starts at 0"""
+    if chunk_len >= n_frames:
+        return [0]
+    starts = list(range(0, n_frames - chunk_len + 1, chunk_hop))
+    if (n_frames - chunk_len) % chunk_hop != 0:
+        starts.append(n_frames - chunk_len)
+    return starts
+
+
+def split_test_chunks(feat, chunk_len: int, chunk_hop_len: int):
+    """feat (b, C, T, F) -> (b * n_chunks, C, chunk_len, F), file-major (all chunks of file 0, then file 1, ...), the chunks of a
+    file at get_segment_idxes(T, chunk_len, chunk_hop_len, 1, 0)'s starts (regular hops plus the leftover chunk flush with the
+    end): one gather on feat's device.  A single chunk that is the whole clip is returned as it is."""
+    import torch
+    b, ch, T, F = feat.shape
+    starts, _ = get_segment_idxes(T, chunk_len, chunk_hop_len, 1, 0)
+    if len(starts) == 1 and chunk_len == T:
+        return feat
+    t = torch.as_tensor(starts, device=feat.device)[:, None, None] + torch.arange(chunk_len, device=feat.device)   # (n, 1, L)
+    bi = torch.arange(b, device=feat.device)[:, None, None, None]
+    ci = torch.arange(ch, device=feat.device)[:, None]
+    return feat[bi, ci, t].reshape(b * len(starts), ch, chunk_len, F)                 # (b, n, C, L, F) in one indexing kernel
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def decode_dcase_rows(sed, xyz, chunk_len: int, chunk_hop: int, n_frames: int = 600, sed_threshold: float = 0.3,
+                      combine_method: str = 'mean', return_file_outputs: bool = False):
+    """sed (n_files, n_chunks, chunk_len, nc) ACTIVITIES (Trainer.infer's first output, for reg_xyz and accdoa alike) and xyz
+    (n_files, n_chunks, chunk_len, 3 nc): CUDA float32 tensors at the label rate, chunk_len / chunk_hop in label frames; a 3-D
+    (n_files, chunk_len, .) pair is one chunk per file.  -> rows (n_files, n_frames * nc, 4) int16 = (frame, class, azimuth,
+    elevation), of which the first counts[f] of file f are written (the rest is uninitialised memory), counts (n_files,) int32, and
+    with return_file_outputs the combined float32 file_sed (n_files, n_frames, nc) and file_xyz (.., 3 nc) -- what the reference's
+    write_output_prediction stores.  One launch on the current stream of the tensors' device, no synchronisation; there is no
+    host fallback: CPU tensors are refused (crnn/postprocess.py holds the host functions)."""
+    import torch
+    if combine_method not in COMBINE:
+        raise ValueError('combine method {} is unknown'.format(combine_method))
+    if sed.dim() == 3 and xyz.dim() == 3:
+        sed, xyz = sed[:, None], xyz[:, None]
+    if sed.dim() != 4 or xyz.dim() != 4 or sed.shape[:3] != xyz.shape[:3] or xyz.shape[3] != 3 * sed.shape[3]:
+        raise ValueError('decode_dcase_rows: sed %s / xyz %s are not (files, chunks, frames, nc) / (.., 3 nc)' % (tuple(sed.shape), tuple(xyz.shape)))
+    if not (sed.is_cuda and xyz.is_cuda and sed.device == xyz.device and sed.dtype == torch.float32 and xyz.dtype == torch.float32):
+        raise ValueError('decode_dcase_rows takes float32 tensors on one CUDA device (the host path is postprocess.combine_chunks + to_dcase_rows)')
+    n_files, n_chunks, L, nc = sed.shape
+    if L != chunk_len:
+        raise ValueError('decode_dcase_rows: chunks of %d frames, chunk_len = %d' % (L, chunk_len))
+    if n_files == 0:
+        raise ValueError('decode_dcase_rows: no files')
+    sed, xyz = sed.contiguous(), xyz.contiguous()
+    dev = sed.device
+    rows = torch.empty((n_files, n_frames * nc, 4), dtype=torch.int16, device=dev)
+    counts = torch.empty((n_files,), dtype=torch.int32, device=dev)
+    fs = torch.empty((n_files, n_frames, nc), dtype=torch.float32, device=dev) if return_file_outputs else None
+    fx = torch.empty((n_files, n_frames, 3 * nc), dtype=torch.float32, device=dev) if return_file_outputs else None
+    with torch.cuda.device(dev):
+        rc = _lib.load().salsa_nn_seld_decode(_ptr(sed), _ptr(xyz), n_files, n_chunks, chunk_len, chunk_hop, n_frames, nc,
+                                              float(sed_threshold), COMBINE[combine_method], _ptr(rows), _ptr(counts), _ptr(fs),
+                                              _ptr(fx), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == _lib.E_INVAL:
+        raise ValueError('salsa_nn_seld_decode refused %d chunks of %d frames at hop %d for %d frames x %d classes (expected %d chunks)'
+                         % (n_chunks, chunk_len, chunk_hop, n_frames, nc, len(chunk_starts(n_frames, chunk_len, max(1, chunk_hop)))))
+    if rc:
+        raise RuntimeError('salsa_nn_seld_decode failed (%d)' % rc)
+    return (rows, counts, fs, fx) if return_file_outputs else (rows, counts)
+
+
+def rows_to_list(rows, counts, eval_version: str = '2021', as_array: bool = False) -> list:
+    """decode_dcase_rows' rows (n_files, capacity, 4) and counts (n_files,) ON THE HOST (numpy arrays or CPU tensors) -> per file
+    exactly what to_dcase_rows returns: [frame, class, 0, azimuth, elevation] rows for eval_version '2021' (the zero track column
+    is added here), [frame, class, azimuth, elevation] otherwise; int64, a list of lists or with as_array one (n, 5 | 4) array."""
+    rows = rows.numpy() if hasattr(rows, 'numpy') else np.asarray(rows)
+    counts = counts.numpy() if hasattr(counts, 'numpy') else np.asarray(counts)
+    out = []
+    for f in range(rows.shape[0]):
+        r = rows[f, :int(counts[f])].astype(np.int64)
+        if eval_version == '2021':
+            r = np.concatenate([r[:, :2], np.zeros((r.shape[0], 1), dtype=np.int64), r[:, 2:]], axis=1)
+        out.append(r if as_array else r.tolist())
+    return out

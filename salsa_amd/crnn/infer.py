@@ -19,47 +19,108 @@ from ..distributed import shard_list
 from .postprocess import combine_chunks, to_dcase_rows
 
 
+def _forward_chunks(feat, forward, chunk_len, chunk_hop_len, chunk_batch, sub_batch, n_label_frames):
+    """one sub-batch of clips through test chunks: split -> forward on at most chunk_batch chunks at a time -> the chunk outputs as
+    (files, n_chunks, Lc, .), with the label-rate chunk length and hop (models/interfaces.py:107-108)"""
+    import torch
+    from .decode import chunk_starts, split_test_chunks
+    b, T = feat.shape[0], feat.shape[2]
+    chunks = split_test_chunks(feat, chunk_len, chunk_hop_len)
+    n_chunks = chunks.shape[0] // b
+    if n_chunks > 1 and chunk_hop_len > chunk_len:
+        raise ValueError('chunk_hop_len %d > chunk_len %d leaves frames between the %d chunks uncovered' % (chunk_hop_len, chunk_len, n_chunks))
+    lab_len, lab_hop = chunk_len * n_label_frames // T, chunk_hop_len * n_label_frames // T
+    if lab_len < 1 or lab_hop < 1 or (n_chunks > 1 and len(chunk_starts(n_label_frames, lab_len, lab_hop)) != n_chunks):
+        raise ValueError('%d chunks of %d feature frames at hop %d do not map onto %d label frames (chunks of %d at hop %d)'
+                         % (n_chunks, chunk_len, chunk_hop_len, n_label_frames, lab_len, lab_hop))
+    step = chunk_batch if chunk_batch is not None else max(1, sub_batch * T // chunk_len)
+    outs = [forward(chunks[i:i + step]) for i in range(0, chunks.shape[0], step)]
+    prob = torch.cat([o[0].detach().float() for o in outs]) if len(outs) > 1 else outs[0][0].detach().float()
+    xyz = torch.cat([o[1].detach().float() for o in outs]) if len(outs) > 1 else outs[0][1].detach().float()
+    if prob.shape[1] != lab_len or xyz.shape[1] != lab_len:
+        raise ValueError('forward gave %d label frames for a chunk of %d feature frames, expected %d' % (prob.shape[1], chunk_len, lab_len))
+    return prob.reshape((b, n_chunks) + tuple(prob.shape[1:])), xyz.reshape((b, n_chunks) + tuple(xyz.shape[1:])), lab_len, lab_hop
+
+
 def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'], forward: Callable[['torch.Tensor'], tuple],
                     sub_batch: int = 32, depth: int = 2, sed_threshold: float = 0.3, n_label_frames: int = 600,
-                    as_array: bool = False, stamps: Optional[list] = None) -> list:
+                    as_array: bool = False, stamps: Optional[list] = None, chunk_len: Optional[int] = None,
+                    chunk_hop_len: Optional[int] = None, decode: str = 'host', combine_method: str = 'mean',
+                    eval_version: str = '2021', n_classes: int = 12, chunk_batch: Optional[int] = None) -> list:
     """featurize(lo, hi) -> feature tensor [hi - lo, 7, T, F] of items lo..hi-1 on the model's device; forward(features) ->
     (event probabilities [b, n_label_frames, 12], xyz [b, n_label_frames, 36]).  Returns the DCASE rows of every item, in
-    item order.  The device is never idle waiting for the host: up to `depth` sub-batches are in flight."""
+    item order.  The device is never idle waiting for the host: up to `depth` sub-batches are in flight.
+
+    chunk_len / chunk_hop_len (FEATURE frames; decode.test_chunk_frames gives them for the reference's test_chunk_len_s /
+    test_chunk_hop_len_s): every clip is cut into test chunks (decode.split_test_chunks), forward sees at most chunk_batch chunks
+    at a time (default: as many as keep chunk_batch * chunk_len <= sub_batch * T, the whole-clip call's activation footprint) and
+    returns [chunks, Lc, .] for them, and the chunk outputs are combined per file (combine_method 'mean' | 'gmean').
+    decode = 'host': the float outputs are copied to the host and combine_chunks + to_dcase_rows run there; 'device': one
+    salsa_nn_seld_decode launch on the model's stream (decode.decode_dcase_rows) and only the int16 rows and the counts are copied,
+    behind the same event -- for chunks and for whole clips alike.  With none of these given the call does what it always did."""
     import torch
     assert depth >= 1 and sub_batch >= 1
+    if decode not in ('host', 'device'):
+        raise ValueError("decode must be 'host' or 'device', not {!r}".format(decode))
+    if combine_method not in ('mean', 'gmean'):
+        raise ValueError('combine method {} is unknown'.format(combine_method))
+    if chunk_len is None and chunk_hop_len is not None:
+        raise ValueError('chunk_hop_len without chunk_len')
+    if chunk_len is not None and (chunk_len < 1 or (chunk_hop_len is not None and chunk_hop_len < 1) or (chunk_batch is not None and chunk_batch < 1)):
+        raise ValueError('chunk_len, chunk_hop_len and chunk_batch must be positive')
     results = [None] * n_items
     slots: Dict[int, dict] = {}
     pending = collections.deque()
 
-    def finish(k, lo, hi, t_issue):
+    def finish(k, lo, hi, t_issue, lab_len, lab_hop):
         s = slots[k % depth]
         if s['event'] is not None:
             s['event'].synchronize()                     # this sub-batch's outputs are on the host (nothing else is waited for)
-        p, d = s['p'][:hi - lo].numpy(), s['d'][:hi - lo].numpy()
-        for i in range(lo, hi):
-            # one chunk per file (test_chunk_len = the whole clip): combine_chunks places it, as the reference does
-            fp = combine_chunks(p[i - lo][None], n_label_frames, n_label_frames, n_frames=n_label_frames)
-            fd = combine_chunks(d[i - lo][None], n_label_frames, n_label_frames, n_frames=n_label_frames)
-            results[i] = to_dcase_rows(fp, fd, sed_threshold=sed_threshold, max_nframes_per_file=n_label_frames, as_array=as_array)
+        if decode == 'device':
+            from .decode import rows_to_list
+            results[lo:hi] = rows_to_list(s['rows'][:hi - lo], s['counts'][:hi - lo], eval_version=eval_version, as_array=as_array)
+        else:
+            p, d = s['p'][:hi - lo].numpy(), s['d'][:hi - lo].numpy()
+            for i in range(lo, hi):
+                # one chunk per file (test_chunk_len = the whole clip): combine_chunks places it, as the reference does
+                pi, di = (p[i - lo], d[i - lo]) if chunk_len is not None else (p[i - lo][None], d[i - lo][None])
+                fp = combine_chunks(pi, lab_len, lab_hop, n_frames=n_label_frames, combine_method=combine_method)
+                fd = combine_chunks(di, lab_len, lab_hop, n_frames=n_label_frames, combine_method=combine_method)
+                results[i] = to_dcase_rows(fp, fd, sed_threshold=sed_threshold, n_classes=n_classes, max_nframes_per_file=n_label_frames,
+                                           eval_version=eval_version, as_array=as_array)
         if stamps is not None:
             stamps.append((lo, hi, t_issue, time.perf_counter()))
 
     for k, lo in enumerate(range(0, n_items, sub_batch)):
         hi = min(n_items, lo + sub_batch)
         t_issue = time.perf_counter()
-        prob, xyz = forward(featurize(lo, hi))
-        prob, xyz = prob.detach().float(), xyz.detach().float()
+        if chunk_len is not None:
+            prob, xyz, lab_len, lab_hop = _forward_chunks(featurize(lo, hi), forward, chunk_len,
+                                                          chunk_hop_len if chunk_hop_len is not None else chunk_len, chunk_batch,
+                                                          sub_batch, n_label_frames)
+        else:
+            prob, xyz = forward(featurize(lo, hi))
+            prob, xyz = prob.detach().float(), xyz.detach().float()
+            lab_len = lab_hop = n_label_frames
         on_gpu = prob.is_cuda
+        if decode == 'device':
+            from .decode import decode_dcase_rows
+            if chunk_len is None:                        # whole clips: one chunk of the forward's length, trimmed to n_label_frames
+                lab_len = lab_hop = prob.shape[1]
+            rows, counts = decode_dcase_rows(prob, xyz, lab_len, lab_hop, n_frames=n_label_frames, sed_threshold=sed_threshold,
+                                             combine_method=combine_method)
+            out = {'rows': rows, 'counts': counts}       # 8 bytes per possible row + one count per clip instead of the float outputs
+        else:
+            out = {'p': prob, 'd': xyz}
         s = slots.get(k % depth)
-        if s is None or s['p'].shape[0] < hi - lo:
-            s = slots[k % depth] = {'p': torch.empty((hi - lo,) + tuple(prob.shape[1:]), dtype=torch.float32, pin_memory=on_gpu),
-                                    'd': torch.empty((hi - lo,) + tuple(xyz.shape[1:]), dtype=torch.float32, pin_memory=on_gpu),
-                                    'event': torch.cuda.Event() if on_gpu else None}
-        s['p'][:hi - lo].copy_(prob, non_blocking=True)
-        s['d'][:hi - lo].copy_(xyz, non_blocking=True)
+        if s is None or any(s[n].shape[0] < hi - lo for n in out):
+            s = slots[k % depth] = {n: torch.empty((hi - lo,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=on_gpu) for n, t in out.items()}
+            s['event'] = torch.cuda.Event() if on_gpu else None
+        for n, t in out.items():
+            s[n][:hi - lo].copy_(t, non_blocking=True)
         if s['event'] is not None:
             s['event'].record()
-        pending.append((k, lo, hi, t_issue))
+        pending.append((k, lo, hi, t_issue, lab_len, lab_hop))
         while len(pending) >= depth:                     # slot (k + 1) % depth is free again before sub-batch k + 1 is issued
             finish(*pending.popleft())
     while pending:
@@ -70,14 +131,20 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
 def infer_clips_sharded(names: Sequence[str], featurize: Callable[[List[str]], 'torch.Tensor'],
                         forward: Callable[['torch.Tensor'], tuple], rank: int = 0, world: int = 1, sub_batch: int = 32,
                         sed_threshold: float = 0.3, n_label_frames: int = 600, gather: bool = True, depth: int = 2,
-                        stamps: Optional[list] = None) -> Dict[str, list]:
+                        stamps: Optional[list] = None, chunk_len: Optional[int] = None, chunk_hop_len: Optional[int] = None,
+                        decode: str = 'host', combine_method: str = 'mean', eval_version: str = '2021', n_classes: int = 12,
+                        chunk_batch: Optional[int] = None) -> Dict[str, list]:
     """names: all clip names (any order; sharded over the SORTED list).  featurize(list of names) -> feature tensor
     [b, 7, T, F] on the model's device (e.g. SalsaExtractor.extract of the clips' audio with the scaler attached, cropped
     to 8 * n_label_frames frames); forward(features) -> (event probabilities [b, n_label_frames, 12], xyz [b, .., 36]), e.g.
-    Trainer.infer.  Returns {clip name: DCASE rows} for ALL clips on every rank (gather=True) or for this rank's shard."""
+    Trainer.infer.  Returns {clip name: DCASE rows} for ALL clips on every rank (gather=True) or for this rank's shard.
+    chunk_len, chunk_hop_len, decode, combine_method, eval_version, n_classes, chunk_batch: infer_pipelined's test-chunk and
+    device-decoding options, handed through."""
     mine = shard_list(sorted(names), rank, world)
     rows = infer_pipelined(len(mine), lambda lo, hi: featurize(mine[lo:hi]), forward, sub_batch=sub_batch, depth=depth,
-                           sed_threshold=sed_threshold, n_label_frames=n_label_frames, stamps=stamps)
+                           sed_threshold=sed_threshold, n_label_frames=n_label_frames, stamps=stamps, chunk_len=chunk_len,
+                           chunk_hop_len=chunk_hop_len, decode=decode, combine_method=combine_method, eval_version=eval_version,
+                           n_classes=n_classes, chunk_batch=chunk_batch)
     out = dict(zip(mine, rows))
     if gather and world > 1:
         import torch.distributed as dist
