@@ -52,7 +52,8 @@ typedef struct salsa_baseline_params {
     int win_len;            /* <= n_fft; periodic Hann centred in the FFT frame */
     int n_mels;             /* mel types: mel bands (and kept GCC lags); ignored by the lin types */
     int feature_type;       /* SALSA_BASELINE_* */
-    double fmin, fmax;      /* mel types: librosa.filters.mel's fmin / fmax in Hz (fmax <= 0: fs / 2); fmax is clamped to fs // 2 */
+    double fmin, fmax;      /* mel types: librosa.filters.mel's fmin / fmax in Hz (fmax <= 0: fs / 2), used as given:
+                             * only extract_features (Python) clamps fmax to fs // 2, as the reference's extract_features does */
     int is_compressed_freq; /* lin types: 1 -> 200 | 100 rows (bins above 9 kHz in groups of 8), 0 -> n_fft / 2 rows */
     int reserved;           /* 0 */
 } salsa_baseline_params;

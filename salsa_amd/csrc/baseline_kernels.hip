@@ -100,9 +100,12 @@ template <typename T, int N, int NTR> __device__ __forceinline__ void block_fft(
 }
 
 // z[p][n] = w[n] (y_{2p}[s] + i y_{2p+1}[s]), s = t hop - N/2 + n reflected at both clip ends (np.pad(mode='reflect'): one fold
-// suffices because the host refuses clips of <= N/2 samples); samples under a zero window are not read
+// suffices because the host refuses clips of <= N/2 samples); samples under a zero window are not read.  nz[c] (zero on entry)
+// is set when channel c has a non-zero sample under the window: the packed transform leaves a digitally silent channel the
+// round-off of its partner (~1e-16 |X_partner|) where the FFT of zeros is exactly 0, and angle(R) / IV / (||IV|| + 1e-8) of that
+// round-off are not small, so unpack4 writes an exact 0 for a channel without a set flag.
 template <int N> __device__ __forceinline__ void load_frame(cplx<double> *z, const float *__restrict__ clip, int Ns, int t, int hop,
-                                                            const double *__restrict__ win)
+                                                            const double *__restrict__ win, int *nz)
 {
     for (int e = threadIdx.x; e < 2 * N; e += BL_NT) {
         const int p = e / N, n = e % N;
@@ -112,22 +115,25 @@ template <int N> __device__ __forceinline__ void load_frame(cplx<double> *z, con
             int s = t * hop - N / 2 + n;
             s = s < 0 ? -s : s;
             s = s >= Ns ? 2 * (Ns - 1) - s : s;
-            v = {w * (double)clip[(size_t)(2 * p) * Ns + s], w * (double)clip[(size_t)(2 * p + 1) * Ns + s]};
+            const float ya = clip[(size_t)(2 * p) * Ns + s], yb = clip[(size_t)(2 * p + 1) * Ns + s];
+            if (ya != 0.f) nz[2 * p] = 1;     // (every writer stores the same value)
+            if (yb != 0.f) nz[2 * p + 1] = 1;
+            v = {w * (double)ya, w * (double)yb};
         }
         z[e] = v;
     }
 }
 
-// X[c][k] (complex64), k = 0 .. N/2, from the two packed transforms
-template <int N> __device__ __forceinline__ void unpack4(const cplx<double> *z, float2 *X)
+// X[c][k] (complex64), k = 0 .. N/2, from the two packed transforms; exactly 0 for a channel that load_frame found silent
+template <int N> __device__ __forceinline__ void unpack4(const cplx<double> *z, float2 *X, const int *nz)
 {
     constexpr int NB = N / 2 + 1;
     for (int e = threadIdx.x; e < 2 * NB; e += BL_NT) {
         const int p = e / NB, k = e % NB;
         cplx<double> x0, x1;
         salsa::unpack_pair_prescaled(z[p * N + k], z[p * N + ((N - k) & (N - 1))], x0, x1);
-        X[(2 * p) * NB + k] = make_float2((float)x0.re, (float)x0.im);
-        X[(2 * p + 1) * NB + k] = make_float2((float)x1.re, (float)x1.im);
+        X[(2 * p) * NB + k] = nz[2 * p] ? make_float2((float)x0.re, (float)x0.im) : make_float2(0.f, 0.f);
+        X[(2 * p + 1) * NB + k] = nz[2 * p + 1] ? make_float2((float)x1.re, (float)x1.im) : make_float2(0.f, 0.f);
     }
 }
 
@@ -136,7 +142,8 @@ __device__ __forceinline__ float power32(const float2 x) // |x|^2 in float32: th
     const float t = x.x * x.x;
     return __builtin_fmaf(x.y, x.y, t);
 }
-__device__ __forceinline__ float db10(float p) { return 3.01029995663981195f * __log2f(fmaxf(1e-10f, p)); } // 10 log10(max(1e-10, p))
+// 10 log10(max(1e-10, p)); the clamp's own value is written as the constant -100, whatever the last bit of __log2f(1e-10f)
+__device__ __forceinline__ float db10(float p) { return p > 1e-10f ? 3.01029995663981195f * __log2f(p) : -100.f; }
 
 // rows [c0, c0 + nrows) of frame t: row c at feature f = g(sum_k W[f][k] * val(c, k))
 template <typename V, typename G> __device__ __forceinline__ void project_rows(const BParams &kp, int nrows, int c0, float *o, int t, V val, G g)
@@ -176,15 +183,18 @@ __global__ __launch_bounds__(BL_NT) void baseline_kernel(const BParams kp, const
     __shared__ cplx<double> z[KIND == KIND_GCC ? 2 * N2 : 2 * N]; // the forward transforms; then the GCC's 3 float32 inverse transforms
     __shared__ float2 X[KIND == KIND_GCC ? 4 * NB2 : 4 * NB];     // complex64 spectra of the 4 channels
     __shared__ float ivn[KIND == KIND_IV ? 3 * NB : 1];           // IV / ||IV|| per bin
+    __shared__ int nz[4];                                         // channel c has a non-zero sample in the current frame
 
     const int t = blockIdx.x, b = blockIdx.y;
     const float *clip = audio + (size_t)b * 4 * Ns;
     float *o = out + (size_t)b * kp.C * kp.T * kp.F;
 
-    load_frame<N>(z, clip, Ns, t, kp.hop, kp.win1);
+    if (threadIdx.x < 4) nz[threadIdx.x] = 0;
+    __syncthreads();
+    load_frame<N>(z, clip, Ns, t, kp.hop, kp.win1, nz);
     __syncthreads();
     block_fft<double, N, 2>(z, kp.tw1);
-    unpack4<N>(z, X);
+    unpack4<N>(z, X, nz);
     __syncthreads();
     project_rows(kp, 4, 0, o, t, [&](int c, int k) { return power32(X[c * NB + k]); }, [](float a) { return db10(a); });
 
@@ -207,11 +217,12 @@ __global__ __launch_bounds__(BL_NT) void baseline_kernel(const BParams kp, const
     }
 
     if (KIND == KIND_GCC) {
+        if (threadIdx.x < 4) nz[threadIdx.x] = 0; // (unpack4's reads of the first frame's flags ended at the barrier behind it)
         __syncthreads(); // the log rows' reads of X are done
-        load_frame<N2>(z, clip, Ns, t, kp.hop, kp.win2);
+        load_frame<N2>(z, clip, Ns, t, kp.hop, kp.win2, nz);
         __syncthreads();
         block_fft<double, N2, 2>(z, kp.tw2);
-        unpack4<N2>(z, X);
+        unpack4<N2>(z, X, nz);
         __syncthreads();
         // spectra of the 3 packed inverse transforms, conjugated (IDFT(S) = conj(DFT(conj(S)))): transform g carries pair 2g in
         // its real part and pair 2g+1 in its imaginary part, both Hermitian-extended; DC and Nyquist are real (np.fft.irfft drops

@@ -5,6 +5,26 @@ import numpy as np
 
 PAIRS = [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]
 
+# --------------------------------------------------------------------------------------------------------- comparison rules
+# An implementation whose float32 STFT may differ from this one's in the last bit (float64 FFTs in another order, rounded to
+# complex64) is held per value to  base + K * bound :  base is the fixed tolerance of its channel group (what g21 is held to),
+# bound(...) below the largest change of that value when every spectral component moves by one float32 ulp.  Both constants are
+# measured from this restatement alone (tests/test_baseline_off_default_cpu.py re-measures them on every clip the GPU tests run):
+#   K          margin over the measured 1-ulp movement (4, as flex_reference.DELTA_STFT takes it).  On the g21 cases K * bound stays
+#              under base for every held value (largest bound / base seen: log 0.10, IV 0.18 held / 0.95 over all, GCC 0.006), so
+#              the tolerance is within 2 x the fixed one and K is not reduced.
+#   BOUND_MAX  a value is ill-conditioned under a 1-ulp STFT, and left out of the value comparison (range check only), where its
+#              bound exceeds BOUND_MAX * base; 1 / K, i.e. exactly where the tolerance would pass 2 x base.  Seen over the 735 built
+#              clips: largest bound / base log 0.13, IV 0.82, GCC 0.006, so only IV values are ever left out (near-cancelling
+#              Re(conj(X_0) X_j) in all three components), at most 0.44 % of one (setting, family) -- under EXCLUDED_SHARE_MAX.
+# test_baseline_off_default_gpu.py prints the largest |out - ref| / (base + K * bound) of the HIP kernels per setting and group.
+K = 4
+BOUND_MAX = 0.25
+EXCLUDED_SHARE_MAX = 1e-2
+BOUND_SEEDS = 4
+ATOL_DB, RTOL = 2e-5, 1e-5      # the log rows' tolerance of tests/test_baseline_features_gpu.py
+GCC_RANGE = 1.0 + 1e-5          # |GCC| of a left-out value
+
 
 def stft(y, n_fft, hop, win_len):
     """(n_fft//2 + 1, T) complex64 of one channel"""
@@ -60,23 +80,107 @@ def gcc(Xm, Xn, L, f64):
     """kept lags (T, L) of irfft(exp(i angle(Xm conj(Xn)))) in float64"""
     R = Xm.astype(np.complex128) * np.conj(Xn.astype(np.complex128)) if f64 else Xm * np.conj(Xn)
     ph = np.exp(1j * np.angle(R).astype(np.float64))
+    # a digitally silent channel: R is a signed zero, whose angle numpy makes 0 or pi by the signs of the OTHER channel's parts
+    # alone ((a + bi)(0 - 0i) has real part -0 iff a, b < 0).  That sign carries nothing; R == 0 is the phasor 1, as it is where
+    # every channel is silent (+0, the only such case in g21).
+    ph[R == 0] = 1.0
     cc = np.fft.irfft(ph, axis=0).T
     return np.concatenate((cc[:, -(L // 2 + L % 2):], cc[:, :L // 2]), axis=1)
 
 
-def extract(feature_type, audio, fs=24000, n_fft=512, hop=300, win_len=None, n_mels=128, fmin=50, fmax=12000, compress=True):
-    """(C, T, F) float32 of one (4, N) clip"""
+def spectra(audio, n_fft, hop, win_len=None, gcc=False):
+    """-> (X, X2): the complex64 STFTs [4][n_fft/2 + 1][T] of a (4, N) clip and, with gcc, the 2 n_fft ones [4][n_fft + 1][T] the
+    GCC types take their cross spectra from (else None)"""
     win_len = win_len or n_fft
+    X = np.stack([stft(audio[c], n_fft, hop, win_len) for c in range(4)])
+    X2 = np.stack([stft(audio[c], 2 * n_fft, hop, win_len) for c in range(4)]) if gcc else None
+    return X, X2
+
+
+def features_from_spectra(feature_type, X, X2=None, fs=24000, n_fft=512, n_mels=128, fmin=50, fmax=12000, compress=True):
+    """(C, T, F) float32 from the spectra of `spectra`"""
     lin = feature_type.startswith('lin')
-    W = lin_matrix(n_fft, compress) if lin else mel_matrix(fs, n_fft, n_mels, fmin, fmax)
-    X = [stft(audio[c], n_fft, hop, win_len) for c in range(4)]
+    W = lin_matrix(n_fft, compress) if lin else mel_matrix(fs, n_fft, n_mels, fmin, fmax or fs / 2.0)
     rows = [db((W @ (np.abs(x) ** 2)).T) for x in X]
     if feature_type.endswith('iv'):
         iv = [np.real(np.conj(X[0]) * X[j]) for j in (1, 2, 3)]
         nrm = np.sqrt(iv[0] ** 2 + iv[1] ** 2 + iv[2] ** 2) + np.float32(1e-8)
         rows += [(W @ (v / nrm)).T for v in iv]
     elif feature_type.endswith('gcc'):
-        n2 = 2 * n_fft
-        X2 = [stft(audio[c], n2, hop, win_len) for c in range(4)]
         rows += [gcc(X2[m], X2[n], W.shape[0], not lin) for n, m in PAIRS]
     return np.stack(rows).astype(np.float32)
+
+
+def extract(feature_type, audio, fs=24000, n_fft=512, hop=300, win_len=None, n_mels=128, fmin=50, fmax=12000, compress=True):
+    """(C, T, F) float32 of one (4, N) clip"""
+    X, X2 = spectra(audio, n_fft, hop, win_len, feature_type.endswith('gcc'))
+    return features_from_spectra(feature_type, X, X2, fs, n_fft, n_mels, fmin, fmax, compress)
+
+
+def group_slices(feature_type):
+    """channel groups of the (C, T, F) output: the 4 log rows, then the IV or GCC planes"""
+    g = {'log': slice(0, 4)}
+    if feature_type.endswith('iv'):
+        g['iv'] = slice(4, 7)
+    elif feature_type.endswith('gcc'):
+        g['gcc'] = slice(4, 10)
+    return g
+
+
+def bound(feature_type, audio, fs=24000, n_fft=512, hop=300, win_len=None, n_mels=128, fmin=50, fmax=12000, compress=True,
+          seeds=BOUND_SEEDS):
+    """(C, T, F) float64: per output value, the largest |change| of features_from_spectra when every component of the spectra is
+    moved by one float32 ulp (flex_reference.ulp_perturbed: seeded coin per component, exact zeros stay), over `seeds` seeds.  How
+    far a correct float32 STFT can move that value; made of the reference alone."""
+    from flex_reference import ulp_perturbed
+    X, X2 = spectra(audio, n_fft, hop, win_len, feature_type.endswith('gcc'))
+    f0 = features_from_spectra(feature_type, X, X2, fs, n_fft, n_mels, fmin, fmax, compress).astype(np.float64)
+    b = np.zeros_like(f0)
+    for s in range(seeds):
+        Xp = ulp_perturbed(X, 1000 + s)
+        X2p = ulp_perturbed(X2, 2000 + s) if X2 is not None else None
+        f = features_from_spectra(feature_type, Xp, X2p, fs, n_fft, n_mels, fmin, fmax, compress)
+        b = np.maximum(b, np.abs(f.astype(np.float64) - f0))
+    return b
+
+
+def base_tolerance(group, ref):
+    """the fixed per-value tolerance of a channel group (tests/test_baseline_features_gpu.py)"""
+    a = np.abs(np.asarray(ref, np.float64))
+    return {'log': ATOL_DB + RTOL * a, 'iv': 1e-6 + 1e-5 * a, 'gcc': np.full(a.shape, 1e-5)}[group]
+
+
+def row_sums(feature_type, fs=24000, n_fft=512, hop=300, win_len=None, n_mels=128, fmin=50, fmax=12000, compress=True):
+    """(F,) float64 row sums of the projection matrix: the range of an IV projection (every per-bin value has modulus <= 1)"""
+    W = lin_matrix(n_fft, compress) if feature_type.startswith('lin') else mel_matrix(fs, n_fft, n_mels, fmin, fmax or fs / 2.0)
+    return W.astype(np.float64).sum(axis=1)
+
+
+def compare(out, ref, bnd, feature_type, wsum, what=''):
+    """`out` (C, T, F) of an implementation against extract(...) `ref` with bound(...) `bnd`: every value within base + K * bound,
+    except where bound > BOUND_MAX * base (range check only; their share of a channel group capped).  `out` None: the reference
+    alone (the shares).  -> {group: (worst |out - ref| / tolerance, left-out share)}"""
+    res = {}
+    for g, sl in group_slices(feature_type).items():
+        r, b = ref[sl].astype(np.float64), bnd[sl]
+        base = base_tolerance(g, r)
+        held = b <= BOUND_MAX * base
+        share = 1.0 - held.mean()
+        assert share <= EXCLUDED_SHARE_MAX, '%s %s: %.4f of the values are ill-conditioned under a 1-ulp STFT' % (what, g, share)
+        assert g == 'iv' or held.all(), '%s %s: only IV values may be left out' % (what, g)
+        worst = 0.0
+        if out is not None:
+            o = out[sl].astype(np.float64)
+            assert o.shape == r.shape and np.isfinite(o).all(), (what, g)
+            ratio = np.where(held, np.abs(o - r) / (base + K * b), 0.0)
+            worst = float(ratio.max())
+            i = np.unravel_index(ratio.argmax(), ratio.shape)
+            assert worst <= 1.0, '%s %s: |out - ref| = %.3e is %.2f x its tolerance at %s (ref %.6g, bound %.3e)' % (
+                what, g, abs(o[i] - r[i]), worst, i, r[i], b[i])
+            if g == 'iv':
+                # every per-bin IV / (||IV|| + 1e-8) has modulus <= 1; 1e-6: the float32 roundings of the quotient and of the row's sum
+                assert (np.abs(o) <= wsum[None, None, :] * (1 + 1e-6))[~held].all(), '%s: a left-out IV value is out of range' % what
+            elif g == 'gcc':
+                assert (np.abs(o) <= GCC_RANGE)[~held].all(), what
+        res[g] = (worst, share)
+    return res
