@@ -264,6 +264,28 @@ int salsa_nn_seld_decode(const float *sed, const float *xyz, int n_files, int n_
                          int nc, float sed_threshold, int combine, int16_t *rows, int *counts, float *file_sed, float *file_xyz,
                          void *hip_stream);
 
+/* DCASE rows against ground-truth rows: the SELD 2021 counters of crnn/metrics.py::SeldMetrics.update (reference metrics/
+ * SELD2021_evaluation_metrics.py:81-195) per (file, segment), on the device (salsa_amd/csrc/seld_score.hip; statements in
+ * seld_score.h).  pred_rows [n_files][pred_capacity][4] int16 (frame, class, azimuth, elevation in integer degrees; 8-byte aligned)
+ * with pred_counts [n_files] -- what salsa_nn_seld_decode writes -- and gt_rows / gt_counts / gt_capacity in the same layout; rows
+ * may come in any order.  n_seg = ceil(n_frames / label_rate) segments per file; record = file * n_seg + segment.  Outputs, every
+ * element written: counters [records][10] int32 (TP FP FN S D I Nref DE_TP DE_FP DE_FN), total_de [records] float64, status
+ * [records] int32: 0 scored; 1 doubt (in some frame another pairing costs within `margin` degrees of the best, or a slot average
+ * lies within `margin` of doa_threshold -- the device's sin / cos / acos are not the host's bit for bit, so the host decides);
+ * 2 refused (a (class, frame) cell with more than 4 DOAs on a side, or a count that is negative or above its capacity, in which
+ * case no row of the file is read).  Records of status 1 and 2 carry zeros.  Distances are metrics.py::angular_distance_deg in
+ * float64 without fma; the pairing is the minimum-total-cost injective map by brute force.  sum_counters [10] int64 and sum_de
+ * [1] float64 (both or neither NULL) receive the status-0 records added up, total_de as one running sum in record order.
+ * Bit-reproducible (no atomics).  Returns 0; -1, before any device call, for a NULL or misaligned pointer, n_files outside
+ * 1 .. 65535, n_frames outside 1 .. 32767, a capacity < 1, label_rate or n_classes outside 1 .. 32, a NaN threshold or a margin that
+ * is negative, NaN or infinite; -6 when a launch fails. */
+int salsa_nn_seld_score(const int16_t *pred_rows, const int *pred_counts, int pred_capacity, const int16_t *gt_rows, const int *gt_counts,
+                        int gt_capacity, int n_files, int n_frames, int label_rate, int n_classes, double doa_threshold, double margin,
+                        int *counters, double *total_de, int *status, int64_t *sum_counters, double *sum_de, void *hip_stream);
+/* salsa_nn_seld_score's distance statement alone: quads [n][4] int16 (azimuth1, elevation1, azimuth2, elevation2) -> out [n]
+ * float64 degrees (tools/probe_score_distance.py measures its deviation from the host's, which sizes `margin`). */
+int salsa_nn_seld_distance(const int16_t *quads, int64_t n, double *out, void *hip_stream);
+
 /* The decoder's frequency mean (reference models/decoders.py: x.mean(dim=3) then (B, C, T) -> (B, T, C)) in one pass:
  * x bf16 channels-last [N][H][W][C] -> float32 y [H][N][C] (time_major != 0: the GRU scans' order) or [N][H][C]; C % 8 == 0.
  * _bwd: dx[n][h][w][c] = g[row(n, h)][c] / W, bf16 channels-last. */

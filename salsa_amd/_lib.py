@@ -14,6 +14,7 @@ CONV_1X1_SRC_PATH = os.path.join(_HERE, 'csrc', 'conv_1x1.hip')
 BASELINE_SRC_PATH = os.path.join(_HERE, 'csrc', 'baseline_kernels.hip')
 LSTM_SRC_PATH = os.path.join(_HERE, 'csrc', 'lstm_scan.hip')
 DECODE_SRC_PATH = os.path.join(_HERE, 'csrc', 'seld_decode.hip')
+SCORE_SRC_PATH = os.path.join(_HERE, 'csrc', 'seld_score.hip')
 
 FORMAT = {'foa': 0, 'mic': 1}
 FEATURE = {'salsa': 0, 'salsa_lite': 1, 'salsa_ipd': 2}
@@ -50,7 +51,7 @@ _lib = None
 
 def build_command():
     return ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC', '-o', LIB_PATH, SRC_PATH, GRU_SRC_PATH, NN_SRC_PATH, CONV_SRC_PATH, CONV_WIDE_SRC_PATH, CONV_1X1_SRC_PATH,
-            BASELINE_SRC_PATH, LSTM_SRC_PATH, DECODE_SRC_PATH]
+            BASELINE_SRC_PATH, LSTM_SRC_PATH, DECODE_SRC_PATH, SCORE_SRC_PATH]
 
 
 def load():
@@ -131,6 +132,8 @@ def load():
     L.salsa_nn_accdoa_loss.argtypes = [vp, vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp, vp]
     L.salsa_nn_accdoa_sed.argtypes = [vp, vp, C.c_int64, C.c_int, vp]
     L.salsa_nn_seld_decode.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp]
+    L.salsa_nn_seld_score.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
+    L.salsa_nn_seld_distance.argtypes = [vp, C.c_int64, vp, vp]
     L.salsa_nn_freq_mean_fwd.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.salsa_nn_freq_mean_bwd.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.salsa_nn_freq_pool_fwd.argtypes = [vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -211,6 +214,7 @@ LSTM_EXPORTS = ['salsa_lstm_scan_fwd', 'salsa_lstm_scan_bwd']
 NN_EXPORTS = ['salsa_nn_avgpool2x2_fwd', 'salsa_nn_avgpool2x2_bwd', 'salsa_nn_conv3x3_c64', 'salsa_nn_conv3x3_c64_bias_act', 'salsa_nn_conv3x3_c64_wrw', 'salsa_nn_conv3x3_stem', 'salsa_nn_conv3x3_c64_bias_act_pool', 'salsa_nn_conv3x3_wide_supported', 'salsa_nn_conv3x3_wide', 'salsa_nn_conv3x3_wide_bias_act', 'salsa_nn_conv3x3_wide_wrw_supported', 'salsa_nn_conv3x3_wide_table_len', 'salsa_nn_conv3x3_wide_tile_count', 'salsa_nn_conv3x3_wide_tables', 'salsa_nn_conv3x3_wide_wrw', 'salsa_nn_bn_supported', 'salsa_nn_bn_workspace_bytes', 'salsa_nn_bn_train_fwd',
               'salsa_nn_bn_eval_fwd', 'salsa_nn_bn_bwd', 'salsa_nn_bn_train_fwd_pool', 'salsa_nn_bn_bwd_pool', 'salsa_nn_conv_filter_bank', 'salsa_nn_conv3x3_c64_stats_blocks', 'salsa_nn_conv3x3_c64_config', 'salsa_nn_conv3x3_c64_stats', 'salsa_nn_conv3x3_stem_wrw', 'salsa_nn_conv3x3_stem_stats_blocks', 'salsa_nn_conv3x3_stem_stats', 'salsa_nn_conv3x3_stem_wrw_bn', 'salsa_nn_conv1x1_supported', 'salsa_nn_conv1x1', 'salsa_nn_conv1x1_wrw_supported', 'salsa_nn_conv1x1_wrw', 'salsa_nn_seld_loss', 'salsa_nn_seld_loss_bwd', 'salsa_nn_accdoa_loss', 'salsa_nn_accdoa_sed', 'salsa_nn_freq_mean_fwd',
               'salsa_nn_freq_mean_bwd', 'salsa_nn_colsum2', 'salsa_nn_conv3x3_wide_stats', 'salsa_nn_conv3x3_wide_stats_blocks', 'salsa_nn_conv3x3_wide_config', 'salsa_nn_set_deterministic', 'salsa_nn_get_deterministic', 'salsa_nn_conv3x3_stem_wrw_bnf', 'salsa_nn_conv3x3_stem_wrw_bnf_ws_bytes', 'salsa_nn_conv3x3_stem16_wrw_bnf_ws_bytes', 'salsa_nn_bn_train_finalize', 'salsa_nn_conv3x3_c64_xform_stats', 'salsa_nn_conv3x3_c64_wrw_xform', 'salsa_nn_adam_step', 'salsa_nn_bn_train_fwd_bits',
-              'salsa_nn_bn_train_fwd_pool_bits', 'salsa_nn_bn_bwd_pool_bits', 'salsa_nn_freq_pool_fwd', 'salsa_nn_freq_pool_bwd', 'salsa_nn_seld_decode']
+              'salsa_nn_bn_train_fwd_pool_bits', 'salsa_nn_bn_bwd_pool_bits', 'salsa_nn_freq_pool_fwd', 'salsa_nn_freq_pool_bwd', 'salsa_nn_seld_decode', 'salsa_nn_seld_score',
+              'salsa_nn_seld_distance']
 BASELINE_EXPORTS = ['salsa_baseline_plan_create', 'salsa_baseline_plan_destroy', 'salsa_baseline_output_shape',
                     'salsa_baseline_workspace_bytes', 'salsa_baseline_extract_batch', 'salsa_baseline_mel_matrix']

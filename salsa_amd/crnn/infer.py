@@ -46,7 +46,8 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
                     sub_batch: int = 32, depth: int = 2, sed_threshold: float = 0.3, n_label_frames: int = 600,
                     as_array: bool = False, stamps: Optional[list] = None, chunk_len: Optional[int] = None,
                     chunk_hop_len: Optional[int] = None, decode: str = 'host', combine_method: str = 'mean',
-                    eval_version: str = '2021', n_classes: int = 12, chunk_batch: Optional[int] = None) -> list:
+                    eval_version: str = '2021', n_classes: int = 12, chunk_batch: Optional[int] = None,
+                    score: Optional[tuple] = None) -> list:
     """featurize(lo, hi) -> feature tensor [hi - lo, 7, T, F] of items lo..hi-1 on the model's device; forward(features) ->
     (event probabilities [b, n_label_frames, 12], xyz [b, n_label_frames, 36]).  Returns the DCASE rows of every item, in
     item order.  The device is never idle waiting for the host: up to `depth` sub-batches are in flight.
@@ -57,7 +58,12 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
     returns [chunks, Lc, .] for them, and the chunk outputs are combined per file (combine_method 'mean' | 'gmean').
     decode = 'host': the float outputs are copied to the host and combine_chunks + to_dcase_rows run there; 'device': one
     salsa_nn_seld_decode launch on the model's stream (decode.decode_dcase_rows) and only the int16 rows and the counts are copied,
-    behind the same event -- for chunks and for whole clips alike.  With none of these given the call does what it always did."""
+    behind the same event -- for chunks and for whole clips alike.  With none of these given the call does what it always did.
+
+    score = (gt_rows, gt_counts, accumulator), with decode='device' only: the ground truth of all n_items items on the model's device
+    (score.gt_rows_to_device) and a score.DeviceSeldScore.  Each sub-batch's rows are scored against their slice of the ground truth
+    on the same stream right behind the decode launch (score.score_dcase_rows_async, with the accumulator's n_classes, threshold,
+    label_rate and margin) and merged into the accumulator when the sub-batch is finished.  The rows returned are unchanged."""
     import torch
     assert depth >= 1 and sub_batch >= 1
     if decode not in ('host', 'device'):
@@ -68,6 +74,12 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
         raise ValueError('chunk_hop_len without chunk_len')
     if chunk_len is not None and (chunk_len < 1 or (chunk_hop_len is not None and chunk_hop_len < 1) or (chunk_batch is not None and chunk_batch < 1)):
         raise ValueError('chunk_len, chunk_hop_len and chunk_batch must be positive')
+    if score is not None:
+        if decode != 'device':
+            raise ValueError("score= scores the rows of decode='device'; with decode={!r} use metrics.SeldMetrics on the returned rows".format(decode))
+        gt_rows, gt_counts, accumulator = score
+        if gt_rows.shape[0] != n_items or gt_counts.shape[0] != n_items:
+            raise ValueError('score=: ground truth of %d files for %d items' % (gt_rows.shape[0], n_items))
     results = [None] * n_items
     slots: Dict[int, dict] = {}
     pending = collections.deque()
@@ -76,6 +88,8 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
         s = slots[k % depth]
         if s['event'] is not None:
             s['event'].synchronize()                     # this sub-batch's outputs are on the host (nothing else is waited for)
+        if s.get('score') is not None:
+            accumulator.merge(s.pop('score').result())
         if decode == 'device':
             from .decode import rows_to_list
             results[lo:hi] = rows_to_list(s['rows'][:hi - lo], s['counts'][:hi - lo], eval_version=eval_version, as_array=as_array)
@@ -120,6 +134,11 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
             s[n][:hi - lo].copy_(t, non_blocking=True)
         if s['event'] is not None:
             s['event'].record()
+        if score is not None:
+            from .score import score_dcase_rows_async
+            s['score'] = score_dcase_rows_async(rows, counts, gt_rows[lo:hi], gt_counts[lo:hi], n_frames=n_label_frames,
+                                                label_rate=accumulator.label_rate, n_classes=accumulator.n_classes,
+                                                doa_threshold=accumulator.doa_threshold, margin=accumulator.margin)
         pending.append((k, lo, hi, t_issue, lab_len, lab_hop))
         while len(pending) >= depth:                     # slot (k + 1) % depth is free again before sub-batch k + 1 is issued
             finish(*pending.popleft())
@@ -133,18 +152,20 @@ def infer_clips_sharded(names: Sequence[str], featurize: Callable[[List[str]], '
                         sed_threshold: float = 0.3, n_label_frames: int = 600, gather: bool = True, depth: int = 2,
                         stamps: Optional[list] = None, chunk_len: Optional[int] = None, chunk_hop_len: Optional[int] = None,
                         decode: str = 'host', combine_method: str = 'mean', eval_version: str = '2021', n_classes: int = 12,
-                        chunk_batch: Optional[int] = None) -> Dict[str, list]:
+                        chunk_batch: Optional[int] = None, score: Optional[tuple] = None) -> Dict[str, list]:
     """names: all clip names (any order; sharded over the SORTED list).  featurize(list of names) -> feature tensor
     [b, 7, T, F] on the model's device (e.g. SalsaExtractor.extract of the clips' audio with the scaler attached, cropped
     to 8 * n_label_frames frames); forward(features) -> (event probabilities [b, n_label_frames, 12], xyz [b, .., 36]), e.g.
     Trainer.infer.  Returns {clip name: DCASE rows} for ALL clips on every rank (gather=True) or for this rank's shard.
     chunk_len, chunk_hop_len, decode, combine_method, eval_version, n_classes, chunk_batch: infer_pipelined's test-chunk and
-    device-decoding options, handed through."""
+    device-decoding options, handed through.  score = (gt_rows, gt_counts, accumulator): infer_pipelined's, for THIS rank's shard
+    (the ground truth of shard_list(sorted(names), rank, world), in that order); every rank's accumulator holds its shard's score,
+    to be combined with DeviceSeldScore.merge."""
     mine = shard_list(sorted(names), rank, world)
     rows = infer_pipelined(len(mine), lambda lo, hi: featurize(mine[lo:hi]), forward, sub_batch=sub_batch, depth=depth,
                            sed_threshold=sed_threshold, n_label_frames=n_label_frames, stamps=stamps, chunk_len=chunk_len,
                            chunk_hop_len=chunk_hop_len, decode=decode, combine_method=combine_method, eval_version=eval_version,
-                           n_classes=n_classes, chunk_batch=chunk_batch)
+                           n_classes=n_classes, chunk_batch=chunk_batch, score=score)
     out = dict(zip(mine, rows))
     if gather and world > 1:
         import torch.distributed as dist

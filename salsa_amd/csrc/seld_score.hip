@@ -1,0 +1,209 @@
+// seld_score.hip -- salsa_nn_seld_score (include/salsa_nn.h): DCASE rows against ground-truth rows, the SELD 2021 counters of
+// crnn/metrics.py::SeldMetrics per (file, segment), on the device.  The statements are seld_score.h's; this file bins the rows.
+//
+// One workgroup of 256 threads (4 waves) per (file, segment).  Each side's rows are walked in tiles of 256 consecutive rows, one
+// 8-byte load per row; the tile's rows of this segment are compacted in ARRIVAL order (one ballot per wave, the wave counts through
+// LDS, as seld_decode.hip does), and a compacted row's slot in its (class, frame) cell is the cell's count so far plus the number
+// of earlier rows of the tile in the same cell: the cells fill in arrival order with no atomics, so two runs are bit-identical.
+// Then one pass with a thread per cell pairs the cells that hold both sides, a thread per class does the class bookkeeping, and
+// thread 0 writes the record.  Everything is float64 (a few hundred distances per workgroup: the float64 rate is no concern here,
+// the walk over the rows is the cost).  salsa_nn_seld_score_sum adds the scored records up in record order in one workgroup.
+#include "build_guard.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/salsa_nn.h"
+#include "seld_score.h"
+
+namespace {
+
+using namespace seld_score;
+
+constexpr int SCORE_THREADS = 256, SCORE_WAVES = SCORE_THREADS / 64;
+
+struct alignas(8) DcaseRow { int16_t frame, cls, azimuth, elevation; };
+
+struct ScoreLds {                                                             // 46 KB
+    Cell cells[MAX_CELLS];
+    int gfirst[MAX_CELLS];
+    uint8_t gcnt[MAX_CELLS], pcnt[MAX_CELLS], matched[MAX_CELLS], cell_doubt[MAX_CELLS];
+    int list_cell[SCORE_THREADS];
+    int32_t list_doa[SCORE_THREADS];
+    int list_row[SCORE_THREADS];
+    int wave_count[SCORE_WAVES];
+    ClassResult res[MAX_CLASSES];
+};
+
+// the rows of one side of one file into the segment's cells, in arrival order (uniform trip counts: every thread reaches the barriers)
+template <bool IS_GT>
+__device__ void bin_rows(ScoreLds &s, const DcaseRow *__restrict__ rows, int count, int seg, int label_rate, int n_classes)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    uint8_t *cnt = IS_GT ? s.gcnt : s.pcnt;
+    for (int tile = 0; tile < count; tile += SCORE_THREADS) {
+        const int i = tile + tid;
+        int cell = -1;
+        DcaseRow r = {0, 0, 0, 0};
+        if (i < count) {                                                       // count <= capacity: checked by the caller
+            r = rows[i];
+            cell = cell_of(r.frame, r.cls, seg, label_rate, n_classes);
+        }
+        const unsigned long long mask = __ballot(cell >= 0);
+        if (lane == 0) s.wave_count[wave] = __popcll(mask);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < SCORE_WAVES; w++) {
+            const int c = s.wave_count[w];
+            if (w < wave) before += c;
+            total += c;
+        }
+        if (cell >= 0) {
+            const int at = before + __popcll(mask & ((1ull << lane) - 1ull));  // < SCORE_THREADS: one entry per row of the tile at most
+            s.list_cell[at] = cell;
+            s.list_doa[at] = pack_doa(r.azimuth, r.elevation);
+            s.list_row[at] = i;
+        }
+        __syncthreads();
+        int my_cell = -1, slot = 0;
+        bool last = true;
+        if (tid < total) {
+            my_cell = s.list_cell[tid];
+            slot = cnt[my_cell];
+            for (int j = 0; j < tid; j++) slot += s.list_cell[j] == my_cell;
+            for (int j = tid + 1; j < total; j++) last = last && s.list_cell[j] != my_cell;
+        }
+        __syncthreads();                                                       // every count of before this tile has been read
+        if (my_cell >= 0) {
+            if (slot < MAX_DOAS) (IS_GT ? s.cells[my_cell].in.g : s.cells[my_cell].in.p)[slot] = s.list_doa[tid];
+            if (IS_GT && slot == 0) s.gfirst[my_cell] = s.list_row[tid];
+            if (last) cnt[my_cell] = (uint8_t)(slot + 1 < COUNT_SAT ? slot + 1 : COUNT_SAT);
+        }
+        __syncthreads();                                                       // the list and wave_count are rewritten by the next tile
+    }
+}
+
+__global__ __launch_bounds__(SCORE_THREADS) void seld_score_kernel(const DcaseRow *__restrict__ pred, const int *__restrict__ pred_counts,
+                                                                   int pred_capacity, const DcaseRow *__restrict__ gt,
+                                                                   const int *__restrict__ gt_counts, int gt_capacity, int n_seg,
+                                                                   int label_rate, int n_classes, double threshold, double margin,
+                                                                   int *__restrict__ counters, double *__restrict__ total_de,
+                                                                   int *__restrict__ status)
+{
+    __shared__ ScoreLds s;
+    const int tid = threadIdx.x, seg = blockIdx.x, n_cells = n_classes * label_rate;
+    const size_t file = blockIdx.y, record = file * (size_t)n_seg + seg;
+    const int n_pred = pred_counts[file], n_gt = gt_counts[file];
+    if (n_pred < 0 || n_pred > pred_capacity || n_gt < 0 || n_gt > gt_capacity) {   // (uniform) a count its slab cannot hold: nothing is read
+        if (tid < N_COUNTERS) counters[record * N_COUNTERS + tid] = 0;
+        if (tid == 0) {
+            total_de[record] = 0.0;
+            status[record] = REFUSED;
+        }
+        return;
+    }
+    for (int c = tid; c < n_cells; c += SCORE_THREADS) {
+        s.gcnt[c] = s.pcnt[c] = s.matched[c] = s.cell_doubt[c] = 0;
+        s.gfirst[c] = 0;
+    }
+    __syncthreads();
+    bin_rows<true>(s, gt + file * (size_t)gt_capacity, n_gt, seg, label_rate, n_classes);
+    bin_rows<false>(s, pred + file * (size_t)pred_capacity, n_pred, seg, label_rate, n_classes);
+    for (int c = tid; c < n_cells; c += SCORE_THREADS) {
+        const int ng = s.gcnt[c], np = s.pcnt[c];
+        if (ng < 1 || np < 1 || ng > MAX_DOAS || np > MAX_DOAS) continue;     // (a cell of more than 4 refuses its class in score_class)
+        int32_t g[MAX_DOAS], p[MAX_DOAS];
+        double cost[MAX_DOAS] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < MAX_DOAS; k++) {
+            g[k] = s.cells[c].in.g[k];
+            p[k] = s.cells[c].in.p[k];
+        }
+        bool doubt;
+        const unsigned m = pair_cell(g, ng, p, np, margin, cost, &doubt);
+        for (int k = 0; k < MAX_DOAS; k++) s.cells[c].cost[k] = cost[k];      // (over the DOAs just read)
+        s.matched[c] = (uint8_t)m;
+        s.cell_doubt[c] = doubt ? 1 : 0;
+    }
+    __syncthreads();
+    if (tid < n_classes) {
+        const int at = tid * label_rate;
+        score_class(s.cells + at, s.gcnt + at, s.pcnt + at, s.matched + at, s.cell_doubt + at, s.gfirst + at, label_rate, threshold, margin,
+                    &s.res[tid]);
+    }
+    __syncthreads();
+    if (tid == 0) segment_record(s.res, n_classes, counters + record * N_COUNTERS, total_de + record, status + record);
+}
+
+// the scored records added up: the counters exactly (int64), total_DE as ONE running float64 sum in record order (thread 0 adds
+// each tile of 256 values from LDS), so the sum does not depend on anything but the records
+__global__ __launch_bounds__(SCORE_THREADS) void seld_score_sum_kernel(const int *__restrict__ counters, const double *__restrict__ total_de,
+                                                                       const int *__restrict__ status, int64_t n_records,
+                                                                       int64_t *__restrict__ sum_counters, double *__restrict__ sum_de)
+{
+    __shared__ double de[SCORE_THREADS];
+    __shared__ int64_t part[SCORE_THREADS];
+    const int tid = threadIdx.x;
+    int64_t acc[N_COUNTERS];
+    for (int k = 0; k < N_COUNTERS; k++) acc[k] = 0;
+    double sum = 0.0;
+    for (int64_t tile = 0; tile < n_records; tile += SCORE_THREADS) {
+        const int64_t i = tile + tid;
+        const bool scored = i < n_records && status[i] == SCORED;
+        de[tid] = scored ? total_de[i] : 0.0;                                  // (x + 0.0 == x: the others do not change the sum)
+        if (scored)
+            for (int k = 0; k < N_COUNTERS; k++) acc[k] += counters[i * N_COUNTERS + k];
+        __syncthreads();
+        if (tid == 0)
+            for (int j = 0; j < SCORE_THREADS; j++) sum += de[j];
+        __syncthreads();
+    }
+    for (int k = 0; k < N_COUNTERS; k++) {
+        part[tid] = acc[k];
+        __syncthreads();
+        for (int step = SCORE_THREADS / 2; step > 0; step >>= 1) {
+            if (tid < step) part[tid] += part[tid + step];
+            __syncthreads();
+        }
+        if (tid == 0) sum_counters[k] = part[0];
+        __syncthreads();
+    }
+    if (tid == 0) *sum_de = sum;
+}
+
+__global__ void seld_distance_kernel(const int16_t *__restrict__ quads, int64_t n, double *__restrict__ out)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i < n) out[i] = distance_deg(quads[4 * i], quads[4 * i + 1], quads[4 * i + 2], quads[4 * i + 3]);
+}
+
+} // namespace
+
+extern "C" int salsa_nn_seld_score(const int16_t *pred_rows, const int *pred_counts, int pred_capacity, const int16_t *gt_rows,
+                                   const int *gt_counts, int gt_capacity, int n_files, int n_frames, int label_rate, int n_classes,
+                                   double doa_threshold, double margin, int *counters, double *total_de, int *status, int64_t *sum_counters,
+                                   double *sum_de, void *hip_stream)
+{
+    // everything is checked before the first device call (the CPU suite exercises these returns without a GPU)
+    if (!pred_rows || !pred_counts || !gt_rows || !gt_counts || !counters || !total_de || !status) return -1;
+    if (((uintptr_t)pred_rows & 7) || ((uintptr_t)gt_rows & 7) || ((uintptr_t)total_de & 7) || ((uintptr_t)sum_de & 7) || ((uintptr_t)sum_counters & 7)) return -1;
+    if ((sum_counters == nullptr) != (sum_de == nullptr)) return -1;
+    if (n_files < 1 || n_files > 65535 || n_frames < 1 || n_frames > 32767 || pred_capacity < 1 || gt_capacity < 1) return -1;
+    if (label_rate < 1 || label_rate > MAX_RATE || n_classes < 1 || n_classes > MAX_CLASSES) return -1;
+    if (!(doa_threshold == doa_threshold) || !(margin >= 0.0) || margin == INFINITY) return -1;
+    const int n_seg = n_segments(n_frames, label_rate);
+    hipLaunchKernelGGL(seld_score_kernel, dim3((unsigned)n_seg, (unsigned)n_files), dim3(SCORE_THREADS), 0, (hipStream_t)hip_stream,
+                       (const DcaseRow *)pred_rows, pred_counts, pred_capacity, (const DcaseRow *)gt_rows, gt_counts, gt_capacity, n_seg,
+                       label_rate, n_classes, doa_threshold, margin, counters, total_de, status);
+    if (hipGetLastError() != hipSuccess) return -6;
+    if (sum_counters) {
+        hipLaunchKernelGGL(seld_score_sum_kernel, dim3(1), dim3(SCORE_THREADS), 0, (hipStream_t)hip_stream, counters, total_de, status,
+                           (int64_t)n_files * n_seg, sum_counters, sum_de);
+        if (hipGetLastError() != hipSuccess) return -6;
+    }
+    return 0;
+}
+
+extern "C" int salsa_nn_seld_distance(const int16_t *quads, int64_t n, double *out, void *hip_stream)
+{
+    if (!quads || !out || n < 1 || n > ((int64_t)1 << 40) / 256 || ((uintptr_t)out & 7)) return -1;
+    hipLaunchKernelGGL(seld_distance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, quads, n, out);
+    return hipGetLastError() == hipSuccess ? 0 : -6;
+}
