@@ -33,9 +33,64 @@ def test_every_declared_symbol_is_exported(lib):
     gru = re.sub(r'/\*.*?\*/', '', gru, flags=re.S)
     gnames = set(re.findall(r'\b(salsa_gru_[a-z_]+)\s*\(', gru))
     assert gnames == set(_lib.GRU_EXPORTS) and all(hasattr(lib, n) for n in gnames)
+    lnames = set(re.findall(r'\b(salsa_lstm_[a-z_]+)\s*\(', gru))
+    assert lnames == set(_lib.LSTM_EXPORTS) and all(hasattr(lib, n) for n in lnames)
     nn = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'salsa_nn.h')).read(), flags=re.S)
     nnames = set(re.findall(r'\b(salsa_nn_[a-z0-9_]+)\s*\(', nn))
     assert nnames == set(_lib.NN_EXPORTS) and all(hasattr(lib, n) for n in nnames)
+    base = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'salsa_baseline.h')).read(), flags=re.S)
+    bnames = set(re.findall(r'\b(salsa_baseline_[a-z_]+)\s*\(', base))
+    assert bnames == set(_lib.BASELINE_EXPORTS) and all(hasattr(lib, n) for n in bnames)
+    # the header parser that binds the library sees exactly these, each once: nothing is skipped, nothing invented
+    every = names | gnames | lnames | nnames | bnames
+    parsed = {n: v for h in _lib.HEADERS for n, v in _lib.PROTOTYPES[h].items()}
+    assert len(every) >= 104 and set(parsed) == every and sum(len(_lib.PROTOTYPES[h]) for h in _lib.HEADERS) == len(every)
+    for n, (restype, argtypes) in parsed.items():                # ... and load() bound each of them as parsed
+        assert getattr(lib, n).restype is restype and list(getattr(lib, n).argtypes) == argtypes, n
+
+
+def test_parsed_signatures_match_hand_written_ones(lib):
+    """The binding is derived from include/*.h (salsa_amd/_lib.py parse_prototypes); these ten are spelled out by hand from the headers
+    and cover every kind of its table: int / int64_t / size_t / float / double / uint32_t parameters, data, struct, plan and
+    pointer-to-pointer parameters, int / int64_t / size_t / const char * returns, and (void)."""
+    vp, i, i64, sz, f, d, u32 = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float, C.c_double, C.c_uint32
+    want = {
+        'salsa_nn_bn_train_fwd_bits': (i, [vp, vp, vp, i, i64, i, vp, vp, f, f, vp, vp, vp, vp, vp, i, f, u32, vp, vp, i, vp, vp]),
+        'salsa_nn_adam_step': (i, [vp, vp, i, vp, i, d, d, d, d, d, i64, vp]),
+        'salsa_resample_batch': (i, [vp, i, i64, vp, i64, i64, d, vp, vp, i, i, vp, vp]),
+        'salsa_workspace_bytes': (sz, [vp, i, i64]),
+        'salsa_nn_conv3x3_wide_table_len': (i64, [i64, i, i]),
+        'salsa_last_error': (C.c_char_p, []),
+        'salsa_nn_get_deterministic': (i, []),
+        'salsa_plan_read_timing': (i, [vp, vp, vp, vp]),
+        'salsa_nn_seld_score': (i, [vp, vp, i, vp, vp, i, i, i, i, i, d, d, vp, vp, vp, vp, vp, vp]),
+        'salsa_baseline_mel_matrix': (i, [i, i, i, d, d, vp]),
+    }
+    for name, (restype, argtypes) in want.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, name
+        assert list(fn.argtypes) == argtypes, name
+
+
+def test_parser_refuses_a_type_outside_its_table():
+    from salsa_amd import _lib
+    ok = _lib.parse_prototypes('/* c */\n#define X 1\nsize_t salsa_fine(const int64_t n, const char **names, float);\n')
+    assert ok == {'salsa_fine': (C.c_size_t, [C.c_int64, C.c_void_p, C.c_float])}
+    for bad in ('int salsa_made_up(int n, long double x);', 'int salsa_made_up(unsigned short n, float *p);', 'int salsa_made_up(salsa_params p);',
+                'float *salsa_made_up(int n);', 'void salsa_made_up(int n);', 'unsigned salsa_made_up(void);',
+                'int salsa_made_up(int (*callback)(int), void *user);'):
+        with pytest.raises(TypeError, match='salsa_made_up'):
+            _lib.parse_prototypes('int salsa_before(int a);\n' + bad + '\nint salsa_after(void);\n')
+
+
+def test_one_source_list():
+    """Every salsa_amd/csrc/*.hip is compiled by the product's build, in sorted order, and nothing from elsewhere is."""
+    from salsa_amd import _lib
+    csrc = os.path.join(ROOT, 'salsa_amd', 'csrc')
+    hips = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith('.hip'))
+    cmd = _lib.build_command()
+    assert len(hips) >= 10 and [a for a in cmd if a.endswith('.hip')] == hips
+    assert [a for a in cmd if os.sep in a and a not in hips] == [_lib.LIB_PATH]
 
 
 def test_host_helpers_match_reference(lib):
