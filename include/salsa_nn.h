@@ -282,6 +282,19 @@ int salsa_nn_seld_decode(const float *sed, const float *xyz, int n_files, int n_
 int salsa_nn_seld_score(const int16_t *pred_rows, const int *pred_counts, int pred_capacity, const int16_t *gt_rows, const int *gt_counts,
                         int gt_capacity, int n_files, int n_frames, int label_rate, int n_classes, double doa_threshold, double margin,
                         int *counters, double *total_de, int *status, int64_t *sum_counters, double *sum_de, void *hip_stream);
+/* The same rows by the SELD 2020 metric: the counters of crnn/metrics.py::SeldMetrics2020.update (reference metrics/
+ * SELD2020_evaluation_metrics.py:159-229, the scorer eval_version '2020' selects) per (file, segment).  Parameters, layouts, record
+ * order, alignment rules, sums and return codes are salsa_nn_seld_score's; the same kernel bins the rows.  counters [records][10]
+ * int32 are TP FP FN TN S D I Nref Nsys DE_TP (Nref / Nsys count the classes PRESENT in the segment), total_de [records] float64
+ * the sum over the classes, in class order, of the mean cost of the class's common frames walked in ascending frame order; a
+ * frame's cost is the least total distance over the injective maps of the smaller side into the larger, the best map's distances
+ * added in reference-slot order.  status: 0 scored; 1 doubt -- some class average lies within `margin` of doa_threshold, the ONLY
+ * doubt rule (a rival map of nearly equal cost is none: only the value of the minimum enters this metric); 2 refused as above.
+ * Records of status 1 and 2 carry zeros; every output element is written.  Bit-reproducible (no atomics). */
+int salsa_nn_seld_score2020(const int16_t *pred_rows, const int *pred_counts, int pred_capacity, const int16_t *gt_rows,
+                            const int *gt_counts, int gt_capacity, int n_files, int n_frames, int label_rate, int n_classes,
+                            double doa_threshold, double margin, int *counters, double *total_de, int *status, int64_t *sum_counters,
+                            double *sum_de, void *hip_stream);
 /* salsa_nn_seld_score's distance statement alone: quads [n][4] int16 (azimuth1, elevation1, azimuth2, elevation2) -> out [n]
  * float64 degrees (tools/probe_score_distance.py measures its deviation from the host's, which sizes `margin`). */
 int salsa_nn_seld_distance(const int16_t *quads, int64_t n, double *out, void *hip_stream);

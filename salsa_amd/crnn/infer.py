@@ -63,7 +63,8 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
     score = (gt_rows, gt_counts, accumulator), with decode='device' only: the ground truth of all n_items items on the model's device
     (score.gt_rows_to_device) and a score.DeviceSeldScore.  Each sub-batch's rows are scored against their slice of the ground truth
     on the same stream right behind the decode launch (score.score_dcase_rows_async, with the accumulator's n_classes, threshold,
-    label_rate and margin) and merged into the accumulator when the sub-batch is finished.  The rows returned are unchanged."""
+    label_rate and margin) and merged into the accumulator when the sub-batch is finished.  The rows returned are unchanged.  The
+    TYPE of the accumulator selects the metric (score.DeviceSeldScore2020: the SELD 2020 one); eval_version only shapes the rows."""
     import torch
     assert depth >= 1 and sub_batch >= 1
     if decode not in ('host', 'device'):
@@ -135,10 +136,12 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
         if s['event'] is not None:
             s['event'].record()
         if score is not None:
+            from .metrics import SeldMetrics2020
             from .score import score_dcase_rows_async
             s['score'] = score_dcase_rows_async(rows, counts, gt_rows[lo:hi], gt_counts[lo:hi], n_frames=n_label_frames,
                                                 label_rate=accumulator.label_rate, n_classes=accumulator.n_classes,
-                                                doa_threshold=accumulator.doa_threshold, margin=accumulator.margin)
+                                                doa_threshold=accumulator.doa_threshold, margin=accumulator.margin,
+                                                eval_version='2020' if isinstance(accumulator, SeldMetrics2020) else '2021')
         pending.append((k, lo, hi, t_issue, lab_len, lab_hop))
         while len(pending) >= depth:                     # slot (k + 1) % depth is free again before sub-batch k + 1 is issued
             finish(*pending.popleft())

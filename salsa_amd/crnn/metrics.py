@@ -126,11 +126,94 @@ class SeldMetrics:
         return (ER + (1.0 - F) + LE / 180.0 + (1.0 - LR)) / 4
 
 
+class SeldMetrics2020:
+    """The SELD 2020 metric (metrics/SELD2020_evaluation_metrics.py:159-229 update_seld_scores, :49-83 compute_seld_scores, :266-294
+    least_distance_between_gt_pred), the scorer the reference's eval_version '2020' selects (models/interfaces.py:46-53).  Per 1-s
+    segment and class it counts PRESENCE (Nref, Nsys), not tracks; where both sides hold the class, the reference frames are walked
+    in ascending frame order (dcase_utils.segment_labels walks the audio frames in order, whatever the order of the rows), every
+    frame that also has predictions costs the minimum total distance of pairing the smaller side into the larger -- only the value
+    of that minimum enters, not the pairing -- and the class is a hit when the mean cost over those frames is within
+    ``doa_threshold`` degrees; a miss of any kind is a false NEGATIVE.  Same surface as SeldMetrics."""
+
+    def __init__(self, n_classes: int = 12, doa_threshold: float = 20):
+        self.n_classes, self.doa_threshold = n_classes, doa_threshold
+        self.TP = self.FP = self.FN = self.TN = 0
+        self.S = self.D = self.I = 0
+        self.Nref = self.Nsys = 0
+        self.total_DE = 0.0
+        self.DE_TP = 0
+
+    def update(self, pred_rows, gt_rows, max_frames: int = 600, label_rate: int = 10):
+        pred, gt = segment_rows(pred_rows, max_frames, label_rate), segment_rows(gt_rows, max_frames, label_rate)
+        for s in range(len(gt)):
+            loc_fn = loc_fp = 0
+            for c in range(self.n_classes):
+                g, p = gt[s].get(c), pred[s].get(c)
+                self.Nref += 1 if g else 0
+                self.Nsys += 1 if p else 0
+                if g and p:
+                    total, n = 0.0, 0
+                    for frame in sorted(g):                                # ascending frames; DOAs inside a frame keep file order
+                        if frame not in p:
+                            continue
+                        ga, pa = np.array(g[frame], dtype=np.float64), np.array(p[frame], dtype=np.float64)
+                        cost = angular_distance_deg(ga[:, None, 0], ga[:, None, 1], pa[None, :, 0], pa[None, :, 1])
+                        if cost.shape == (1, 1):
+                            total += cost[0, 0]
+                        else:
+                            ri, ci = linear_sum_assignment(cost)
+                            total += cost[ri, ci].sum()                    # (at most 4 values: numpy adds them in reference-row order)
+                        n += 1
+                    if n == 0:                                             # no frame in common
+                        loc_fn += 1
+                        self.FN += 1
+                    else:
+                        avg = total / n
+                        self.total_DE += avg
+                        self.DE_TP += 1
+                        if avg <= self.doa_threshold:
+                            self.TP += 1
+                        else:
+                            loc_fn += 1
+                            self.FN += 1
+                elif g:
+                    loc_fn += 1
+                    self.FN += 1
+                elif p:
+                    loc_fp += 1
+                    self.FP += 1
+                else:
+                    self.TN += 1
+            self.S += min(loc_fp, loc_fn)
+            self.D += max(0, loc_fn - loc_fp)
+            self.I += max(0, loc_fp - loc_fn)
+
+    def scores(self):
+        """-> (ER, F, LE, LR) (SELD2020...:49-83, eps where the reference places it).  The reference itself raises ZeroDivisionError
+        on an empty reference, in an auxiliary list it never returns (Nsys / Nref); that list is not computed here."""
+        ER = (self.S + self.D + self.I) / float(self.Nref + _EPS)
+        prec, recall = float(self.TP) / float(self.Nsys + _EPS), float(self.TP) / float(self.Nref + _EPS)
+        F = 2 * prec * recall / (prec + recall + _EPS)
+        LE = self.total_DE / float(self.DE_TP + _EPS) if self.DE_TP else 180
+        de_prec, de_recall = float(self.DE_TP) / float(self.Nsys + _EPS), float(self.DE_TP) / float(self.Nref + _EPS)
+        LR = 2 * de_prec * de_recall / (de_prec + de_recall + _EPS)
+        return ER, F, LE, LR
+
+    def seld_error(self):
+        """Aggregate used for model selection (interfaces.py:179): mean of ER, 1-F, LE/180, 1-LR."""
+        ER, F, LE, LR = self.scores()
+        return (ER + (1.0 - F) + LE / 180.0 + (1.0 - LR)) / 4
+
+
 def evaluate_csv_dirs(pred_dir: str, gt_dir: str, filenames, n_classes: int = 12, doa_threshold: float = 20,
-                      max_frames: int = 600, label_rate: int = 10):
-    """evaluate_output_prediction_csv (interfaces.py:163-180): -> (ER, F, LE, LR, seld_error) over the listed CSV files."""
+                      max_frames: int = 600, label_rate: int = 10, eval_version: str = '2021'):
+    """evaluate_output_prediction_csv (interfaces.py:163-180): -> (ER, F, LE, LR, seld_error) over the listed CSV files, by the
+    metric class eval_version selects (interfaces.py:46-53): '2021' SeldMetrics, '2020' SeldMetrics2020."""
     import os
-    m = SeldMetrics(n_classes, doa_threshold)
+    if eval_version not in ('2020', '2021'):
+        raise ValueError('Unknown eval_version {}'.format(eval_version))
+    m = (SeldMetrics2020 if eval_version == '2020' else SeldMetrics)(n_classes, doa_threshold)
     for fn in filenames:
-        m.update(load_dcase_csv(os.path.join(pred_dir, fn)), load_dcase_csv(os.path.join(gt_dir, fn)), max_frames, label_rate)
+        m.update(load_dcase_csv(os.path.join(pred_dir, fn), version=eval_version),
+                 load_dcase_csv(os.path.join(gt_dir, fn), version=eval_version), max_frames, label_rate)
     return m.scores() + (m.seld_error(),)

@@ -1,34 +1,39 @@
-"""SELD 2021 scoring of DCASE rows on the device (salsa_nn_seld_score, include/salsa_nn.h): the int16 rows `decode_dcase_rows`
-leaves in device memory are scored against ground-truth rows in one launch, per (file, 1-s segment), and ten integers, one double
-and a status per segment come back instead of the rows.  crnn/metrics.py::SeldMetrics stays the host scorer, the default
-everywhere and the yardstick; what is computed is exactly what its `update` computes.
+"""SELD scoring of DCASE rows on the device (salsa_nn_seld_score, and salsa_nn_seld_score2020 for eval_version '2020';
+include/salsa_nn.h): the int16 rows `decode_dcase_rows` leaves in device memory are scored against ground-truth rows in one launch,
+per (file, 1-s segment), and ten integers, one double and a status per segment come back instead of the rows.
+crnn/metrics.py::SeldMetrics (2021, the default everywhere) and SeldMetrics2020 stay the host scorers and the yardsticks; what is
+computed is exactly what their `update` computes.
 
 The device never decides a close call.  Its sin / cos / acos are not the host's bit for bit, and the metric compares a float64
 arccos with `<=` against the threshold and lets scipy break ties between pairings.  So a segment in which another pairing costs
 within `margin` degrees of the best, or a slot average lies within `margin` of the threshold, comes back with status 1 (doubt) and
 zero counters; a (class, frame) cell with more than 4 DOAs on a side gives status 2 (refused).  `score_dcase_rows` fetches the rows
-of those files and runs `SeldMetrics.update` on the rows of each such segment alone (every other segment is empty, so nothing
+of those files and runs `SeldMetrics.update` on the rows of each such segment alone (as a file of that one segment, so nothing
 else is added): the numpy + scipy semantics, exactly.  DEFAULT_MARGIN is at least 16 times the largest deviation of the device's distance
 from `angular_distance_deg` over every integer (elevation, elevation, |azimuth difference|) triple, measured by
-tools/probe_score_distance.py (profiles/seld_score_distance.txt)."""
+tools/probe_score_distance.py (profiles/seld_score_distance.txt).
+
+The 2020 metric (eval_version='2020', DeviceSeldScore2020) uses only the VALUE of a frame's least pairing cost, never the pairing,
+so a rival pairing is no doubt there: status 1 means a class average within `margin` of the threshold, nothing else, and the host
+resolves such segments with `SeldMetrics2020.update`."""
 import ctypes as C
 
 import numpy as np
 
 from .. import _lib
-from .metrics import SeldMetrics
+from .metrics import SeldMetrics, SeldMetrics2020
 
 # degrees; the worst |device distance - angular_distance_deg| over all 181 x 181 x 361 integer triples is 1.207e-6 (profiles/
-# seld_score_distance.txt): 83 times that, where at least 16 is asked
+# seld_score_distance.txt): 83 times that, where at least 16 is asked.  A 2020 class average is a mean over frames of sums of at most
+# four distances, each within those 1.207e-6 of the host's, so the average is within 4.83e-6: the margin is 20 times that.
 DEFAULT_MARGIN = 1e-4
 COUNTERS = ('TP', 'FP', 'FN', 'S', 'D', 'I', 'Nref', 'DE_TP', 'DE_FP', 'DE_FN')
+COUNTERS_2020 = ('TP', 'FP', 'FN', 'TN', 'S', 'D', 'I', 'Nref', 'Nsys', 'DE_TP')
 SCORED, DOUBT, REFUSED = 0, 1, 2
 
 
-class DeviceSeldScore(SeldMetrics):
-    """SeldMetrics' counters, `scores()` and `seld_error()`, filled by `score_dcase_rows`; `n_segments`, `n_doubt` and `n_refused`
-    count the segments scored in all and those handed to the host; `merge` adds another result (sub-batches, ranks).  label_rate
-    and margin are what `infer_pipelined(score=...)` scores with when this is its accumulator."""
+class _DeviceScore:
+    """what DeviceSeldScore and DeviceSeldScore2020 add to their host scorer"""
 
     def __init__(self, n_classes: int = 12, doa_threshold: float = 20, label_rate: int = 10, margin: float = DEFAULT_MARGIN):
         super().__init__(n_classes, doa_threshold)
@@ -36,13 +41,40 @@ class DeviceSeldScore(SeldMetrics):
         self.n_segments = self.n_doubt = self.n_refused = 0
 
     def merge(self, other):
+        if getattr(other, 'eval_version', None) != self.eval_version:
+            raise ValueError('merge: %s into SELD %s scores' % (type(other).__name__, self.eval_version))
         if (other.n_classes, other.doa_threshold) != (self.n_classes, self.doa_threshold):
             raise ValueError('merge: scores of %d classes at %s degrees into %d classes at %s degrees'
                              % (other.n_classes, other.doa_threshold, self.n_classes, self.doa_threshold))
-        for name in COUNTERS + ('n_segments', 'n_doubt', 'n_refused'):
+        for name in self.counter_names + ('n_segments', 'n_doubt', 'n_refused'):
             setattr(self, name, getattr(self, name) + getattr(other, name, 0))
         self.total_DE += other.total_DE
         return self
+
+
+class DeviceSeldScore(_DeviceScore, SeldMetrics):
+    """SeldMetrics' counters, `scores()` and `seld_error()`, filled by `score_dcase_rows`; `n_segments`, `n_doubt` and `n_refused`
+    count the segments scored in all and those handed to the host; `merge` adds another result (sub-batches, ranks).  label_rate
+    and margin are what `infer_pipelined(score=...)` scores with when this is its accumulator."""
+
+    counter_names, eval_version = COUNTERS, '2021'
+
+
+class DeviceSeldScore2020(_DeviceScore, SeldMetrics2020):
+    """DeviceSeldScore for the SELD 2020 metric: SeldMetrics2020's counters, `scores()` and `seld_error()`, filled by
+    `score_dcase_rows(eval_version='2020')`.  As the accumulator of `infer_pipelined(score=...)` its TYPE selects the 2020 metric;
+    merging the other version's scores into either is a ValueError."""
+
+    counter_names, eval_version = COUNTERS_2020, '2020'
+
+
+_VERSIONS = {'2021': (DeviceSeldScore, SeldMetrics, 'salsa_nn_seld_score'), '2020': (DeviceSeldScore2020, SeldMetrics2020, 'salsa_nn_seld_score2020')}
+
+
+def _version(eval_version):
+    if eval_version not in _VERSIONS:
+        raise ValueError('Unknown eval_version {}'.format(eval_version))
+    return _VERSIONS[eval_version]
 
 
 def segment_rows_of(rows, segment: int, label_rate: int):
@@ -50,13 +82,22 @@ def segment_rows_of(rows, segment: int, label_rate: int):
     return [r for r in rows if segment * label_rate <= r[0] < (segment + 1) * label_rate]
 
 
+def segment_alone(rows, segment: int, label_rate: int):
+    """`segment` of a file as a file of that one segment: its rows with the frames counted from the segment's start.  Scored with
+    max_frames = label_rate it adds the segment's share and nothing else (the 2020 metric books every class of an EMPTY segment as a
+    true negative, so the segment's rows in a file of full length would add those of all the other segments again)."""
+    return [(r[0] - segment * label_rate,) + tuple(r[1:]) for r in segment_rows_of(rows, segment, label_rate)]
+
+
 def resolve_records(sum_counters, sum_de, status, fetch_file, n_frames: int = 600, label_rate: int = 10, n_classes: int = 12,
-                    doa_threshold: float = 20, margin: float = DEFAULT_MARGIN) -> DeviceSeldScore:
+                    doa_threshold: float = 20, margin: float = DEFAULT_MARGIN, eval_version: str = '2021') -> DeviceSeldScore:
     """The host's half of `score_dcase_rows`: sum_counters (10,) and sum_de, the status-0 records added up; status (n_files, n_seg);
     fetch_file(f) -> (pred rows, gt rows) of file f as row lists, called once per file that has a segment of status 1 or 2.  Those
-    segments are scored by SeldMetrics.update on their own rows, in record order."""
-    out = DeviceSeldScore(n_classes, doa_threshold, label_rate, margin)
-    for name, v in zip(COUNTERS, sum_counters):
+    segments are scored by SeldMetrics.update (eval_version '2020': SeldMetrics2020.update, -> DeviceSeldScore2020) on their own
+    rows, each as a file of one segment (segment_alone), in record order."""
+    result_cls, host_cls, _ = _version(eval_version)
+    out = result_cls(n_classes, doa_threshold, label_rate, margin)
+    for name, v in zip(out.counter_names, sum_counters):
         setattr(out, name, int(v))
     out.total_DE = float(sum_de)
     status = np.asarray(status)
@@ -65,10 +106,10 @@ def resolve_records(sum_counters, sum_de, status, fetch_file, n_frames: int = 60
     for f in np.nonzero((status != SCORED).any(axis=1))[0]:
         pred, gt = fetch_file(int(f))
         for s in np.nonzero(status[f] != SCORED)[0]:
-            m = SeldMetrics(n_classes, doa_threshold)
-            m.update(segment_rows_of(pred, int(s), label_rate), segment_rows_of(gt, int(s), label_rate), max_frames=n_frames,
+            m = host_cls(n_classes, doa_threshold)
+            m.update(segment_alone(pred, int(s), label_rate), segment_alone(gt, int(s), label_rate), max_frames=label_rate,
                      label_rate=label_rate)
-            for name in COUNTERS:
+            for name in out.counter_names:
                 setattr(out, name, getattr(out, name) + getattr(m, name))
             out.total_DE += m.total_DE
     return out
@@ -118,11 +159,13 @@ def _ptr(t):
 
 
 class PendingScore:
-    """one salsa_nn_seld_score launch whose totals and status array are on their way into pinned host memory behind an event;
-    `result()` waits for that event only and resolves the doubt / refused segments on the host"""
+    """one salsa_nn_seld_score (eval_version '2020': salsa_nn_seld_score2020) launch whose totals and status array are on their way
+    into pinned host memory behind an event; `result()` waits for that event only and resolves the doubt / refused segments on the host"""
 
-    def __init__(self, pred_rows, pred_counts, gt_rows, gt_counts, n_frames, label_rate, n_classes, doa_threshold, margin):
+    def __init__(self, pred_rows, pred_counts, gt_rows, gt_counts, n_frames, label_rate, n_classes, doa_threshold, margin,
+                 eval_version='2021'):
         import torch
+        export = _version(eval_version)[2]
         for name, r, c in (('pred', pred_rows, pred_counts), ('gt', gt_rows, gt_counts)):
             if not (r.is_cuda and c.is_cuda and r.device == pred_rows.device and c.device == pred_rows.device):
                 raise ValueError('score_dcase_rows takes tensors on one CUDA device (the host scorer is metrics.SeldMetrics)')
@@ -135,7 +178,7 @@ class PendingScore:
         self.pred_rows, self.pred_counts = pred_rows.contiguous(), pred_counts.contiguous()
         self.gt_rows, self.gt_counts = gt_rows.contiguous(), gt_counts.contiguous()
         self.args = dict(n_frames=int(n_frames), label_rate=int(label_rate), n_classes=int(n_classes), doa_threshold=float(doa_threshold),
-                         margin=float(margin))
+                         margin=float(margin), eval_version=eval_version)
         n_files = pred_rows.shape[0]
         n_seg = -(-int(n_frames) // int(label_rate)) if label_rate > 0 and n_frames > 0 else 1
         counters = torch.empty((n_files * n_seg, 10), dtype=torch.int32, device=dev)
@@ -144,16 +187,16 @@ class PendingScore:
         sums = torch.empty((10,), dtype=torch.int64, device=dev)
         sum_de = torch.empty((1,), dtype=torch.float64, device=dev)
         with torch.cuda.device(dev):
-            rc = _lib.load().salsa_nn_seld_score(_ptr(self.pred_rows), _ptr(self.pred_counts), self.pred_rows.shape[1], _ptr(self.gt_rows),
-                                                 _ptr(self.gt_counts), self.gt_rows.shape[1], n_files, int(n_frames), int(label_rate),
-                                                 int(n_classes), float(doa_threshold), float(margin), _ptr(counters), _ptr(total_de),
-                                                 _ptr(status), _ptr(sums), _ptr(sum_de), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = getattr(_lib.load(), export)(_ptr(self.pred_rows), _ptr(self.pred_counts), self.pred_rows.shape[1], _ptr(self.gt_rows),
+                                              _ptr(self.gt_counts), self.gt_rows.shape[1], n_files, int(n_frames), int(label_rate),
+                                              int(n_classes), float(doa_threshold), float(margin), _ptr(counters), _ptr(total_de),
+                                              _ptr(status), _ptr(sums), _ptr(sum_de), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
             if rc == _lib.E_INVAL:
-                raise ValueError('salsa_nn_seld_score refused %d files of %d frames at label rate %d with %d classes, capacities %d / %d, '
-                                 'threshold %r, margin %r' % (n_files, n_frames, label_rate, n_classes, self.pred_rows.shape[1],
+                raise ValueError('%s refused %d files of %d frames at label rate %d with %d classes, capacities %d / %d, '
+                                 'threshold %r, margin %r' % (export, n_files, n_frames, label_rate, n_classes, self.pred_rows.shape[1],
                                                               self.gt_rows.shape[1], doa_threshold, margin))
             if rc:
-                raise RuntimeError('salsa_nn_seld_score failed (%d)' % rc)
+                raise RuntimeError('%s failed (%d)' % (export, rc))
             self.records = (counters, total_de, status)                       # (per-record outputs: kept for callers that want them)
             self.host = {}
             for name, t in (('sums', sums), ('sum_de', sum_de), ('status', status), ('pred_counts', self.pred_counts), ('gt_counts', self.gt_counts)):
@@ -176,18 +219,20 @@ class PendingScore:
 
 
 def score_dcase_rows_async(pred_rows, pred_counts, gt_rows, gt_counts, n_frames: int = 600, label_rate: int = 10, n_classes: int = 12,
-                           doa_threshold: float = 20, margin: float = DEFAULT_MARGIN) -> PendingScore:
+                           doa_threshold: float = 20, margin: float = DEFAULT_MARGIN, eval_version: str = '2021') -> PendingScore:
     """score_dcase_rows without the wait: the launch and the copies are issued on the current stream; `.result()` finishes"""
-    return PendingScore(pred_rows, pred_counts, gt_rows, gt_counts, n_frames, label_rate, n_classes, doa_threshold, margin)
+    return PendingScore(pred_rows, pred_counts, gt_rows, gt_counts, n_frames, label_rate, n_classes, doa_threshold, margin, eval_version)
 
 
 def score_dcase_rows(pred_rows, pred_counts, gt_rows, gt_counts, n_frames: int = 600, label_rate: int = 10, n_classes: int = 12,
-                     doa_threshold: float = 20, margin: float = DEFAULT_MARGIN) -> DeviceSeldScore:
+                     doa_threshold: float = 20, margin: float = DEFAULT_MARGIN, eval_version: str = '2021') -> DeviceSeldScore:
     """pred_rows (n_files, capacity, 4) int16 = (frame, class, azimuth, elevation) with pred_counts (n_files,) int32 -- what
     decode_dcase_rows returns -- against gt_rows / gt_counts in the same layout (gt_rows_to_device), CUDA tensors of one device.
     One salsa_nn_seld_score call on the current stream scores every (file, segment) and adds the undoubted records up on the device
     (integers exactly, total_DE as one float64 sum in record order); eleven totals, the status array and the counts are copied
     back.  Segments of status 1 (doubt) or 2 (refused) are scored by SeldMetrics.update on the host from their file's rows, fetched
     once per such file.  -> DeviceSeldScore with SeldMetrics' counters.  No host fallback: CPU tensors are refused.  A count above
-    its slab's capacity is a ValueError (the kernel reads no row of such a file)."""
-    return score_dcase_rows_async(pred_rows, pred_counts, gt_rows, gt_counts, n_frames, label_rate, n_classes, doa_threshold, margin).result()
+    its slab's capacity is a ValueError (the kernel reads no row of such a file).  eval_version '2020': the SELD 2020 metric, by
+    one salsa_nn_seld_score2020 call and SeldMetrics2020 -> DeviceSeldScore2020; any other value is a ValueError."""
+    return score_dcase_rows_async(pred_rows, pred_counts, gt_rows, gt_counts, n_frames, label_rate, n_classes, doa_threshold, margin,
+                                  eval_version).result()

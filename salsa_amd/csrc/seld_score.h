@@ -1,5 +1,6 @@
 // seld_score.h -- per-element statements of salsa_nn_seld_score (seld_score.hip): the great-circle distance of two integer-degree
-// directions, the pairing of one (class, frame) cell, the bookkeeping of one class of a segment and the record of the segment.
+// directions, the pairing of one (class, frame) cell, the bookkeeping of one class of a segment and the record of the segment;
+// behind them the same three for the SELD 2020 metric (salsa_nn_seld_score2020; tests/hostemu/score2020_emu.cpp, SeldMetrics2020).
 // Host + device inline functions over plain arrays (LDS on the device); the same header compiles with g++
 // (tests/hostemu/score_emu.cpp), so the CPU suite holds every statement to crnn/metrics.py::SeldMetrics.  That host build is a test
 // harness, never a fallback of the product.
@@ -219,6 +220,136 @@ SCORE_HD void segment_record(const ClassResult *res, int n_classes, int *counter
     cnt[C_S] = seg_fp < seg_fn ? seg_fp : seg_fn;
     cnt[C_D] = seg_fn > seg_fp ? seg_fn - seg_fp : 0;
     cnt[C_I] = seg_fp > seg_fn ? seg_fp - seg_fn : 0;
+    const int st = flags & 2 ? REFUSED : (flags & 1 ? DOUBT : SCORED);
+    for (int k = 0; k < N_COUNTERS; k++) counters[k] = st == SCORED ? cnt[k] : 0;
+    *total_de = st == SCORED ? total : 0.0;
+    *status = st;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The SELD 2020 metric (salsa_nn_seld_score2020; crnn/metrics.py::SeldMetrics2020 is the restatement golden g29 pins to the reference):
+//   metrics/SELD2020_evaluation_metrics.py:159-229  SELDMetrics.update_seld_scores: per 1-s segment and class, PRESENCE counts; the
+//                                                   reference frames in ascending order, each common frame costing the least total
+//                                                   distance of pairing the smaller side into the larger; the mean cost decides
+//   metrics/SELD2020_evaluation_metrics.py:266-294  least_distance_between_gt_pred
+// Only the VALUE of a frame's minimum enters, never which map attains it, so a rival map of nearly equal cost is no doubt here: the
+// one close call is a class average within `margin` of the threshold.
+enum { C20_TP, C20_FP, C20_FN, C20_TN, C20_S, C20_D, C20_I, C20_NREF, C20_NSYS, C20_DE_TP };
+
+// One cell with 1 .. 4 DOAs on both sides: the least total cost over the at most 24 injective maps of the smaller side into the
+// larger.  The best map's costs are added in reference-slot order, the order of cost_mat[row_ind, col_ind].sum().
+SCORE_HD double cell_cost2020(const int32_t *g, int ng, const int32_t *p, int np)
+{
+#if defined(__HIPCC__)
+#pragma clang fp contract(off)
+#endif
+    double c[MAX_DOAS][MAX_DOAS];
+    for (int r = 0; r < ng; r++)
+        for (int q = 0; q < np; q++) c[r][q] = distance_deg(doa_azimuth(g[r]), doa_elevation(g[r]), doa_azimuth(p[q]), doa_elevation(p[q]));
+    const bool g_small = ng <= np;
+    const int small = g_small ? ng : np, large = g_small ? np : ng;
+    int n_codes = 1;
+    for (int i = 0; i < small; i++) n_codes *= large;                        // digit i of a code (base `large`): where item i of the smaller side goes
+    double best = INFINITY;
+    int best_code = 0;
+    for (int code = 0; code < n_codes; code++) {
+        unsigned used = 0;
+        double total = 0.0;
+        bool injective = true;
+        for (int i = 0, rest = code; i < small; i++, rest /= large) {
+            const int to = rest % large;
+            if (used >> to & 1u) injective = false;
+            used |= 1u << to;
+            total += g_small ? c[i][to] : c[to][i];
+        }
+        if (injective && total < best) {
+            best = total;
+            best_code = code;
+        }
+    }
+    int col[MAX_DOAS] = {-1, -1, -1, -1};                                    // the predicted DOA of every matched reference slot
+    for (int i = 0, rest = best_code; i < small; i++, rest /= large) {
+        const int to = rest % large;
+        col[g_small ? i : to] = g_small ? to : i;
+    }
+    double total = 0.0;
+    for (int r = 0; r < ng; r++)
+        if (col[r] >= 0) total += c[r][col[r]];
+    return total;
+}
+
+// One class of one segment from its label_rate cells: gcnt / pcnt the saturated DOA counts, cells[f].cost[0] what cell_cost2020
+// gave for the cells with both sides present.  The frames are walked in ascending order, as dcase_utils.segment_labels leaves them
+// whatever the order of the rows.  counters: the C20_ ones (S, D, I stay 0); seg_fp / seg_fn the segment's loc_FP / loc_FN.
+SCORE_HD void score_class2020(const Cell *cells, const uint8_t *gcnt, const uint8_t *pcnt, int label_rate, double threshold, double margin,
+                              ClassResult *out)
+{
+#if defined(__HIPCC__)
+#pragma clang fp contract(off)
+#endif
+    ClassResult res;
+    for (int k = 0; k < N_COUNTERS; k++) res.counters[k] = 0;
+    res.seg_fp = res.seg_fn = res.n_avg = res.flags = 0;
+    for (int k = 0; k < MAX_DOAS; k++) res.avg[k] = 0.0;
+    int n_g = 0, n_p = 0, n = 0;
+    for (int f = 0; f < label_rate; f++) {
+        n_g = gcnt[f] > n_g ? gcnt[f] : n_g;
+        n_p = pcnt[f] > n_p ? pcnt[f] : n_p;
+    }
+    if (n_g > MAX_DOAS || n_p > MAX_DOAS) {                                  // (such a cell has no cost)
+        res.flags = 2;
+        *out = res;
+        return;
+    }
+    double total = 0.0;
+    for (int f = 0; f < label_rate; f++)
+        if (gcnt[f] && pcnt[f]) {
+            total += cells[f].cost[0];
+            n++;
+        }
+    res.counters[C20_NREF] = n_g ? 1 : 0;
+    res.counters[C20_NSYS] = n_p ? 1 : 0;
+    if (n_g && n_p) {
+        if (!n) {                                                            // no common frame
+            res.counters[C20_FN] = res.seg_fn = 1;
+        } else {
+            const double avg = total / (double)n;
+            res.avg[res.n_avg++] = avg;
+            res.counters[C20_DE_TP] = 1;
+            if (fabs(avg - threshold) <= margin) res.flags |= 1;
+            if (avg <= threshold) res.counters[C20_TP] = 1;
+            else res.counters[C20_FN] = res.seg_fn = 1;
+        }
+    } else if (n_g) {
+        res.counters[C20_FN] = res.seg_fn = 1;
+    } else if (n_p) {
+        res.counters[C20_FP] = res.seg_fp = 1;
+    } else {
+        res.counters[C20_TN] = 1;
+    }
+    *out = res;
+}
+
+// The record of one segment from its classes, in class order: total_DE is ONE running sum over the class averages, as
+// SeldMetrics2020 keeps it.  A segment in doubt or refused carries zero counters (the host scores it whole).
+SCORE_HD void segment_record2020(const ClassResult *res, int n_classes, int *counters, double *total_de, int *status)
+{
+#if defined(__HIPCC__)
+#pragma clang fp contract(off)
+#endif
+    int cnt[N_COUNTERS], seg_fp = 0, seg_fn = 0, flags = 0;
+    double total = 0.0;
+    for (int k = 0; k < N_COUNTERS; k++) cnt[k] = 0;
+    for (int c = 0; c < n_classes; c++) {
+        for (int k = 0; k < N_COUNTERS; k++) cnt[k] += res[c].counters[k];
+        for (int k = 0; k < res[c].n_avg; k++) total += res[c].avg[k];
+        seg_fp += res[c].seg_fp;
+        seg_fn += res[c].seg_fn;
+        flags |= res[c].flags;
+    }
+    cnt[C20_S] = seg_fp < seg_fn ? seg_fp : seg_fn;
+    cnt[C20_D] = seg_fn > seg_fp ? seg_fn - seg_fp : 0;
+    cnt[C20_I] = seg_fp > seg_fn ? seg_fp - seg_fn : 0;
     const int st = flags & 2 ? REFUSED : (flags & 1 ? DOUBT : SCORED);
     for (int k = 0; k < N_COUNTERS; k++) counters[k] = st == SCORED ? cnt[k] : 0;
     *total_de = st == SCORED ? total : 0.0;

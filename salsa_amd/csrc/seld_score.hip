@@ -1,12 +1,14 @@
-// seld_score.hip -- salsa_nn_seld_score (include/salsa_nn.h): DCASE rows against ground-truth rows, the SELD 2021 counters of
-// crnn/metrics.py::SeldMetrics per (file, segment), on the device.  The statements are seld_score.h's; this file bins the rows.
+// seld_score.hip -- salsa_nn_seld_score and salsa_nn_seld_score2020 (include/salsa_nn.h): DCASE rows against ground-truth rows, the
+// SELD 2021 counters of crnn/metrics.py::SeldMetrics, or the SELD 2020 counters of SeldMetrics2020, per (file, segment), on the
+// device.  The statements are seld_score.h's; this file bins the rows, the same way for both metrics.
 //
 // One workgroup of 256 threads (4 waves) per (file, segment).  Each side's rows are walked in tiles of 256 consecutive rows, one
 // 8-byte load per row; the tile's rows of this segment are compacted in ARRIVAL order (one ballot per wave, the wave counts through
 // LDS, as seld_decode.hip does), and a compacted row's slot in its (class, frame) cell is the cell's count so far plus the number
 // of earlier rows of the tile in the same cell: the cells fill in arrival order with no atomics, so two runs are bit-identical.
 // Then one pass with a thread per cell pairs the cells that hold both sides, a thread per class does the class bookkeeping, and
-// thread 0 writes the record.  Everything is float64 (a few hundred distances per workgroup: the float64 rate is no concern here,
+// thread 0 writes the record (2020: a thread per cell takes the cell's least total cost, a thread per class walks its frames in
+// ascending order).  Everything is float64 (a few hundred distances per workgroup: the float64 rate is no concern here,
 // the walk over the rows is the cost).  salsa_nn_seld_score_sum adds the scored records up in record order in one workgroup.
 #include "build_guard.h"
 #include <hip/hip_runtime.h>
@@ -81,6 +83,8 @@ __device__ void bin_rows(ScoreLds &s, const DcaseRow *__restrict__ rows, int cou
     }
 }
 
+// V2020: the SELD 2020 statements on the same cells
+template <bool V2020>
 __global__ __launch_bounds__(SCORE_THREADS) void seld_score_kernel(const DcaseRow *__restrict__ pred, const int *__restrict__ pred_counts,
                                                                    int pred_capacity, const DcaseRow *__restrict__ gt,
                                                                    const int *__restrict__ gt_counts, int gt_capacity, int n_seg,
@@ -111,25 +115,35 @@ __global__ __launch_bounds__(SCORE_THREADS) void seld_score_kernel(const DcaseRo
         const int ng = s.gcnt[c], np = s.pcnt[c];
         if (ng < 1 || np < 1 || ng > MAX_DOAS || np > MAX_DOAS) continue;     // (a cell of more than 4 refuses its class in score_class)
         int32_t g[MAX_DOAS], p[MAX_DOAS];
-        double cost[MAX_DOAS] = {0.0, 0.0, 0.0, 0.0};
         for (int k = 0; k < MAX_DOAS; k++) {
             g[k] = s.cells[c].in.g[k];
             p[k] = s.cells[c].in.p[k];
         }
-        bool doubt;
-        const unsigned m = pair_cell(g, ng, p, np, margin, cost, &doubt);
-        for (int k = 0; k < MAX_DOAS; k++) s.cells[c].cost[k] = cost[k];      // (over the DOAs just read)
-        s.matched[c] = (uint8_t)m;
-        s.cell_doubt[c] = doubt ? 1 : 0;
+        if constexpr (V2020) {
+            s.cells[c].cost[0] = cell_cost2020(g, ng, p, np);                 // (over the DOAs just read)
+        } else {
+            double cost[MAX_DOAS] = {0.0, 0.0, 0.0, 0.0};
+            bool doubt;
+            const unsigned m = pair_cell(g, ng, p, np, margin, cost, &doubt);
+            for (int k = 0; k < MAX_DOAS; k++) s.cells[c].cost[k] = cost[k];  // (over the DOAs just read)
+            s.matched[c] = (uint8_t)m;
+            s.cell_doubt[c] = doubt ? 1 : 0;
+        }
     }
     __syncthreads();
     if (tid < n_classes) {
         const int at = tid * label_rate;
-        score_class(s.cells + at, s.gcnt + at, s.pcnt + at, s.matched + at, s.cell_doubt + at, s.gfirst + at, label_rate, threshold, margin,
-                    &s.res[tid]);
+        if constexpr (V2020)
+            score_class2020(s.cells + at, s.gcnt + at, s.pcnt + at, label_rate, threshold, margin, &s.res[tid]);
+        else
+            score_class(s.cells + at, s.gcnt + at, s.pcnt + at, s.matched + at, s.cell_doubt + at, s.gfirst + at, label_rate, threshold, margin,
+                        &s.res[tid]);
     }
     __syncthreads();
-    if (tid == 0) segment_record(s.res, n_classes, counters + record * N_COUNTERS, total_de + record, status + record);
+    if (tid == 0) {
+        if constexpr (V2020) segment_record2020(s.res, n_classes, counters + record * N_COUNTERS, total_de + record, status + record);
+        else segment_record(s.res, n_classes, counters + record * N_COUNTERS, total_de + record, status + record);
+    }
 }
 
 // the scored records added up: the counters exactly (int64), total_DE as ONE running float64 sum in record order (thread 0 adds
@@ -174,12 +188,11 @@ __global__ void seld_distance_kernel(const int16_t *__restrict__ quads, int64_t 
     if (i < n) out[i] = distance_deg(quads[4 * i], quads[4 * i + 1], quads[4 * i + 2], quads[4 * i + 3]);
 }
 
-} // namespace
-
-extern "C" int salsa_nn_seld_score(const int16_t *pred_rows, const int *pred_counts, int pred_capacity, const int16_t *gt_rows,
-                                   const int *gt_counts, int gt_capacity, int n_files, int n_frames, int label_rate, int n_classes,
-                                   double doa_threshold, double margin, int *counters, double *total_de, int *status, int64_t *sum_counters,
-                                   double *sum_de, void *hip_stream)
+// both exports: the argument checks, the per-segment launch of either metric and the shared sum
+template <bool V2020>
+int launch_score(const int16_t *pred_rows, const int *pred_counts, int pred_capacity, const int16_t *gt_rows, const int *gt_counts,
+                 int gt_capacity, int n_files, int n_frames, int label_rate, int n_classes, double doa_threshold, double margin,
+                 int *counters, double *total_de, int *status, int64_t *sum_counters, double *sum_de, void *hip_stream)
 {
     // everything is checked before the first device call (the CPU suite exercises these returns without a GPU)
     if (!pred_rows || !pred_counts || !gt_rows || !gt_counts || !counters || !total_de || !status) return -1;
@@ -189,7 +202,7 @@ extern "C" int salsa_nn_seld_score(const int16_t *pred_rows, const int *pred_cou
     if (label_rate < 1 || label_rate > MAX_RATE || n_classes < 1 || n_classes > MAX_CLASSES) return -1;
     if (!(doa_threshold == doa_threshold) || !(margin >= 0.0) || margin == INFINITY) return -1;
     const int n_seg = n_segments(n_frames, label_rate);
-    hipLaunchKernelGGL(seld_score_kernel, dim3((unsigned)n_seg, (unsigned)n_files), dim3(SCORE_THREADS), 0, (hipStream_t)hip_stream,
+    hipLaunchKernelGGL(seld_score_kernel<V2020>, dim3((unsigned)n_seg, (unsigned)n_files), dim3(SCORE_THREADS), 0, (hipStream_t)hip_stream,
                        (const DcaseRow *)pred_rows, pred_counts, pred_capacity, (const DcaseRow *)gt_rows, gt_counts, gt_capacity, n_seg,
                        label_rate, n_classes, doa_threshold, margin, counters, total_de, status);
     if (hipGetLastError() != hipSuccess) return -6;
@@ -199,6 +212,26 @@ extern "C" int salsa_nn_seld_score(const int16_t *pred_rows, const int *pred_cou
         if (hipGetLastError() != hipSuccess) return -6;
     }
     return 0;
+}
+
+} // namespace
+
+extern "C" int salsa_nn_seld_score(const int16_t *pred_rows, const int *pred_counts, int pred_capacity, const int16_t *gt_rows,
+                                   const int *gt_counts, int gt_capacity, int n_files, int n_frames, int label_rate, int n_classes,
+                                   double doa_threshold, double margin, int *counters, double *total_de, int *status, int64_t *sum_counters,
+                                   double *sum_de, void *hip_stream)
+{
+    return launch_score<false>(pred_rows, pred_counts, pred_capacity, gt_rows, gt_counts, gt_capacity, n_files, n_frames, label_rate, n_classes,
+                               doa_threshold, margin, counters, total_de, status, sum_counters, sum_de, hip_stream);
+}
+
+extern "C" int salsa_nn_seld_score2020(const int16_t *pred_rows, const int *pred_counts, int pred_capacity, const int16_t *gt_rows,
+                                       const int *gt_counts, int gt_capacity, int n_files, int n_frames, int label_rate, int n_classes,
+                                       double doa_threshold, double margin, int *counters, double *total_de, int *status,
+                                       int64_t *sum_counters, double *sum_de, void *hip_stream)
+{
+    return launch_score<true>(pred_rows, pred_counts, pred_capacity, gt_rows, gt_counts, gt_capacity, n_files, n_frames, label_rate, n_classes,
+                              doa_threshold, margin, counters, total_de, status, sum_counters, sum_de, hip_stream);
 }
 
 extern "C" int salsa_nn_seld_distance(const int16_t *quads, int64_t n, double *out, void *hip_stream)
