@@ -196,6 +196,26 @@ int salsa_augment_gcc_batch(const float *d_in, int64_t in_batch_stride, int64_t 
                             int64_t n_frames, int n_freq, const int *d_params, const float *d_uval, const float *d_minmax,
                             void *hip_stream);
 
+/* One training batch straight from the feature bank (dataset/database.py:230-231's concatenated layout; SeldDataset.__getitem__,
+ * dataset/dataloader.py:37-62, for B chunks at once): gather B windows of chunk_frames frames, augment them as salsa_augment_batch /
+ * salsa_augment_gcc_batch would (the same per-element code: the results are equal bit for bit) and cut the label windows, with the
+ * target half of the channel swap applied.  d_bank: float32 [n_channels][bank_frames][n_freq], n_channels 7 or 10; d_sed_all float32
+ * [label_frames_total][n_classes], d_doa_all float32 [label_frames_total][3 n_classes]; d_start / d_gt_start: int64 [batch], the first
+ * feature frame / label frame of every chunk (0 <= start <= bank_frames - chunk_frames: the caller checks them; a window outside
+ * the bank is left unwritten); recipe: SALSA_BANK_* (foa / mic: 7 channels, the last n_zero_channels of them zero-filled by the
+ * cutout; gcc: 10 channels); d_params / d_uval as salsa_augment_batch takes them (NULL for SALSA_BANK_NONE).  has_rects != 0 (the
+ * host drew at least one rectangle in the batch): the fill range, min / max of every UNAUGMENTED chunk, is first computed into
+ * d_minmax_ws (8 bytes per sample, contents private); with has_rects == 0 that launch is skipped and d_minmax_ws may be NULL.
+ * Outputs: d_x float32 [batch][n_channels][chunk_frames][n_freq], d_sed [batch][label_frames][n_classes], d_doa
+ * [batch][label_frames][3 n_classes].  All five label arguments NULL: features only (whole clips with SALSA_BANK_NONE).  At most
+ * three launches on hip_stream, no synchronisation; bank offsets are 64-bit. */
+enum { SALSA_BANK_NONE = 0, SALSA_BANK_FOA = 1, SALSA_BANK_MIC = 2, SALSA_BANK_GCC = 3 };
+int salsa_bank_batch(const float *d_bank, int n_channels, int64_t bank_frames, int n_freq, const float *d_sed_all,
+                     const float *d_doa_all, int64_t label_frames_total, int n_classes, const int64_t *d_start,
+                     const int64_t *d_gt_start, int batch, int chunk_frames, int label_frames, int recipe, int n_zero_channels,
+                     const int *d_params, const float *d_uval, int has_rects, float *d_x, float *d_sed, float *d_doa,
+                     void *d_minmax_ws, void *hip_stream);
+
 /* Per-kernel timing of salsa_extract_batch with HIP events recorded on the call's stream (for roofline reporting).
  * enable == 1 brackets each launch with an event pair.  enable = K > 1 launches every kernel of the call K times back to
  * back between ONE event pair (each kernel is idempotent on the audio / spill / mask buffers, so the results are those of

@@ -13,6 +13,7 @@ HEADERS = ('salsa_hip.h', 'salsa_gru.h', 'salsa_nn.h', 'salsa_baseline.h')
 FORMAT = {'foa': 0, 'mic': 1}
 FEATURE = {'salsa': 0, 'salsa_lite': 1, 'salsa_ipd': 2}
 LAYOUT = {'planar': 0, 'interleaved': 1}
+BANK_RECIPE = {'none': 0, 'foa': 1, 'mic': 2, 'gcc': 3}   # salsa_bank_batch: SALSA_BANK_*
 FLAG_FLEX, FLAG_NO_CLIP_FREQS, FLAG_CLIP_SPATIAL_ALIAS = 1, 2, 4
 FLAG_FORCE_F64 = 8  # verification: the all-float64 instantiation of the covariance / eigen kernel (include/salsa_hip.h)
 PIPE_SPLIT_PAIRS, PIPE_GRAPH = 1, 2

@@ -1,0 +1,178 @@
+"""Whole training runs from a feature bank: the loop of the reference's ``make train`` (experiments/train.py:53-104 with Lightning's
+fit loop, models/seld_models.py:84-108) around Trainer.train_step -- shuffled epochs from dataset.BankLoader (one salsa_bank_batch
+call per step), the reference's step-indexed learning-rate / momentum schedule (utilities/learning_utils.py:17-52), validation every
+``val_interval`` epochs through infer_pipelined with the rows decoded and scored on the device, the latest checkpoint and the best one
+by valSeld under the reference's file names, and resuming.
+
+Files (experiments/train.py:62-66; picked up by experiments/inference.py:49-67 -- ``startswith('epoch')``, ``int(f[6:9])``, and the second
+number in a best file's name is valSeld):
+    <out_dir>/checkpoint/epoch=003.ckpt                                              the latest epoch only
+    <out_dir>/best/epoch=003-valSeld=0.512-valER=0.700-valF1=0.400-valLE=25.000-valLR=0.600.ckpt   mode 'crossval' only; one file
+A checkpoint is a torch.save dict: ``state_dict`` under the reference's key names (checkpoint.reference_state_dict), the optimizer's
+state, epoch, global_step, the history, and what a resumed run needs to repeat the uninterrupted one bit for bit -- torch's CPU and
+device generator states (dropout seeds come from the CPU generator) and the loader's seed."""
+import os
+
+import numpy as np
+import torch
+
+from .checkpoint import load_reference_state_dict, reference_state_dict
+from .train import LRS, MILESTONES
+
+MOMS = (0.9, 0.9, 0.9, 0.9)
+
+
+def lr_mom_at_step(step, steps_per_epoch, max_epochs, milestones=MILESTONES, lrs=LRS, moms=MOMS):
+    """(lr, momentum) of global step ``step``: LearningRateScheduler's arithmetic exactly (learning_utils.py:26-27, :44-46) --
+    np.interp over the INTEGER step milestones int(m * n_steps), n_steps = int(max_epochs * steps_per_epoch).  (train.lr_at
+    interpolates over step / total_steps instead; the two agree at the shipped 50 x 1313 steps and differ for short runs.)"""
+    n_steps = int(max_epochs * steps_per_epoch)
+    step_milestones = [int(m * n_steps) for m in milestones]
+    return float(np.interp(step, step_milestones, lrs)), float(np.interp(step, step_milestones, moms))
+
+
+def best_name(epoch, val):
+    """ModelCheckpoint's '{epoch:03d}-{valSeld:.3f}-{valER:.3f}-{valF1:.3f}-{valLE:.3f}-{valLR:.3f}' (train.py:65-66; Lightning
+    writes every key as name=value)"""
+    return ('epoch=%03d-valSeld=%.3f-valER=%.3f-valF1=%.3f-valLE=%.3f-valLR=%.3f.ckpt'
+            % (epoch, val['valSeld'], val['valER'], val['valF1'], val['valLE'], val['valLR']))
+
+
+def _ckpt_files(d):
+    return sorted(f for f in os.listdir(d) if f.startswith('epoch') and f.endswith('ckpt')) if os.path.isdir(d) else []
+
+
+def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, combine_method='mean', sed_threshold=0.3,
+             doa_threshold=20, eval_version='2021', sub_batch=8, return_rows=False):
+    """One validation pass (models/seld_models.py:96-108 + interfaces.py:163-180): every clip of ``val_bank`` through
+    infer_pipelined(Trainer.infer) in test chunks, rows against ``val_gt`` (per clip a list of rows, metrics.load_dcase_csv).  On the
+    GPU the rows are decoded and scored on the device (DeviceSeldScore / DeviceSeldScore2020 by eval_version), on the CPU by the host
+    classes.  -> dict valER valF1 valLE valLR valSeld (+ the scorer under 'scorer', and 'rows' when asked)."""
+    from .infer import infer_pipelined
+    from .metrics import SeldMetrics, SeldMetrics2020
+    from .score import DeviceSeldScore, DeviceSeldScore2020, gt_rows_to_device
+    if eval_version not in ('2020', '2021'):
+        raise ValueError('Unknown eval_version {}'.format(eval_version))
+    n = len(val_bank.clip_len)
+    if n == 0 or len(val_gt) != n:
+        raise ValueError('validation: ground truth of %d clips for a bank of %d' % (len(val_gt), n))
+    if len(set(val_bank.clip_len)) != 1:
+        raise ValueError('validation: clips of unequal length in the bank: %s frames' % sorted(set(val_bank.clip_len)))
+    n_label = val_bank.clip_len[0] // val_bank.upsample
+    nc, rate = trainer.n_classes, val_bank.label_rate
+    on_gpu = trainer.device.type == 'cuda'
+    kw = dict(sub_batch=sub_batch, sed_threshold=sed_threshold, n_label_frames=n_label, chunk_len=chunk_len, chunk_hop_len=chunk_hop_len,
+              combine_method=combine_method, n_classes=nc,
+              eval_version='2020')       # (the ROW shape only: (frame, class, azimuth, elevation), what SeldMetrics.update reads)
+    if on_gpu:
+        scorer = (DeviceSeldScore2020 if eval_version == '2020' else DeviceSeldScore)(nc, doa_threshold, rate)
+        gt_rows, gt_counts = gt_rows_to_device(val_gt, trainer.device)
+        rows = infer_pipelined(n, val_bank.clip_batch, trainer.infer, decode='device', score=(gt_rows, gt_counts, scorer), **kw)
+    else:
+        scorer = (SeldMetrics2020 if eval_version == '2020' else SeldMetrics)(nc, doa_threshold)
+        rows = infer_pipelined(n, val_bank.clip_batch, trainer.infer, decode='host', **kw)
+        for pred, gt in zip(rows, val_gt):
+            scorer.update(pred, gt, max_frames=n_label, label_rate=rate)
+    ER, F, LE, LR = (float(v) for v in scorer.scores())
+    out = dict(valER=ER, valF1=F, valLE=LE, valLR=LR, valSeld=float(scorer.seld_error()), scorer=scorer)
+    if return_rows:
+        out['rows'] = rows
+    return out
+
+
+def _save(path, trainer, loader, epoch, global_step, history, best, val=None):
+    dev = trainer.device
+    ckpt = dict(state_dict=reference_state_dict(trainer.raw_model), optimizer=trainer.opt.state_dict(), epoch=epoch,
+                global_step=global_step, history=history, best=best, val=val, loader_seed=loader.seed,
+                rng_cpu=torch.get_rng_state(), rng_device=torch.cuda.get_rng_state(dev) if dev.type == 'cuda' else None)
+    tmp = path + '.tmp'
+    torch.save(ckpt, tmp)
+    os.replace(tmp, path)                                                       # (a killed job never leaves half a checkpoint)
+
+
+def _load(path, trainer, loader):
+    ckpt = torch.load(path, map_location='cpu', weights_only=False)
+    if ckpt['loader_seed'] != loader.seed:
+        raise ValueError('resume: the checkpoint was trained with loader seed %d, this run has %d' % (ckpt['loader_seed'], loader.seed))
+    load_reference_state_dict(trainer.raw_model, ckpt['state_dict'])
+    trainer.opt.load_state_dict(ckpt['optimizer'])
+    torch.set_rng_state(ckpt['rng_cpu'])
+    if ckpt['rng_device'] is not None and trainer.device.type == 'cuda':
+        torch.cuda.set_rng_state(ckpt['rng_device'], trainer.device)
+    trainer.step_idx = ckpt['global_step']
+    return ckpt
+
+
+def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, max_epochs=50, epochs=None, milestones=MILESTONES,
+        lrs=LRS, moms=MOMS, val_interval=1, train_fraction=1.0, audio_format='foa', feature_type='salsa', augment=True, seed=2021,
+        mode='crossval', eval_version='2021', resume=False, chunk_len=None, chunk_hop_len=None, combine_method='mean',
+        sed_threshold=0.3, doa_threshold=20, val_sub_batch=8, loader=None):
+    """Train ``trainer`` for ``max_epochs`` epochs of ``bank`` (a finalized GpuFeatureBank).  The keywords are the YAML's keys
+    (INTEGRATION.md has the table): batch_size = training.train_batch_size; milestones / lrs / moms = training.lr_scheduler.*;
+    max_epochs, val_interval = training.*; train_fraction, n_classes (Trainer's) = data.*; eval_version; mode ('crossval': the best
+    checkpoint by valSeld is kept, 'eval': the latest only).  ``epochs`` caps how many epochs THIS call runs (time-sliced jobs);
+    ``resume`` continues from the lexicographically last file of <out_dir>/checkpoint (train.py:37-45; none there: from scratch).
+    val_bank / val_gt: the validation clips and their ground-truth rows; chunk_len .. sed_threshold go to the validation pass.
+    -> the history: dict(steps=[epoch, step, lr, mom, loss, sed_loss, doa_loss per step], val=[dict per validated epoch],
+    best=dict | None, epoch=epochs finished, global_step)."""
+    from ..dataset import BankLoader
+    if mode not in ('crossval', 'eval'):
+        raise ValueError('Invalid mode {}'.format(mode))
+    if (val_bank is None) != (val_gt is None):
+        raise ValueError('val_bank and val_gt come together')
+    if val_bank is not None and len(set(val_bank.clip_len)) != 1:
+        raise ValueError('validation: clips of unequal length in the bank: %s frames' % sorted(set(val_bank.clip_len)))
+    if loader is None:
+        loader = BankLoader(bank, batch_size=batch_size, seed=seed, audio_format=audio_format, feature_type=feature_type,
+                            augment=augment, train_fraction=train_fraction)
+    spe = loader.steps_per_epoch
+    if spe < 1:
+        raise ValueError('no training step in an epoch (train_fraction %s of %d batches)' % (train_fraction, loader.n_batches))
+    ckpt_dir = os.path.join(out_dir, 'checkpoint') if out_dir is not None else None
+    best_dir = os.path.join(out_dir, 'best') if out_dir is not None else None
+    history = dict(steps=[], val=[], best=None, epoch=0, global_step=0)
+    first_epoch = 0
+    if resume:
+        if out_dir is None:
+            raise ValueError('resume needs out_dir')
+        found = _ckpt_files(ckpt_dir)
+        if found:
+            ckpt = _load(os.path.join(ckpt_dir, found[-1]), trainer, loader)
+            history, first_epoch = ckpt['history'], ckpt['epoch'] + 1
+    last_epoch = max_epochs if epochs is None else min(max_epochs, first_epoch + epochs)
+    for epoch in range(first_epoch, last_epoch):
+        on_device, sched = [], []
+        for step, (x, sed, doa, _) in enumerate(loader.epoch(epoch)):
+            lr, mom = lr_mom_at_step(epoch * spe + step, spe, max_epochs, milestones, lrs, moms)
+            on_device.append(torch.stack(trainer.train_step(x, sed, doa, lr=lr, beta1=mom)))     # (no host synchronisation in the step)
+            sched.append((epoch, step, lr, mom))
+        losses = torch.stack(on_device).cpu().tolist()                           # the epoch's only read-back of the losses
+        history['steps'] += [s + tuple(l) for s, l in zip(sched, losses)]
+        history['epoch'], history['global_step'] = epoch + 1, (epoch + 1) * spe
+        val = None
+        if val_bank is not None and (epoch + 1) % val_interval == 0:
+            val = validate(trainer, val_bank, val_gt, chunk_len, chunk_hop_len, combine_method, sed_threshold, doa_threshold,
+                           eval_version, val_sub_batch)
+            val.pop('scorer')
+            val['epoch'] = epoch
+            history['val'].append(val)
+        improved = val is not None and mode == 'crossval' and (history['best'] is None or val['valSeld'] < history['best']['valSeld'])
+        if improved:
+            history['best'] = dict(val)
+        if out_dir is not None:
+            os.makedirs(ckpt_dir, exist_ok=True)
+            old = _ckpt_files(ckpt_dir)
+            name = 'epoch=%03d.ckpt' % epoch
+            _save(os.path.join(ckpt_dir, name), trainer, loader, epoch, history['global_step'], history, history['best'], val)
+            for f in old:
+                if f != name:
+                    os.remove(os.path.join(ckpt_dir, f))
+            if improved:
+                os.makedirs(best_dir, exist_ok=True)
+                old = _ckpt_files(best_dir)
+                name = best_name(epoch, val)
+                _save(os.path.join(best_dir, name), trainer, loader, epoch, history['global_step'], history, history['best'], val)
+                for f in old:
+                    if f != name:
+                        os.remove(os.path.join(best_dir, f))
+    return history

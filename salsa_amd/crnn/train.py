@@ -45,11 +45,12 @@ def synthetic_batch(batch: int, device, seed: int = 0, n_frames: int = 640, n_fr
 class Trainer:
     def __init__(self, device, amp_dtype=torch.bfloat16, ddp: bool = None, total_steps: int = 1313 * 50,
                  bf16_grad_allreduce: bool = True, seed: int = 2021, n_input_channels: int = 7, decoder_type: str = 'bigru',
-                 freq_pool: str = 'avg', decoder_size: int = 256, output_format: str = 'reg_xyz'):
+                 freq_pool: str = 'avg', decoder_size: int = 256, output_format: str = 'reg_xyz', n_classes: int = 12):
         """n_input_channels: 7 (SALSA, melspeciv, linspeciv) or 10 (melspecgcc, linspecgcc), experiments/configs/seld.yml;
         decoder_type ('bigru' | 'gru' | 'lstm' | 'bilstm'), freq_pool ('avg' | 'max' | 'avg_max') and decoder_size: the YAML's
         model.decoder keys of the same names (SeldCRNN); output_format: the YAML's data.output_format, 'reg_xyz' (SED from the
-        event head, loss.seld_loss) or 'accdoa' (SED = length of each class's xyz vector, loss.accdoa_loss)."""
+        event head, loss.seld_loss) or 'accdoa' (SED = length of each class's xyz vector, loss.accdoa_loss); n_classes: the YAML's
+        data.n_classes (12 for TNSSE2021, 14 for TNSSE2020)."""
         if output_format not in OUTPUT_FORMATS:
             raise ValueError('invalid output_format %r (supported: %s)' % (output_format, ', '.join(OUTPUT_FORMATS)))
         self.output_format = output_format
@@ -60,7 +61,8 @@ class Trainer:
         self.amp_dtype = amp_dtype
         self.total_steps = total_steps
         self.step_idx = 0
-        model = SeldCRNN(n_input_channels=n_input_channels, decoder_type=decoder_type, freq_pool=freq_pool,
+        self.n_classes = n_classes
+        model = SeldCRNN(n_input_channels=n_input_channels, n_classes=n_classes, decoder_type=decoder_type, freq_pool=freq_pool,
                          decoder_size=decoder_size).to(self.device)
         self.channels_last = self.device.type == 'cuda' and os.environ.get('SALSA_CHANNELS_LAST', '1') == '1'
         if self.channels_last:
@@ -104,11 +106,16 @@ class Trainer:
             return x
         return x.contiguous(memory_format=torch.channels_last)
 
-    def train_step(self, x, sed, doa):
+    def train_step(self, x, sed, doa, lr=None, beta1=None):
+        """lr / beta1: the step's learning rate and Adam momentum from the caller's schedule (fit: lr_mom_at_step); without them the
+        built-in schedule lr_at over step_idx / total_steps and the optimizer's betas as they are."""
         self.model.train()
-        lr = lr_at(self.step_idx / max(1, self.total_steps))
+        if lr is None:
+            lr = lr_at(self.step_idx / max(1, self.total_steps))
         for gparam in self.opt.param_groups:
             gparam['lr'] = lr
+            if beta1 is not None:
+                gparam['betas'] = (beta1, gparam['betas'][1])
         x = self._input_layout(x)
         self.opt.zero_grad(set_to_none=True)
         if self.grad_sync is not None:
@@ -122,6 +129,11 @@ class Trainer:
         self.opt.step()
         self.step_idx += 1
         return loss.detach(), sed_l.detach(), doa_l.detach()
+
+    def fit(self, bank, **kwargs):
+        """whole epochs from a finalized GpuFeatureBank, with validation and checkpoints: fit.fit(self, bank, ...)"""
+        from .fit import fit
+        return fit(self, bank, **kwargs)
 
     @torch.no_grad()
     def infer(self, x):

@@ -28,6 +28,7 @@
 
 #include "../../include/salsa_hip.h"
 #include "salsa_math.h"
+#include "bank_batch.h"
 
 using salsa::cplx;
 
@@ -2116,7 +2117,8 @@ template <typename S> __global__ __launch_bounds__(256) void pcm_to_planar_kerne
 // reflect padding (:298-320), then the cutout rectangles (:87-121, :149-194, :223-254; last rectangle wins; the spatial rows
 // get zeros).  One thread = all 7 channels of one (clip, frame, bin).  par: int32 [B][AUG_NPAR] = m0..m3, shift, up, 0, 0,
 // top[8], h[8], left[8], w[8] ; uval: float32 [B][8] in [0,1) ; minmax: float32 [B][2] -> fill = min + (max - min) * u.
-constexpr int AUG_NPAR = 40;
+constexpr int AUG_NPAR = bank_batch::NPAR;
+// (the per-element body is bank_batch.h's, shared with salsa_bank_batch)
 __global__ __launch_bounds__(256) void augment_kernel(const float *__restrict__ in, long in_batch, long in_chan,
                                                       float *__restrict__ out, int T, int F,
                                                       int format, int n_zero, const int *__restrict__ par,
@@ -2126,53 +2128,10 @@ __global__ __launch_bounds__(256) void augment_kernel(const float *__restrict__ 
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= T * F) return;
     const int t = i / F, f = i - t * F;
-    const int *p = par + b * AUG_NPAR;
     const long plane = (long)T * F;
-    const float *src = in + (long)b * in_batch; // the input may be a time-cropped view: its own batch / channel strides
-    float *dst = out + (long)b * 7 * plane + i;
-    int hit = -1;
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const int top = p[8 + r], h = p[16 + r], left = p[24 + r], w = p[32 + r];
-        if (t >= top && t < top + h && f >= left && f < left + w) hit = r;
-    }
-    if (hit >= 0) {
-#pragma clang fp contract(off) // min + (max - min) * u as three rounded operations, like the host-side restatement (no FMA)
-        const float lo = minmax[2 * b], hi = minmax[2 * b + 1];
-        const float v = lo + (hi - lo) * uval[b * 8 + hit];
-#pragma unroll
-        for (int c = 0; c < 7; c++) dst[c * plane] = c < 7 - n_zero ? v : 0.f;
-        return;
-    }
-    const int s = p[4];
-    int fs = f;
-    if (s > 0) {
-        if (p[5]) fs = f - s < 0 ? s - f : f - s;                    // shifted up: pad s bins at the front (reflect at bin 0)
-        else fs = f + s > F - 1 ? 2 * (F - 1) - (f + s) : f + s;       // shifted down: pad at the back (reflect at bin F-1)
-    }
-    float x[7];
-#pragma unroll
-    for (int c = 0; c < 7; c++) x[c] = src[c * in_chan + (long)t * F + fs];
-    if (format == SALSA_FORMAT_FOA) { // W Y Z X | Iy Iz Ix : swap x<->y, negate x, y, z
-        if (p[0]) { float a = x[1]; x[1] = x[3]; x[3] = a; a = x[4]; x[4] = x[6]; x[6] = a; }
-        if (p[1]) x[6] = -x[6];
-        if (p[2]) x[4] = -x[4];
-        if (p[3]) x[5] = -x[5];
-    } else {                          // M1 M2 M3 M4 | p12 p13 p14
-        if (p[0]) { float a = x[1]; x[1] = x[2]; x[2] = a; a = x[4]; x[4] = x[5]; x[5] = a; }
-        if (p[1]) {
-            const float c0 = x[0], c3 = x[3], c4 = x[4], c5 = x[5], c6 = x[6];
-            x[0] = c3; x[3] = c0;
-            x[6] = -c6; x[5] = c5 - c6; x[4] = c4 - c6;
-        }
-        if (p[2]) {
-            const float c0 = x[0], c1 = x[1], c2 = x[2], c3 = x[3], c4 = x[4], c5 = x[5], c6 = x[6];
-            x[0] = c1; x[1] = c0; x[2] = c3; x[3] = c2;
-            x[4] = -c4; x[5] = c6 - c4; x[6] = c5 - c4;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 7; c++) dst[c * plane] = x[c];
+    // the input may be a time-cropped view: its own batch / channel strides
+    bank_batch::augment7(in + (long)b * in_batch, in_chan, out + (long)b * 7 * plane + i, plane, t, f, F, format != SALSA_FORMAT_FOA,
+                         n_zero, par + b * AUG_NPAR, uval + b * 8, minmax + 2 * b);
 }
 
 // The baseline GCC recipe (dataset/datamodule.py:83-100) on [B][10][T][F] = M1..M4 | xc12 xc13 xc14 xc23 xc24 xc34: the
@@ -2180,14 +2139,6 @@ __global__ __launch_bounds__(256) void augment_kernel(const float *__restrict__ 
 // m0..m2 acts on the features), some GCC rows also flipped along the lag axis (f -> F-1-f); RandomShiftUpDownNp with
 // n_last_channels = 6 (only the four spectrogram rows shift); the cutout rectangles with the last 6 rows zeroed.  Pure gathers:
 // every output value is an input value or the fill value.  One thread = all 10 channels of one (clip, frame, bin).
-__constant__ signed char gcc_src[4][10] = {{0, 1, 2, 3, 4, 5, 6, 7, 8, 9},  // no swap
-                                           {0, 2, 1, 3, 5, 4, 6, 7, 9, 8},  // m0: swap M2 / M3
-                                           {3, 1, 2, 0, 8, 9, 6, 7, 4, 5},  // m1: swap M1 / M4
-                                           {1, 0, 3, 2, 4, 8, 7, 6, 5, 9}}; // m2: swap M1 / M2 and M3 / M4
-__constant__ signed char gcc_flip[4][10] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-                                            {0, 0, 0, 0, 0, 0, 0, 1, 0, 0},
-                                            {0, 0, 0, 0, 1, 1, 1, 0, 1, 1},
-                                            {0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
 __global__ __launch_bounds__(256) void augment_gcc_kernel(const float *__restrict__ in, long in_batch, long in_chan,
                                                           float *__restrict__ out, int T, int F, const int *__restrict__ par,
                                                           const float *__restrict__ uval, const float *__restrict__ minmax)
@@ -2196,39 +2147,9 @@ __global__ __launch_bounds__(256) void augment_gcc_kernel(const float *__restric
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= T * F) return;
     const int t = i / F, f = i - t * F;
-    const int *p = par + b * AUG_NPAR;
     const long plane = (long)T * F;
-    const float *src = in + (long)b * in_batch;
-    float *dst = out + (long)b * 10 * plane + i;
-    int hit = -1;
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const int top = p[8 + r], h = p[16 + r], left = p[24 + r], w = p[32 + r];
-        if (t >= top && t < top + h && f >= left && f < left + w) hit = r;
-    }
-    if (hit >= 0) {
-#pragma clang fp contract(off)
-        const float lo = minmax[2 * b], hi = minmax[2 * b + 1];
-        const float v = lo + (hi - lo) * uval[b * 8 + hit];
-#pragma unroll
-        for (int c = 0; c < 10; c++) dst[c * plane] = c < 4 ? v : 0.f;
-        return;
-    }
-    const int s = p[4];
-    int fs = f;
-    if (s > 0) {
-        if (p[5]) fs = f - s < 0 ? s - f : f - s;
-        else fs = f + s > F - 1 ? 2 * (F - 1) - (f + s) : f + s;
-    }
-    fs = fs < 0 ? 0 : fs > F - 1 ? F - 1 : fs;        // (a shift of F bins or more: stay inside the row)
-    const int k = p[0] ? 1 : p[1] ? 2 : p[2] ? 3 : 0;
-    const float *row = src + (long)t * F;
-#pragma unroll
-    for (int c = 0; c < 10; c++) {
-        const int g = c < 4 ? fs : f;                  // the shift moves the spectrogram rows only
-        const int gf = gcc_flip[k][c] ? F - 1 - g : g; // the swap's lag flip, taken before the shift
-        dst[c * plane] = row[gcc_src[k][c] * in_chan + gf];
-    }
+    bank_batch::augment10(in + (long)b * in_batch, in_chan, out + (long)b * 10 * plane + i, plane, t, f, F, par + b * AUG_NPAR,
+                          uval + b * 8, minmax + 2 * b);
 }
 
 __global__ __launch_bounds__(256) void db10_kernel(const float *__restrict__ p, float *__restrict__ o, long n)

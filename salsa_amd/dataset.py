@@ -13,6 +13,7 @@ import os
 import numpy as np
 import torch
 
+from . import _lib
 from .extractor import SalsaExtractor, normalize_, scaler_accumulate, scaler_finish
 
 
@@ -98,6 +99,7 @@ class GpuFeatureBank(torch.utils.data.Dataset):
         self.upsample = int((fs / hop_len) / label_rate)                       # feature frames per label frame (8)
         self.max_frames = int(max_clip_s * label_rate) * self.upsample         # "make sure we have 4800 frames" (:205-207)
         self.blocks, self.names, self.chunk_idx, self.chunk_name = [], [], [], []
+        self.clip_start, self.clip_len = [], []                               # every clip's first frame in the bank and its frames
         self.sed, self.doa, self.gt_idx = [], [], []
         self.pointer = self.gt_pointer = 0
         self.features = None
@@ -140,6 +142,12 @@ class GpuFeatureBank(torch.utils.data.Dataset):
         self.set_scaler(z['mean'], z['std'])
         return self.mean, self.std
 
+    def add_features(self, feats, names, sed=None, doa=None, gt_meta=None):
+        """Feature tensors float32 [B,C,T,F] as they are (labels as add_clips takes them).  The scaler's sums and the normalisation
+        are HIP kernels, so a bank on the CPU -- what the composed torch path of batch_augmented and the CPU suite work on -- holds
+        features that are normalised already and is closed with finalize(normalize=False)."""
+        self._ingest(feats.to(self.device), names, sed, doa, gt_meta)
+
     def _ingest(self, feats, names, sed=None, doa=None, gt_meta=None):
         assert gt_meta is None or (sed is None and doa is None), 'give either metadata CSVs or label arrays'
         n_frames = min(feats.shape[2], self.max_frames)
@@ -148,13 +156,16 @@ class GpuFeatureBank(torch.utils.data.Dataset):
         if self.n_scaler_channels is None:
             from .baseline_features import BaselineExtractor
             self.n_scaler_channels = feats.shape[1] if isinstance(self.ex, BaselineExtractor) else 4
-        self._sums = scaler_accumulate(feats, self._sums, self.n_scaler_channels)
+        if feats.is_cuda:                                                      # (a CPU bank: add_features)
+            self._sums = scaler_accumulate(feats, self._sums, self.n_scaler_channels)
         self._n += feats.shape[0] * n_frames
         if gt_meta is not None:
             assert len(gt_meta) == len(names)
             labels = [load_classwise_gt(fn, n_frames, self.n_classes, self.upsample) for fn in gt_meta]
             sed, doa = [lab[0] for lab in labels], [lab[1] for lab in labels]
         for i, name in enumerate(names):
+            self.clip_start.append(self.pointer)
+            self.clip_len.append(n_frames)
             idxes, self.pointer = get_segment_idxes(n_frames, self.chunk_len, self.chunk_hop_len, 1, self.pointer)
             gidx, self.gt_pointer = get_segment_idxes(n_frames, self.chunk_len, self.chunk_hop_len, self.upsample,
                                                       self.gt_pointer)
@@ -180,11 +191,13 @@ class GpuFeatureBank(torch.utils.data.Dataset):
     def set_scaler(self, mean, std):
         self.mean, self.std = torch.as_tensor(np.asarray(mean, np.float32)), torch.as_tensor(np.asarray(std, np.float32))
 
-    def finalize(self):
-        """concatenate along time (database.py:230) and normalise the scaler's channels in place."""
-        assert self.mean is not None, 'call fit_scaler() or set_scaler() first'
+    def finalize(self, normalize=True):
+        """concatenate along time (database.py:230) and normalise the scaler's channels in place (normalize=False: the features
+        are normalised already, add_features)."""
+        assert self.mean is not None or not normalize, 'call fit_scaler() or set_scaler() first'
         feats = torch.cat(self.blocks, dim=1).contiguous()                   # (C, sum T, F)
-        normalize_(feats[None], self.mean, self.std)
+        if normalize:
+            normalize_(feats[None], self.mean, self.std)
         self.features = feats
         self.sed_all, self.doa_all = torch.cat(self.sed), torch.cat(self.doa)
         self.blocks = []
@@ -204,3 +217,187 @@ class GpuFeatureBank(torch.utils.data.Dataset):
     def batch(self, indices):
         xs, ss, ds, ns = zip(*(self[i] for i in indices))
         return torch.stack(xs), torch.stack(ss), torch.stack(ds), list(ns)
+
+    # -------------------------------------------------------------------------------------------- one-call batches
+    def _fused(self):
+        """the one switch of the hand-written batch path: CUDA banks go through salsa_bank_batch unless SALSA_BANK_BATCH=0"""
+        return self.features.is_cuda and os.environ.get('SALSA_BANK_BATCH', '1') != '0'
+
+    def _check_indices(self, indices):
+        """host integers, checked here: the kernel trusts the starts it is handed"""
+        idx = [int(i) for i in (indices.tolist() if hasattr(indices, 'tolist') else indices)]
+        if not idx:
+            raise ValueError('an empty batch')
+        n = len(self.chunk_idx)
+        for i in idx:
+            if not 0 <= i < n:
+                raise IndexError('chunk index %d outside the bank of %d chunks' % (i, n))
+        return idx
+
+    def batch_augmented(self, indices, draws=None, audio_format='foa', feature_type='salsa'):
+        """The training batch of chunks ``indices`` (host integers) with the drawn augmentation ``draws`` (augment.draw_augment's dict;
+        None: no augmentation) of the recipe of (audio_format, feature_type): x (B,C,T,F), sed (B,L,nc), doa (B,L,3 nc) with the target
+        half of the swap, names.  On a CUDA bank this is ONE call of libsalsa_hip.so (salsa_bank_batch: gather, augment and label in at
+        most three launches, no stacked copy, no host synchronisation); on a CPU bank, or with SALSA_BANK_BATCH=0, the composed path --
+        batch(), then augment.apply_augment_hip (CPU: apply_augment_torch), then augment.swap_targets -- whose result it equals bit for
+        bit."""
+        from . import augment as aug
+        assert self.features is not None, 'call finalize() first'
+        idx = self._check_indices(indices)
+        swap, _, n_zero, _ = aug.recipe(audio_format, feature_type)
+        Cn, n_bank, F = self.features.shape
+        if Cn != (10 if swap == 'gcc' else 7):
+            raise ValueError('the %s recipe takes %d channels, the bank has %d' % (swap, 10 if swap == 'gcc' else 7, Cn))
+        B, T, L = len(idx), self.chunk_len, self.chunk_len // self.upsample
+        names = [self.chunk_name[i] for i in idx]
+        if draws is not None and any(tuple(draws[k].shape[:1]) != (B,) for k in ('m', 'shift', 'up', 'top', 'h', 'left', 'w', 'u')):
+            raise ValueError('draws for another batch size than %d' % B)
+        if not self._fused():
+            x, sed, doa, _ = self.batch(idx)
+            if draws is None:
+                return x, sed, doa, names
+            if not x.is_cuda:
+                x, doa = aug.apply_augment_torch(x, doa, draws, audio_format, self.n_classes, feature_type)
+                return x, sed, doa, names
+            m_dev = draws['m'].pin_memory().to(x.device, non_blocking=True)
+            return (aug.apply_augment_hip(x, draws, audio_format, feature_type), sed,
+                    aug.swap_targets(doa, m_dev, 'foa' if swap == 'foa' else 'mic', self.n_classes), names)
+        starts, gts = [self.chunk_idx[i] for i in idx], [self.gt_idx[i] for i in idx]
+        if min(starts) < 0 or max(starts) + T > n_bank or min(gts) < 0 or max(gts) + L > self.sed_all.shape[0]:
+            raise IndexError('a chunk window lies outside the bank')
+        # ONE pinned staging buffer, one copy: starts and gt starts (int64), the 40 parameters and the 8 fill draws of every sample
+        host = torch.empty(52 * B, dtype=torch.int32, pin_memory=True)
+        host[:4 * B].view(torch.int64).copy_(torch.tensor([starts, gts], dtype=torch.int64).reshape(-1))
+        par, u = host[4 * B:44 * B].view(B, 40), host[44 * B:].view(torch.float32).view(B, 8)
+        has_rects = False
+        if draws is None:
+            par.zero_()
+            u.zero_()
+        else:
+            par.zero_()
+            par[:, 0:4] = draws['m']
+            par[:, 4], par[:, 5] = draws['shift'], draws['up']
+            par[:, 8:16], par[:, 16:24], par[:, 24:32], par[:, 32:40] = draws['top'], draws['h'], draws['left'], draws['w']
+            u.copy_(draws['u'].float())
+            has_rects = bool(((draws['h'] > 0) & (draws['w'] > 0)).any())    # (FOA SALSA draws none: no min / max launch)
+        dev = self.features.device
+        staged = host.to(dev, non_blocking=True)
+        x = torch.empty((B, Cn, T, F), dtype=torch.float32, device=dev)
+        sed = torch.empty((B, L, self.n_classes), dtype=torch.float32, device=dev)
+        doa = torch.empty((B, L, 3 * self.n_classes), dtype=torch.float32, device=dev)
+        ws = torch.empty((B, 2), dtype=torch.int32, device=dev) if has_rects else None
+        rec = _lib.BANK_RECIPE[swap if draws is not None else 'none']
+        base = staged.data_ptr()
+        self._bank_call(x, sed, doa, base, base + 8 * B, B, T, L, rec, n_zero or 0, base + 16 * B, base + 176 * B, has_rects, ws)
+        return x, sed, doa, names
+
+    def _bank_call(self, x, sed, doa, p_start, p_gt, B, T, L, rec, n_zero, p_par, p_u, has_rects, ws):
+        import ctypes as C
+        Cn, n_bank, F = self.features.shape
+        dev = self.features.device
+        vp = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)      # noqa: E731
+        labels = sed is not None
+        with torch.cuda.device(dev):
+            rc = _lib.load().salsa_bank_batch(
+                vp(self.features), Cn, n_bank, F, vp(self.sed_all if labels else None), vp(self.doa_all if labels else None),
+                self.sed_all.shape[0], self.n_classes, C.c_void_p(p_start), C.c_void_p(p_gt if labels else None), B, T, L, rec, n_zero,
+                C.c_void_p(p_par), C.c_void_p(p_u), int(has_rects), vp(x), vp(sed), vp(doa), vp(ws),
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc:
+            raise RuntimeError('salsa_bank_batch failed: ' + _lib.last_error())
+
+    def clip_batch(self, lo, hi):
+        """Whole clips lo..hi-1 as one tensor (hi - lo, C, T, F) -- what infer_pipelined's featurize hands the model -- through the
+        same call with the recipe 'none' (CPU bank or SALSA_BANK_BATCH=0: stacked slices).  The clips must be equally long."""
+        assert self.features is not None, 'call finalize() first'
+        if not 0 <= lo < hi <= len(self.clip_start):
+            raise IndexError('clips %d..%d of a bank of %d' % (lo, hi, len(self.clip_start)))
+        T = self.clip_len[lo]
+        if any(n != T for n in self.clip_len[lo:hi]):
+            raise ValueError('clips %d..%d differ in length: %s' % (lo, hi, sorted(set(self.clip_len[lo:hi]))))
+        starts = self.clip_start[lo:hi]
+        if min(starts) < 0 or max(starts) + T > self.features.shape[1]:
+            raise IndexError('a clip window lies outside the bank')
+        if not self._fused():
+            return torch.stack([self.features[:, s:s + T] for s in starts])
+        dev = self.features.device
+        staged = torch.tensor(starts, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        x = torch.empty((hi - lo, self.features.shape[0], T, self.features.shape[2]), dtype=torch.float32, device=dev)
+        self._bank_call(x, None, None, staged.data_ptr(), None, hi - lo, T, max(1, T // self.upsample), _lib.BANK_RECIPE['none'], 0,
+                        None, None, False, None)
+        return x
+
+
+def _mix_seed(*parts):
+    """one 63-bit generator seed from a tuple of small integers (seed, epoch, step, rank): a fixed arithmetic, so any step's draws can
+    be replayed from its coordinates"""
+    h = 0x9E3779B97F4A7C15
+    for p in parts:
+        h = ((h ^ (int(p) & 0xFFFFFFFFFFFFFFFF)) * 0xBF58476D1CE4E5B9 + 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+        h ^= h >> 31
+    return h & 0x7FFFFFFFFFFFFFFF
+
+
+class BankLoader:
+    """The epochs of the reference's ``DataLoader(train_dataset, batch_size, shuffle=True)`` (dataset/datamodule.py) over a finalized
+    GpuFeatureBank, without workers: a seeded permutation per epoch, batches of ``batch_size`` with the short last one kept (the
+    reference has no drop_last), ``train_fraction`` as Lightning's limit_train_batches (experiments/train.py:53), and per step one
+    batch_augmented call with draws from a generator seeded by (seed, epoch, step, rank).  ``rank`` / ``world`` split the permutation
+    as torch's DistributedSampler does: padded by wrapping to a multiple of ``world``, then every world-th index from ``rank``, so all
+    ranks take the same number of steps.  Items: (x, sed, doa, names) plus ``indices`` and ``draws`` when asked for."""
+
+    def __init__(self, bank, batch_size=32, seed=2021, audio_format='foa', feature_type='salsa', augment=True, train_fraction=1.0,
+                 rank=0, world=1, with_indices=False, with_draws=False):
+        if batch_size < 1 or world < 1 or not 0 <= rank < world or not 0.0 <= train_fraction <= 1.0:
+            raise ValueError('BankLoader: bad batch_size, rank / world or train_fraction')
+        if len(bank) == 0:
+            raise ValueError('BankLoader: the bank holds no chunk')
+        self.bank, self.batch_size, self.seed = bank, int(batch_size), int(seed)
+        self.audio_format, self.feature_type, self.augment = audio_format, feature_type, augment
+        self.train_fraction, self.rank, self.world = train_fraction, rank, world
+        self.with_indices, self.with_draws = with_indices, with_draws
+        n_rank = -(-len(bank) // world)
+        self.n_batches = -(-n_rank // self.batch_size)
+        self.steps_per_epoch = int(self.n_batches * train_fraction)
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    def epoch_indices(self, epoch):
+        """the permutation of epoch ``epoch`` (all ranks')"""
+        return torch.randperm(len(self.bank), generator=torch.Generator().manual_seed(self.seed + int(epoch)))
+
+    def rank_indices(self, epoch):
+        """this rank's share of the permutation (world 1: all of it)"""
+        perm = self.epoch_indices(epoch)
+        if self.world == 1:
+            return perm
+        total = -(-len(perm) // self.world) * self.world
+        while len(perm) < total:                                               # (wrap: DistributedSampler's padding)
+            perm = torch.cat([perm, perm[:total - len(perm)]])
+        return perm[self.rank:total:self.world]
+
+    def step_indices(self, epoch, step):
+        return self.rank_indices(epoch)[step * self.batch_size:(step + 1) * self.batch_size]
+
+    def step_draws(self, epoch, step, batch):
+        """the augmentation draws of one step, None with augment=False"""
+        if not self.augment:
+            return None
+        from .augment import draw_augment
+        gen = torch.Generator().manual_seed(_mix_seed(self.seed, epoch, step, self.rank))
+        return draw_augment(batch, self.bank.chunk_len, self.bank.features.shape[2], self.audio_format, gen,
+                            feature_type=self.feature_type)
+
+    def epoch(self, epoch, first_step=0):
+        """the items of one epoch from step ``first_step`` on"""
+        mine = self.rank_indices(epoch)
+        for step in range(first_step, self.steps_per_epoch):
+            idx = mine[step * self.batch_size:(step + 1) * self.batch_size]
+            draws = self.step_draws(epoch, step, len(idx))
+            item = self.bank.batch_augmented(idx, draws, self.audio_format, self.feature_type)
+            if self.with_indices:
+                item = item + (idx,)
+            if self.with_draws:
+                item = item + (draws,)
+            yield item
