@@ -1,5 +1,5 @@
 // bank_batch.h -- per-element arithmetic of the training augmentation, shared by salsa_augment_batch / salsa_augment_gcc_batch
-// (salsa_kernels.hip: a feature batch [B][C][T][F] in, the augmented batch out) and salsa_bank_batch (bank_batch.hip: the same
+// (feature_utils.hip: a feature batch [B][C][T][F] in, the augmented batch out) and salsa_bank_batch (bank_batch.hip: the same
 // result gathered straight from the feature bank [C][bank_frames][F]).  One call = all C channels of one (clip, frame, bin): which
 // cutout rectangle covers it (last rectangle wins), the fill value lo + (hi - lo) * u, the reflect-shifted source bin, the loads,
 // and the swap's sign flips and differences.  The kernels differ only in where a sample's (channel 0, frame 0) lies and how far

@@ -19,8 +19,7 @@
 #include <stdint.h>
 #include "../../include/salsa_hip.h"
 #include "bank_batch.h"
-
-extern "C" void salsa_set_last_error_(const char *msg); // salsa_kernels.hip: the message salsa_last_error() returns
+#include "salsa_internal.h" // salsa_set_last_error_: the message salsa_last_error() returns (salsa_plan.hip)
 
 namespace {
 

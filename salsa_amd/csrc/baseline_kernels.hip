@@ -28,10 +28,9 @@
 #include "../../include/salsa_hip.h"
 #include "../../include/salsa_baseline.h"
 #include "salsa_math.h"
+#include "salsa_internal.h" // salsa_set_last_error_: the message salsa_last_error() returns (salsa_plan.hip)
 
 using salsa::cplx;
-
-extern "C" void salsa_set_last_error_(const char *msg); // salsa_kernels.hip: the message salsa_last_error() returns
 
 namespace {
 

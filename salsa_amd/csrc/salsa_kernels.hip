@@ -1,91 +1,32 @@
-// salsa_kernels.hip -- gfx950 (MI355X, CDNA4) kernels of the SALSA / SALSA-Lite feature extractor + the C ABI
-// declared in include/salsa_hip.h.  Written for wave64 / 160 KiB LDS / HBM3E; no CUDA or multi-backend paths.
+// salsa_kernels.hip -- the three production kernels of the SALSA / SALSA-Lite feature path for gfx950 (MI355X, CDNA4) and their
+// launchers.  Written for wave64 / 160 KiB LDS / HBM3E; no CUDA or multi-backend paths.
 //
-// Pipeline of salsa_extract_batch (full SALSA), all on the caller's stream:
 //   K1 stft_kernel      one wave per packed 512-point complex FFT (two real channels), Stockham radix-8 through LDS;
 //                       unpacks to the 4 channel spectra, writes the log-spectrogram channels 0-3 straight to the
 //                       output and spills the DOA band of the spectra (float32-rounded, like the reference's
 //                       complex64 STFT) to the workspace as Xs[b][t][channel pair][bin] (float4).
+//                       SALSA-Lite / IPD is K1 alone (log-spectrogram + inter-channel phase fused into the unpack).
 //   K2 tracker_kernel   one lane per (clip, bin): 3-frame RMS of channel 0 and the sequential noise-floor tracker
 //                       in float64 -> valid32[b][32-bin group][t] (per-frame indicator mask of the group's bins).
-//   K3 cov_eig_kernel   per tile of 8 frames x 256 bins the gated TF bins are compacted into an LDS work list (an item = two
+//   K3 cov_eig_kernel   per tile of 8 frames x 128 bins the gated TF bins are compacted into an LDS work list (an item = two
 //                       neighbouring frames of one bin, at least one gated in: their 7-frame windows share 6 frames);
 //                       one lane per item: Hermitian covariances accumulated in registers, eigen-gate + principal
 //                       eigenvector (salsa_math.h), FOA / MIC normalisation, writes channels 4-6 (zeros where gated).
-// Further entry points: salsa_eigvec_batch (K2 + K3 on caller-supplied spectra), salsa_logspec_batch (K1 only), the scaler /
-// normalise kernels, the contrib-surface variants (SALSA_FLAG_FLEX; salsa_extract_multichannel for 5 - 8 microphones: K1 over
-// 3 / 4 channel pairs + cov_eig_n_kernel), salsa_to_freq_major, salsa_augment_batch, the pipelined schedules
-// (salsa_plan_set_pipeline).
-// SALSA-Lite / IPD is K1 alone (log-spectrogram + inter-channel phase fused into the unpack).
+//                       gate_doubt_kernel re-decides the bins K3 flags; flex_allpass_kernel is K3's epilogue on the contrib surface.
+// The kernels sit in this unit's anonymous namespace.  The host side -- the plan and the schedules of salsa_extract_batch, in
+// salsa_plan.hip, and the N-microphone path in multichannel.hip -- reaches them through the launchers at the end of the file
+// (declared in salsa_internal.h): launch_stft / launch_k1 / launch_stft_multi, launch_tracker, launch_cov_eig, launch_flex_allpass.
 //
 // Arithmetic types follow the reference (see DESIGN.md "Precision"): STFT evaluated in float64 and rounded to
 // float32, log-spectrogram in float32, tracker / covariance / eigen-solve in float64.
 #include "build_guard.h" // probe switches need -DSALSA_PROBE_BUILD; SALSA_BUILD_FLAGS (generated: tools/gen_build_guard.py)
-#include <hip/hip_runtime.h>
+#include "salsa_internal.h"
 #include <type_traits>
-#include <stdio.h>
-#include <string.h>
-
-#include "../../include/salsa_hip.h"
-#include "salsa_math.h"
-#include "bank_batch.h"
 
 using salsa::cplx;
+using namespace salsa_impl;
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, const char *a = "", long b = 0)
-{
-    snprintf(g_err, sizeof(g_err), fmt, a, b);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            snprintf(g_err, sizeof(g_err), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-            return SALSA_EHIP;                                                                    \
-        }                                                                                         \
-    } while (0)
-
-struct KParams {
-    int B;
-    int N;    // samples per channel (host checks 4*N < 2^31)
-    int T;    // frames (host checks 7*T*F < 2^31 and the per-clip spill < 2^31 elements)
-    int hop;
-    int lower, upper, nd; // DOA band [lower, upper), nd = upper - lower
-    int cutoff;           // lite: spectrogram band [lower, cutoff)
-    int F;                // feature bins per frame
-    int OC;               // output channels (7, or 4 for logspec-only)
-    int ident;            // identity rows of W (192 | 96 | n_fft/2)
-    int spec_lo, spec_hi; // bins [spec_lo, spec_hi) map to spectrogram rows k - spec_lo (1 .. ident+1 for the dataset scripts)
-    int flex;             // contrib/salsa_flexible.py semantics (SALSA_FLAG_FLEX): raw-|X0| tracker, gate without tracking, ...
-    int compress;
-    int layout;
-    int feature;          // SALSA_FEATURE_* ; 3 = logspec only
-    int format;
-    int tracking;
-    int n_hop;
-    int pair_sel;         // K1: -1 = both channel pairs of every frame in one launch; 0 / 1 = only channels {0,1} / {2,3}
-    int nch;              // audio channels per clip (even): 4, or 6 / 8 on the multichannel contrib surface; OC = 2*nch - 1
-    double cond;
-    double inv_cond;      // 1/cond (0 when cond == 0: unused, cond <= 1 short-circuits the gate)
-    double delta;         // 2 pi fs / (n_fft * 343)
-    double snr_ratio;     // indicator_sig = mag > snr_ratio * floor (1.5, :36; contrib: floor_mask_ratio)
-    const float *sc_mean; // optional fused normalise-on-load of the spectrogram channels: [4][F] mean / std, or NULL
-    const float *sc_std;
-    unsigned long long *stats; // optional solver counters (salsa_plan_set_stats), or NULL
-    int force_f64;             // SALSA_FLAG_FORCE_F64: the float64 instantiation of the covariance / eigen kernel
-    unsigned *doubt32;         // [B][32-bin group][T] bit mask of the TF bins whose coherence test the quartic could not decide
-                               // (salsa_math.h SALSA_GATE_DOUBT; decided by gate_doubt_kernel after the launch), or NULL (ungated plans)
-    unsigned *doubt_flag;      // one word per launch group: non-zero once ANY bin was flagged (zeroed by the tracker launch before the
-                               // covariance / eigen launch, or by a memset on the tracker-less gated path): gate_doubt_kernel reads it and exits
-};
-
-constexpr int FEATURE_LOGSPEC_ONLY = 3;
 
 // ------------------------------------------------------------------------------------------------------------ K1
 // STFT + log-spectrogram (+ spill of the DOA band, or the SALSA-Lite phase features).
@@ -117,44 +58,10 @@ template <int N> struct fft_cfg {
     static constexpr int NP = (NS == 512) ? 2 : 3;               // twiddled passes (p = R, R^2, ...)
 };
 
-__device__ __forceinline__ int swz(int e) { return e ^ ((e >> 3) & 7); }
-
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Store policy (round 5, profiles/r5_ab_nt_stores.txt): the 16-byte write-once streams -- K1's spill (K1_SPILL_NT) and K3's rows of
 // channels 4 - 6 (K3_OUT_NT) -- leave as NON-TEMPORAL stores (nothing re-reads them before they leave the L2, and the audio lines
 // consecutive frames share stay cached longer); the 4-byte spectrogram rows stay PLAIN stores: the write-back L2 merges them into
 // full lines, which nt stores forgo (all-nt was measured slower, 0.54 vs 0.49 ms).  The fused kernel's ring / row stores are plain.
-// |x|^2 of a complex64 spectrum value in float32, as ONE explicitly written FMA of an explicitly rounded product.  Written
-// `x.x * x.x + x.y * x.y` the compiler is free to contract it either way round (or not at all), and did so differently in two
-// unrolled instances of the STFT kernel once the code around it changed (session 3: the spectrogram of bins 128 - 191 moved by one
-// ulp against the fused kernel's, which the bit-identity test of the two schedules caught).
-__device__ __forceinline__ float power32(const float2 x)
-{
-    const float t = x.x * x.x;
-    return __builtin_fmaf(x.y, x.y, t);
-}
-// max(a, b) as ONE v_max_f32: fmaxf() first canonicalises its operand (a second v_max_f32 v, v, v per value -- a quieting no-op for
-// anything but a signalling NaN, which no arithmetic here produces); same result, NaN handling included (IEEE maxNum)
-__device__ __forceinline__ float max_raw(float a, float b)
-{
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float db10(float p) { return 3.01029995663981195f * __log2f(max_raw(1e-10f, p)); } // 10*log10(max(1e-10,p))
-
-// Addressing: a wave-uniform base pointer (SGPR pair) + a 32-bit unsigned BYTE offset per lane lets the compiler use the
-// "saddr" form of global loads/stores; `ptr[int_index]` instead costs two or three 64-bit VALU instructions per access
-// (sign extension, shift, 64-bit add), and K1 / K3 are VALU-issue bound.  The host checks that a clip's arrays stay
-// below 4 GiB.
-template <typename V> __device__ __forceinline__ void st_off(V *base, unsigned byte_off, const V v) { *(V *)((char *)base + byte_off) = v; }
-template <typename V> __device__ __forceinline__ V ld_off(const V *base, unsigned byte_off) { return *(const V *)((const char *)base + byte_off); }
 // base + zero-extended lane offset + a COMPILE-TIME byte constant added after the extension: the constant lands in the load's
 // immediate offset field (inside the 32-bit sum it cannot -- the unsigned addition may wrap as far as the compiler knows -- and
 // costs a v_add_u32 per load)
@@ -642,7 +549,6 @@ __global__ __launch_bounds__(256, LITE ? (STD ? K1_LITE_STD_WAVES : N == 1024 ? 
 // ahead of the consumer wave, computing mag[t][bin] into an LDS ring.  Spill layout: Xs[b][t][pair][bin] as float4
 // (c0.re, c0.im, c1.re, c1.im); channel 0 is the .xy of pair 0.  Output: valid32[b][32-bin group][t] = indicator_sig mask
 // of frame t (bit j = bin 32*group + j).
-constexpr int TR_CH = 64;       // frames per chunk
 #ifndef TR_WAVES_N
 #define TR_WAVES_N 8
 #endif
@@ -720,7 +626,6 @@ __device__ __forceinline__ void tracker_mag(const float2 *x, int first, double *
 //  * producers keep TWO register sets of spectra and alternate them (the chunk loop is unrolled by two): the loads issued in
 //    one iteration are first used in the next, a whole chunk later.  (Round 1 copied "next" into "current" at the end of every
 //    iteration, which made each iteration wait for the loads it had just issued.)
-constexpr int TR_BINS = 32;
 #ifndef TR_IDLE4
 #define TR_IDLE4 1
 #endif
@@ -942,23 +847,13 @@ __global__ __launch_bounds__(64 * TR_WAVES) void tracker_kernel(const KParams kp
 // ------------------------------------------------------------------------------------------------------------ K3
 // Covariance + eigen-gate + eigenvector.  Only TF bins that pass the noise gate need the (float64, ~700 instruction)
 // solve, and they are scattered: a wave that owns 64 fixed bins runs the solve if ANY lane is valid.  So each workgroup
-// takes a tile of K3_FT frames x (<=256) bins of one clip, compacts the valid (frame, bin) pairs into an LDS work list
+// takes a tile of K3_FT frames x K3_NT (128) bins of one clip, compacts the valid (frame, bin) pairs into an LDS work list
 // (lane order preserved, so neighbouring lanes still read neighbouring bins), writes zeros for the rest, and then the
 // 256 lanes walk the dense list.  FEAT: write float32 channels 4-6 of the feature array (zeros above the DOA band up
 // to F); otherwise write the float64 (3, n_bins, n_frames) array of extract_normalized_eigenvector (+ gate codes).
-#ifndef K3_FT_N
-#define K3_FT_N 8 // measured 2/4/8/16/32/64: 8 is fastest (tiles in bursts do ~10x the work of quiet ones: small tiles balance)
-#endif
-constexpr int K3_FT = K3_FT_N; // frames per tile; divides TR_CH so a tile's gate words sit in one chunk
 #ifndef K3_GROUP
 #define K3_GROUP 2
 #endif
-#ifndef K3_NT_N
-#define K3_NT_N 128 // threads = bins per workgroup (a multiple of 64: every wave owns one 64-bin group of the tracker's masks).  Measured 256 / 128 / 64:
-                    // cov_eig 0.365 / 0.340 / 0.348 ms, step 1.023 / 1.000 / 1.013 (profiles/r4_ab_notes.txt): the work list of a tile is ~1.5 x 256
-                    // items, so with 256 threads half the waves sat out the second pass at the barrier; two waves share evenly
-#endif
-constexpr int K3_NT = K3_NT_N;
 constexpr int K3_OW = K3_NT + 8; // columns of the LDS output tile: a block's bins + the zero band above them when it fits
 // Tile order.  Workgroups are dealt round-robin to the 8 XCDs (workgroup b runs on XCD b % 8, each with its own L2), so with
 // tile = blockIdx.x two neighbouring 8-frame tiles -- which share 6 of the 14 spill frames they read -- always sit on
@@ -979,13 +874,6 @@ constexpr int K3_OW = K3_NT + 8; // columns of the LDS output tile: a block's bi
 // A frame whose gate margin, pivot or feature conditioning is inside the float32 error bound comes back `unsure` and joins the
 // float64 cold list, which recomputes its covariance in float64 from the spill (~1 % of the gated frames of the bench clips:
 // tools/pk_study.py), so every gate decision the packed solve keeps equals the float64 one.
-#ifndef SALSA_PK
-#define SALSA_PK 1
-#endif
-// The packed solve's gate certificate needs |q'(c)| * (error of c = mu1 / cond) well below SALSA_PK_GATE_TOL: both
-// grow as cond -> 1 (c -> mu1, where q' = prod(mu1 - mu_i)), so plans with cond_num below 2 take the float64 instantiation
-// (the dataset scripts use 5; the goldens 5 and 2).
-#define SALSA_PK_COND_MIN 2.0
 #ifndef K3_STAGE_LDS
 #define K3_STAGE_LDS 0
 #endif
@@ -1409,583 +1297,6 @@ __global__ __launch_bounds__(256) void gate_doubt_kernel(const KParams kp, const
     }
 }
 
-template <bool FEAT>
-static void launch_gate_doubt(const KParams &kp, hipStream_t s, const float4 *Xs, float *out_feat, double *out_eig, unsigned char *gate)
-{
-    if (!kp.doubt32) return;
-    const long nwords = (long)kp.B * ((kp.nd + TR_BINS - 1) / TR_BINS) * kp.T;
-    const unsigned blocks = (unsigned)(nwords < 256L * 64 ? (nwords + 255) / 256 : 64);
-    hipLaunchKernelGGL(gate_doubt_kernel<FEAT>, dim3(blocks ? blocks : 1u), dim3(256), 0, s, kp, Xs, out_feat, out_eig, gate);
-}
-
-template <bool FEAT>
-static void launch_cov_eig(const KParams &kp, dim3 grid, hipStream_t s, const float4 *Xs, const unsigned *valid,
-                           float *out_feat, double *out_eig, unsigned char *gate)
-{
-    const bool gated = kp.tracking || kp.flex; // (!ungated: the coherence test decides, so passing bins have a spectral gap)
-    if (kp.doubt32 && !kp.tracking) (void)hipMemsetAsync(kp.doubt_flag, 0, sizeof(unsigned), s); // (no tracker launch zeroed it: contrib's gate without tracking)
-    // (the packed pair solve: feature output only -- salsa_eigvec_batch keeps float64 results -- and never for contrib's variant)
-    if (FEAT && SALSA_PK && K3_GROUP == 2 && kp.n_hop == 3 && gated && SALSA_COL0 && !kp.flex && kp.cond >= SALSA_PK_COND_MIN && kp.cond < 1e6 && !kp.force_f64)
-        hipLaunchKernelGGL((cov_eig_kernel<FEAT, 3, true, FEAT && K3_GROUP == 2>), grid, dim3(K3_NT), 0, s, kp, Xs, valid, out_feat, out_eig, gate);
-    else if (kp.n_hop == 3 && gated && SALSA_COL0)
-        hipLaunchKernelGGL((cov_eig_kernel<FEAT, 3, true>), grid, dim3(K3_NT), 0, s, kp, Xs, valid, out_feat, out_eig, gate);
-    else if (kp.n_hop == 3)
-        hipLaunchKernelGGL((cov_eig_kernel<FEAT, 3>), grid, dim3(K3_NT), 0, s, kp, Xs, valid, out_feat, out_eig, gate);
-    else
-        hipLaunchKernelGGL((cov_eig_kernel<FEAT, -1>), grid, dim3(K3_NT), 0, s, kp, Xs, valid, out_feat, out_eig, gate);
-    launch_gate_doubt<FEAT>(kp, s, Xs, out_feat, out_eig, gate); // (a no-op unless kp.doubt32: gated plans)
-}
-
-// ------------------------------------------------------------------------------------------------------------ fused K1 + K3
-// Round 5: the STFT spill removed from the path.  One workgroup WALKS a segment of L consecutive frames of one clip in steps of
-// FZ_S = 8 frames: its eight waves FFT the step's eight frames (both channel pairs each, exactly stft_kernel's arithmetic), write the
-// log-spectrogram rows of the segment's own frames to the output as before -- and the DOA band of the spectra NOT to a 0.94-GB
-// spill in HBM but into a ring of FZ_RING = 14 frames in LDS ([frame][pair][bin] float4, the spill's own layout); then the same
-// eight waves compact the gated TF bins of the eight frames whose +-3-frame windows are now complete into a work list and run
-// cov_eig_kernel's packed-float32 pair solve with the sixteen 16-byte gathers of an item answered by LDS instead of L2 / HBM.
-// What is recomputed is the 3-frame halo at either end of a SEGMENT (6 / L of the FFT work: 4 % at L = 152), not of an 8-frame
-// tile.  The tracker's masks come from the separate launch before it.
-//  * A wave's audio for the NEXT step is loaded into registers before the solve phase of this one (the barriers between the
-//    phases order LDS traffic only), so the FFT phase starts on data that has arrived.
-//  * The frames the packed solve hands back to float64 (~0.3 % FOA, ~3 % MIC) are not solved inside the step -- one lane's float64
-//    solve would hold the whole workgroup at the step's barrier, 7 k cycles for 1.8 frames per step -- but written out as records
-//    (the 7-frame window, 240 bytes) into a per-workgroup slice of the workspace and solved together at the end of the segment;
-//    a slice that is full (FZ_COLD_CAP records: never on natural signals) falls back to the in-step cold loop.
-//
-// LDS (dynamic, <= 160 KB; one workgroup per CU): [0, 64 KB) the eight waves' FFT buffers -- reused by the solve phase for the
-// output tile of channels 4-6, the work list and the cold list; then the ring (14 x 2 x nd x 16 B: 85.6 KB at nd = 191), the
-// window, the row-offset table and counters, the optional scaler tables.
-constexpr int FZ_S = 8;
-constexpr int FZ_W = 8;
-constexpr int FZ_NT = 64 * FZ_W;
-constexpr int FZ_RING = FZ_S + 6;
-constexpr int FZ_COLD_CAP = 256;    // deferred float64 records per workgroup
-constexpr unsigned FZ_OFF_OTILE = 0, FZ_OFF_LIST = 24576, FZ_OFF_SLOW = FZ_OFF_LIST + 2048, FZ_OFF_RING = 65536;
-struct fz_cold_rec {
-    float4 x[14];                   // window frame k: x[2k] = channel pair 0, x[2k+1] = pair 1
-    int t, bl, pad0, pad1;
-};
-static size_t fused_lds_bytes(int nd, int F, bool scaler) { return FZ_OFF_RING + (size_t)FZ_RING * 32 * nd + 4096 + 128 + (scaler ? 2 * 4 * (size_t)F * 4 : 0); }
-
-template <bool MIC>
-__global__ __launch_bounds__(FZ_NT, 1) void fused_kernel(const KParams kp, const float *__restrict__ audio,
-                                                        const double *__restrict__ window, const cplx<double> *__restrict__ tw,
-                                                        float *__restrict__ out, const unsigned *__restrict__ valid32, const int L,
-                                                        fz_cold_rec *__restrict__ cold_all, const int cold_cap)
-{
-    constexpr int N = 512, R = 8, NP = 2;
-    using T = double;
-    extern __shared__ __attribute__((aligned(16))) unsigned char fz_lds[];
-    const int nd = kp.nd, F = kp.F, Tn = kp.T, Ns = kp.N;
-    const int OWs = (F + 3) & ~3;                                    // columns of the output tile (the zero band above nd included)
-    const unsigned frame_bytes = 32u * (unsigned)nd, half = 16u * (unsigned)nd;
-    cplx<T> *zall = (cplx<T> *)fz_lds;
-    float *otile = (float *)(fz_lds + FZ_OFF_OTILE);
-    unsigned short *list = (unsigned short *)(fz_lds + FZ_OFF_LIST), *slow = (unsigned short *)(fz_lds + FZ_OFF_SLOW);
-    unsigned char *ringb = fz_lds + FZ_OFF_RING;
-    T *wins = (T *)(ringb + (size_t)FZ_RING * frame_bytes);
-    unsigned *rowoff = (unsigned *)(wins + N);                       // [14] + counters (never aliased by the FFT buffers)
-    int *count = (int *)(rowoff + 16), *nslow = count + 1, *ncold = count + 2;
-    float *sct0 = (float *)(rowoff + 32), *sct1 = sct0 + 4 * F;
-
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int b = blockIdx.y;
-    const int f0 = blockIdx.x * L, f1 = f0 + L < Tn ? f0 + L : Tn;   // own frames [f0, f1)
-    fz_cold_rec *cold = cold_all + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * FZ_COLD_CAP;
-    for (int i = tid; i < N; i += FZ_NT) wins[i] = (T)(0.5 * window[i]);
-    if (kp.sc_mean)
-        for (int i = tid; i < 4 * F; i += FZ_NT) sct0[i] = kp.sc_mean[i], sct1[i] = kp.sc_std[i];
-    if (tid == 0) *count = 0, *nslow = 0, *ncold = 0;
-    cplx<T> w1[NP];
-    {
-        int p = R;
-#pragma unroll
-        for (int q = 0; q < NP; q++, p *= R) {
-            const cplx<double> wd = tw[salsa::stockham_tw(lane, 1, p, N, R)];
-            w1[q] = {(T)wd.re, (T)wd.im};
-        }
-    }
-    __syncthreads();
-    cplx<T> *z = zall + w * N;
-    float *pw = (float *)z;                                          // the compressed band's powers: in the wave's FFT buffer, free after the last pass
-    const float *clip = audio + (long)b * 4 * Ns;
-    const bool planar = kp.layout == SALSA_LAYOUT_PLANAR;
-    const int sstride = planar ? 1 : 4;
-    float *o = out + (long)b * kp.OC * Tn * F;
-    const int mlane = (64 - lane) & 63;
-    const unsigned plane = 4u * (unsigned)(Tn * F);
-    auto spec = [&](const float p, const int c, const int f) -> float {
-        const float v = db10(p);
-        const int i = c * F + f;
-        return kp.sc_mean ? (v - sct0[i]) / sct1[i] : v;
-    };
-    auto wrap_frame = [&](const int vf) { // np.pad(..., 'wrap') on the time axis (:43): the halo of the clip's first / last segment
-        int t = vf;
-        t = t < 0 ? t + Tn : t;
-        return t >= Tn ? t - Tn : t;
-    };
-    // the 2 x 2 x 8 samples a lane contributes to the two packed FFTs of one frame
-    auto load_frame = [&](const int vf, float (&y)[2][2][R]) {
-        const int t = wrap_frame(vf);
-        const int base = t * kp.hop - N / 2;
-        const unsigned step = 4u * (unsigned)sstride;
-#pragma unroll
-        for (int pr = 0; pr < 2; pr++) {
-            const int c0 = 2 * pr;
-            const unsigned ch0 = 4u * (unsigned)(planar ? c0 * Ns : c0), ch1 = ch0 + 4u * (unsigned)(planar ? Ns : 1);
-#ifdef FZ_PROBE_NOLOAD
-            if (true) {
-#pragma unroll
-                for (int r = 0; r < R; r++) y[pr][0][r] = (float)(lane + r + t) * 1e-3f, y[pr][1][r] = (float)(lane - r + c0) * 1e-3f;
-            } else
-#endif
-            if (base >= 0 && base + N <= Ns) {
-                const unsigned q = (unsigned)(base + lane) * step;
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    y[pr][0][r] = ld_off(clip, ch0 + q + (unsigned)(r * (N / R)) * step);
-                    y[pr][1][r] = ld_off(clip, ch1 + q + (unsigned)(r * (N / R)) * step);
-                }
-            } else { // a frame that overlaps a clip end: np.pad(mode='reflect')
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    int sidx = base + salsa::stockham_in(lane, r, N, R);
-                    sidx = sidx < 0 ? -sidx : sidx;
-                    sidx = sidx >= Ns ? 2 * (Ns - 1) - sidx : sidx;
-                    y[pr][0][r] = ld_off(clip, ch0 + (unsigned)sidx * step);
-                    y[pr][1][r] = ld_off(clip, ch1 + (unsigned)sidx * step);
-                }
-            }
-        }
-    };
-    // one frame: both channel pairs (stft_kernel's item, twice)
-    auto fft_frame = [&](const int vf, const float (&y)[2][2][R]) {
-        const int t = wrap_frame(vf);
-        const bool own = vf >= f0 && vf < f1;
-        const int sl = (vf - (f0 - 3)) % FZ_RING;
-        float4 *slot = (float4 *)(ringb + (unsigned)sl * frame_bytes);
-#pragma unroll 1
-        for (int pr = 0; pr < 2; pr++) { // (rolled: unrolled, the two transforms' live ranges overlap and spill)
-            const int c0 = 2 * pr;
-            cplx<T> v[R];
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const T wn = wins[salsa::stockham_in(lane, r, N, R)];
-                const float ya = pr ? y[1][0][r] : y[0][0][r], yb = pr ? y[1][1][r] : y[0][1][r]; // (wave-uniform selects)
-                v[r] = {wn * (T)ya, wn * (T)yb};
-            }
-            salsa::dftR<R>(v);
-#pragma unroll
-            for (int r = 0; r < R; r++) z[swz(salsa::stockham_out(lane, r, 1, R))] = v[r];
-            {
-                int p = R;
-#pragma unroll
-                for (int q = 0; q < NP; q++, p *= R) {
-                    wave_lds_fence();
-#pragma unroll
-                    for (int r = 0; r < R; r++) v[r] = z[swz(salsa::stockham_in(lane, r, N, R))];
-                    wave_lds_fence();
-                    {
-                        const cplx<T> a1 = w1[q], a2 = salsa::cmul(a1, a1), a3 = salsa::cmul(a2, a1), a4 = salsa::cmul(a2, a2);
-                        v[1] = salsa::cmul(v[1], a1);
-                        v[2] = salsa::cmul(v[2], a2);
-                        v[3] = salsa::cmul(v[3], a3);
-                        v[4] = salsa::cmul(v[4], a4);
-                        v[5] = salsa::cmul(v[5], salsa::cmul(a4, a1));
-                        v[6] = salsa::cmul(v[6], salsa::cmul(a3, a3));
-                        v[7] = salsa::cmul(v[7], salsa::cmul(a4, a3));
-                    }
-                    salsa::dftR<R>(v);
-                    if (q + 1 < NP) {
-#pragma unroll
-                        for (int r = 0; r < R; r++) z[swz(salsa::stockham_out(lane, r, p, R))] = v[r];
-                    }
-                }
-            }
-            auto emit_bin = [&](const int k, const cplx<T> a, const cplx<T> bm) {
-                cplx<T> Xa, Xb;
-                salsa::unpack_pair_prescaled(a, bm, Xa, Xb);
-                const float2 xa = make_float2((float)Xa.re, (float)Xa.im); // the reference stores its STFT as complex64
-                const float2 xb = make_float2((float)Xb.re, (float)Xb.im);
-                if (k >= kp.lower && k < kp.upper) slot[pr * nd + (k - kp.lower)] = make_float4(xa.x, xa.y, xb.x, xb.y);
-                if (own) {
-                    const float pa = power32(xa), pb = power32(xb);
-                    if (k >= kp.spec_lo && k < kp.spec_hi) {
-                        const unsigned off = 4u * (unsigned)((c0 * Tn + t) * F + (k - kp.spec_lo));
-                        st_off(o, off, spec(pa, c0, k - kp.spec_lo));
-                        st_off(o, off + plane, spec(pb, c0 + 1, k - kp.spec_lo));
-                    } else if (kp.compress && k > kp.ident && k < N / 2) {
-                        pw[k - kp.ident - 1] = pa;
-                        pw[64 + k - kp.ident - 1] = pb;
-                    }
-                }
-            };
-#pragma unroll
-            for (int r = 0; r < R / 2; r++) {
-                cplx<T> bm = {__shfl(v[R - 1 - r].re, mlane), __shfl(v[R - 1 - r].im, mlane)};
-                if (lane == 0) bm = v[(R - r) & (R - 1)];
-                emit_bin(lane + 64 * r, v[r], bm);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // (the Nyquist bin belongs to no spectrogram row and no DOA band of the default configuration: a wave-uniform skip)
-            if ((kp.spec_hi > N / 2 || kp.upper > N / 2) && lane == 0) emit_bin(N / 2, v[R / 2], v[R / 2]);
-            if (own && kp.compress) {
-                wave_lds_fence();
-                const int ng = F - kp.ident;
-                const int h = lane & 1, gi = lane >> 1;
-                if (gi < ng) {
-                    const int cnt = gi < ng - 1 ? 8 : 7;
-                    float acc = 0.f;
-                    for (int q = 0; q < cnt; q++) acc += 0.125f * pw[64 * h + 8 * gi + q];
-                    st_off(o, 4u * (unsigned)(((c0 + h) * Tn + t) * F + kp.ident + gi), spec(acc, c0 + h, kp.ident + gi));
-                }
-            }
-            wave_lds_fence();
-        }
-    };
-    auto lds_barrier = [&]() { // orders LDS traffic only: global loads / stores stay in flight across it
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    // float64 covariance of one 7-frame window + the general solve (cov_eig_kernel's cold path); e[] = the feature or zeros
-    auto cold_solve = [&](auto getx, const int bl, double *e) -> bool { // getx(k, a, c): the two float4 of window frame k
-        salsa::herm4<double> Rm = {};
-#pragma unroll 1
-        for (int k = 0; k < 7; k++) {
-            float4 a, c;
-            getx(k, a, c);
-            const cplx<double> x[4] = {{(double)a.x, (double)a.y}, {(double)a.z, (double)a.w},
-                                       {(double)c.x, (double)c.y}, {(double)c.z, (double)c.w}};
-            salsa::herm4_rank1_add(Rm, x);
-        }
-        salsa::eig_result<double> er = salsa::herm4_gate_eigvec<2>(Rm, kp.cond, kp.inv_cond, false, MIC);
-        if (er.doubt) { // the threshold sits ON a root of the quartic (salsa_math.h SALSA_GATE_DOUBT): decided on the matrix, in place --
-                        // the three-kernel path's gate_doubt_kernel reads the spill, which this kernel's records have overwritten
-            const bool r1 = salsa::herm4_rank1_by_jacobi(Rm, kp.cond);
-            if (r1) er = salsa::herm4_gate_eigvec<2>(Rm, kp.cond, kp.inv_cond, true, MIC);
-            er.rank1 = r1;
-        }
-        if (!er.rank1) return false;
-        if (MIC) salsa::normalise_mic(er.u, kp.delta * (double)(bl + kp.lower), e);
-        else salsa::normalise_foa(er.u, e, false);
-        return true;
-    };
-
-    float y[2][2][R];
-    // prologue: the six frames around the segment's first step that no step produces (v = f0-3 .. f0+2)
-#ifndef FZ_PROBE_NOFFT
-    if (w < 6) {
-        load_frame(f0 - 3 + w, y);
-        fft_frame(f0 - 3 + w, y);
-    }
-    if (f0 + 3 + w < f1 + 3) load_frame(f0 + 3 + w, y);
-#endif
-    const int ng32 = (nd + TR_BINS - 1) / TR_BINS, ng64 = (nd + 63) >> 6;
-    float *of = out + ((long)b * kp.OC + 4) * Tn * F;                 // channels 4-6 of this clip, [3][T][F]
-    const float fcond = (float)kp.cond, finv = (float)kp.inv_cond;
-    for (int fs0 = f0; fs0 < f1; fs0 += FZ_S) {
-        const int nft = f1 - fs0 < FZ_S ? f1 - fs0 : FZ_S;
-        // the tracker's masks of this step's frames (two 32-bin groups x 8 frames per wave of the compaction): issued before the
-        // FFTs, first used after them
-        unsigned myw = 0u;
-        if (w < ng64 && lane < 2 * FZ_S) {
-            const int ft = lane % FZ_S, hf = lane / FZ_S;
-            if (ft < nft && 2 * w + hf < ng32) myw = valid32[((long)b * ng32 + 2 * w + hf) * Tn + fs0 + ft];
-        }
-        // ---- FFT phase: frames fs0+3 .. fs0+10 (as far as the segment's window reaches), then the next step's audio on its way
-#ifndef FZ_PROBE_NOFFT
-        {
-            const int vf = fs0 + 3 + w;
-            if (vf < f1 + 3) fft_frame(vf, y);
-            if (fs0 + FZ_S < f1 && vf + FZ_S < f1 + 3) load_frame(vf + FZ_S, y);
-        }
-#endif
-        lds_barrier(); // B1: the ring holds fs0-3 .. fs0+10; the FFT buffers are free
-#ifdef FZ_PROBE_NOSOLVE
-        if (myw == 0xdeadbeefu) otile[tid] = 1.f;
-        continue;
-#endif
-        // ---- output tile zeroed, row offsets, compaction of the gated TF bins (waves 0 .. ng64-1: one 64-bin group each)
-        for (int i = tid; i < 3 * FZ_S * OWs / 4; i += FZ_NT) ((float4 *)otile)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tid < FZ_RING) rowoff[tid] = (unsigned)((fs0 - f0 + tid) % FZ_RING) * frame_bytes;
-        if (w < ng64) {
-            const int bl = tid;
-            const bool in = bl < nd;
-            const unsigned long long inmask = __ballot(in);
-            unsigned long long words[FZ_S];
-            int total = 0;
-#pragma unroll
-            for (int ft = 0; ft < FZ_S; ft++) {
-                const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)myw, ft), hi = (unsigned)__builtin_amdgcn_readlane((int)myw, FZ_S + ft);
-                words[ft] = (((unsigned long long)hi << 32) | lo) & inmask;
-            }
-#pragma unroll
-            for (int ft = 0; ft < FZ_S; ft += 2) total += __popcll(words[ft] | words[ft + 1]);
-            int base = 0;
-            if (lane == 0 && total) base = atomicAdd(count, total);
-            base = __builtin_amdgcn_readfirstlane(base);
-#pragma unroll
-            for (int ft = 0; ft < FZ_S; ft += 2) {
-                const unsigned long long wd = words[ft] | words[ft + 1];
-                if (in) {
-                    const unsigned v = ((unsigned)(words[ft] >> lane) & 1u) | (((unsigned)(words[ft + 1] >> lane) & 1u) << 1);
-                    if (v) list[base + __popcll(wd & ((1ull << lane) - 1))] = (unsigned short)((v << 12) | ((ft / 2) << 8) | bl);
-                }
-                base += __popcll(wd);
-            }
-        }
-        lds_barrier(); // B2
-        const int n = *count;
-        // ---- hot loop: the packed-float32 pair solve of cov_eig_kernel<true, 3, true, true>, windows read from the ring
-        for (int s = tid; s < n; s += FZ_NT) {
-            const int i = list[s];
-            const int ft = 2 * ((i >> 8) & 15), bl = i & 255;
-            constexpr int NW = 8;
-            const unsigned *ro = rowoff + ft;
-            const unsigned boff = 16u * (unsigned)bl;
-            float4 xa[NW], xc[NW];
-#pragma unroll
-            for (int k = 0; k < NW; k++) {
-                const unsigned r = ro[k];
-                xa[k] = *(const float4 *)(ringb + r + boff);
-                xc[k] = *(const float4 *)(ringb + r + boff + half);
-            }
-            auto chans = [&](int k, salsa::pk2f *v) {
-                v[0] = salsa::pk2f{xa[k].x, xa[k].y};
-                v[1] = salsa::pk2f{xa[k].z, xa[k].w};
-                v[2] = salsa::pk2f{xc[k].x, xc[k].y};
-                v[3] = salsa::pk2f{xc[k].z, xc[k].w};
-            };
-            salsa::cov4pk Cc = {}, C0, C1;
-            salsa::pk2f v[4];
-#pragma unroll
-            for (int k = 1; k <= 6; k++) {
-                chans(k, v);
-                salsa::cov4pk_rank1(Cc, Cc, v);
-            }
-            chans(0, v);
-            salsa::cov4pk_rank1(C0, Cc, v);
-            chans(7, v);
-            salsa::cov4pk_rank1(C1, Cc, v);
-            const int live = (i >> 12) & 3;
-            int odd;
-            const salsa::herm4<salsa::pk2f> A = salsa::herm4_pk_from_windows(C0, C1, odd);
-            salsa::pk2f e[3];
-            salsa::pk_eig r = salsa::herm4_gate_eigvec_pk<MIC>(A, fcond, finv, live & ~odd);
-            if (r.pass) {
-                if (MIC) salsa::normalise_mic_pk(r, (float)(kp.delta * (double)(bl + kp.lower)), e);
-                else salsa::normalise_foa_pk(r, e);
-            }
-            r.unsure |= odd & live;
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                if ((r.unsure >> j) & 1) { // float64 decides: a record for the end of the segment (or, slice full, the in-step cold list)
-                    const int ci = atomicAdd(ncold, 1);
-                    if (ci < cold_cap) {
-                        fz_cold_rec *rec = cold + ci;
-#pragma unroll
-                        for (int k = 0; k < 7; k++) {
-                            const unsigned rr = ro[j + k];
-                            rec->x[2 * k] = *(const float4 *)(ringb + rr + boff);
-                            rec->x[2 * k + 1] = *(const float4 *)(ringb + rr + boff + half);
-                        }
-                        rec->t = fs0 + ft + j;
-                        rec->bl = bl;
-                    } else slow[atomicAdd(nslow, 1)] = (unsigned short)(((ft + j) << 8) | bl);
-                } else if ((r.pass >> j) & 1) {
-#pragma unroll
-                    for (int q = 0; q < 3; q++) otile[(q * FZ_S + ft + j) * OWs + bl] = e[q][j];
-                }
-            }
-        }
-        lds_barrier(); // B3
-        const int ns = *nslow;
-        if (kp.stats && tid == 0) {
-            int lv = 0;
-            for (int s = 0; s < n; s++) lv += __popc((list[s] >> 12) & 3);
-            atomicAdd(&kp.stats[0], (unsigned long long)n);
-            atomicAdd(&kp.stats[1], (unsigned long long)lv);
-            atomicAdd(&kp.stats[3], 1ull);
-        }
-        if (ns) { // (wave-uniform; only when the record slice overflowed) the in-step cold loop
-            for (int s = tid; s < ns; s += FZ_NT) {
-                const int i = slow[s];
-                const int ft = i >> 8, bl = i & 255;
-                double e[3] = {0.0, 0.0, 0.0};
-                if (cold_solve([&](int k, float4 &a, float4 &c) {
-                        const unsigned rr = rowoff[ft + k] + 16u * (unsigned)bl;
-                        a = *(const float4 *)(ringb + rr);
-                        c = *(const float4 *)(ringb + rr + half);
-                    }, bl, e)) {
-#pragma unroll
-                    for (int q = 0; q < 3; q++) otile[(q * FZ_S + ft) * OWs + bl] = (float)e[q];
-                }
-            }
-            lds_barrier(); // B4
-        }
-        // ---- channels 4-6 of the step's frames: whole rows (the zeros above the DOA band included, :373-374)
-        if (tid == 0) *count = 0, *nslow = 0;
-        if (!(F & 3)) {
-            const int q = F >> 2;
-            for (int i = tid; i < 3 * nft * q; i += FZ_NT) {
-                const int row = i / q, col = i - row * q, c = row / nft, ft = row - c * nft;
-                *(float4 *)(of + ((long)(c * Tn + fs0 + ft) * F + 4 * col)) = *(const float4 *)(otile + (c * FZ_S + ft) * OWs + 4 * col);
-            }
-        } else {
-            for (int i = tid; i < 3 * nft * F; i += FZ_NT) {
-                const int row = i / F, col = i - row * F, c = row / nft, ft = row - c * nft;
-                of[(long)(c * Tn + fs0 + ft) * F + col] = otile[(c * FZ_S + ft) * OWs + col];
-            }
-        }
-        lds_barrier(); // B5: the tile has been read; the next step's FFTs may overwrite it (and the ring's oldest frames)
-    }
-    // ---- the segment's deferred float64 frames: their rows (zeros there) were stored above by this workgroup; __syncthreads()
-    // waits for those stores and for the records, then the passing frames' three values go straight to the output
-    __syncthreads();
-    const int nc = *ncold < cold_cap ? *ncold : cold_cap;
-    if (kp.stats && tid == 0) atomicAdd(&kp.stats[2], (unsigned long long)*ncold);
-#ifndef FZ_PROBE_NOCOLD
-    for (int s = tid; s < nc; s += FZ_NT) {
-        const fz_cold_rec *rec = cold + s;
-        const int t = rec->t, bl = rec->bl;
-        double e[3] = {0.0, 0.0, 0.0};
-        if (cold_solve([&](int k, float4 &a, float4 &c) { a = rec->x[2 * k]; c = rec->x[2 * k + 1]; }, bl, e)) {
-#pragma unroll
-            for (int q = 0; q < 3; q++) of[(long)(q * Tn + t) * F + bl] = (float)e[q];
-        }
-    }
-#endif
-}
-
-// ------------------------------------------------------------------------------------------------------------ K3, N channels
-// contrib/salsa_flexible.py takes ANY number of microphones (stacked_covmat_eigh :52-77: an N x N Hermitian eigenproblem per
-// gated TF bin).  The 4 x 4 closed form above does not generalise, so 5 - 8 microphones (padded to an even count NCH = 6 | 8
-// with a silent channel, which only adds a zero eigenvalue) take this kernel: one lane per (frame, bin), summed covariance of
-// the 2*n_hop+1 frames in float64, cyclic complex Jacobi with the rotations accumulated (eigenvalues = the diagonal, eigen-
-// vectors = the accumulated columns), gate "largest > second largest * ew_thresh" (:353), feature angle(conj(u_0) u_c) / f
-// (:360-362).  A completeness path, not a tuned one: the 2 x NCH^2 float64 matrices spill to scratch.
-// NCH > 0: compile-time size, fully unrolled (6 | 8).  NCH == 0: any even count up to HERMN_MAX = 16 read from kp.nch -- the same code
-// with run-time loop bounds and dynamically indexed scratch arrays (9 - 16 microphones: slower still, and as rare).
-// The solver itself (hermn, hermn_rotate, hermn_gate_eigvec) is in salsa_math.h, where the host emulation reaches it.
-using salsa::hermn;
-static_assert(salsa::HERMN_MAX == SALSA_MAX_MICS, "the run-time-sized solver holds SALSA_MAX_MICS channels");
-
-template <int NCH>
-__global__ __launch_bounds__(64) void cov_eig_n_kernel(const KParams kp, const float4 *__restrict__ Xs,
-                                                       const unsigned *__restrict__ valid32, float *__restrict__ out)
-{
-    constexpr int S = hermn<NCH>::S;
-    const int n = NCH > 0 ? NCH : kp.nch, NP = n / 2;
-    const int t = blockIdx.x, b = blockIdx.y, Tn = kp.T;
-    const int ng32 = (kp.nd + TR_BINS - 1) / TR_BINS;
-    float *of = out + ((long)b * kp.OC + n) * Tn * kp.F + (long)t * kp.F; // first spatial plane, this frame's row
-    const long plane = (long)Tn * kp.F;
-    const float4 *xclip = Xs + (long)b * Tn * NP * kp.nd;
-    for (int bin = threadIdx.x; bin < kp.F; bin += 64) {
-        float e[S - 1];
-#pragma unroll
-        for (int c = 0; c < S - 1; c++) e[c] = 0.f;
-        bool gated = bin < kp.nd;
-        if (gated && kp.tracking) gated = (valid32[((long)b * ng32 + (bin >> 5)) * Tn + t] >> (bin & 31)) & 1u;
-        if (gated) {
-            hermn<NCH> A, V;
-#pragma unroll
-            for (int i = 0; i < n; i++)
-#pragma unroll
-                for (int j = 0; j < n; j++) {
-                    A.ar[i][j] = A.ai[i][j] = 0.0;
-                    V.ar[i][j] = i == j ? 1.0 : 0.0;
-                    V.ai[i][j] = 0.0;
-                }
-            for (int k = -kp.n_hop; k <= kp.n_hop; k++) { // summed covariance, wrap on the time axis (:316-318, :347-349)
-                int tt = t + k;
-                while (tt < 0) tt += Tn;
-                while (tt >= Tn) tt -= Tn;
-                double xr[S], xi[S];
-#pragma unroll
-                for (int pr = 0; pr < NP; pr++) {
-                    const float4 v = xclip[((long)tt * NP + pr) * kp.nd + bin];
-                    xr[2 * pr] = v.x; xi[2 * pr] = v.y; xr[2 * pr + 1] = v.z; xi[2 * pr + 1] = v.w;
-                }
-#pragma unroll
-                for (int i = 0; i < n; i++)
-#pragma unroll
-                    for (int j = 0; j < n; j++) { // x_i conj(x_j)
-                        A.ar[i][j] += xr[i] * xr[j] + xi[i] * xi[j];
-                        A.ai[i][j] += xi[i] * xr[j] - xr[i] * xi[j];
-                    }
-            }
-            double ur[S], ui[S];
-            int sweeps;
-            const bool good = salsa::hermn_gate_eigvec<NCH>(A, V, n, kp.cond, ur, ui, sweeps);
-            if (good) {
-                const int kb = bin + kp.lower;
-                const double den = (double)((float)(kb == 0 ? 1 : kb) * (float)kp.delta); // float32 norm_freq (:188-190)
-#pragma unroll
-                for (int c = 1; c < n; c++) { // angle(conj(u_0) u_c) / f   (:360-362)
-                    const double wr = ur[0] * ur[c] + ui[0] * ui[c], wi = ur[0] * ui[c] - ui[0] * ur[c];
-                    e[c - 1] = (float)(atan2(wi, wr) / den);
-                }
-            }
-            if (!good && !kp.tracking) e[0] = __builtin_nanf(""); // marks "failed the test" for flex_allpass_kernel
-        }
-#pragma unroll
-        for (int c = 0; c < n - 1; c++) of[c * plane + bin] = e[c];
-    }
-}
-
-// reference layout (n_bins, n_frames, 4) complex64 -> internal Xs[b][t][pair][bin] float4
-__global__ void relayout_kernel(const float4 *__restrict__ X, float4 *__restrict__ Xs, int B, int nb, int Tn)
-{
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long total = (long)B * nb * Tn * 2;
-    if (idx >= total) return;
-    const int bin = (int)(idx % nb);
-    long r = idx / nb;
-    const int pr = (int)(r % 2);
-    r /= 2;
-    const int t = (int)(r % Tn);
-    const int b = (int)(r / Tn);
-    Xs[idx] = X[(((long)b * nb + bin) * Tn + t) * 2 + pr];
-}
-
-// ------------------------------------------------------------------------------------------------------------ scaler
-// compute_scaler (:204-262) on device: float64 sum and sum of squares over time of the first n_sc channels, per
-// frequency.  One block per (clip, channel, tile of 64 frames); lane = frequency (coalesced rows; frequencies beyond 256 in further
-// trips); one float64 atomic pair per frequency per block.  sums: [2][n_sc][F] (sum, sumsq), accumulated into (caller zeroes it once).
-__global__ __launch_bounds__(256) void scaler_accumulate_kernel(const float *__restrict__ feat, int C, int T, int F,
-                                                                int n_sc, double *__restrict__ sums)
-{
-    const int c = blockIdx.y, b = blockIdx.z;
-    const int t0 = blockIdx.x * 64, t1 = t0 + 64 < T ? t0 + 64 : T;
-    for (int f = threadIdx.x; f < F; f += 256) { // (one trip while F <= 256; SALSA-Lite at n_fft 1024 has F = 382)
-        const float *p = feat + (((long)b * C + c) * T) * F + f;
-        double s = 0.0, ss = 0.0;
-        for (int t = t0; t < t1; t++) {
-            const double v = (double)p[(long)t * F];
-            s += v;
-            ss += v * v;
-        }
-        atomicAdd(&sums[(long)c * F + f], s);
-        atomicAdd(&sums[((long)n_sc + c) * F + f], ss);
-    }
-}
-
-// normalise-on-load (dataset/database.py:197-202): feature[:n_sc] = (feature[:n_sc] - mean) / std, in place;
-// mean/std: [n_sc][F] float32.  Channels >= n_sc (the spatial channels) are left untouched.
-__global__ __launch_bounds__(256) void normalize_kernel(float *__restrict__ feat, long rows, int C, int T, int F, int n_sc,
-                                                        const float *__restrict__ mean, const float *__restrict__ std)
-{
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6); // one wave per (b, c, t) row of F floats
-    if (row >= rows) return;
-    const int t = (int)(row % T);
-    const int c = (int)((row / T) % n_sc);
-    const long b = row / ((long)T * n_sc);
-    float *p = feat + ((b * C + c) * T + t) * F;
-    for (int f = threadIdx.x & 63; f < F; f += 64) p[f] = (p[f] - mean[c * F + f]) / std[c * F + f];
-}
-
 // contrib/salsa_flexible.py with is_tracking=False: ONE all-pass mask array is created (:336-337) and then narrowed in
 // place by "mask[mask] = good_coherence_mask" (:354), so a bin that fails the coherence test once is never looked at
 // again in that clip.  cov_eig_kernel marks failures with NaN in channel 4; this pass (lane = bin, coalesced rows,
@@ -2005,530 +1316,52 @@ __global__ __launch_bounds__(256) void flex_allpass_kernel(const KParams kp, flo
     }
 }
 
-// [rows][T][F] float32 (time-major, what the extract kernels write) -> [rows][F][T] float64 (the freq-major float64
-// array contrib/salsa_flexible.py returns, :264).  64 x 64 tiles through LDS (+1 padding), both sides coalesced.
-__global__ __launch_bounds__(256) void to_freq_major_kernel(const float *__restrict__ in, double *__restrict__ out, int T, int F)
-{
-    __shared__ float tile[64][65];
-    const long row = blockIdx.z;
-    const int t0 = blockIdx.y * 64, f0 = blockIdx.x * 64;
-    const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
-    const float *src = in + row * (long)T * F;
-    double *dst = out + row * (long)T * F;
-    for (int i = ly; i < 64; i += 4)
-        if (t0 + i < T && f0 + lx < F) tile[i][lx] = src[(long)(t0 + i) * F + f0 + lx];
-    __syncthreads();
-    for (int i = ly; i < 64; i += 4)
-        if (f0 + i < F && t0 + lx < T) dst[(long)(f0 + i) * T + t0 + lx] = (double)tile[lx][i];
-}
-
-// ------------------------------------------------------------------------------------------------------------- resampling
-// The resampling step of the reference's loader: librosa.load(path, sr=fs) (salsa_feature_extraction.py:353, lite :93) on a
-// file of another native rate calls librosa 0.8.0 core/audio.py::resample -> resampy 0.2.2 (requirements.yml:181)
-// resample(x, sr_orig, sr_new, filter='kaiser_best'): a windowed-sinc interpolator whose inner loop (resampy/interpn.py
-// ::resample_f, numba) walks the filter's left wing from sample n = int(time_register) downwards and its right wing from
-// n + 1 upwards, with the filter linearly interpolated between table entries and the float32 output element updated in
-// place -- i.e. every tap is `y = float32(float64(y) + weight * float64(x))`, left wing first.  One thread per output
-// sample does exactly that sequence (no FMA contraction), so the result is the sequential loop's bit for bit.  The
-// filter table, its first differences and the time registers (a sequential float64 accumulation in the reference) are
-// the caller's: salsa_amd/resample.py builds them once per (rate pair, length).  Bandwidth is irrelevant here (n_out x
-// ~2 * 64 / scale taps from L2-resident tables): it is a loader step, not the hot path.
-__global__ __launch_bounds__(256) void resample_kernel(const float *__restrict__ x, float *__restrict__ y, long n_in, long n_out,
-                                                       long n_fix, const double *__restrict__ win, const double *__restrict__ delta,
-                                                       int nwin, int num_table, double scale, int index_step,
-                                                       const double *__restrict__ treg)
-{
-#pragma clang fp contract(off)
-    const long t = blockIdx.x * 256L + threadIdx.x;
-    if (t >= n_fix) return;
-    const long row = blockIdx.y;
-    const float *xr = x + row * n_in;
-    float acc = 0.f;                                     // (t >= n_out: librosa's fix_length pads with zeros)
-    if (t < n_out) {
-        const double tr = treg[t];
-        const long n = (long)tr;
-        double frac = scale * (tr - (double)n);
-        double index_frac = frac * (double)num_table;
-        int offset = (int)index_frac;
-        double eta = index_frac - (double)offset;
-        long m = (nwin - offset) / index_step;
-        const long i_max = n + 1 < m ? n + 1 : m;
-        for (long i = 0; i < i_max; i++) {
-            const long idx = offset + i * index_step;
-            const double w = win[idx] + eta * delta[idx];
-            acc = (float)((double)acc + w * (double)xr[n - i]);
-        }
-        frac = scale - frac;
-        index_frac = frac * (double)num_table;
-        offset = (int)index_frac;
-        eta = index_frac - (double)offset;
-        m = (nwin - offset) / index_step;
-        const long k_max = n_in - n - 1 < m ? n_in - n - 1 : m;
-        for (long k = 0; k < k_max; k++) {
-            const long idx = offset + k * index_step;
-            const double w = win[idx] + eta * delta[idx];
-            acc = (float)((double)acc + w * (double)xr[n + k + 1]);
-        }
-    }
-    y[row * n_fix + t] = acc;
-}
-
-// ---------------------------------------------------------------------------------------------------------- PCM -> planar float32
-// What librosa.load(path, sr=fs, mono=False, dtype=np.float32) (salsa_feature_extraction.py:353) does to a WAV file's samples before
-// anything else: soundfile reads the interleaved PCM frames as float32 (libsndfile's normalisation: int16 / 2^15, int32 / 2^31,
-// uint8 (x - 128) / 2^7, float32 as is -- all exact in float32 up to the one rounding of a 32-bit integer) and librosa transposes to
-// (channels, samples).  The file pipeline uploads the file's data chunk as it is (half the PCIe bytes for 16-bit clips, no host
-// arithmetic) and this kernel converts + de-interleaves: one thread per frame, one vector load of the frame's samples, one
-// coalesced 4-byte store per channel plane.
-template <typename S, int NCH> __device__ __forceinline__ void pcm_frame(const void *pcm, long n, float *v)
-{
-    struct alignas(sizeof(S) * NCH) vec { S x[NCH]; };
-    const vec f = ((const vec *)pcm)[n];
-#pragma unroll
-    for (int c = 0; c < NCH; c++) {
-        if constexpr (sizeof(S) == 2) v[c] = (float)f.x[c] * (1.0f / 32768.0f);
-        else if constexpr (sizeof(S) == 1) v[c] = ((float)f.x[c] - 128.0f) * (1.0f / 128.0f);
-        else if constexpr (std::is_same<S, int>::value) v[c] = (float)((double)f.x[c] * (1.0 / 2147483648.0));
-        else v[c] = f.x[c];
-    }
-}
-template <typename S> __global__ __launch_bounds__(256) void pcm_to_planar_kernel(const void *__restrict__ pcm, float *__restrict__ out, long n_frames, int nch)
-{
-    const long n = blockIdx.x * 256L + threadIdx.x;
-    if (n >= n_frames) return;
-    if (nch == 4) {
-        float v[4];
-        pcm_frame<S, 4>(pcm, n, v);
-#pragma unroll
-        for (int c = 0; c < 4; c++) out[c * n_frames + n] = v[c];
-    } else {
-        for (int c = 0; c < nch; c++) {
-            float v[1];
-            pcm_frame<S, 1>(pcm, n * nch + c, v);
-            out[c * n_frames + n] = v[0];
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------ augmentation
-// The reference's SALSA training augmentation (utilities/transforms.py; recipe in dataset/datamodule.py:45-52, :73-82) as
-// ONE gather pass over a feature batch [B][7][T][F]: channel swap (FOA :394-437 / MIC :469-523, applied in the reference's
-// order with its float32 arithmetic: the MIC swap re-references the three phase rows by differences), frequency shift with
-// reflect padding (:298-320), then the cutout rectangles (:87-121, :149-194, :223-254; last rectangle wins; the spatial rows
-// get zeros).  One thread = all 7 channels of one (clip, frame, bin).  par: int32 [B][AUG_NPAR] = m0..m3, shift, up, 0, 0,
-// top[8], h[8], left[8], w[8] ; uval: float32 [B][8] in [0,1) ; minmax: float32 [B][2] -> fill = min + (max - min) * u.
-constexpr int AUG_NPAR = bank_batch::NPAR;
-// (the per-element body is bank_batch.h's, shared with salsa_bank_batch)
-__global__ __launch_bounds__(256) void augment_kernel(const float *__restrict__ in, long in_batch, long in_chan,
-                                                      float *__restrict__ out, int T, int F,
-                                                      int format, int n_zero, const int *__restrict__ par,
-                                                      const float *__restrict__ uval, const float *__restrict__ minmax)
-{
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= T * F) return;
-    const int t = i / F, f = i - t * F;
-    const long plane = (long)T * F;
-    // the input may be a time-cropped view: its own batch / channel strides
-    bank_batch::augment7(in + (long)b * in_batch, in_chan, out + (long)b * 7 * plane + i, plane, t, f, F, format != SALSA_FORMAT_FOA,
-                         n_zero, par + b * AUG_NPAR, uval + b * 8, minmax + 2 * b);
-}
-
-// The baseline GCC recipe (dataset/datamodule.py:83-100) on [B][10][T][F] = M1..M4 | xc12 xc13 xc14 xc23 xc24 xc34: the
-// GccRandomSwapChannelMic permutation (transforms.py:568-602; its branches are if / elif / elif, so only the FIRST set bit of
-// m0..m2 acts on the features), some GCC rows also flipped along the lag axis (f -> F-1-f); RandomShiftUpDownNp with
-// n_last_channels = 6 (only the four spectrogram rows shift); the cutout rectangles with the last 6 rows zeroed.  Pure gathers:
-// every output value is an input value or the fill value.  One thread = all 10 channels of one (clip, frame, bin).
-__global__ __launch_bounds__(256) void augment_gcc_kernel(const float *__restrict__ in, long in_batch, long in_chan,
-                                                          float *__restrict__ out, int T, int F, const int *__restrict__ par,
-                                                          const float *__restrict__ uval, const float *__restrict__ minmax)
-{
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= T * F) return;
-    const int t = i / F, f = i - t * F;
-    const long plane = (long)T * F;
-    bank_batch::augment10(in + (long)b * in_batch, in_chan, out + (long)b * 10 * plane + i, plane, t, f, F, par + b * AUG_NPAR,
-                          uval + b * 8, minmax + 2 * b);
-}
-
-__global__ __launch_bounds__(256) void db10_kernel(const float *__restrict__ p, float *__restrict__ o, long n)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) o[i] = db10(p[i]);
-}
-
 } // namespace
 
-// ================================================================================================== plan + C ABI
-constexpr int SALSA_MAX_GROUPS = 16;
+namespace salsa_impl {
 
-struct salsa_plan {
-    salsa_params p;
-    int device;
-    int lower, upper, cutoff, nd, F, ident;
-    int spec_lo, spec_hi, flex;
-    double delta, snr_ratio;
-    double *d_window;     // the log-spectrogram window: win_len Hann centre-padded to n_fft (SALSA); n_fft Hann (SALSA-Lite / IPD, contrib)
-    double *d_window_doa; // the DOA spectra's window, n_fft Hann: the same table as d_window unless a SALSA plan has win_len < n_fft
-    cplx<double> *d_tw;
-    const float *sc_mean, *sc_std; // caller-owned device arrays set by salsa_plan_set_scaler (or NULL)
-    unsigned long long *stats;     // caller-owned device counters set by salsa_plan_set_stats (or NULL)
-    int fused;                     // salsa_plan_set_fused: 0 = three kernels; 1 = STFT -> tracker -> fused STFT + covariance / eigen (stage a)
-    int timing;
-    int stop_after; // measurement only: 1 = issue the STFT launch alone, 2 = STFT + tracker, 0 = the whole path (salsa_plan_set_timing(plan, -1 | -2))
-    int n_kernels;
-    hipEvent_t ev0[SALSA_MAX_KERNELS], ev1[SALSA_MAX_KERNELS]; // start/stop of each launch (timing mode only)
-    const char *names[SALSA_MAX_KERNELS];
-    // clip-group pipeline (salsa_plan_set_pipeline): stream 0 runs the STFT kernels of all groups back to back; group g's
-    // tracker and covariance/eigen kernels run on stream 1+g, so the latency-bound tracker of one group hides under the
-    // STFT / eigen work of its neighbours.  With SALSA_PIPE_SPLIT_PAIRS the STFT of a group is two launches (channels 0/1,
-    // then 2/3) and the tracker -- which only needs channel 0 -- starts after the first.  With SALSA_PIPE_GRAPH the whole
-    // fork/join is captured ONCE per (buffers, sizes) into a hipGraph and replayed with a single hipGraphLaunch.
-    int n_groups;
-    int pipe_flags;
-    hipStream_t streams[SALSA_MAX_GROUPS + 1];
-    hipEvent_t ev_fork, ev_stft[SALSA_MAX_GROUPS], ev_stft2[SALSA_MAX_GROUPS], ev_join[SALSA_MAX_GROUPS + 1];
-    hipStream_t cap_stream;
-    hipGraphExec_t gexec;
-    struct {
-        const float *audio;
-        float *out;
-        void *ws;
-        const float *sc_mean, *sc_std;
-        int batch, n_groups, flags;
-        int64_t n_samples;
-    } gkey;
-};
-
-// the fused kernel serves the dataset scripts' main configuration (what cov_eig_kernel's packed instantiation serves) at sizes
-// whose ring fits the LDS; everything else keeps the three-kernel path
-static bool fused_eligible(const salsa_plan *pl, const KParams &kp)
+void launch_tracker(const KParams &kp, hipStream_t s, const float4 *Xs, unsigned *valid32)
 {
-    return SALSA_PK && pl->d_window == pl->d_window_doa && pl->p.n_fft == 512 && kp.feature == SALSA_FEATURE_SALSA && kp.nch == 4 && kp.n_hop == 3 && kp.tracking &&
-           !kp.flex && kp.cond >= SALSA_PK_COND_MIN && kp.cond < 1e6 && !kp.force_f64 && kp.nd >= 1 && kp.T >= 4 * FZ_S && kp.F <= 256 &&
-           fused_lds_bytes(kp.nd, kp.F, kp.sc_mean != nullptr) <= 160 * 1024;
-}
-// frames per segment: enough workgroups for every CU, whole rounds of them when the batch allows, segments long enough that
-// the 6-frame halo stays a few percent
-static int fused_segment_frames(const KParams &kp)
-{
-    const long total = (long)kp.B * kp.T;
-    long rounds = (total + 256L * 160 - 1) / (256L * 160);
-    long nseg = (256 * rounds + kp.B - 1) / kp.B;
-    if (nseg < 1) nseg = 1;
-    long Lf = (kp.T + nseg - 1) / nseg;
-    Lf = (Lf + FZ_S - 1) / FZ_S * FZ_S;
-    if (Lf < 4 * FZ_S) Lf = 4 * FZ_S;
-    return (int)Lf;
-}
-static size_t fused_cold_bytes(const KParams &kp) { return (size_t)kp.B * ((kp.T + fused_segment_frames(kp) - 1) / fused_segment_frames(kp)) * FZ_COLD_CAP * sizeof(fz_cold_rec); }
-static int launch_fused(salsa_plan *pl, const KParams &kp, const float *d_audio, float *d_out, const unsigned *valid, void *cold, hipStream_t s)
-{
-    const size_t lds = fused_lds_bytes(kp.nd, kp.F, kp.sc_mean != nullptr);
-    static bool attr_set[64][2] = {};
-    const bool mic = kp.format == SALSA_FORMAT_MIC;
-    if (pl->device >= 0 && pl->device < 64 && !attr_set[pl->device][mic]) {
-        if (mic) HIP_TRY(hipFuncSetAttribute((const void *)fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        else HIP_TRY(hipFuncSetAttribute((const void *)fused_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[pl->device][mic] = true;
-    }
-    const int L = fused_segment_frames(kp);
-    dim3 grid((unsigned)((kp.T + L - 1) / L), (unsigned)kp.B);
-    if (mic) hipLaunchKernelGGL(fused_kernel<true>, grid, dim3(FZ_NT), lds, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, valid, L, (fz_cold_rec *)cold, pl->fused == 2 ? 0 : FZ_COLD_CAP);
-    else hipLaunchKernelGGL(fused_kernel<false>, grid, dim3(FZ_NT), lds, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, valid, L, (fz_cold_rec *)cold, pl->fused == 2 ? 0 : FZ_COLD_CAP);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
+    hipLaunchKernelGGL(tracker_kernel, dim3(tracker_grid(kp)), dim3(64 * TR_WAVES), 0, s, kp, Xs, valid32);
 }
 
-template <int NPAIRS>
-static int launch_stft_multi(salsa_plan *pl, const KParams &kp, const float *d_audio, float *d_out, float4 *Xs, hipStream_t s)
+template <bool FEAT>
+static void launch_gate_doubt(const KParams &kp, hipStream_t s, const float4 *Xs, float *out_feat, double *out_eig, unsigned char *gate)
 {
-    const bool lite = kp.feature == SALSA_FEATURE_LITE;
-    constexpr int NF = 4;
-    dim3 grid((unsigned)((kp.T + 4 * NF - 1) / (4 * NF)), (unsigned)kp.B);
-    if (pl->p.n_fft == 512) {
-        if (lite) hipLaunchKernelGGL((stft_kernel<512, double, true, NF, NPAIRS>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
-        else hipLaunchKernelGGL((stft_kernel<512, double, false, NF, NPAIRS>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
-    } else {
-        if (lite) hipLaunchKernelGGL((stft_kernel<256, double, true, NF, NPAIRS>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
-        else hipLaunchKernelGGL((stft_kernel<256, double, false, NF, NPAIRS>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
-    }
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
+    if (!kp.doubt32) return;
+    const long nwords = (long)kp.B * ((kp.nd + TR_BINS - 1) / TR_BINS) * kp.T;
+    const unsigned blocks = (unsigned)(nwords < 256L * 64 ? (nwords + 255) / 256 : 64);
+    hipLaunchKernelGGL(gate_doubt_kernel<FEAT>, dim3(blocks ? blocks : 1u), dim3(256), 0, s, kp, Xs, out_feat, out_eig, gate);
 }
 
-extern "C" {
-
-int salsa_abi_version(void) { return SALSA_ABI_VERSION; }
-const char *salsa_build_flags(void) { return SALSA_BUILD_FLAGS; }
-const char *salsa_last_error(void) { return g_err; }
-// the other translation units' failures (baseline_kernels.hip) land in the same per-thread message; not part of the public ABI
-__attribute__((visibility("hidden"))) void salsa_set_last_error_(const char *msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
-
-int salsa_bin_limits(int fs, int n_fft, int fmin_doa, int fmax_doa, int *lower_bin, int *upper_bin, int *cutoff_bin)
+template <bool FEAT>
+void launch_cov_eig(const KParams &kp, dim3 grid, hipStream_t s, const float4 *Xs, const unsigned *valid,
+                    float *out_feat, double *out_eig, unsigned char *gate)
 {
-    if (fs <= 0 || n_fft <= 0 || !lower_bin || !upper_bin) return fail(SALSA_EINVAL, "salsa_bin_limits: bad argument%s");
-    // salsa_feature_extraction.py:298-304: fmax = min(fmax, fs//2); int(floor(f * n_fft / float(fs))); lower = max(1, lower)
-    const int fmax = fmax_doa < fs / 2 ? fmax_doa : fs / 2;
-    int lo = (int)floor((double)((int64_t)fmin_doa * n_fft) / (double)fs);
-    const int up = (int)floor((double)((int64_t)fmax * n_fft) / (double)fs);
-    if (lo < 1) lo = 1;
-    *lower_bin = lo;
-    *upper_bin = up;
-    if (cutoff_bin) *cutoff_bin = (int)floor((double)((int64_t)9000 * n_fft) / (double)fs); // lite :57-58
-    return SALSA_OK;
+    const bool gated = kp.tracking || kp.flex; // (!ungated: the coherence test decides, so passing bins have a spectral gap)
+    if (kp.doubt32 && !kp.tracking) (void)hipMemsetAsync(kp.doubt_flag, 0, sizeof(unsigned), s); // (no tracker launch zeroed it: contrib's gate without tracking)
+    // (the packed pair solve: feature output only -- salsa_eigvec_batch keeps float64 results -- and never for contrib's variant)
+    if (FEAT && SALSA_PK && K3_GROUP == 2 && kp.n_hop == 3 && gated && SALSA_COL0 && !kp.flex && kp.cond >= SALSA_PK_COND_MIN && kp.cond < 1e6 && !kp.force_f64)
+        hipLaunchKernelGGL((cov_eig_kernel<FEAT, 3, true, FEAT && K3_GROUP == 2>), grid, dim3(K3_NT), 0, s, kp, Xs, valid, out_feat, out_eig, gate);
+    else if (kp.n_hop == 3 && gated && SALSA_COL0)
+        hipLaunchKernelGGL((cov_eig_kernel<FEAT, 3, true>), grid, dim3(K3_NT), 0, s, kp, Xs, valid, out_feat, out_eig, gate);
+    else if (kp.n_hop == 3)
+        hipLaunchKernelGGL((cov_eig_kernel<FEAT, 3>), grid, dim3(K3_NT), 0, s, kp, Xs, valid, out_feat, out_eig, gate);
+    else
+        hipLaunchKernelGGL((cov_eig_kernel<FEAT, -1>), grid, dim3(K3_NT), 0, s, kp, Xs, valid, out_feat, out_eig, gate);
+    launch_gate_doubt<FEAT>(kp, s, Xs, out_feat, out_eig, gate); // (a no-op unless kp.doubt32: gated plans)
 }
 
-static int freq_dim(int n_fft, int compress)
-{
-    if (n_fft != 512 && n_fft != 256) return -1;
-    if (compress) return n_fft == 512 ? 200 : 100;
-    return n_fft / 2;
-}
+template void launch_cov_eig<true>(const KParams &, dim3, hipStream_t, const float4 *, const unsigned *, float *, double *, unsigned char *);
+template void launch_cov_eig<false>(const KParams &, dim3, hipStream_t, const float4 *, const unsigned *, float *, double *, unsigned char *);
 
-int salsa_compress_matrix(int n_fft, int compress, float *W)
+void launch_flex_allpass(const KParams &kp, hipStream_t s, float *out)
 {
-    const int F = freq_dim(n_fft, compress);
-    if (F < 0) return fail(SALSA_ENFFT, "nfft is not 512 or 256%s");
-    if (!W) return fail(SALSA_EINVAL, "salsa_compress_matrix: NULL output%s");
-    const int nb = n_fft / 2 + 1;
-    memset(W, 0, sizeof(float) * (size_t)F * nb);
-    const int ident = compress ? (n_fft == 512 ? 192 : 96) : n_fft / 2;
-    for (int i = 0; i < ident; i++) W[(size_t)i * nb + i + 1] = 1.0f;
-    for (int i = ident; i < F; i++) {
-        const int cnt = i < F - 1 ? 8 : 7;
-        for (int k = 0; k < cnt; k++) W[(size_t)i * nb + ident + 1 + (i - ident) * 8 + k] = 0.125f;
-    }
-    return SALSA_OK;
-}
-
-int salsa_plan_create(const salsa_params *params, salsa_plan **out_plan)
-{
-    if (!params || !out_plan) return fail(SALSA_EINVAL, "salsa_plan_create: NULL argument%s");
-    const salsa_params &p = *params;
-    // full SALSA: the reference's own assert (salsa_feature_extraction.py:152, :306).  Its SALSA-Lite / IPD script has none; here those
-    // two features also take 1024 (stft_kernel<1024, ...>), on the dataset scripts' surface (not contrib's SALSA_FLAG_FLEX); every other size is refused
-    const bool lite_1024 = p.n_fft == 1024 && (p.feature_type == SALSA_FEATURE_LITE || p.feature_type == SALSA_FEATURE_IPD) && !(p.flags & SALSA_FLAG_FLEX);
-    if (p.n_fft != 512 && p.n_fft != 256 && !lite_1024) {
-        if (p.feature_type == SALSA_FEATURE_LITE || p.feature_type == SALSA_FEATURE_IPD)
-            return fail(SALSA_ENFFT, "only 256, 512 or 1024 fft is supported for SALSA-Lite and SALSA-IPD (256 or 512 with the contrib flags)%s");
-        return fail(SALSA_ENFFT, "only 256 or 512 fft is supported%s");
-    }
-    if (p.fs <= 0 || p.hop_len <= 0 || p.win_len <= 0 || p.win_len > p.n_fft)
-        return fail(SALSA_EINVAL, "bad fs / hop_len / win_len (window length must be <= nfft)%s");
-    if (p.audio_format != SALSA_FORMAT_FOA && p.audio_format != SALSA_FORMAT_MIC)
-        return fail(SALSA_EFORMAT, "Unknown audio format%s");
-    if (p.feature_type < SALSA_FEATURE_SALSA || p.feature_type > SALSA_FEATURE_IPD)
-        return fail(SALSA_EINVAL, "Invalid feature type%s");
-    if (p.feature_type != SALSA_FEATURE_SALSA && p.audio_format != SALSA_FORMAT_MIC)
-        return fail(SALSA_EFORMAT, "SALSA-Lite and SALSA-IPD are only for MIC format!%s");
-    if (p.n_hopframes < 0 || p.n_hopframes > 16) return fail(SALSA_EINVAL, "n_hopframes out of range%s");
-    salsa_plan *pl = new salsa_plan();
-    memset(pl, 0, sizeof(*pl));
-    pl->p = p;
-    salsa_bin_limits(p.fs, p.n_fft, p.fmin_doa, p.fmax_doa, &pl->lower, &pl->upper, &pl->cutoff);
-    const int nbins = p.n_fft / 2 + 1;
-    pl->flex = (p.flags & SALSA_FLAG_FLEX) != 0;
-    pl->snr_ratio = p.floor_mask_ratio > 0 ? p.floor_mask_ratio : 1.5;
-    if (pl->flex) {
-        // contrib/salsa_flexible.py SpatialFeaturesAbstract.__init__ (:177-184) + __call__ (:252-263): no fs/2 clamp on
-        // fmax_doa, the spectrogram cutoff comes from fmax_spec, spectrogram and spatial features share ONE band
-        // [lo, hi) (the cropped axis, or all n_fft/2+1 bins), spatial rows >= upper_bin OF THAT AXIS optionally zeroed.
-        if (p.audio_format != SALSA_FORMAT_MIC || p.feature_type == SALSA_FEATURE_IPD) {
-            delete pl;
-            return fail(SALSA_EFORMAT, "the contrib (flex) surface has the MIC-style SALSA and SALSA-Lite features only%s");
-        }
-        pl->upper = (int)floor((double)((int64_t)p.fmax_doa * p.n_fft) / (double)p.fs);
-        pl->cutoff = (int)floor((double)((int64_t)(p.fmax_spec > 0 ? p.fmax_spec : 9000) * p.n_fft) / (double)p.fs);
-        if (pl->upper > pl->cutoff) {
-            delete pl;
-            return fail(SALSA_EBINS, "Upper bin for spatial feature is higher than cutoff bin for spectrogram!%s");
-        }
-        const bool crop = !(p.flags & SALSA_FLAG_NO_CLIP_FREQS);
-        const int lo = crop ? pl->lower : 0, hi = crop ? (pl->cutoff < nbins ? pl->cutoff : nbins) : nbins;
-        const int zero_from = (p.flags & SALSA_FLAG_CLIP_SPATIAL_ALIAS) ? pl->upper : hi - lo; // index into the band
-        pl->lower = lo;
-        pl->cutoff = hi;
-        pl->F = hi - lo;
-        if (pl->F <= 0) {
-            delete pl;
-            return fail(SALSA_EBINS, "empty spectrogram band%s");
-        }
-        pl->ident = p.n_fft / 2;
-        pl->spec_lo = lo;
-        pl->spec_hi = hi;
-        if (p.feature_type == SALSA_FEATURE_SALSA) {
-            pl->nd = zero_from < pl->F ? zero_from : pl->F; // bins above it are never evaluated: cov_eig zero-fills them
-            pl->upper = lo + pl->nd;
-        } else {
-            pl->nd = 0;
-            pl->upper = zero_from;                           // the lite kernel zeroes band rows >= kp.upper
-        }
-    } else if (p.feature_type == SALSA_FEATURE_SALSA) {
-        pl->F = freq_dim(p.n_fft, p.is_compress_high_freq);
-        pl->ident = p.is_compress_high_freq ? (p.n_fft == 512 ? 192 : 96) : p.n_fft / 2;
-        pl->spec_lo = 1;
-        pl->spec_hi = pl->ident + 1;
-        pl->nd = pl->upper - pl->lower;
-        if (pl->nd < 0 || pl->nd > pl->F || pl->upper > nbins) {
-            delete pl;
-            return fail(SALSA_EBINS, "DOA band [lower_bin, upper_bin) does not fit the feature axis%s");
-        }
-    } else {
-        if (pl->upper > pl->cutoff) {
-            delete pl;
-            return fail(SALSA_EBINS, "Upper bin for spatial feature is higher than cutoff bin for spectrogram!%s");
-        }
-        if (pl->cutoff > nbins) pl->cutoff = nbins; // numpy slicing clips [lower:cutoff] at n_bins
-        pl->F = pl->cutoff - pl->lower;
-        pl->ident = 0;
-        pl->nd = 0;
-        if (pl->F <= 0) {
-            delete pl;
-            return fail(SALSA_EBINS, "empty spectrogram band%s");
-        }
-    }
-    pl->delta = 2.0 * 3.14159265358979323846 * p.fs / (p.n_fft * 343.0);
-    if (hipGetDevice(&pl->device) != hipSuccess) {
-        delete pl;
-        return fail(SALSA_EHIP, "hipGetDevice failed (no HIP device?)%s");
-    }
-    // windows: scipy.signal.get_window('hann', win, fftbins=True), centre-padded to n_fft (librosa pad_center: (n_fft - win) // 2
-    // zeros on the left) ; twiddles W_N^m.  Only the SALSA log-spectrogram honours win_len (salsa_feature_extraction.py:186-192); its
-    // DOA STFT (:360-361) and both SALSA-Lite STFTs (salsa_lite_feature_extraction.py:97-98, win_len read at :44 and unused) pass no
-    // win_length, i.e. the n_fft window.  Equal lengths: one table.
-    const int spec_win = (p.feature_type == SALSA_FEATURE_SALSA && !pl->flex) ? p.win_len : p.n_fft;
-    const int nwin = spec_win == p.n_fft ? 1 : 2;
-    double *hw = new double[2 * p.n_fft];
-    cplx<double> *htw = new cplx<double>[p.n_fft];
-    for (int i = 0; i < 2 * p.n_fft; i++) hw[i] = 0.0;
-    for (int n = 0; n < spec_win; n++) hw[(p.n_fft - spec_win) / 2 + n] = 0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * n / spec_win);
-    for (int n = 0; n < p.n_fft; n++) hw[p.n_fft + n] = 0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * n / p.n_fft);
-    for (int m = 0; m < p.n_fft; m++)
-        htw[m] = {cos(-2.0 * 3.14159265358979323846 * m / p.n_fft), sin(-2.0 * 3.14159265358979323846 * m / p.n_fft)};
-    hipError_t e1 = hipMalloc((void **)&pl->d_window, sizeof(double) * p.n_fft * nwin);
-    hipError_t e2 = hipMalloc((void **)&pl->d_tw, sizeof(cplx<double>) * p.n_fft);
-    if (e1 == hipSuccess && e2 == hipSuccess) {
-        e1 = hipMemcpy(pl->d_window, hw, sizeof(double) * p.n_fft * nwin, hipMemcpyHostToDevice);
-        e2 = hipMemcpy(pl->d_tw, htw, sizeof(cplx<double>) * p.n_fft, hipMemcpyHostToDevice);
-    }
-    if (e1 == hipSuccess) pl->d_window_doa = nwin == 2 ? pl->d_window + p.n_fft : pl->d_window;
-    delete[] hw;
-    delete[] htw;
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        salsa_plan_destroy(pl);
-        return fail(SALSA_EHIP, "plan table upload failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-    }
-    pl->n_groups = 1; // measured on ROCm 7.2: multi-stream issue costs more host time than the overlap returns
-    *out_plan = pl;
-    return SALSA_OK;
-}
-
-int salsa_plan_destroy(salsa_plan *pl)
-{
-    if (!pl) return SALSA_OK;
-    if (pl->d_window) (void)hipFree(pl->d_window);
-    if (pl->d_tw) (void)hipFree(pl->d_tw);
-    for (int i = 0; i < SALSA_MAX_KERNELS; i++) {
-        if (pl->ev0[i]) (void)hipEventDestroy(pl->ev0[i]);
-        if (pl->ev1[i]) (void)hipEventDestroy(pl->ev1[i]);
-    }
-    for (int i = 0; i <= SALSA_MAX_GROUPS; i++) {
-        if (pl->streams[i]) (void)hipStreamDestroy(pl->streams[i]);
-        if (pl->ev_join[i]) (void)hipEventDestroy(pl->ev_join[i]);
-        if (i < SALSA_MAX_GROUPS && pl->ev_stft[i]) (void)hipEventDestroy(pl->ev_stft[i]);
-        if (i < SALSA_MAX_GROUPS && pl->ev_stft2[i]) (void)hipEventDestroy(pl->ev_stft2[i]);
-    }
-    if (pl->gexec) (void)hipGraphExecDestroy(pl->gexec);
-    if (pl->cap_stream) (void)hipStreamDestroy(pl->cap_stream);
-    if (pl->ev_fork) (void)hipEventDestroy(pl->ev_fork);
-    delete pl;
-    return SALSA_OK;
-}
-
-int salsa_output_shape(const salsa_plan *pl, int64_t n_samples, int *C, int64_t *T, int *F)
-{
-    if (!pl || n_samples < 0) return fail(SALSA_EINVAL, "salsa_output_shape: bad argument%s");
-    if (C) *C = 7;
-    if (T) *T = 1 + n_samples / pl->p.hop_len;
-    if (F) *F = pl->F;
-    return SALSA_OK;
-}
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-// one [B][32-bin group][T] uint32 bit mask (the tracker's gate masks; the doubt mask of the coherence test), rounded up to whole
-// 64-frame chunks and 64-bin groups
-static size_t mask_bytes(int batch, size_t T, int nd) { return align256((size_t)batch * ((T + 63) / 64) * ((nd + 63) / 64) * 64 * 8); }
-
-size_t salsa_workspace_bytes(const salsa_plan *pl, int batch, int64_t n_samples)
-{
-    if (!pl || batch <= 0 || n_samples <= 0 || pl->p.feature_type != SALSA_FEATURE_SALSA) return 0;
-    const size_t T = 1 + n_samples / pl->p.hop_len;
-    return align256((size_t)batch * T * 4 * pl->nd * sizeof(float2)) + 2 * mask_bytes(batch, T, pl->nd) + align256(sizeof(unsigned) * (size_t)batch) + 256; // spill, gate masks, doubt mask, doubt flags
-}
-
-size_t salsa_eigvec_workspace_bytes(const salsa_plan *pl, int batch, int n_bins, int64_t n_frames)
-{
-    if (!pl || batch <= 0 || n_bins <= 0 || n_frames <= 0) return 0;
-    return align256((size_t)batch * n_frames * 4 * n_bins * sizeof(float2)) + 2 * mask_bytes(batch, (size_t)n_frames, n_bins) + align256(sizeof(unsigned) * (size_t)batch) + 256;
-}
-
-static KParams make_kparams(const salsa_plan *pl, int batch, int64_t n_samples)
-{
-    KParams kp;
-    memset(&kp, 0, sizeof(kp));
-    kp.B = batch;
-    kp.N = (int)n_samples;
-    kp.T = (int)(1 + n_samples / pl->p.hop_len);
-    kp.hop = pl->p.hop_len;
-    kp.lower = pl->lower;
-    kp.upper = pl->upper;
-    kp.nd = pl->nd;
-    kp.cutoff = pl->cutoff;
-    kp.F = pl->F;
-    kp.OC = 7;
-    kp.ident = pl->ident;
-    kp.spec_lo = pl->spec_lo;
-    kp.spec_hi = pl->spec_hi;
-    kp.flex = pl->flex;
-    kp.snr_ratio = pl->snr_ratio;
-    kp.compress = pl->flex ? 0 : pl->p.is_compress_high_freq;
-    kp.layout = pl->p.audio_layout;
-    kp.feature = pl->p.feature_type;
-    kp.format = pl->p.audio_format;
-    kp.tracking = pl->p.is_tracking;
-    kp.n_hop = pl->p.n_hopframes;
-    kp.pair_sel = -1;
-    kp.nch = 4;
-    kp.cond = pl->p.cond_num;
-    kp.inv_cond = pl->p.cond_num > 0 ? 1.0 / pl->p.cond_num : 0.0;
-    kp.delta = pl->delta;
-    kp.sc_mean = pl->sc_mean;
-    kp.sc_std = pl->sc_std;
-    kp.stats = pl->stats;
-    kp.force_f64 = (pl->p.flags & SALSA_FLAG_FORCE_F64) != 0;
-    return kp;
-}
-
-// timing mode: bracket one launch with events on ITS stream
-static int mark_begin(salsa_plan *pl, hipStream_t s, const char *name)
-{
-    if (!pl->timing || pl->n_kernels >= SALSA_MAX_KERNELS) return -1;
-    const int i = pl->n_kernels++;
-    pl->names[i] = name;
-    if (!pl->ev0[i]) (void)hipEventCreate(&pl->ev0[i]);
-    if (!pl->ev1[i]) (void)hipEventCreate(&pl->ev1[i]);
-    (void)hipEventRecord(pl->ev0[i], s);
-    return i;
-}
-static void mark_end(salsa_plan *pl, hipStream_t s, int i)
-{
-    if (i >= 0) (void)hipEventRecord(pl->ev1[i], s);
+    hipLaunchKernelGGL(flex_allpass_kernel, dim3((unsigned)((kp.nd + 255) / 256), (unsigned)kp.B), dim3(256), 0, s, kp, out);
 }
 
 // one K1 launch with the window `win` (one of the plan's two tables)
-static int launch_stft(salsa_plan *pl, const KParams &kp, const double *win, const float *d_audio, float *d_out, float4 *Xs, hipStream_t s)
+int launch_stft(salsa_plan *pl, const KParams &kp, const double *win, const float *d_audio, float *d_out, float4 *Xs, hipStream_t s)
 {
     const bool lite = kp.feature == SALSA_FEATURE_LITE || kp.feature == SALSA_FEATURE_IPD;
     const bool single = !lite && kp.pair_sel >= 0; // one channel pair per launch: twice the frames per wave, same work per wave
@@ -2579,7 +1412,7 @@ static int launch_stft(salsa_plan *pl, const KParams &kp, const double *win, con
 // n_fft window and the log-spectrogram channels from the win_len window, so the general kernel runs twice: with the DOA window
 // (spill + provisional channels 0-3), then log-spec only (no spill store) with the spectrogram window, overwriting channels 0-3 of
 // the 7-channel output (fused scaler included).  Same stream: the second launch's stores land last.
-static int launch_k1(salsa_plan *pl, const KParams &kp, const float *d_audio, float *d_out, float4 *Xs, hipStream_t s)
+int launch_k1(salsa_plan *pl, const KParams &kp, const float *d_audio, float *d_out, float4 *Xs, hipStream_t s)
 {
     if (pl->d_window == pl->d_window_doa || kp.feature != SALSA_FEATURE_SALSA) return launch_stft(pl, kp, pl->d_window, d_audio, d_out, Xs, s);
     const int rc = launch_stft(pl, kp, pl->d_window_doa, d_audio, d_out, Xs, s);
@@ -2589,530 +1422,25 @@ static int launch_k1(salsa_plan *pl, const KParams &kp, const float *d_audio, fl
     return launch_stft(pl, lp, pl->d_window, d_audio, d_out, nullptr, s);
 }
 
-int salsa_extract_batch(salsa_plan *pl, const float *d_audio, int batch, int64_t n_samples, float *d_out,
-                        void *d_workspace, size_t workspace_bytes, void *hip_stream)
+// K1 of salsa_extract_multichannel: NPAIRS channel pairs per clip (0: the count at run time, kp.nch / 2)
+template <int NPAIRS>
+int launch_stft_multi(salsa_plan *pl, const KParams &kp, const float *d_audio, float *d_out, float4 *Xs, hipStream_t s)
 {
-    if (!pl || !d_audio || !d_out || batch <= 0 || n_samples <= 0)
-        return fail(SALSA_EINVAL, "salsa_extract_batch: bad argument%s");
-    if (n_samples <= pl->p.n_fft / 2)
-        return fail(SALSA_EINVAL, "clip shorter than n_fft/2 samples cannot be reflect-padded%s");
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != pl->device)
-            return fail(SALSA_EINVAL, "the plan's tables live on the device that was current at salsa_plan_create; make it current%s");
-    }
-    {   // kernels index inside one clip with 32-bit offsets
-        const int64_t T64 = 1 + n_samples / pl->p.hop_len;
-        if (n_samples * 16 >= INT32_MAX || T64 * 7 * pl->F >= INT32_MAX / 2 || T64 * 2 * (pl->nd > 0 ? pl->nd : 1) >= INT32_MAX / 8)
-            return fail(SALSA_EINVAL, "clip too long for 32-bit per-clip indexing (split it)%s");
-        if ((T64 + K3_FT - 1) / K3_FT > 65535) return fail(SALSA_EINVAL, "clip too long for one launch (split it)%s");
-    }
-    hipStream_t s = (hipStream_t)hip_stream;
-    KParams kp = make_kparams(pl, batch, n_samples);
-    const bool full = pl->p.feature_type == SALSA_FEATURE_SALSA;
-    float4 *Xs = nullptr;
-    unsigned *valid = nullptr;
-    if (full) {
-        const size_t need = salsa_workspace_bytes(pl, batch, n_samples);
-        if (!d_workspace || workspace_bytes < need) return fail(SALSA_EWORKSPACE, "workspace too small%s (need %ld bytes)", "", (long)need);
-        Xs = (float4 *)d_workspace;
-        valid = (unsigned *)((unsigned char *)d_workspace + align256((size_t)batch * kp.T * 4 * kp.nd * sizeof(float2)));
-        if ((kp.tracking || kp.flex) && kp.cond > 1.0 && kp.nd > 0) {
-            kp.doubt32 = (unsigned *)((unsigned char *)valid + mask_bytes(batch, (size_t)kp.T, kp.nd));
-            kp.doubt_flag = (unsigned *)((unsigned char *)kp.doubt32 + mask_bytes(batch, (size_t)kp.T, kp.nd)); // [batch]: one per launch group
-        }
-    }
-    pl->n_kernels = 0;
-    const long T = kp.T;
-    const size_t nchunks = (size_t)((T + TR_CH - 1) / TR_CH);
-    // group g = clips [g0, g1): every buffer is clip-major, so a group is just a pointer offset.  s1 runs the STFT launch(es);
-    // s2 the tracker and the covariance/eigen kernel (s1 == s2: plain in-order issue on one stream).
-    auto run_group = [&](int g0, int g1, hipStream_t s1, hipStream_t s2, hipEvent_t after_first, hipEvent_t after_second,
-                         bool split) -> int {
-        KParams gp = kp;
-        gp.B = g1 - g0;
-        const float *a = d_audio + (size_t)g0 * 4 * kp.N;
-        float *o = d_out + (size_t)g0 * 7 * T * kp.F;
-        float4 *xs = Xs ? Xs + (size_t)g0 * T * 2 * kp.nd : nullptr;
-        unsigned *vm = valid ? valid + (size_t)g0 * ((kp.nd + TR_BINS - 1) / TR_BINS) * T : nullptr; // [b][32-bin group][t]
-        if (kp.doubt32) gp.doubt32 = kp.doubt32 + (size_t)g0 * ((kp.nd + TR_BINS - 1) / TR_BINS) * T, gp.doubt_flag = kp.doubt_flag + g0;
-        const bool two = split && full && gp.nd > 0;
-        gp.pair_sel = two ? 0 : -1;
-        // timing mode with a repeat count (salsa_plan_set_timing(plan, K > 1)): every kernel is launched K times back to
-        // back between ONE event pair -- all of them are idempotent on (audio, spill, masks) -- so the per-launch figure is
-        // elapsed / K with no event between the launches (an event pair around a single launch adds ~12 % to it)
-        const int reps = pl->timing > 1 ? pl->timing : 1;
-        int m = mark_begin(pl, s1, "stft_logspec");
-        int rc = SALSA_OK;
-        for (int r = 0; r < reps && !rc; r++) rc = launch_k1(pl, gp, a, o, xs, s1);
-        mark_end(pl, s1, m);
-        if (rc || !full) return rc;
-        if (pl->stop_after == 1) return SALSA_PARTIAL; // (measurement mode: the caller is told the outputs are NOT complete)
-        if (s1 != s2) {
-            HIP_TRY(hipEventRecord(after_first, s1));
-            HIP_TRY(hipStreamWaitEvent(s2, after_first, 0));
-        }
-        if (gp.nd == 0) { // empty DOA band: channels 4-6 are all zero (:373-374)
-            HIP_TRY(hipMemset2DAsync(o + 4 * T * kp.F, sizeof(float) * 7 * T * kp.F, 0, sizeof(float) * 3 * T * kp.F, (size_t)gp.B, s2));
-            return SALSA_OK;
-        }
-        if (two) { // channels 2/3 (the tracker below only needs channel 0 and may run beside this launch)
-            gp.pair_sel = 1;
-            m = mark_begin(pl, s1, "stft_logspec");
-            rc = launch_stft(pl, gp, pl->d_window, a, o, xs, s1);
-            mark_end(pl, s1, m);
-            if (rc) return rc;
-            gp.pair_sel = -1;
-            if (s1 != s2) HIP_TRY(hipEventRecord(after_second, s1));
-        }
-        if (gp.tracking) {
-            m = mark_begin(pl, s2, "noise_floor_tracker");
-            for (int r = 0; r < reps; r++)
-                hipLaunchKernelGGL(tracker_kernel, dim3(tracker_grid(gp)), dim3(64 * TR_WAVES), 0, s2, gp, xs, vm);
-            mark_end(pl, s2, m);
-            HIP_TRY(hipGetLastError());
-        }
-        if (pl->stop_after == 2) return SALSA_PARTIAL;
-        if (two && s1 != s2) HIP_TRY(hipStreamWaitEvent(s2, after_second, 0));
-        // stage (a): the fused kernel on the masks of the launches above; its float64 records go where the spill was (dead
-        // once the tracker has read it: same stream)
-        if (pl->fused >= 1 && !two && fused_eligible(pl, gp) && fused_cold_bytes(gp) <= (size_t)gp.B * T * 4 * gp.nd * sizeof(float2)) {
-            m = mark_begin(pl, s2, "fused_stft_cov_eig");
-            for (int r = 0; r < reps && !rc; r++) rc = launch_fused(pl, gp, a, o, vm, (void *)xs, s2);
-            mark_end(pl, s2, m);
-            return rc;
-        }
-        m = mark_begin(pl, s2, "cov_eig");
-        const unsigned ntile = (unsigned)((gp.T + K3_FT - 1) / K3_FT);
-        dim3 grid(ntile, (unsigned)gp.B, (unsigned)((gp.nd + K3_NT - 1) / K3_NT));
-        for (int r = 0; r < reps; r++) launch_cov_eig<true>(gp, grid, s2, xs, vm, o, (double *)nullptr, (unsigned char *)nullptr);
-        mark_end(pl, s2, m);
-        HIP_TRY(hipGetLastError());
-        if (gp.flex && !gp.tracking && gp.nd > 0) {
-            m = mark_begin(pl, s2, "flex_allpass");
-            hipLaunchKernelGGL(flex_allpass_kernel, dim3((unsigned)((gp.nd + 255) / 256), (unsigned)gp.B), dim3(256), 0, s2, gp, o);
-            mark_end(pl, s2, m);
-            HIP_TRY(hipGetLastError());
-        }
-        return SALSA_OK;
-    };
-    // (a plan with two windows keeps the plain in-order schedule: the pipelined one launches K1 per channel pair with one window)
-    const bool piped = full && !pl->timing && !pl->stop_after && kp.nd > 0 && pl->d_window == pl->d_window_doa &&
-                       (pl->n_groups > 1 || (pl->pipe_flags & SALSA_PIPE_SPLIT_PAIRS));
-    if (!piped) return run_group(0, batch, s, s, nullptr, nullptr, false);
-    const int G = batch < pl->n_groups ? batch : pl->n_groups;
-    const bool split = (pl->pipe_flags & SALSA_PIPE_SPLIT_PAIRS) != 0;
-    // fork from `origin`, run the groups on the plan's streams, join back into `origin`
-    auto issue = [&](hipStream_t origin) -> int {
-        HIP_TRY(hipEventRecord(pl->ev_fork, origin));
-        HIP_TRY(hipStreamWaitEvent(pl->streams[0], pl->ev_fork, 0));
-        for (int g = 0; g < G; g++) {
-            HIP_TRY(hipStreamWaitEvent(pl->streams[1 + g], pl->ev_fork, 0)); // orders this call after the caller's earlier work
-            const int g0 = (int)((long)batch * g / G), g1 = (int)((long)batch * (g + 1) / G);
-            const int rc = run_group(g0, g1, pl->streams[0], pl->streams[1 + g], pl->ev_stft[g], pl->ev_stft2[g], split);
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(pl->ev_join[1 + g], pl->streams[1 + g]));
-            HIP_TRY(hipStreamWaitEvent(origin, pl->ev_join[1 + g], 0));
-        }
-        HIP_TRY(hipEventRecord(pl->ev_join[0], pl->streams[0]));
-        HIP_TRY(hipStreamWaitEvent(origin, pl->ev_join[0], 0));
-        return SALSA_OK;
-    };
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s) (void)hipStreamIsCapturing(s, &cap);
-    if (!(pl->pipe_flags & SALSA_PIPE_GRAPH) || cap != hipStreamCaptureStatusNone)
-        return issue(s); // eager fork/join (inside a caller's capture it becomes part of the caller's graph)
-    // one hipGraphLaunch per call: the fork/join above captured once for these buffers and sizes
-    const bool hit = pl->gexec && pl->gkey.audio == d_audio && pl->gkey.out == d_out && pl->gkey.ws == d_workspace &&
-                     pl->gkey.sc_mean == pl->sc_mean && pl->gkey.sc_std == pl->sc_std && pl->gkey.batch == batch &&
-                     pl->gkey.n_samples == n_samples && pl->gkey.n_groups == G && pl->gkey.flags == pl->pipe_flags;
-    if (!hit) {
-        if (pl->gexec) {
-            (void)hipGraphExecDestroy(pl->gexec);
-            pl->gexec = nullptr;
-        }
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(pl->cap_stream, hipStreamCaptureModeThreadLocal));
-        const int rc = issue(pl->cap_stream);
-        const hipError_t e = hipStreamEndCapture(pl->cap_stream, &graph);
-        if (rc) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc;
-        }
-        HIP_TRY(e);
-        const hipError_t ei = hipGraphInstantiate(&pl->gexec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        HIP_TRY(ei);
-        pl->gkey.audio = d_audio;
-        pl->gkey.out = d_out;
-        pl->gkey.ws = d_workspace;
-        pl->gkey.sc_mean = pl->sc_mean;
-        pl->gkey.sc_std = pl->sc_std;
-        pl->gkey.batch = batch;
-        pl->gkey.n_samples = n_samples;
-        pl->gkey.n_groups = G;
-        pl->gkey.flags = pl->pipe_flags;
-    }
-    HIP_TRY(hipGraphLaunch(pl->gexec, s));
-    return SALSA_OK;
-}
-
-size_t salsa_multichannel_workspace_bytes(const salsa_plan *pl, int n_channels, int batch, int64_t n_samples)
-{
-    if (!pl || batch <= 0 || n_samples <= 0 || n_channels < 4 || n_channels > SALSA_MAX_MICS || (n_channels & 1)) return 0;
-    if (pl->p.feature_type != SALSA_FEATURE_SALSA) return 256;
-    const size_t T = 1 + n_samples / pl->p.hop_len;
-    return align256((size_t)batch * T * n_channels * pl->nd * sizeof(float2)) +
-           align256((size_t)batch * ((pl->nd + TR_BINS - 1) / TR_BINS) * T * sizeof(unsigned)) + 256;
-}
-
-int salsa_extract_multichannel(salsa_plan *pl, const float *d_audio, int n_channels, int batch, int64_t n_samples, float *d_out,
-                               void *d_workspace, size_t workspace_bytes, void *hip_stream)
-{
-    if (!pl || !d_audio || !d_out || batch <= 0 || n_samples <= 0) return fail(SALSA_EINVAL, "salsa_extract_multichannel: bad argument%s");
-    if (!pl->flex || pl->p.audio_layout != SALSA_LAYOUT_PLANAR)
-        return fail(SALSA_EINVAL, "salsa_extract_multichannel is the contrib (SALSA_FLAG_FLEX) surface, planar audio%s");
-    if (n_channels < 6 || n_channels > SALSA_MAX_MICS || (n_channels & 1))
-        return fail(SALSA_EINVAL, "salsa_extract_multichannel takes an even number of channels from 6 to 16 (pad an odd count with a silent channel; <= 4: salsa_extract_batch)%s");
-    if (n_samples <= pl->p.n_fft / 2) return fail(SALSA_EINVAL, "clip shorter than n_fft/2 samples cannot be reflect-padded%s");
-    const int64_t T64 = 1 + n_samples / pl->p.hop_len;
-    const int OC = 2 * n_channels - 1;
-    if (n_samples * 4 * n_channels >= INT32_MAX || T64 * OC * pl->F >= INT32_MAX / 2 || T64 * n_channels * (pl->nd > 0 ? pl->nd : 1) >= INT32_MAX / 16 ||
-        T64 > 65535 * 16)
-        return fail(SALSA_EINVAL, "clip too long for 32-bit per-clip indexing (split it)%s");
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != pl->device)
-            return fail(SALSA_EINVAL, "the plan's tables live on the device that was current at salsa_plan_create; make it current%s");
-    }
-    hipStream_t s = (hipStream_t)hip_stream;
-    KParams kp = make_kparams(pl, batch, n_samples);
-    kp.nch = n_channels;
-    kp.OC = OC;
-    kp.sc_mean = kp.sc_std = nullptr;
-    const bool full = pl->p.feature_type == SALSA_FEATURE_SALSA;
-    float4 *Xs = nullptr;
-    unsigned *valid = nullptr;
-    if (full) {
-        const size_t need = salsa_multichannel_workspace_bytes(pl, n_channels, batch, n_samples);
-        if (!d_workspace || workspace_bytes < need) return fail(SALSA_EWORKSPACE, "workspace too small%s (need %ld bytes)", "", (long)need);
-        Xs = (float4 *)d_workspace;
-        valid = (unsigned *)((unsigned char *)d_workspace + align256((size_t)batch * kp.T * n_channels * kp.nd * sizeof(float2)));
-    }
-    int rc = n_channels == 6 ? launch_stft_multi<3>(pl, kp, d_audio, d_out, Xs, s)
-           : n_channels == 8 ? launch_stft_multi<4>(pl, kp, d_audio, d_out, Xs, s)
-                             : launch_stft_multi<0>(pl, kp, d_audio, d_out, Xs, s); // 10 - 16: channel count at run time
-    if (rc || !full) return rc;
-    if (kp.tracking && kp.nd > 0) {
-        hipLaunchKernelGGL(tracker_kernel, dim3(tracker_grid(kp)), dim3(64 * TR_WAVES), 0, s, kp, Xs, valid);
-        HIP_TRY(hipGetLastError());
-    }
-    dim3 grid((unsigned)kp.T, (unsigned)kp.B);
-    if (n_channels == 6) hipLaunchKernelGGL(cov_eig_n_kernel<6>, grid, dim3(64), 0, s, kp, Xs, valid, d_out);
-    else if (n_channels == 8) hipLaunchKernelGGL(cov_eig_n_kernel<8>, grid, dim3(64), 0, s, kp, Xs, valid, d_out);
-    else hipLaunchKernelGGL(cov_eig_n_kernel<0>, grid, dim3(64), 0, s, kp, Xs, valid, d_out);
-    HIP_TRY(hipGetLastError());
-    if (!kp.tracking && kp.nd > 0) {
-        hipLaunchKernelGGL(flex_allpass_kernel, dim3((unsigned)((kp.nd + 255) / 256), (unsigned)kp.B), dim3(256), 0, s, kp, d_out);
-        HIP_TRY(hipGetLastError());
-    }
-    return SALSA_OK;
-}
-
-int salsa_logspec_batch(salsa_plan *pl, const float *d_audio, int batch, int n_channels, int64_t n_samples,
-                        float *d_out, void *hip_stream)
-{
-    if (!pl || !d_audio || !d_out || batch <= 0 || n_samples <= 0) return fail(SALSA_EINVAL, "salsa_logspec_batch: bad argument%s");
-    if (n_channels != 4) return fail(SALSA_EINVAL, "salsa_logspec_batch: n_channels must be 4 (pad with silent channels)%s");
-    if (freq_dim(pl->p.n_fft, pl->p.is_compress_high_freq) < 0) return fail(SALSA_ENFFT, "nfft is not 512 or 256%s"); // (MagStftExtractor, :152)
-    if (n_samples <= pl->p.n_fft / 2) return fail(SALSA_EINVAL, "clip shorter than n_fft/2 samples cannot be reflect-padded%s");
-    if (n_samples * 16 >= INT32_MAX || (1 + n_samples / pl->p.hop_len) * 7 * 256 >= INT32_MAX / 2)
-        return fail(SALSA_EINVAL, "clip too long for 32-bit per-clip indexing (split it)%s");
-    KParams kp = make_kparams(pl, batch, n_samples);
-    kp.feature = FEATURE_LOGSPEC_ONLY;
-    kp.OC = 4;
-    kp.sc_mean = kp.sc_std = nullptr; // MagStftExtractor.extract returns raw dB
-    kp.layout = SALSA_LAYOUT_PLANAR;
-    kp.F = freq_dim(pl->p.n_fft, pl->p.is_compress_high_freq);
-    kp.ident = pl->p.is_compress_high_freq ? (pl->p.n_fft == 512 ? 192 : 96) : pl->p.n_fft / 2;
-    kp.compress = pl->p.is_compress_high_freq;
-    kp.spec_lo = 1;
-    kp.spec_hi = kp.ident + 1;
-    return launch_stft(pl, kp, pl->d_window, d_audio, d_out, nullptr, (hipStream_t)hip_stream); // (the spectrogram window: win_len)
-}
-
-int salsa_eigvec_batch(salsa_plan *pl, const float *d_X, int batch, int n_bins, int64_t n_frames, int lower_bin,
-                       double *d_out, unsigned char *d_gate, void *d_workspace, size_t workspace_bytes,
-                       void *hip_stream)
-{
-    if (!pl || !d_X || !d_out || batch <= 0 || n_bins <= 0 || n_frames <= 0)
-        return fail(SALSA_EINVAL, "salsa_eigvec_batch: bad argument%s");
-    if ((int64_t)n_frames * 2 * n_bins >= INT32_MAX) return fail(SALSA_EINVAL, "block too large for 32-bit per-clip indexing%s");
-    const size_t need = salsa_eigvec_workspace_bytes(pl, batch, n_bins, n_frames);
-    if (!d_workspace || workspace_bytes < need) return fail(SALSA_EWORKSPACE, "workspace too small%s (need %ld bytes)", "", (long)need);
-    hipStream_t s = (hipStream_t)hip_stream;
-    KParams kp = make_kparams(pl, batch, 0);
-    kp.T = (int)n_frames;
-    kp.nd = n_bins;
-    kp.lower = lower_bin;
-    kp.upper = lower_bin + n_bins;
-    kp.F = n_bins;
-    kp.feature = SALSA_FEATURE_SALSA;
-    float4 *Xs = (float4 *)d_workspace;
-    unsigned *valid = (unsigned *)((unsigned char *)d_workspace + align256((size_t)batch * n_frames * 4 * n_bins * sizeof(float2)));
-    if ((kp.tracking || kp.flex) && kp.cond > 1.0) {
-        kp.doubt32 = (unsigned *)((unsigned char *)valid + mask_bytes(batch, (size_t)n_frames, n_bins));
-        kp.doubt_flag = (unsigned *)((unsigned char *)kp.doubt32 + mask_bytes(batch, (size_t)n_frames, n_bins));
-    }
-    const long total = (long)batch * n_bins * n_frames * 2;
-    hipLaunchKernelGGL(relayout_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float4 *)d_X, Xs, batch, n_bins, (int)n_frames);
-    HIP_TRY(hipGetLastError());
-    if (kp.tracking) {
-        hipLaunchKernelGGL(tracker_kernel, dim3(tracker_grid(kp)), dim3(64 * TR_WAVES), 0, s, kp, Xs, valid);
-        HIP_TRY(hipGetLastError());
-    }
-    const unsigned ntile = (unsigned)((kp.T + K3_FT - 1) / K3_FT);
-    dim3 grid(ntile, (unsigned)kp.B, (unsigned)((n_bins + K3_NT - 1) / K3_NT));
-    launch_cov_eig<false>(kp, grid, s, Xs, valid, (float *)nullptr, d_out, d_gate);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
-}
-
-int salsa_eigvec_feature_batch(salsa_plan *pl, const float *d_X, int batch, int n_bins, int64_t n_frames, int lower_bin,
-                               float *d_feat, void *d_workspace, size_t workspace_bytes, void *hip_stream)
-{
-    if (!pl || !d_X || !d_feat || batch <= 0 || n_bins <= 0 || n_frames <= 0)
-        return fail(SALSA_EINVAL, "salsa_eigvec_feature_batch: bad argument%s");
-    if ((int64_t)n_frames * 2 * n_bins >= INT32_MAX / 8 || (int64_t)n_frames * 7 * n_bins >= INT32_MAX / 2)
-        return fail(SALSA_EINVAL, "block too large for 32-bit per-clip indexing%s");
-    if ((n_frames + K3_FT - 1) / K3_FT > 65535) return fail(SALSA_EINVAL, "block too long for one launch%s");
-    const size_t need = salsa_eigvec_workspace_bytes(pl, batch, n_bins, n_frames);
-    if (!d_workspace || workspace_bytes < need) return fail(SALSA_EWORKSPACE, "workspace too small%s (need %ld bytes)", "", (long)need);
-    hipStream_t s = (hipStream_t)hip_stream;
-    KParams kp = make_kparams(pl, batch, 0);
-    kp.T = (int)n_frames;
-    kp.nd = n_bins;
-    kp.lower = lower_bin;
-    kp.upper = lower_bin + n_bins;
-    kp.F = n_bins;
-    kp.OC = 7;
-    kp.feature = SALSA_FEATURE_SALSA;
-    float4 *Xs = (float4 *)d_workspace;
-    unsigned *valid = (unsigned *)((unsigned char *)d_workspace + align256((size_t)batch * n_frames * 4 * n_bins * sizeof(float2)));
-    if ((kp.tracking || kp.flex) && kp.cond > 1.0) {
-        kp.doubt32 = (unsigned *)((unsigned char *)valid + mask_bytes(batch, (size_t)n_frames, n_bins));
-        kp.doubt_flag = (unsigned *)((unsigned char *)kp.doubt32 + mask_bytes(batch, (size_t)n_frames, n_bins));
-    }
-    const long total = (long)batch * n_bins * n_frames * 2;
-    hipLaunchKernelGGL(relayout_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float4 *)d_X, Xs, batch, n_bins, (int)n_frames);
-    HIP_TRY(hipGetLastError());
-    if (kp.tracking) {
-        hipLaunchKernelGGL(tracker_kernel, dim3(tracker_grid(kp)), dim3(64 * TR_WAVES), 0, s, kp, Xs, valid);
-        HIP_TRY(hipGetLastError());
-    }
-    const unsigned ntile = (unsigned)((kp.T + K3_FT - 1) / K3_FT);
-    dim3 grid(ntile, (unsigned)kp.B, (unsigned)((n_bins + K3_NT - 1) / K3_NT));
-    launch_cov_eig<true>(kp, grid, s, Xs, valid, d_feat, (double *)nullptr, (unsigned char *)nullptr);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
-}
-
-int salsa_plan_set_fused(salsa_plan *pl, int mode)
-{
-    if (!pl || mode < 0 || mode > 2) return fail(SALSA_EINVAL, "salsa_plan_set_fused: bad argument%s");
-    pl->fused = mode;
-    return SALSA_OK;
-}
-
-int salsa_plan_set_stats(salsa_plan *pl, unsigned long long *d_counters)
-{
-    if (!pl) return fail(SALSA_EINVAL, "salsa_plan_set_stats: NULL plan%s");
-    pl->stats = d_counters;
-    return SALSA_OK;
-}
-
-int salsa_plan_set_timing(salsa_plan *pl, int enable)
-{
-    if (!pl) return fail(SALSA_EINVAL, "salsa_plan_set_timing: NULL plan%s");
-    pl->timing = enable > 0 ? enable : 0; // 1: an event pair around every launch; K > 1: K launches per event pair
-    pl->stop_after = enable < 0 ? (enable >= -2 ? -enable : 0) : 0; // -1 / -2: plain issue of a PREFIX of the path (no events)
-    pl->n_kernels = 0;
-    return SALSA_OK;
-}
-
-int salsa_plan_read_timing(salsa_plan *pl, float *ms, const char **names, int *n_out)
-{
-    if (!pl || !ms || !n_out) return fail(SALSA_EINVAL, "salsa_plan_read_timing: NULL argument%s");
-    *n_out = 0;
-    if (!pl->timing || pl->n_kernels == 0) return SALSA_OK;
-    for (int i = 0; i < pl->n_kernels; i++) {
-        HIP_TRY(hipEventSynchronize(pl->ev1[i]));
-        HIP_TRY(hipEventElapsedTime(&ms[i], pl->ev0[i], pl->ev1[i]));
-        if (pl->timing > 1) ms[i] /= (float)pl->timing; // per launch
-        if (names) names[i] = pl->names[i];
-    }
-    *n_out = pl->n_kernels;
-    return SALSA_OK;
-}
-
-int salsa_scaler_accumulate(const float *d_feat, int batch, int n_channels, int64_t n_frames, int n_freq,
-                            int n_scaler_channels, double *d_sums, void *hip_stream)
-{
-    if (!d_feat || !d_sums || batch <= 0 || n_channels <= 0 || n_frames <= 0 || n_freq <= 0 ||
-        n_scaler_channels <= 0 || n_scaler_channels > n_channels || n_frames >= INT32_MAX)
-        return fail(SALSA_EINVAL, "salsa_scaler_accumulate: bad argument%s");
-    dim3 grid((unsigned)((n_frames + 63) / 64), (unsigned)n_scaler_channels, (unsigned)batch);
-    hipLaunchKernelGGL(scaler_accumulate_kernel, grid, dim3(256), 0, (hipStream_t)hip_stream, d_feat, n_channels,
-                       (int)n_frames, n_freq, n_scaler_channels, d_sums);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
-}
-
-int salsa_normalize_batch(float *d_feat, int batch, int n_channels, int64_t n_frames, int n_freq, int n_scaler_channels,
-                          const float *d_mean, const float *d_std, void *hip_stream)
-{
-    if (!d_feat || !d_mean || !d_std || batch <= 0 || n_channels <= 0 || n_frames <= 0 || n_freq <= 0 ||
-        n_scaler_channels <= 0 || n_scaler_channels > n_channels || n_frames >= INT32_MAX)
-        return fail(SALSA_EINVAL, "salsa_normalize_batch: bad argument%s");
-    const long rows = (long)batch * n_scaler_channels * n_frames;
-    if ((rows + 3) / 4 >= INT32_MAX) return fail(SALSA_EINVAL, "salsa_normalize_batch: too many rows for one launch%s");
-    hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, d_feat,
-                       rows, n_channels, (int)n_frames, n_freq, n_scaler_channels, d_mean, d_std);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
-}
-
-static int ensure_group_streams(salsa_plan *pl)
-{
-    if (pl->streams[0]) return SALSA_OK;
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi); // hi = numerically lowest = highest priority
-    bool ok = true;
-    for (int i = 0; i <= SALSA_MAX_GROUPS && ok; i++)
-        ok = hipStreamCreateWithPriority(&pl->streams[i], hipStreamNonBlocking, i == 0 ? lo : hi) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&pl->cap_stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < SALSA_MAX_GROUPS && ok; i++)
-        ok = hipEventCreateWithFlags(&pl->ev_stft[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&pl->ev_stft2[i], hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i <= SALSA_MAX_GROUPS && ok; i++) ok = hipEventCreateWithFlags(&pl->ev_join[i], hipEventDisableTiming) == hipSuccess;
-    return ok ? SALSA_OK : fail(SALSA_EHIP, "stream / event creation failed%s");
-}
-
-int salsa_plan_set_scaler(salsa_plan *pl, const float *d_mean, const float *d_std)
-{
-    if (!pl || ((d_mean == nullptr) != (d_std == nullptr))) return fail(SALSA_EINVAL, "salsa_plan_set_scaler: bad argument%s");
-    pl->sc_mean = d_mean;
-    pl->sc_std = d_std;
-    return SALSA_OK;
-}
-
-int salsa_plan_set_pipeline(salsa_plan *pl, int n_groups, int flags)
-{
-    if (!pl || n_groups < 1 || (flags & ~(SALSA_PIPE_SPLIT_PAIRS | SALSA_PIPE_GRAPH)))
-        return fail(SALSA_EINVAL, "salsa_plan_set_pipeline: bad argument%s");
-    if (n_groups > 1 || (flags & SALSA_PIPE_SPLIT_PAIRS)) { // the plan-owned streams are only created when a pipeline is requested
-        const int rc = ensure_group_streams(pl);
-        if (rc) return rc;
-    }
-    pl->n_groups = n_groups > SALSA_MAX_GROUPS ? SALSA_MAX_GROUPS : n_groups;
-    pl->pipe_flags = flags;
-    return SALSA_OK;
-}
-
-int salsa_plan_set_groups(salsa_plan *pl, int n_groups)
-{
-    if (!pl) return fail(SALSA_EINVAL, "salsa_plan_set_groups: bad argument%s");
-    return salsa_plan_set_pipeline(pl, n_groups, pl->pipe_flags);
-}
-
-int salsa_augment_batch(const float *d_in, int64_t in_batch_stride, int64_t in_channel_stride, float *d_out, int batch,
-                        int64_t n_frames, int n_freq, int audio_format, int n_zero_channels, const int *d_params,
-                        const float *d_uval, const float *d_minmax, void *hip_stream)
-{
-    if (in_channel_stride < n_frames * n_freq || in_batch_stride < 7 * in_channel_stride)
-        return fail(SALSA_EINVAL, "salsa_augment_batch: input strides smaller than the [7][T][F] block%s");
-    if (!d_in || !d_out || d_in == d_out || !d_params || !d_uval || !d_minmax || batch <= 0 || batch > 65535 || n_frames <= 0 ||
-        n_freq <= 1 || n_frames * n_freq >= INT32_MAX || n_zero_channels < 0 || n_zero_channels > 7)
-        return fail(SALSA_EINVAL, "salsa_augment_batch: bad argument%s");
-    if (audio_format != SALSA_FORMAT_FOA && audio_format != SALSA_FORMAT_MIC) return fail(SALSA_EFORMAT, "Unknown audio format%s");
-    const long n = (long)n_frames * n_freq;
-    hipLaunchKernelGGL(augment_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, (hipStream_t)hip_stream,
-                       d_in, (long)in_batch_stride, (long)in_channel_stride, d_out, (int)n_frames, n_freq, audio_format,
-                       n_zero_channels, d_params, d_uval, d_minmax);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
-}
-
-int salsa_augment_gcc_batch(const float *d_in, int64_t in_batch_stride, int64_t in_channel_stride, float *d_out, int batch,
-                            int64_t n_frames, int n_freq, const int *d_params, const float *d_uval, const float *d_minmax,
-                            void *hip_stream)
-{
-    if (in_channel_stride < n_frames * n_freq || in_batch_stride < 10 * in_channel_stride)
-        return fail(SALSA_EINVAL, "salsa_augment_gcc_batch: input strides smaller than the [10][T][F] block%s");
-    if (!d_in || !d_out || d_in == d_out || !d_params || !d_uval || !d_minmax || batch <= 0 || batch > 65535 || n_frames <= 0 ||
-        n_freq <= 1 || n_frames * n_freq >= INT32_MAX)
-        return fail(SALSA_EINVAL, "salsa_augment_gcc_batch: bad argument%s");
-    const long n = (long)n_frames * n_freq;
-    hipLaunchKernelGGL(augment_gcc_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, (hipStream_t)hip_stream,
-                       d_in, (long)in_batch_stride, (long)in_channel_stride, d_out, (int)n_frames, n_freq, d_params, d_uval, d_minmax);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
-}
-
-int salsa_selftest_decibel(const float *d_power, float *d_db, int64_t n, void *hip_stream)
-{
-    if (!d_power || !d_db || n <= 0 || (n + 255) / 256 >= INT32_MAX) return fail(SALSA_EINVAL, "salsa_selftest_decibel: bad argument%s");
-    hipLaunchKernelGGL(db10_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, d_power, d_db, (long)n);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
-}
-
-int salsa_to_freq_major(const float *d_feat, int64_t n_rows, int64_t n_frames, int n_freq, double *d_out, void *hip_stream)
-{
-    if (!d_feat || !d_out || n_rows <= 0 || n_frames <= 0 || n_freq <= 0 || n_rows > 65535 || (n_frames + 63) / 64 > 65535)
-        return fail(SALSA_EINVAL, "salsa_to_freq_major: bad argument%s");
-    dim3 grid((unsigned)((n_freq + 63) / 64), (unsigned)((n_frames + 63) / 64), (unsigned)n_rows);
-    hipLaunchKernelGGL(to_freq_major_kernel, grid, dim3(256), 0, (hipStream_t)hip_stream, d_feat, d_out, (int)n_frames, n_freq);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
-}
-
-int salsa_resample_batch(const float *d_x, int n_rows, int64_t n_in, float *d_y, int64_t n_out, int64_t n_out_fixed, double sample_ratio,
-                         const double *d_interp_win, const double *d_interp_delta, int n_win, int num_table,
-                         const double *d_time_register, void *hip_stream)
-{
-    if (!d_x || !d_y || !d_interp_win || !d_interp_delta || !d_time_register || n_rows <= 0 || n_rows > 65535 || n_in <= 0 ||
-        n_out < 0 || n_out_fixed < n_out || n_out_fixed <= 0 || !(sample_ratio > 0.0) || n_win <= 0 || num_table <= 0 ||
-        (n_out_fixed + 255) / 256 >= INT32_MAX)
-        return fail(SALSA_EINVAL, "salsa_resample_batch: bad argument%s");
-    const double scale = sample_ratio < 1.0 ? sample_ratio : 1.0;          // resampy/interpn.py: scale = min(1.0, sample_ratio)
-    const int index_step = (int)(scale * (double)num_table);              //                     index_step = int(scale * num_table)
-    if (index_step < 1) return fail(SALSA_EINVAL, "salsa_resample_batch: sample_ratio * num_table < 1%s");
-    dim3 grid((unsigned)((n_out_fixed + 255) / 256), (unsigned)n_rows);
-    hipLaunchKernelGGL(resample_kernel, grid, dim3(256), 0, (hipStream_t)hip_stream, d_x, d_y, (long)n_in, (long)n_out, (long)n_out_fixed,
-                       d_interp_win, d_interp_delta, n_win, num_table, scale, index_step, d_time_register);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
-}
-
-int salsa_pcm_to_planar(const void *d_pcm, int sample_format, int n_channels, int64_t n_frames, float *d_out, void *hip_stream)
-{
-    if (!d_pcm || !d_out || n_channels <= 0 || n_channels > 64 || n_frames <= 0 || (n_frames + 255) / 256 >= INT32_MAX)
-        return fail(SALSA_EINVAL, "salsa_pcm_to_planar: bad argument%s");
-    const size_t fb = (size_t)n_channels * (sample_format == SALSA_PCM_S16 ? 2 : sample_format == SALSA_PCM_U8 ? 1 : 4);
-    if (n_channels == 4 && ((uintptr_t)d_pcm % fb)) return fail(SALSA_EINVAL, "salsa_pcm_to_planar: d_pcm must be aligned to one frame%s");
-    dim3 grid((unsigned)((n_frames + 255) / 256));
-    hipStream_t s = (hipStream_t)hip_stream;
-    switch (sample_format) {
-    case SALSA_PCM_S16: hipLaunchKernelGGL(pcm_to_planar_kernel<short>, grid, dim3(256), 0, s, d_pcm, d_out, (long)n_frames, n_channels); break;
-    case SALSA_PCM_S32: hipLaunchKernelGGL(pcm_to_planar_kernel<int>, grid, dim3(256), 0, s, d_pcm, d_out, (long)n_frames, n_channels); break;
-    case SALSA_PCM_U8: hipLaunchKernelGGL(pcm_to_planar_kernel<unsigned char>, grid, dim3(256), 0, s, d_pcm, d_out, (long)n_frames, n_channels); break;
-    case SALSA_PCM_F32: hipLaunchKernelGGL(pcm_to_planar_kernel<float>, grid, dim3(256), 0, s, d_pcm, d_out, (long)n_frames, n_channels); break;
-    default: return fail(SALSA_EINVAL, "salsa_pcm_to_planar: unknown sample format%s");
+    const bool lite = kp.feature == SALSA_FEATURE_LITE;
+    constexpr int NF = 4;
+    dim3 grid((unsigned)((kp.T + 4 * NF - 1) / (4 * NF)), (unsigned)kp.B);
+    if (pl->p.n_fft == 512) {
+        if (lite) hipLaunchKernelGGL((stft_kernel<512, double, true, NF, NPAIRS>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
+        else hipLaunchKernelGGL((stft_kernel<512, double, false, NF, NPAIRS>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
+    } else {
+        if (lite) hipLaunchKernelGGL((stft_kernel<256, double, true, NF, NPAIRS>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
+        else hipLaunchKernelGGL((stft_kernel<256, double, false, NF, NPAIRS>), grid, dim3(256), 0, s, kp, d_audio, pl->d_window, pl->d_tw, d_out, Xs);
     }
     HIP_TRY(hipGetLastError());
     return SALSA_OK;
 }
+template int launch_stft_multi<3>(salsa_plan *, const KParams &, const float *, float *, float4 *, hipStream_t);
+template int launch_stft_multi<4>(salsa_plan *, const KParams &, const float *, float *, float4 *, hipStream_t);
+template int launch_stft_multi<0>(salsa_plan *, const KParams &, const float *, float *, float4 *, hipStream_t);
 
-} // extern "C"
+} // namespace salsa_impl

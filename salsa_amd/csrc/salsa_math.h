@@ -2,8 +2,8 @@
 //
 // Everything here is register-level math with no memory traffic: the radix-8/4 butterflies of the LDS-staged FFT, the
 // packed-real-FFT unpack, the 4x4 Hermitian covariance / eigen-gate / principal-eigenvector solver and the FOA / MIC
-// normalisations.  The kernels in salsa_kernels.hip own all addressing and staging.  The same header compiles with
-// g++ (tests/hostemu) so this arithmetic is unit-tested on CPU against the oracle before it ever runs on a GPU; that
+// normalisations.  The kernels (salsa_kernels.hip, fused_kernel.hip, multichannel.hip) own all addressing and
+// staging.  The same header compiles with g++ (tests/hostemu) so this arithmetic is unit-tested on CPU against the oracle before it ever runs on a GPU; that
 // host build is a test harness, never a fallback of the product.
 //
 // Reference semantics implemented (paths relative to the upstream repo):

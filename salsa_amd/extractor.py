@@ -1,7 +1,8 @@
 """Device-side front end: a plan over libsalsa_hip.so operating on torch CUDA(HIP) tensors.
 
 torch is plumbing only (device memory, streams): every FLOP of the feature path runs in the hand-written HIP kernels
-of salsa_amd/csrc/salsa_kernels.hip behind the C ABI of include/salsa_hip.h."""
+of salsa_amd/csrc (salsa_kernels.hip: STFT, tracker, covariance / eigen; the plan and its schedules: salsa_plan.hip) behind the
+C ABI of include/salsa_hip.h."""
 import contextlib
 import ctypes as C
 
