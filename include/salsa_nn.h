@@ -299,6 +299,30 @@ int salsa_nn_seld_score2020(const int16_t *pred_rows, const int *pred_counts, in
  * float64 degrees (tools/probe_score_distance.py measures its deviation from the host's, which sizes `margin`). */
 int salsa_nn_seld_distance(const int16_t *quads, int64_t n, double *out, void *hip_stream);
 
+/* Test-time augmentation and model ensembling around the forward (salsa_amd/csrc/tta.hip, statements in tta.h).
+ * kind: 1 foa (V = 16 variants, 7 channels), 2 mic (V = 8, 7 channels), 3 gcc (V = 4, 10 channels) -- SALSA_BANK_FOA / _MIC / _GCC.
+ * Variant v of foa / mic has the swap bits m[j] = (v >> j) & 1; of gcc: v = 0 no swap, v = 1, 2, 3 the one-hot m with bit v - 1 set.
+ *
+ * salsa_nn_tta_variant: d_out float32 dense [batch][C][n_frames][n_freq] = the channel swap of variant v applied to d_in, bit-equal
+ * to the training augmentation's swap (salsa_augment_batch / salsa_augment_gcc_batch with no shift and no cutout: the same
+ * per-element code).  d_in: float32 [batch][C][n_frames][n_freq] with dense (n_frames, n_freq) blocks and the given batch / channel
+ * strides in elements (a time-cropped view needs no copy); not d_out.  16-byte accesses when n_frames * n_freq, both strides (and
+ * for gcc n_freq) are multiples of four and both pointers are 16-byte aligned, 4-byte accesses otherwise.
+ *
+ * salsa_nn_tta_merge: the N = n_models * n_variants forward outputs in the slabs d_prob_slab [N][batch][label_frames][n_classes] and
+ * d_xyz_slab [N][..][3 n_classes] (blocks x | y | z), slab n = model * n_variants + i holding the output for variant variant_ids[i]:
+ * every xyz is rotated back by the inverse of the target swap of its variant (exact: selection and negation), then prob and xyz are
+ * added in float32 in slab order starting from slab 0 and divided once by float(N), correctly rounded.  variant_ids is a HOST array
+ * of n_variants <= 16 ids (any order, each in [0, V)); it is read during the call and travels in the kernel arguments.  Outputs
+ * [batch][label_frames][n_classes] and [..][3 n_classes], every element written.  Bit-reproducible (no atomics).
+ *
+ * Both return 0; -1, before any device call and with the reason in salsa_last_error, for an unknown kind, a variant id outside
+ * [0, V), N < 1, a NULL pointer, a non-positive or oversized shape, or input strides smaller than the block; -6 when the launch fails. */
+int salsa_nn_tta_variant(const float *d_in, int64_t in_batch_stride, int64_t in_channel_stride, float *d_out, int batch, int n_frames,
+                         int n_freq, int kind, int v, void *hip_stream);
+int salsa_nn_tta_merge(const float *d_prob_slab, const float *d_xyz_slab, int n_models, const int *variant_ids, int n_variants, int kind,
+                       int batch, int label_frames, int n_classes, float *d_prob_out, float *d_xyz_out, void *hip_stream);
+
 /* The decoder's frequency mean (reference models/decoders.py: x.mean(dim=3) then (B, C, T) -> (B, T, C)) in one pass:
  * x bf16 channels-last [N][H][W][C] -> float32 y [H][N][C] (time_major != 0: the GRU scans' order) or [N][H][C]; C % 8 == 0.
  * _bwd: dx[n][h][w][c] = g[row(n, h)][c] / W, bf16 channels-last. */

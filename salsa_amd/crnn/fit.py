@@ -43,12 +43,15 @@ def _ckpt_files(d):
 
 
 def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, combine_method='mean', sed_threshold=0.3,
-             doa_threshold=20, eval_version='2021', sub_batch=8, return_rows=False):
+             doa_threshold=20, eval_version='2021', sub_batch=8, return_rows=False, tta=None):
     """One validation pass (models/seld_models.py:96-108 + interfaces.py:163-180): every clip of ``val_bank`` through
     infer_pipelined(Trainer.infer) in test chunks, rows against ``val_gt`` (per clip a list of rows, metrics.load_dcase_csv).  On the
     GPU the rows are decoded and scored on the device (DeviceSeldScore / DeviceSeldScore2020 by eval_version), on the CPU by the host
-    classes.  -> dict valER valF1 valLE valLR valSeld (+ the scorer under 'scorer', and 'rows' when asked)."""
+    classes.  tta = (audio_format, feature_type) or a tta.TtaForward: the forward is Trainer.infer under test-time augmentation (all
+    channel-swap variants, the trainer's n_classes and output_format); None: Trainer.infer itself.
+    -> dict valER valF1 valLE valLR valSeld (+ the scorer under 'scorer', and 'rows' when asked)."""
     from .infer import infer_pipelined
+    from .tta import wrap_forward
     from .metrics import SeldMetrics, SeldMetrics2020
     from .score import DeviceSeldScore, DeviceSeldScore2020, gt_rows_to_device
     if eval_version not in ('2020', '2021'):
@@ -61,16 +64,17 @@ def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, comb
     n_label = val_bank.clip_len[0] // val_bank.upsample
     nc, rate = trainer.n_classes, val_bank.label_rate
     on_gpu = trainer.device.type == 'cuda'
+    forward = wrap_forward(trainer.infer, tta, nc, trainer.output_format)
     kw = dict(sub_batch=sub_batch, sed_threshold=sed_threshold, n_label_frames=n_label, chunk_len=chunk_len, chunk_hop_len=chunk_hop_len,
               combine_method=combine_method, n_classes=nc,
               eval_version='2020')       # (the ROW shape only: (frame, class, azimuth, elevation), what SeldMetrics.update reads)
     if on_gpu:
         scorer = (DeviceSeldScore2020 if eval_version == '2020' else DeviceSeldScore)(nc, doa_threshold, rate)
         gt_rows, gt_counts = gt_rows_to_device(val_gt, trainer.device)
-        rows = infer_pipelined(n, val_bank.clip_batch, trainer.infer, decode='device', score=(gt_rows, gt_counts, scorer), **kw)
+        rows = infer_pipelined(n, val_bank.clip_batch, forward, decode='device', score=(gt_rows, gt_counts, scorer), **kw)
     else:
         scorer = (SeldMetrics2020 if eval_version == '2020' else SeldMetrics)(nc, doa_threshold)
-        rows = infer_pipelined(n, val_bank.clip_batch, trainer.infer, decode='host', **kw)
+        rows = infer_pipelined(n, val_bank.clip_batch, forward, decode='host', **kw)
         for pred, gt in zip(rows, val_gt):
             scorer.update(pred, gt, max_frames=n_label, label_rate=rate)
     ER, F, LE, LR = (float(v) for v in scorer.scores())
@@ -106,13 +110,14 @@ def _load(path, trainer, loader):
 def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, max_epochs=50, epochs=None, milestones=MILESTONES,
         lrs=LRS, moms=MOMS, val_interval=1, train_fraction=1.0, audio_format='foa', feature_type='salsa', augment=True, seed=2021,
         mode='crossval', eval_version='2021', resume=False, chunk_len=None, chunk_hop_len=None, combine_method='mean',
-        sed_threshold=0.3, doa_threshold=20, val_sub_batch=8, loader=None):
+        sed_threshold=0.3, doa_threshold=20, val_sub_batch=8, loader=None, tta=None):
     """Train ``trainer`` for ``max_epochs`` epochs of ``bank`` (a finalized GpuFeatureBank).  The keywords are the YAML's keys
     (INTEGRATION.md has the table): batch_size = training.train_batch_size; milestones / lrs / moms = training.lr_scheduler.*;
     max_epochs, val_interval = training.*; train_fraction, n_classes (Trainer's) = data.*; eval_version; mode ('crossval': the best
     checkpoint by valSeld is kept, 'eval': the latest only).  ``epochs`` caps how many epochs THIS call runs (time-sliced jobs);
     ``resume`` continues from the lexicographically last file of <out_dir>/checkpoint (train.py:37-45; none there: from scratch).
-    val_bank / val_gt: the validation clips and their ground-truth rows; chunk_len .. sed_threshold go to the validation pass.
+    val_bank / val_gt: the validation clips and their ground-truth rows; chunk_len .. sed_threshold and tta go to the validation pass
+    (validate).
     -> the history: dict(steps=[epoch, step, lr, mom, loss, sed_loss, doa_loss per step], val=[dict per validated epoch],
     best=dict | None, epoch=epochs finished, global_step)."""
     from ..dataset import BankLoader
@@ -152,7 +157,7 @@ def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, 
         val = None
         if val_bank is not None and (epoch + 1) % val_interval == 0:
             val = validate(trainer, val_bank, val_gt, chunk_len, chunk_hop_len, combine_method, sed_threshold, doa_threshold,
-                           eval_version, val_sub_batch)
+                           eval_version, val_sub_batch, tta=tta)
             val.pop('scorer')
             val['epoch'] = epoch
             history['val'].append(val)

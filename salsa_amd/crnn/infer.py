@@ -47,7 +47,7 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
                     as_array: bool = False, stamps: Optional[list] = None, chunk_len: Optional[int] = None,
                     chunk_hop_len: Optional[int] = None, decode: str = 'host', combine_method: str = 'mean',
                     eval_version: str = '2021', n_classes: int = 12, chunk_batch: Optional[int] = None,
-                    score: Optional[tuple] = None) -> list:
+                    score: Optional[tuple] = None, tta=None) -> list:
     """featurize(lo, hi) -> feature tensor [hi - lo, 7, T, F] of items lo..hi-1 on the model's device; forward(features) ->
     (event probabilities [b, n_label_frames, 12], xyz [b, n_label_frames, 36]).  Returns the DCASE rows of every item, in
     item order.  The device is never idle waiting for the host: up to `depth` sub-batches are in flight.
@@ -64,7 +64,12 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
     (score.gt_rows_to_device) and a score.DeviceSeldScore.  Each sub-batch's rows are scored against their slice of the ground truth
     on the same stream right behind the decode launch (score.score_dcase_rows_async, with the accumulator's n_classes, threshold,
     label_rate and margin) and merged into the accumulator when the sub-batch is finished.  The rows returned are unchanged.  The
-    TYPE of the accumulator selects the metric (score.DeviceSeldScore2020: the SELD 2020 one); eval_version only shapes the rows."""
+    TYPE of the accumulator selects the metric (score.DeviceSeldScore2020: the SELD 2020 one); eval_version only shapes the rows.
+
+    tta = (audio_format, feature_type), or a ready tta.TtaForward (which carries its own forwards): test-time augmentation.  forward is
+    wrapped in a TtaForward over all channel-swap variants of that recipe (n_classes as given, output_format 'reg_xyz'), so each
+    forward call -- with chunks: each chunk batch -- returns the merged outputs; everything behind the forward is untouched.  None:
+    forward is called as it is."""
     import torch
     assert depth >= 1 and sub_batch >= 1
     if decode not in ('host', 'device'):
@@ -81,6 +86,9 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
         gt_rows, gt_counts, accumulator = score
         if gt_rows.shape[0] != n_items or gt_counts.shape[0] != n_items:
             raise ValueError('score=: ground truth of %d files for %d items' % (gt_rows.shape[0], n_items))
+    if tta is not None:
+        from .tta import wrap_forward
+        forward = wrap_forward(forward, tta, n_classes)
     results = [None] * n_items
     slots: Dict[int, dict] = {}
     pending = collections.deque()
@@ -155,7 +163,7 @@ def infer_clips_sharded(names: Sequence[str], featurize: Callable[[List[str]], '
                         sed_threshold: float = 0.3, n_label_frames: int = 600, gather: bool = True, depth: int = 2,
                         stamps: Optional[list] = None, chunk_len: Optional[int] = None, chunk_hop_len: Optional[int] = None,
                         decode: str = 'host', combine_method: str = 'mean', eval_version: str = '2021', n_classes: int = 12,
-                        chunk_batch: Optional[int] = None, score: Optional[tuple] = None) -> Dict[str, list]:
+                        chunk_batch: Optional[int] = None, score: Optional[tuple] = None, tta=None) -> Dict[str, list]:
     """names: all clip names (any order; sharded over the SORTED list).  featurize(list of names) -> feature tensor
     [b, 7, T, F] on the model's device (e.g. SalsaExtractor.extract of the clips' audio with the scaler attached, cropped
     to 8 * n_label_frames frames); forward(features) -> (event probabilities [b, n_label_frames, 12], xyz [b, .., 36]), e.g.
@@ -163,12 +171,12 @@ def infer_clips_sharded(names: Sequence[str], featurize: Callable[[List[str]], '
     chunk_len, chunk_hop_len, decode, combine_method, eval_version, n_classes, chunk_batch: infer_pipelined's test-chunk and
     device-decoding options, handed through.  score = (gt_rows, gt_counts, accumulator): infer_pipelined's, for THIS rank's shard
     (the ground truth of shard_list(sorted(names), rank, world), in that order); every rank's accumulator holds its shard's score,
-    to be combined with DeviceSeldScore.merge."""
+    to be combined with DeviceSeldScore.merge.  tta: infer_pipelined's, handed through."""
     mine = shard_list(sorted(names), rank, world)
     rows = infer_pipelined(len(mine), lambda lo, hi: featurize(mine[lo:hi]), forward, sub_batch=sub_batch, depth=depth,
                            sed_threshold=sed_threshold, n_label_frames=n_label_frames, stamps=stamps, chunk_len=chunk_len,
                            chunk_hop_len=chunk_hop_len, decode=decode, combine_method=combine_method, eval_version=eval_version,
-                           n_classes=n_classes, chunk_batch=chunk_batch, score=score)
+                           n_classes=n_classes, chunk_batch=chunk_batch, score=score, tta=tta)
     out = dict(zip(mine, rows))
     if gather and world > 1:
         import torch.distributed as dist

@@ -148,3 +148,15 @@ class Trainer:
             xyz = out['doa_frame_output'].float()
             return accdoa_sed(xyz, self.raw_model.decoder.n_classes), xyz
         return torch.sigmoid(out['event_frame_logit'].float()), out['doa_frame_output'].float()
+
+    def infer_tta(self, x, audio_format=None, feature_type='salsa', variants='all'):
+        """infer under test-time augmentation (tta.TtaForward over this trainer's infer, output_format and n_classes): the merged SED
+        activities and xyz of the selected channel-swap variants of x.  audio_format None: 'foa'.  The wrapper, with its buffers, is
+        kept per (audio_format, feature_type, variants)."""
+        from .tta import TtaForward
+        key = (audio_format or 'foa', feature_type, variants if isinstance(variants, str) or variants is None else tuple(variants))
+        cache = self.__dict__.setdefault('_tta', {})
+        if key not in cache:
+            cache[key] = TtaForward(self.infer, key[0], feature_type, variants=variants, n_classes=self.n_classes,
+                                    output_format=self.output_format)
+        return cache[key](x)

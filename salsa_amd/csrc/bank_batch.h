@@ -80,6 +80,31 @@ BANK_HD int shift_source(const int *p, int f, int F)
     return fs;
 }
 
+// The channel swap of the seven FOA / MIC SALSA (and IV) rows of one (frame, bin), in place: p[0..3] the swap bits (MIC: three).  The
+// MIC bits act one after the other on the running values, so several set bits give the reference's sequential float32 differences.
+// augment7's swap and tta.h's variant body are this one statement.
+BANK_HD void swap7(float *x, bool mic, const int *p)
+{
+    if (!mic) { // W Y Z X | Iy Iz Ix : swap x<->y, negate x, y, z
+        if (p[0]) { float a = x[1]; x[1] = x[3]; x[3] = a; a = x[4]; x[4] = x[6]; x[6] = a; }
+        if (p[1]) x[6] = -x[6];
+        if (p[2]) x[4] = -x[4];
+        if (p[3]) x[5] = -x[5];
+    } else {    // M1 M2 M3 M4 | p12 p13 p14
+        if (p[0]) { float a = x[1]; x[1] = x[2]; x[2] = a; a = x[4]; x[4] = x[5]; x[5] = a; }
+        if (p[1]) {
+            const float c0 = x[0], c3 = x[3], c4 = x[4], c5 = x[5], c6 = x[6];
+            x[0] = c3; x[3] = c0;
+            x[6] = -c6; x[5] = c5 - c6; x[4] = c4 - c6;
+        }
+        if (p[2]) {
+            const float c0 = x[0], c1 = x[1], c2 = x[2], c3 = x[3], c4 = x[4], c5 = x[5], c6 = x[6];
+            x[0] = c1; x[1] = c0; x[2] = c3; x[3] = c2;
+            x[4] = -c4; x[5] = c6 - c4; x[6] = c5 - c4;
+        }
+    }
+}
+
 // FOA / MIC SALSA (and IV) rows: src = the sample's (channel 0, frame 0, bin 0), chan = elements between its channels; dst = the
 // output element of channel 0, plane = elements between the output's channels.  minmax = the sample's (lo, hi).
 BANK_HD void augment7(const float *src, int64_t chan, float *dst, int64_t plane, int t, int f, int F, bool mic, int n_zero,
@@ -100,24 +125,7 @@ BANK_HD void augment7(const float *src, int64_t chan, float *dst, int64_t plane,
 #pragma unroll
 #endif
     for (int c = 0; c < 7; c++) x[c] = src[c * chan + (int64_t)t * F + fs];
-    if (!mic) { // W Y Z X | Iy Iz Ix : swap x<->y, negate x, y, z
-        if (p[0]) { float a = x[1]; x[1] = x[3]; x[3] = a; a = x[4]; x[4] = x[6]; x[6] = a; }
-        if (p[1]) x[6] = -x[6];
-        if (p[2]) x[4] = -x[4];
-        if (p[3]) x[5] = -x[5];
-    } else {    // M1 M2 M3 M4 | p12 p13 p14
-        if (p[0]) { float a = x[1]; x[1] = x[2]; x[2] = a; a = x[4]; x[4] = x[5]; x[5] = a; }
-        if (p[1]) {
-            const float c0 = x[0], c3 = x[3], c4 = x[4], c5 = x[5], c6 = x[6];
-            x[0] = c3; x[3] = c0;
-            x[6] = -c6; x[5] = c5 - c6; x[4] = c4 - c6;
-        }
-        if (p[2]) {
-            const float c0 = x[0], c1 = x[1], c2 = x[2], c3 = x[3], c4 = x[4], c5 = x[5], c6 = x[6];
-            x[0] = c1; x[1] = c0; x[2] = c3; x[3] = c2;
-            x[4] = -c4; x[5] = c6 - c4; x[6] = c5 - c4;
-        }
-    }
+    swap7(x, mic, p);
 #if defined(__HIPCC__)
 #pragma unroll
 #endif

@@ -6,8 +6,8 @@
 //   salsa_plan.hip      host code only: the plan, the schedules of salsa_extract_batch, the one error message
 // A unit's kernels stay in its own anonymous namespace; another unit reaches them through the launchers declared at the end of this
 // file.  The library is built without -fvisibility=hidden, so everything that crosses a unit boundary is marked SALSA_LOCAL: the
-// shared object exports the C ABI of include/*.h and nothing more.  baseline_kernels.hip and bank_batch.hip include this header for
-// salsa_set_last_error_ alone.
+// shared object exports the C ABI of include/*.h and nothing more.  baseline_kernels.hip, bank_batch.hip and tta.hip include this header
+// for salsa_set_last_error_ alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
