@@ -160,7 +160,8 @@ int salsa_plan_set_stats(salsa_plan *plan, unsigned long long *d_counters);
 
 /* compute_scaler (salsa_feature_extraction.py:204-262) on device: accumulate float64 sum / sum-of-squares over time of
  * the first n_scaler_channels channels per frequency into d_sums [2][n_scaler_channels][n_freq] (zeroed by the caller
- * once; mean = sum/n, std = sqrt(sumsq/n - mean^2), population variance like sklearn's StandardScaler). */
+ * once; mean = sum/n, std = sqrt(sumsq/n - mean^2), population variance like sklearn's StandardScaler).  batch and
+ * n_scaler_channels are grid dimensions of the one launch: above 65535 either is SALSA_EINVAL. */
 int salsa_scaler_accumulate(const float *d_feat, int batch, int n_channels, int64_t n_frames, int n_freq,
                             int n_scaler_channels, double *d_sums, void *hip_stream);
 /* normalise-on-load (dataset/database.py:197-202): d_feat[:, :n_scaler_channels] = (x - mean) / std in place;

@@ -342,7 +342,8 @@ int salsa_nn_freq_pool_bwd(const float *g, const uint8_t *argmax, void *dx, int6
                            void *hip_stream);
 
 /* Column sums of one or two float32 row-major [M][C] matrices, ADDED to out_a / out_b (zero them first; b may be NULL): the GRU's
- * bias gradients db_ih = sum_(t,b) dgi, db_hh = sum_(t,b) dgh in one launch (torch's reduction / a ones-vector GEMV: ~17 us each). */
+ * bias gradients db_ih = sum_(t,b) dgi, db_hh = sum_(t,b) dgh in one launch (torch's reduction / a ones-vector GEMV: ~17 us each).
+ * M <= 65535 * 64 (one workgroup row per 64 matrix rows); more is -1, before any launch. */
 int salsa_nn_colsum2(const float *a, const float *b, float *out_a, float *out_b, int64_t M, int C, void *hip_stream);
 
 /* Deterministic weight gradients (round 4).  Every weight-gradient kernel (salsa_nn_conv3x3_c64_wrw, _stem_wrw, _stem_wrw_bn,

@@ -209,6 +209,8 @@ int salsa_scaler_accumulate(const float *d_feat, int batch, int n_channels, int6
     if (!d_feat || !d_sums || batch <= 0 || n_channels <= 0 || n_frames <= 0 || n_freq <= 0 ||
         n_scaler_channels <= 0 || n_scaler_channels > n_channels || n_frames >= INT32_MAX)
         return fail(SALSA_EINVAL, "salsa_scaler_accumulate: bad argument%s");
+    if (batch > 65535 || n_scaler_channels > 65535) // grid z and grid y
+        return fail(SALSA_EINVAL, "salsa_scaler_accumulate: batch or scaler channels exceed one launch's grid%s");
     dim3 grid((unsigned)((n_frames + 63) / 64), (unsigned)n_scaler_channels, (unsigned)batch);
     hipLaunchKernelGGL(scaler_accumulate_kernel, grid, dim3(256), 0, (hipStream_t)hip_stream, d_feat, n_channels,
                        (int)n_frames, n_freq, n_scaler_channels, d_sums);

@@ -1540,6 +1540,7 @@ int salsa_nn_colsum2(const float *a, const float *b, float *out_a, float *out_b,
 {
     if (!a || !out_a || (b && !out_b) || M <= 0 || C <= 0) return -1;
     const int rpb = 64; // rows per workgroup: 16 per row lane
+    if (M > 65535L * rpb) return -1; // ceil(M / rpb) is grid y
     const unsigned gy = (unsigned)((M + rpb - 1) / rpb);
     int rc = 0;
     float *part = salsa_nn_det_begin((int)gy, 2L * C, (hipStream_t)hip_stream, &rc);

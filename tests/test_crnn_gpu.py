@@ -924,7 +924,8 @@ def test_fused_seld_loss_matches_the_eager_loss():
     """salsa_nn_seld_loss / _bwd (loss + gradients in one launch each) against the eager torch expression of crnn/loss.py
     (reference models/interfaces.py:304-355): the three values to 1e-6 relative, the gradients w.r.t. both predictions to 1e-6
     of their scale, also when the detached parts receive gradients of their own; a batch with no active class gives nan in
-    both (0 / 0), as the reference does."""
+    both (0 / 0), as the reference does.  This is the autograd path at the training shape; the kernels themselves are held to
+    float64 over shapes, masks, extreme logits and every combination of incoming gradients in tests/test_small_kernels_gpu.py."""
     from salsa_amd.crnn import loss as L
     dev = torch.device('cuda:0')
     g = torch.Generator(device='cpu').manual_seed(5)
