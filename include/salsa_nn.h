@@ -245,6 +245,38 @@ int salsa_nn_accdoa_loss(const float *doa, const float *sed_gt, const float *doa
  * xyz [rows][3 nc], float32, bit-equal to numpy's float32 expression (no fma, correctly rounded square root). */
 int salsa_nn_accdoa_sed(const float *xyz, float *sed, int64_t rows, int nc, void *hip_stream);
 
+/* The Multi-ACCDOA output format (output_format 'multi_accdoa'; salsa_amd/csrc/multi_accdoa.hip, statements in
+ * multi_accdoa.h).  C = n_real_classes; three tracks (prediction) / slots (label) per class as pseudo-classes p = n C + c of the usual
+ * layout: sed_gt [rows][3 C] in {0, 1}, doa and doa_gt [rows][9 C] (blocks x | y | z of 3 C columns), float32 contiguous.
+ *
+ * salsa_nn_adpit_loss: auxiliary duplicating permutation-invariant training.  Per item (row, c): the slots with sed_gt > 0.5 are
+ * compacted in slot order into k sources; the candidate assignments (track 0, 1, 2 -> source) are, in index order, k = 0: the zero
+ * target; k = 1: 000; k = 2: 001 010 011 100 101 110; k = 3: 012 021 102 120 201 210.  The cost of a candidate is the sum over
+ * tracks (outer) and axes (inner) of (P - T)^2, one running float64 sum without fma; the chosen candidate is the lowest index of the
+ * least cost (a later one wins only when strictly smaller, so a NaN cost never displaces an earlier candidate); the item loss is
+ * cost / 9 and loss = sum of the items / (rows C), float64 partial sums per workgroup added in a fixed order: bit-reproducible.
+ * out3 = {loss, 0, loss}; g_doa = (float)(2 (P - T_chosen) / (9 rows C)) in float64; g_logit, when not NULL, [rows][3 C] filled with
+ * zeros; chosen, when not NULL, [rows][C] the candidate indices.  The backward is salsa_nn_seld_loss_bwd with w_sed = 0, w_doa = 1.
+ * Returns 0; -1, before any device call, for a NULL required pointer, rows < 1, n_real_classes outside 1 .. 1024 or
+ * rows * 9 C >= INT32_MAX; -6 when a launch fails. */
+#define SALSA_ADPIT_LOSS_WS 64 /* float64 values of scratch (partial_ws) salsa_nn_adpit_loss needs: one per workgroup */
+int salsa_nn_adpit_loss(const float *doa, const float *sed_gt, const float *doa_gt, int64_t rows, int n_real_classes, float *out3,
+                        float *g_logit, float *g_doa, uint8_t *chosen, double *partial_ws, void *hip_stream);
+/* salsa_nn_seld_decode_multi: file-level track activities act [n_files][n_in_frames][3 C] and vectors xyz [..][9 C] -> DCASE rows
+ * with near-identical tracks of one class unified; only the first n_frames <= n_in_frames frames of a file are read.  Track n of
+ * (frame, c) is active when act >= sed_threshold in float32 (NaN: inactive).  similar(i, j): both active and
+ * dot > cos_unify sqrt(ni nj) with dot = (xi xj + yi yj) + zi zj and ni = (xi^2 + yi^2) + zi^2 in float64 without fma; cos_unify is
+ * the cosine of the unification angle, computed by the caller.  With n_sim = sim01 + sim12 + sim20: 0 -- every active track emits
+ * its own vector, in track order; 1 -- the similar pair emits (vi + vj) / 2.0f and the third track, if active, its own vector,
+ * groups ordered by their lowest track; >= 2 -- one vector ((v0 + v1) + v2) / 3.0f (float32 per component, no fma).  rows
+ * [n_files][3 n_frames C][4] int16 (8-byte aligned) receives (frame, real class, azimuth, elevation) -- the angles of
+ * salsa_nn_seld_decode -- frame ascending, class ascending, then group order, in its first counts[f] rows per file; the rows behind
+ * them are not written.  Bit-reproducible (no atomics).  Returns 0; -1, before any device call, for a NULL or misaligned pointer,
+ * n_files < 1, n_frames or C outside 1 .. 32767, n_in_frames < n_frames, n_in_frames * 9 C > INT32_MAX / 4, or a cos_unify that is
+ * NaN or outside [-1, 1]; -6 when the launch fails. */
+int salsa_nn_seld_decode_multi(const float *act, const float *xyz, int n_files, int n_in_frames, int n_frames, int n_real_classes,
+                               float sed_threshold, double cos_unify, int16_t *rows, int *counts, void *hip_stream);
+
 /* Test-time chunk combination and DCASE row decoding in one launch (reference models/interfaces.py:97-139 combine_chunks, then
  * :232-256 of write_classwise_output_to_file; salsa_amd/csrc/seld_decode.hip): sed [n_files][n_chunks][chunk_len][nc] ACTIVITIES (not
  * logits) and xyz [..][3 nc] (blocks x | y | z), float32 contiguous at the label rate; chunk_len and chunk_hop in label frames.

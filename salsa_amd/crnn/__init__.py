@@ -4,4 +4,4 @@ Convolutions, BatchNorm, pools and the GRU scans run on the hand-written HIP ker
 include/salsa_gru.h); torch supplies autograd, the decoder GEMMs (hipBLASLt), the optimizer and DDP over RCCL.  Reference
 checkpoints load through SeldCRNN.load_reference_state_dict (crnn/checkpoint.py)."""
 from .model import SeldCRNN, interpolate_tensor  # noqa: F401
-from .loss import accdoa_loss, seld_loss  # noqa: F401
+from .loss import accdoa_loss, adpit_loss, seld_loss  # noqa: F401

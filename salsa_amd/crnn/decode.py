@@ -97,6 +97,39 @@ def decode_dcase_rows(sed, xyz, chunk_len: int, chunk_hop: int, n_frames: int = 
     return (rows, counts, fs, fx) if return_file_outputs else (rows, counts)
 
 
+def decode_multi_rows(act, xyz, n_frames: int = 600, sed_threshold: float = 0.5, unify_deg: float = 15.0, n_classes: int = 12):
+    """Multi-ACCDOA file outputs on the device: act (n_files, n_in_frames, 3 C) track activities and xyz
+    (n_files, n_in_frames, 9 C), CUDA float32 at the label rate, C = n_classes REAL classes, n_in_frames >= n_frames -> rows
+    (n_files, 3 * n_frames * C, 4) int16 = (frame, real class, azimuth, elevation) with near-identical tracks of a class unified, of
+    which the first counts[f] of file f are written, and counts (n_files,) int32 -- rows_to_list's and the scorers' input.  One
+    salsa_nn_seld_decode_multi launch on the current stream, no synchronisation; CPU tensors are refused (the host function is
+    postprocess.multi_accdoa_rows, whose result this equals)."""
+    import torch
+    from .postprocess import cos_unify_of
+    cos_unify = cos_unify_of(unify_deg)
+    if act.dim() != 3 or xyz.dim() != 3 or act.shape[:2] != xyz.shape[:2] or act.shape[2] != 3 * n_classes or xyz.shape[2] != 9 * n_classes:
+        raise ValueError('decode_multi_rows: act %s / xyz %s are not (files, frames, %d) / (.., %d)'
+                         % (tuple(act.shape), tuple(xyz.shape), 3 * n_classes, 9 * n_classes))
+    if not (act.is_cuda and xyz.is_cuda and act.device == xyz.device and act.dtype == torch.float32 and xyz.dtype == torch.float32):
+        raise ValueError('decode_multi_rows takes float32 tensors on one CUDA device (the host path is postprocess.multi_accdoa_rows)')
+    n_files, n_in = act.shape[:2]
+    if n_files == 0:
+        raise ValueError('decode_multi_rows: no files')
+    act, xyz = act.contiguous(), xyz.contiguous()
+    dev = act.device
+    rows = torch.empty((n_files, 3 * n_frames * n_classes, 4), dtype=torch.int16, device=dev)
+    counts = torch.empty((n_files,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().salsa_nn_seld_decode_multi(_ptr(act), _ptr(xyz), n_files, n_in, n_frames, n_classes, float(sed_threshold),
+                                                    cos_unify, _ptr(rows), _ptr(counts),
+                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == _lib.E_INVAL:
+        raise ValueError('salsa_nn_seld_decode_multi refused %d files of %d frames (%d decoded) x %d classes' % (n_files, n_in, n_frames, n_classes))
+    if rc:
+        raise RuntimeError('salsa_nn_seld_decode_multi failed (%d)' % rc)
+    return rows, counts
+
+
 def rows_to_list(rows, counts, eval_version: str = '2021', as_array: bool = False) -> list:
     """decode_dcase_rows' rows (n_files, capacity, 4) and counts (n_files,) ON THE HOST (numpy arrays or CPU tensors) -> per file
     exactly what to_dcase_rows returns: [frame, class, 0, azimuth, elevation] rows for eval_version '2021' (the zero track column

@@ -43,12 +43,13 @@ def _ckpt_files(d):
 
 
 def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, combine_method='mean', sed_threshold=0.3,
-             doa_threshold=20, eval_version='2021', sub_batch=8, return_rows=False, tta=None):
+             doa_threshold=20, eval_version='2021', sub_batch=8, return_rows=False, tta=None, unify_deg=15.0):
     """One validation pass (models/seld_models.py:96-108 + interfaces.py:163-180): every clip of ``val_bank`` through
     infer_pipelined(Trainer.infer) in test chunks, rows against ``val_gt`` (per clip a list of rows, metrics.load_dcase_csv).  On the
     GPU the rows are decoded and scored on the device (DeviceSeldScore / DeviceSeldScore2020 by eval_version), on the CPU by the host
     classes.  tta = (audio_format, feature_type) or a tta.TtaForward: the forward is Trainer.infer under test-time augmentation (all
-    channel-swap variants, the trainer's n_classes and output_format); None: Trainer.infer itself.
+    channel-swap variants, the trainer's n_classes and output_format); None: Trainer.infer itself.  A 'multi_accdoa' trainer is
+    decoded with track unification (infer_pipelined's output_format / unify_deg): whole clips or non-overlapping chunks, no tta.
     -> dict valER valF1 valLE valLR valSeld (+ the scorer under 'scorer', and 'rows' when asked)."""
     from .infer import infer_pipelined
     from .tta import wrap_forward
@@ -66,7 +67,7 @@ def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, comb
     on_gpu = trainer.device.type == 'cuda'
     forward = wrap_forward(trainer.infer, tta, nc, trainer.output_format)
     kw = dict(sub_batch=sub_batch, sed_threshold=sed_threshold, n_label_frames=n_label, chunk_len=chunk_len, chunk_hop_len=chunk_hop_len,
-              combine_method=combine_method, n_classes=nc,
+              combine_method=combine_method, n_classes=nc, output_format=trainer.output_format, unify_deg=unify_deg,
               eval_version='2020')       # (the ROW shape only: (frame, class, azimuth, elevation), what SeldMetrics.update reads)
     if on_gpu:
         scorer = (DeviceSeldScore2020 if eval_version == '2020' else DeviceSeldScore)(nc, doa_threshold, rate)
@@ -88,6 +89,7 @@ def _save(path, trainer, loader, epoch, global_step, history, best, val=None):
     dev = trainer.device
     ckpt = dict(state_dict=reference_state_dict(trainer.raw_model), optimizer=trainer.opt.state_dict(), epoch=epoch,
                 global_step=global_step, history=history, best=best, val=val, loader_seed=loader.seed,
+                output_format=trainer.output_format, n_classes=trainer.n_classes,
                 rng_cpu=torch.get_rng_state(), rng_device=torch.cuda.get_rng_state(dev) if dev.type == 'cuda' else None)
     tmp = path + '.tmp'
     torch.save(ckpt, tmp)
@@ -98,6 +100,9 @@ def _load(path, trainer, loader):
     ckpt = torch.load(path, map_location='cpu', weights_only=False)
     if ckpt['loader_seed'] != loader.seed:
         raise ValueError('resume: the checkpoint was trained with loader seed %d, this run has %d' % (ckpt['loader_seed'], loader.seed))
+    if ckpt.get('output_format', trainer.output_format) != trainer.output_format:
+        raise ValueError('resume: the checkpoint was trained with output_format %r, this trainer has %r'
+                         % (ckpt['output_format'], trainer.output_format))
     load_reference_state_dict(trainer.raw_model, ckpt['state_dict'])
     trainer.opt.load_state_dict(ckpt['optimizer'])
     torch.set_rng_state(ckpt['rng_cpu'])
@@ -110,14 +115,15 @@ def _load(path, trainer, loader):
 def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, max_epochs=50, epochs=None, milestones=MILESTONES,
         lrs=LRS, moms=MOMS, val_interval=1, train_fraction=1.0, audio_format='foa', feature_type='salsa', augment=True, seed=2021,
         mode='crossval', eval_version='2021', resume=False, chunk_len=None, chunk_hop_len=None, combine_method='mean',
-        sed_threshold=0.3, doa_threshold=20, val_sub_batch=8, loader=None, tta=None):
+        sed_threshold=0.3, doa_threshold=20, val_sub_batch=8, loader=None, tta=None, unify_deg=15.0):
     """Train ``trainer`` for ``max_epochs`` epochs of ``bank`` (a finalized GpuFeatureBank).  The keywords are the YAML's keys
     (INTEGRATION.md has the table): batch_size = training.train_batch_size; milestones / lrs / moms = training.lr_scheduler.*;
     max_epochs, val_interval = training.*; train_fraction, n_classes (Trainer's) = data.*; eval_version; mode ('crossval': the best
     checkpoint by valSeld is kept, 'eval': the latest only).  ``epochs`` caps how many epochs THIS call runs (time-sliced jobs);
     ``resume`` continues from the lexicographically last file of <out_dir>/checkpoint (train.py:37-45; none there: from scratch).
-    val_bank / val_gt: the validation clips and their ground-truth rows; chunk_len .. sed_threshold and tta go to the validation pass
-    (validate).
+    val_bank / val_gt: the validation clips and their ground-truth rows; chunk_len .. sed_threshold, tta and unify_deg go to the
+    validation pass (validate).  The trainer's output_format is stored in every checkpoint and checked on resume; a 'multi_accdoa'
+    trainer takes a bank of trackwise labels (GpuFeatureBank(n_classes=3 C, label_format='trackwise')).
     -> the history: dict(steps=[epoch, step, lr, mom, loss, sed_loss, doa_loss per step], val=[dict per validated epoch],
     best=dict | None, epoch=epochs finished, global_step)."""
     from ..dataset import BankLoader
@@ -157,7 +163,7 @@ def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, 
         val = None
         if val_bank is not None and (epoch + 1) % val_interval == 0:
             val = validate(trainer, val_bank, val_gt, chunk_len, chunk_hop_len, combine_method, sed_threshold, doa_threshold,
-                           eval_version, val_sub_batch, tta=tta)
+                           eval_version, val_sub_batch, tta=tta, unify_deg=unify_deg)
             val.pop('scorer')
             val['epoch'] = epoch
             history['val'].append(val)

@@ -16,7 +16,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from ..distributed import shard_list
-from .postprocess import combine_chunks, to_dcase_rows
+from .postprocess import combine_chunks, multi_accdoa_rows, to_dcase_rows
 
 
 def _forward_chunks(feat, forward, chunk_len, chunk_hop_len, chunk_batch, sub_batch, n_label_frames):
@@ -47,7 +47,7 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
                     as_array: bool = False, stamps: Optional[list] = None, chunk_len: Optional[int] = None,
                     chunk_hop_len: Optional[int] = None, decode: str = 'host', combine_method: str = 'mean',
                     eval_version: str = '2021', n_classes: int = 12, chunk_batch: Optional[int] = None,
-                    score: Optional[tuple] = None, tta=None) -> list:
+                    score: Optional[tuple] = None, tta=None, output_format: str = 'reg_xyz', unify_deg: float = 15.0) -> list:
     """featurize(lo, hi) -> feature tensor [hi - lo, 7, T, F] of items lo..hi-1 on the model's device; forward(features) ->
     (event probabilities [b, n_label_frames, 12], xyz [b, n_label_frames, 36]).  Returns the DCASE rows of every item, in
     item order.  The device is never idle waiting for the host: up to `depth` sub-batches are in flight.
@@ -69,9 +69,26 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
     tta = (audio_format, feature_type), or a ready tta.TtaForward (which carries its own forwards): test-time augmentation.  forward is
     wrapped in a TtaForward over all channel-swap variants of that recipe (n_classes as given, output_format 'reg_xyz'), so each
     forward call -- with chunks: each chunk batch -- returns the merged outputs; everything behind the forward is untouched.  None:
-    forward is called as it is."""
+    forward is called as it is.
+
+    output_format = 'multi_accdoa' (n_classes = the REAL classes C): forward returns the track activities
+    (b, frames, 3 C) and xyz (b, frames, 9 C), e.g. a multi_accdoa Trainer's infer; the rows come from postprocess.multi_accdoa_rows
+    (host) or decode.decode_multi_rows (device, one salsa_nn_seld_decode_multi launch) with tracks of a class closer than unify_deg
+    degrees unified, so a class may hold several rows in a frame.  Whole clips, or test chunks with chunk_hop_len == chunk_len that
+    tile n_label_frames exactly (reshaped to file level, no arithmetic).  The track order is not consistent between two forwards, so
+    averaging track n of one with track n of another is undefined: overlapping chunks and tta= raise ValueError.  score= works as
+    before (an accumulator of C classes).  Any other output_format: forward's outputs are taken as they are."""
     import torch
     assert depth >= 1 and sub_batch >= 1
+    if output_format not in ('reg_xyz', 'accdoa', 'multi_accdoa'):
+        raise ValueError('invalid output_format %r' % (output_format,))
+    multi = output_format == 'multi_accdoa'
+    if multi and tta is not None:
+        raise ValueError("output_format 'multi_accdoa' has no test-time augmentation: the track order differs between forwards, so "
+                         'the variants cannot be averaged track by track')
+    if multi and chunk_len is not None and chunk_hop_len is not None and chunk_hop_len < chunk_len:
+        raise ValueError("output_format 'multi_accdoa' takes whole clips or non-overlapping test chunks (chunk_hop_len %d < chunk_len %d): "
+                         'the track order differs between forwards, so overlaps cannot be averaged' % (chunk_hop_len, chunk_len))
     if decode not in ('host', 'device'):
         raise ValueError("decode must be 'host' or 'device', not {!r}".format(decode))
     if combine_method not in ('mean', 'gmean'):
@@ -105,6 +122,11 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
         else:
             p, d = s['p'][:hi - lo].numpy(), s['d'][:hi - lo].numpy()
             for i in range(lo, hi):
+                if multi:                                # file-level outputs already (chunks were reshaped, not combined)
+                    results[i] = multi_accdoa_rows(p[i - lo], d[i - lo], sed_threshold=sed_threshold, unify_deg=unify_deg,
+                                                   n_classes=n_classes, max_nframes_per_file=n_label_frames, eval_version=eval_version,
+                                                   as_array=as_array)
+                    continue
                 # one chunk per file (test_chunk_len = the whole clip): combine_chunks places it, as the reference does
                 pi, di = (p[i - lo], d[i - lo]) if chunk_len is not None else (p[i - lo][None], d[i - lo][None])
                 fp = combine_chunks(pi, lab_len, lab_hop, n_frames=n_label_frames, combine_method=combine_method)
@@ -126,7 +148,21 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
             prob, xyz = prob.detach().float(), xyz.detach().float()
             lab_len = lab_hop = n_label_frames
         on_gpu = prob.is_cuda
-        if decode == 'device':
+        if multi:
+            if prob.dim() == 4:                          # chunks that tile the file: (files, n_chunks, Lc, .) -> (files, n_chunks Lc, .)
+                if prob.shape[1] > 1 and prob.shape[1] * lab_len != n_label_frames:
+                    raise ValueError("output_format 'multi_accdoa': %d chunks of %d label frames do not tile %d label frames exactly"
+                                     % (prob.shape[1], lab_len, n_label_frames))
+                prob, xyz = prob.reshape(prob.shape[0], -1, prob.shape[3]), xyz.reshape(xyz.shape[0], -1, xyz.shape[3])
+            if prob.shape[1] < n_label_frames or prob.shape[2] != 3 * n_classes or xyz.shape[2] != 9 * n_classes:
+                raise ValueError("output_format 'multi_accdoa': forward gave %s / %s, expected (b, >= %d, %d) / (.., %d)"
+                                 % (tuple(prob.shape), tuple(xyz.shape), n_label_frames, 3 * n_classes, 9 * n_classes))
+        if multi and decode == 'device':
+            from .decode import decode_multi_rows
+            rows, counts = decode_multi_rows(prob, xyz, n_frames=n_label_frames, sed_threshold=sed_threshold, unify_deg=unify_deg,
+                                             n_classes=n_classes)
+            out = {'rows': rows, 'counts': counts}
+        elif decode == 'device':
             from .decode import decode_dcase_rows
             if chunk_len is None:                        # whole clips: one chunk of the forward's length, trimmed to n_label_frames
                 lab_len = lab_hop = prob.shape[1]
@@ -163,7 +199,8 @@ def infer_clips_sharded(names: Sequence[str], featurize: Callable[[List[str]], '
                         sed_threshold: float = 0.3, n_label_frames: int = 600, gather: bool = True, depth: int = 2,
                         stamps: Optional[list] = None, chunk_len: Optional[int] = None, chunk_hop_len: Optional[int] = None,
                         decode: str = 'host', combine_method: str = 'mean', eval_version: str = '2021', n_classes: int = 12,
-                        chunk_batch: Optional[int] = None, score: Optional[tuple] = None, tta=None) -> Dict[str, list]:
+                        chunk_batch: Optional[int] = None, score: Optional[tuple] = None, tta=None, output_format: str = 'reg_xyz',
+                        unify_deg: float = 15.0) -> Dict[str, list]:
     """names: all clip names (any order; sharded over the SORTED list).  featurize(list of names) -> feature tensor
     [b, 7, T, F] on the model's device (e.g. SalsaExtractor.extract of the clips' audio with the scaler attached, cropped
     to 8 * n_label_frames frames); forward(features) -> (event probabilities [b, n_label_frames, 12], xyz [b, .., 36]), e.g.
@@ -171,12 +208,13 @@ def infer_clips_sharded(names: Sequence[str], featurize: Callable[[List[str]], '
     chunk_len, chunk_hop_len, decode, combine_method, eval_version, n_classes, chunk_batch: infer_pipelined's test-chunk and
     device-decoding options, handed through.  score = (gt_rows, gt_counts, accumulator): infer_pipelined's, for THIS rank's shard
     (the ground truth of shard_list(sorted(names), rank, world), in that order); every rank's accumulator holds its shard's score,
-    to be combined with DeviceSeldScore.merge.  tta: infer_pipelined's, handed through."""
+    to be combined with DeviceSeldScore.merge.  tta, output_format, unify_deg: infer_pipelined's, handed through."""
     mine = shard_list(sorted(names), rank, world)
     rows = infer_pipelined(len(mine), lambda lo, hi: featurize(mine[lo:hi]), forward, sub_batch=sub_batch, depth=depth,
                            sed_threshold=sed_threshold, n_label_frames=n_label_frames, stamps=stamps, chunk_len=chunk_len,
                            chunk_hop_len=chunk_hop_len, decode=decode, combine_method=combine_method, eval_version=eval_version,
-                           n_classes=n_classes, chunk_batch=chunk_batch, score=score, tta=tta)
+                           n_classes=n_classes, chunk_batch=chunk_batch, score=score, tta=tta, output_format=output_format,
+                           unify_deg=unify_deg)
     out = dict(zip(mine, rows))
     if gather and world > 1:
         import torch.distributed as dist

@@ -60,6 +60,87 @@ def to_dcase_rows(event_prob: np.ndarray, doa_xyz: np.ndarray, sed_threshold: fl
     return rows if as_array else rows.tolist()
 
 
+def cos_unify_of(unify_deg: float) -> float:
+    """the unification threshold of Multi-ACCDOA as the cosine every decision uses, computed once, in float64 on the host"""
+    import math
+    c = math.cos(float(unify_deg) * math.pi / 180.0)
+    if not -1.0 <= c <= 1.0:
+        raise ValueError('unify_deg %r has no cosine in [-1, 1]' % (unify_deg,))
+    return c
+
+
+def multi_accdoa_cells(act: np.ndarray, xyz: np.ndarray, sed_threshold: float, cos_unify: float, n_classes: int):
+    """The per-cell rule of salsa_nn_seld_decode_multi (csrc/multi_accdoa.h, unify_cell) in numpy, statement for statement: act
+    (T, 3 C), xyz (T, 9 C) float32 -> n_out (T, C) in 0 .. 3, out (T, C, 3, 3) float32 = the emitted vectors in group order (the
+    groups behind n_out are zero) and flags (T, C): bit 0 sim01, bit 1 sim12, bit 2 sim20, bits 4 .. 6 the tracks' activity."""
+    C = n_classes
+    act, xyz = np.asarray(act, np.float32), np.asarray(xyz, np.float32)
+    T = act.shape[0]
+    assert act.shape == (T, 3 * C) and xyz.shape == (T, 9 * C), 'act (T, 3 C) / xyz (T, 9 C)'
+    a = (act.reshape(T, 3, C) >= np.float32(sed_threshold)).transpose(0, 2, 1)         # (T, C, track); NaN is inactive
+    v = xyz.reshape(T, 3, 3, C).transpose(0, 3, 2, 1)                                  # (T, C, track, axis)
+    d = v.astype(np.float64)
+
+    def similar(i, j):
+        xi, yi, zi, xj, yj, zj = d[..., i, 0], d[..., i, 1], d[..., i, 2], d[..., j, 0], d[..., j, 1], d[..., j, 2]
+        dot = (xi * xj + yi * yj) + zi * zj
+        ni, nj = (xi * xi + yi * yi) + zi * zi, (xj * xj + yj * yj) + zj * zj
+        return a[..., i] & a[..., j] & (dot > cos_unify * np.sqrt(ni * nj))
+
+    with np.errstate(invalid='ignore', over='ignore'):
+        s01, s12, s20 = similar(0, 1), similar(1, 2), similar(2, 0)
+        pair01, pair12, pair02 = ((v[..., 0, :] + v[..., 1, :]) / np.float32(2.0), (v[..., 1, :] + v[..., 2, :]) / np.float32(2.0),
+                                  (v[..., 0, :] + v[..., 2, :]) / np.float32(2.0))
+        triple = ((v[..., 0, :] + v[..., 1, :]) + v[..., 2, :]) / np.float32(3.0)
+    flags = (s01.astype(np.int32) | s12.astype(np.int32) << 1 | s20.astype(np.int32) << 2
+             | a[..., 0].astype(np.int32) << 4 | a[..., 1].astype(np.int32) << 5 | a[..., 2].astype(np.int32) << 6)
+    n_sim = s01.astype(np.int32) + s12 + s20
+    out = np.zeros((T, C, 3, 3), dtype=np.float32)
+    n_out = np.zeros((T, C), dtype=np.int32)
+
+    def emit(mask, vec):
+        t, c = np.nonzero(mask)
+        out[t, c, n_out[t, c]] = vec[t, c]
+        n_out[t, c] += 1
+
+    none, one = n_sim == 0, n_sim == 1
+    for n in range(3):                                                                 # no similar pair: the active tracks, in order
+        emit(none & a[..., n], v[..., n, :])
+    emit(one & s01, pair01)                                                            # groups by their lowest track
+    emit(one & s01 & a[..., 2], v[..., 2, :])
+    emit(one & s12 & a[..., 0], v[..., 0, :])
+    emit(one & s12, pair12)
+    emit(one & s20, pair02)
+    emit(one & s20 & a[..., 1], v[..., 1, :])
+    emit(n_sim >= 2, triple)
+    return n_out, out, flags
+
+
+def multi_accdoa_rows(act: np.ndarray, xyz: np.ndarray, sed_threshold: float = 0.5, unify_deg: float = 15.0, n_classes: int = 12,
+                      max_nframes_per_file: int = 600, eval_version: str = '2021', as_array: bool = False):
+    """The host decoder of output_format 'multi_accdoa' (what decode='host' runs and the yardstick of
+    salsa_nn_seld_decode_multi): file-level track activities act (T, 3 n_classes) and vectors xyz (T, 9 n_classes) -> rows
+    [frame, real class, (0,) azimuth, elevation] as to_dcase_rows shapes them, frame ascending, class ascending, then group order;
+    tracks of one class closer than unify_deg degrees are unified (multi_accdoa_cells).  The angles are round-half-even of the
+    float64 atan2 of the float32 vectors (csrc/seld_decode.h, xyz_to_angles; a NaN angle is written as 0)."""
+    act, xyz = np.asarray(act, np.float32), np.asarray(xyz, np.float32)
+    assert act.shape[0] >= max_nframes_per_file, 'n_output_frames < max_nframes_per_file'
+    n_out, out, _ = multi_accdoa_cells(act[:max_nframes_per_file], xyz[:max_nframes_per_file], sed_threshold, cos_unify_of(unify_deg),
+                                       n_classes)
+    t, c, g = np.nonzero(np.arange(3)[None, None, :] < n_out[..., None])
+    vec = out[t, c, g].astype(np.float64)
+    x, y, z = vec[:, 0], vec[:, 1], vec[:, 2]
+    with np.errstate(invalid='ignore', over='ignore'):
+        azi = np.around(np.arctan2(y, x) * 180.0 / np.pi)
+        ele = np.around(np.arctan2(z, np.sqrt(x * x + y * y)) * 180.0 / np.pi)
+    azi = np.where(np.isnan(azi), 0.0, azi).astype(np.int64)
+    ele = np.where(np.isnan(ele), 0.0, ele).astype(np.int64)
+    azi[azi == 180] = -180
+    cols = [t, c, np.zeros_like(t), azi, ele] if eval_version == '2021' else [t, c, azi, ele]
+    rows = np.stack(cols, axis=1).astype(np.int64)
+    return rows if as_array else rows.tolist()
+
+
 def write_dcase_csv(path: str, rows) -> None:
     with open(path, 'w', newline='') as f:
         csv.writer(f).writerows(rows)

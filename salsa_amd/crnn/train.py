@@ -11,12 +11,12 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .loss import accdoa_loss, seld_loss
+from .loss import accdoa_loss, adpit_loss, seld_loss
 from .model import SeldCRNN
 
 MILESTONES = (0.0, 0.1, 0.7, 1.0)
 LRS = (3e-4, 3e-4, 3e-4, 1e-4)
-OUTPUT_FORMATS = ('reg_xyz', 'accdoa')
+OUTPUT_FORMATS = ('reg_xyz', 'accdoa', 'multi_accdoa')
 
 
 def lr_at(progress: float) -> float:
@@ -49,8 +49,10 @@ class Trainer:
         """n_input_channels: 7 (SALSA, melspeciv, linspeciv) or 10 (melspecgcc, linspecgcc), experiments/configs/seld.yml;
         decoder_type ('bigru' | 'gru' | 'lstm' | 'bilstm'), freq_pool ('avg' | 'max' | 'avg_max') and decoder_size: the YAML's
         model.decoder keys of the same names (SeldCRNN); output_format: the YAML's data.output_format, 'reg_xyz' (SED from the
-        event head, loss.seld_loss) or 'accdoa' (SED = length of each class's xyz vector, loss.accdoa_loss); n_classes: the YAML's
-        data.n_classes (12 for TNSSE2021, 14 for TNSSE2020)."""
+        event head, loss.seld_loss), 'accdoa' (SED = length of each class's xyz vector, loss.accdoa_loss) or 'multi_accdoa' (three
+        tracks per class, DESIGN.md section 9i: the model is SeldCRNN(n_classes=3 * n_classes), trained with loss.adpit_loss on
+        trackwise labels, while self.n_classes stays the number of real classes); n_classes: the YAML's data.n_classes (12 for
+        TNSSE2021, 14 for TNSSE2020)."""
         if output_format not in OUTPUT_FORMATS:
             raise ValueError('invalid output_format %r (supported: %s)' % (output_format, ', '.join(OUTPUT_FORMATS)))
         self.output_format = output_format
@@ -62,7 +64,8 @@ class Trainer:
         self.total_steps = total_steps
         self.step_idx = 0
         self.n_classes = n_classes
-        model = SeldCRNN(n_input_channels=n_input_channels, n_classes=n_classes, decoder_type=decoder_type, freq_pool=freq_pool,
+        self.n_model_classes = 3 * n_classes if output_format == 'multi_accdoa' else n_classes    # pseudo-classes: track n, class c -> n C + c
+        model = SeldCRNN(n_input_channels=n_input_channels, n_classes=self.n_model_classes, decoder_type=decoder_type, freq_pool=freq_pool,
                          decoder_size=decoder_size).to(self.device)
         self.channels_last = self.device.type == 'cuda' and os.environ.get('SALSA_CHANNELS_LAST', '1') == '1'
         if self.channels_last:
@@ -122,7 +125,8 @@ class Trainer:
             self.grad_sync.begin()
         with torch.autocast(device_type=self.device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None):
             pred = self.model(x)
-        loss, sed_l, doa_l = (accdoa_loss if self.output_format == 'accdoa' else seld_loss)(pred, sed, doa)
+        loss_fn = {'reg_xyz': seld_loss, 'accdoa': accdoa_loss, 'multi_accdoa': adpit_loss}[self.output_format]
+        loss, sed_l, doa_l = loss_fn(pred, sed, doa)
         loss.backward()
         if self.grad_sync is not None:
             self.grad_sync.finish()                # averaged gradients are in place
@@ -138,12 +142,13 @@ class Trainer:
     @torch.no_grad()
     def infer(self, x):
         """eval forward (bf16 autocast): SED activities and xyz at label rate (inference path, config 5).  The activities are the
-        sigmoid of the event logits (reg_xyz) or the length of each class's xyz vector (accdoa, salsa_nn_accdoa_sed)."""
+        sigmoid of the event logits (reg_xyz) or the length of each class's xyz vector (accdoa, salsa_nn_accdoa_sed); under
+        multi_accdoa the same lengths over the 3 n_classes pseudo-classes: the track activities (b, T, 3 C) next to xyz (b, T, 9 C)."""
         self.model.eval()
         x = self._input_layout(x)
         with torch.autocast(device_type=self.device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None):
             out = self.raw_model(x)
-        if self.output_format == 'accdoa':
+        if self.output_format in ('accdoa', 'multi_accdoa'):
             from .nn_ops import accdoa_sed
             xyz = out['doa_frame_output'].float()
             return accdoa_sed(xyz, self.raw_model.decoder.n_classes), xyz

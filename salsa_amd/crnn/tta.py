@@ -172,6 +172,9 @@ class TtaForward:
         self.forwards = [forwards] if callable(forwards) else list(forwards)
         if not self.forwards or not all(callable(f) for f in self.forwards):
             raise ValueError('forwards: one callable or a non-empty sequence of callables')
+        if output_format == 'multi_accdoa':
+            raise ValueError("output_format 'multi_accdoa' has no test-time augmentation: the track order differs between forwards, so "
+                             'the variants cannot be averaged track by track (DESIGN.md section 9i)')
         if output_format not in ('reg_xyz', 'accdoa'):
             raise ValueError('invalid output_format %r' % (output_format,))
         if isinstance(variants, str):

@@ -82,14 +82,72 @@ def load_classwise_gt(gt_meta_fn, n_frames: int, n_classes: int = 12, label_upsa
     return sed, np.concatenate((x, y, z), axis=-1)
 
 
+def load_trackwise_gt(gt_meta_fn, n_frames: int, n_classes: int = 12, label_upsample_ratio: int = 8, n_slots: int = 3):
+    """The Multi-ACCDOA targets of a clip (the reference has none): the CSV and the float32 trigonometry of
+    load_classwise_gt, but same-class overlaps are KEPT.  Per (frame, class) the distinct tracks present are ordered from the longest
+    track to the shortest (row counts over the file, sort_tracks reversed; ties: the lower track id first) and fill slots 0, 1, ..
+    n_slots - 1, so the active slots are always a prefix; further tracks are dropped.  Within one track the last row in file order
+    wins, as in load_classwise_gt.  -> sed (n_label_frames, n_slots * n_classes) in {0, 1}, doa (n_label_frames, 3 * n_slots *
+    n_classes) = [x | y | z] blocks with slot n of class c at column n * n_classes + c of each block, and n_dropped, the number of
+    (frame, class, track) entries that found no slot.  Without same-class overlaps slot 0 is load_classwise_gt's result bit for
+    bit."""
+    import pandas as pd
+    assert n_frames % label_upsample_ratio == 0, 'mismatch ground truth and feature frame rate'
+    if n_slots < 1:
+        raise ValueError('n_slots must be positive')
+    n_label_frames = n_frames // label_upsample_ratio
+    df = pd.read_csv(gt_meta_fn, header=None, names=['frame_number', 'sound_class_idx', 'track_number', 'azimuth', 'elevation'])
+    frame_number, sound_class_idx = df['frame_number'].values.astype(np.int64), df['sound_class_idx'].values.astype(np.int64)
+    track_number = df['track_number'].values.astype(np.int64)
+    azi_rad, ele_rad = df['azimuth'].values * np.pi / 180.0, df['elevation'].values * np.pi / 180.0
+    nc = n_slots * n_classes
+    sed = np.zeros((n_label_frames, nc), dtype=np.float32)
+    azi = np.zeros((n_label_frames, nc), dtype=np.float32)
+    ele = np.zeros((n_label_frames, nc), dtype=np.float32)
+    n_dropped = 0
+    if len(df):
+        if sound_class_idx.min() < 0 or sound_class_idx.max() >= n_classes or frame_number.min() < 0 or frame_number.max() >= n_label_frames:
+            raise IndexError('a metadata row lies outside %d label frames x %d classes' % (n_label_frames, n_classes))
+        durations = np.bincount(track_number)
+        cells = {}
+        for i in range(len(df)):                                               # the last row of a (frame, class, track) stays
+            cells.setdefault((frame_number[i], sound_class_idx[i]), {})[track_number[i]] = i
+        for (fr, cl), tracks in cells.items():
+            ranked = sorted(tracks, key=lambda t: (-durations[t], t))
+            n_dropped += max(0, len(ranked) - n_slots)
+            for slot, t in enumerate(ranked[:n_slots]):
+                col, i = slot * n_classes + cl, tracks[t]
+                sed[fr, col] = 1.0
+                azi[fr, col] = azi_rad[i]
+                ele[fr, col] = ele_rad[i]
+    x, y, z = np.cos(azi) * np.cos(ele), np.sin(azi) * np.cos(ele), np.sin(ele)
+    off = sed < 1
+    x[off] = 0.0
+    y[off] = 0.0
+    z[off] = 0.0
+    return sed, np.concatenate((x, y, z), axis=-1), n_dropped
+
+
+LABEL_FORMATS = ('classwise', 'trackwise')
+
+
 class GpuFeatureBank(torch.utils.data.Dataset):
     """extractor: a SalsaExtractor, a baseline_features.BaselineExtractor, or None (precomputed feature files).
     n_scaler_channels: the channels fit_scaler() covers and finalize() normalises; None takes it from the data -- every channel
     of a BaselineExtractor's output (the reference's baseline compute_scaler, feature_extraction.py:526-586), else 4 (SALSA).
-    A scaler given by load_feature_scaler / set_scaler normalises its own number of channels, (4 | C, 1, F)."""
+    A scaler given by load_feature_scaler / set_scaler normalises its own number of channels, (4 | C, 1, F).
+    label_format: 'classwise' (gt_meta= is read by load_classwise_gt) or 'trackwise' (Multi-ACCDOA, DESIGN.md section 9i: n_classes
+    = 3 x the real classes, gt_meta= is read by load_trackwise_gt, n_dropped counts what found no slot); sed= / doa= arrays are
+    taken as they are under both."""
 
     def __init__(self, extractor: SalsaExtractor = None, fs=24000, hop_len=300, label_rate=10, chunk_len_s=8.0,
-                 chunk_hop_len_s=0.5, n_classes=12, max_clip_s=60, device=None, n_scaler_channels=None):
+                 chunk_hop_len_s=0.5, n_classes=12, max_clip_s=60, device=None, n_scaler_channels=None, label_format='classwise'):
+        if label_format not in LABEL_FORMATS:
+            raise ValueError('invalid label_format %r (supported: %s)' % (label_format, ', '.join(LABEL_FORMATS)))
+        if label_format == 'trackwise' and n_classes % 3 != 0:
+            raise ValueError("label_format 'trackwise' holds three slots per class: n_classes = 3 x the real classes, not %d" % n_classes)
+        self.label_format = label_format
+        self.n_dropped = 0                                                     # trackwise: (frame, class, track) entries beyond three slots
         self.ex = extractor                                                    # None: a bank of precomputed feature files (add_feature_files)
         self.n_scaler_channels = n_scaler_channels
         self.device = extractor.device if extractor is not None else torch.device(device if device is not None else 'cuda')
@@ -161,7 +219,11 @@ class GpuFeatureBank(torch.utils.data.Dataset):
         self._n += feats.shape[0] * n_frames
         if gt_meta is not None:
             assert len(gt_meta) == len(names)
-            labels = [load_classwise_gt(fn, n_frames, self.n_classes, self.upsample) for fn in gt_meta]
+            if self.label_format == 'trackwise':
+                labels = [load_trackwise_gt(fn, n_frames, self.n_classes // 3, self.upsample) for fn in gt_meta]
+                self.n_dropped += sum(lab[2] for lab in labels)
+            else:
+                labels = [load_classwise_gt(fn, n_frames, self.n_classes, self.upsample) for fn in gt_meta]
             sed, doa = [lab[0] for lab in labels], [lab[1] for lab in labels]
         for i, name in enumerate(names):
             self.clip_start.append(self.pointer)
