@@ -410,6 +410,35 @@ typedef struct { float *p, *m, *v; int64_t n; } salsa_nn_adam_entry;
 int salsa_nn_adam_step(const salsa_nn_adam_entry *table, const float *const *grads, int n_tensors, const int *chunks, int n_chunks,
                        double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, void *hip_stream);
 
+/* The decoder's optional self-attention stage (salsa_amd/csrc/attention.hip), all float32 with products exact in
+ * float32.  Attention core of one multi-head self-attention:
+ *     S_ij = q_i . k_j / sqrt(head_dim),  P = softmax_j(S),  o_i = sum_j P_ij v_j,  lse_i = ln sum_j exp(S_ij)
+ *   qkv  (B, T, 3, n_heads, head_dim) contiguous: the in-projection's output as it is;   out  (B, T, n_heads * head_dim);
+ *   lse  (B, n_heads, T);   d_qkv as qkv.  No mask, no dropout on P.
+ * _bwd recomputes P from lse (no T x T plane is stored): with delta_i = d_o_i . o_i and dS = P o (d_o V^T - delta),
+ *     dQ = dS K / sqrt(head_dim),  dK = dS^T Q / sqrt(head_dim),  dV = P^T d_o.
+ * Every output element is summed by one workgroup in a fixed order (no atomics): both passes are bit-reproducible and a sample's
+ * result does not depend on the rest of the batch.  Supported: head_dim 32 or 64, 1 <= n_heads <= 65535, 1 <= T <= 512, 1 <= B <=
+ * 65535 (salsa_nn_attn_supported: 1 or 0).  The launchers return 0, -1 for an unsupported shape or a null pointer (before any
+ * device call), -6 when the launch fails. */
+int salsa_nn_attn_supported(int T, int n_heads, int head_dim);
+int salsa_nn_attn_fwd(const float *qkv, float *out, float *lse, int B, int T, int n_heads, int head_dim, void *hip_stream);
+int salsa_nn_attn_bwd(const float *qkv, const float *out, const float *lse, const float *d_out, float *d_qkv,
+                      int B, int T, int n_heads, int head_dim, void *hip_stream);
+
+/* y = LayerNorm(x + res) over the last axis of float32 [M][C] rows, C = 256 or 512: biased variance, eps inside the square root (as
+ * torch), two-pass statistics; mean / rstd [M] are kept for the backward.  _bwd: dx [M][C] is the gradient of x AND of res (one
+ * output serves both); dgamma / dbeta [C] are reduced in a fixed order (per-workgroup partial sums into `ws`, then one ordered pass):
+ * bit-reproducible for a given M (not across a reordering of the rows).  ws: salsa_nn_add_layernorm_ws_bytes(M, C) bytes (0 for an
+ * unsupported shape).  Return 0, -1 for bad arguments or a null pointer (before any device call), -5 when ws_bytes is too small,
+ * -6 when the launch fails. */
+size_t salsa_nn_add_layernorm_ws_bytes(int64_t M, int C);
+int salsa_nn_add_layernorm_fwd(const float *x, const float *res, const float *gamma, const float *beta, float *y,
+                               float *mean, float *rstd, int64_t M, int C, float eps, void *hip_stream);
+int salsa_nn_add_layernorm_bwd(const float *dy, const float *x, const float *res, const float *gamma, const float *mean,
+                               const float *rstd, float *dx, float *dgamma, float *dbeta, void *ws, size_t ws_bytes,
+                               int64_t M, int C, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,26 @@ class Head(nn.Module):
         return self.fc2(self.drop2(F.relu(self.fc1(self.drop1(x)), inplace=True)))
 
 
+class AttnBlock(nn.Module):
+    """one self-attention block after the recurrent stack: y = norm(x + drop(mha(x, x, x)[0])) -- no mask,
+    no positional term, no dropout on the probabilities.  Plain torch modules hold the parameters; on the GPU the forward runs
+    through attention.attn_block_forward (the HIP attention core and fused add + LayerNorm)."""
+
+    def __init__(self, d, n_heads=8, dropout=0.05):
+        super().__init__()
+        if n_heads < 1 or d % n_heads != 0:
+            raise ValueError('the attention width %d is not divisible into %d heads' % (d, n_heads))
+        self.mha = nn.MultiheadAttention(d, n_heads, dropout=0.0, batch_first=True)
+        self.norm = nn.LayerNorm(d)
+        self.drop = nn.Dropout(dropout)
+
+    def forward(self, x):
+        if x.is_cuda:
+            from .attention import attn_block_forward
+            return attn_block_forward(self, x, self.training)
+        return self.norm(x + self.drop(self.mha(x, x, x)[0]))
+
+
 DECODER_TYPES = ('gru', 'bigru', 'lstm', 'bilstm')
 FREQ_POOLS = ('avg', 'max', 'avg_max')
 
@@ -168,9 +188,11 @@ FREQ_POOLS = ('avg', 'max', 'avg_max')
 class Decoder(nn.Module):
     """frequency pool -> 2-layer recurrent decoder (size 256) with dropout 0.3 -> SED head + x/y/z heads (decoders.py:13-154).
     decoder_type 'bigru' (the default), 'gru', 'lstm' or 'bilstm'; freq_pool 'avg' (the default), 'max' or 'avg_max'.  The module
-    attribute is ``gru`` or ``lstm``, as in the reference's state dict."""
+    attribute is ``gru`` or ``lstm``, as in the reference's state dict.  n_attn_layers > 0 (beyond the reference) appends that many
+    AttnBlocks of n_attn_heads heads between the recurrent stack and the heads; 0 adds no module and no state-dict key."""
 
-    def __init__(self, n_in=512, n_classes=12, size=256, decoder_type='bigru', freq_pool='avg'):
+    def __init__(self, n_in=512, n_classes=12, size=256, decoder_type='bigru', freq_pool='avg', n_attn_layers=0, n_attn_heads=8,
+                 attn_dropout=0.05):
         super().__init__()
         if decoder_type == 'transformer':
             raise NotImplementedError("decoder_type 'transformer' is not implemented (supported: %s)" % ', '.join(DECODER_TYPES))
@@ -178,6 +200,8 @@ class Decoder(nn.Module):
             raise ValueError('invalid decoder_type %r (supported: %s)' % (decoder_type, ', '.join(DECODER_TYPES)))
         if freq_pool not in FREQ_POOLS:
             raise NotImplementedError('freq pooling %r is not implemented (supported: %s)' % (freq_pool, ', '.join(FREQ_POOLS)))
+        if n_attn_layers < 0:
+            raise ValueError('n_attn_layers must be >= 0, got %r' % (n_attn_layers,))
         self.n_classes, self.decoder_type, self.freq_pool = n_classes, decoder_type, freq_pool
         bidirectional = decoder_type.startswith('bi')
         if decoder_type == 'bigru':
@@ -190,6 +214,7 @@ class Decoder(nn.Module):
             self.lstm = nn.LSTM(n_in, size, num_layers=2, batch_first=True, bidirectional=bidirectional, dropout=0.3)
             _init_rnn_reference(self.lstm)
         d = (2 if bidirectional else 1) * size
+        self.attn = nn.ModuleList(AttnBlock(d, n_attn_heads, attn_dropout) for _ in range(n_attn_layers))
         self.event = Head(d, n_classes)
         self.x, self.y, self.z = Head(d, n_classes), Head(d, n_classes), Head(d, n_classes)
 
@@ -219,12 +244,16 @@ class Decoder(nn.Module):
                         seq = rnn_forward(self.rnn, seq.float(), self.training, half_weights=amp)   # one HIP launch per layer
                     else:
                         seq, _ = self.rnn(seq.float())
+                for block in self.attn:                         # (float32, like the scans: softmax and LayerNorm statistics)
+                    seq = block(seq)
             # the heads too (0.02 % of the FLOPs): under autocast their eight small linears cost 32 cast kernels per step
             # (weights and biases to bf16, their gradients back) around GEMMs of a few microseconds
             with torch.autocast(device_type='cuda', enabled=False):
                 return self._heads(seq.float())
         else:
             seq, _ = self.rnn(seq)
+            for block in self.attn:
+                seq = block(seq)
         return self._heads(seq)
 
     def _heads(self, seq):
@@ -275,13 +304,15 @@ def interpolate_tensor(t, ratio: float):
 class SeldCRNN(nn.Module):
     """forward(x (B,7,T,200)) -> dict at the LABEL rate (seld_models.py:39-66: encoder, decoder, then
     interpolate by time_downsample_ratio * label_rate / feature_rate = 16 * 10 / 80 = 2).  decoder_type, freq_pool and
-    decoder_size are the reference's YAML keys of the same names (see Decoder)."""
+    decoder_size are the reference's YAML keys of the same names (see Decoder); n_attn_layers, n_attn_heads and attn_dropout add
+    self-attention blocks after the recurrent decoder (AttnBlock; 0 layers by default: the reference's network)."""
 
     def __init__(self, n_input_channels=7, n_classes=12, label_rate=10, feature_rate=80, decoder_type='bigru', freq_pool='avg',
-                 decoder_size=256):
+                 decoder_size=256, n_attn_layers=0, n_attn_heads=8, attn_dropout=0.05):
         super().__init__()
         self.encoder = Encoder(n_input_channels)
-        self.decoder = Decoder(self.encoder.n_output_channels, n_classes, decoder_size, decoder_type, freq_pool)
+        self.decoder = Decoder(self.encoder.n_output_channels, n_classes, decoder_size, decoder_type, freq_pool,
+                               n_attn_layers=n_attn_layers, n_attn_heads=n_attn_heads, attn_dropout=attn_dropout)
         self.ratio = self.encoder.time_downsample_ratio * label_rate / feature_rate
 
     def forward(self, x):
