@@ -289,6 +289,35 @@ int salsa_resample_batch(const float *d_x, int n_rows, int64_t n_in, float *d_y,
 #define SALSA_PCM_F32 4
 int salsa_pcm_to_planar(const void *d_pcm, int sample_format, int n_channels, int64_t n_frames, float *d_out, void *hip_stream);
 
+/* Labelled scenes rendered on the device (salsa_amd/scenes.py; the reference has no counterpart: the definition is
+ * this project's).  A clip is a list of items (event, response, onset, gain):
+ *     audio[b, c, n] = ambient[b, c, n] + sum_i gain_i (h[rir_i, c, :] * event_i)[n - onset_i],   0 <= n < n_samples,
+ * `*` the full linear convolution, evaluated in float32 by overlap-save on partitions of 512 samples.  A sample outside every item's
+ * support [onset, onset + length + rir_len - 1) is the ambient's value bit for bit (zero without ambient); two calls give equal bits, and
+ * a clip's result does not depend on the other clips of the call.
+ *
+ * salsa_scene_rir_spectra: d_rirs float32 [n_rirs][n_channels][rir_len] -> the partition spectra, in a 16-byte aligned buffer of
+ * salsa_scene_rir_spectra_bytes (8192 bytes of transform constants, then ceil(rir_len / 512) x 4096 bytes per response and channel).
+ * Once per bank.  Limits: 1 <= n_channels <= 16, 1 <= rir_len <= 16384.
+ *
+ * salsa_scene_render: d_events float32 [n_event_samples], the pool's signals one behind the other.  The item tables are given twice,
+ * with equal contents: on the HOST (clip_start, items, gains), where every entry is checked before the first device call, and on the
+ * device (d_clip_start, d_items, d_gains), where the kernels read them.  clip_start int [n_clips + 1]: clip b owns items clip_start[b]
+ * .. clip_start[b + 1] - 1, at most 256 of them, rendered in that order; items int64 [4][n_items]: the event's first sample in
+ * d_events, the onset in the clip (0 <= onset < n_samples, any value: no alignment), the event's length (1 .. max_event_len) and the
+ * response's index; gains float32 [n_items].  d_ambient: float32 [n_clips][n_channels][n_samples] or NULL (may be d_out); d_out the
+ * same shape.  d_workspace: 16-byte aligned, salsa_scene_workspace_bytes(n_samples, max_event_len, n_items) = n_items x min(
+ * (max_event_len + 510) / 512 + 2, ceil(n_samples / 512)) x 4096 bytes; not needed for n_items = 0.  Two launches on hip_stream, whatever
+ * n_clips and n_items are.  Returns -1 for an argument outside these limits or tables that contradict each other, -5 for a workspace
+ * too small; the two size queries return 0 for arguments the calls would refuse. */
+size_t salsa_scene_rir_spectra_bytes(int n_rirs, int n_channels, int rir_len);
+int salsa_scene_rir_spectra(const float *d_rirs, int n_rirs, int n_channels, int rir_len, float *d_spectra, void *hip_stream);
+size_t salsa_scene_workspace_bytes(int64_t n_samples, int max_event_len, int n_items);
+int salsa_scene_render(const float *d_events, int64_t n_event_samples, const float *d_rir_spectra, int n_rirs, int n_channels, int rir_len,
+                       const int *clip_start, const int64_t *items, const float *gains, const int *d_clip_start, const int64_t *d_items,
+                       const float *d_gains, int n_clips, int n_items, int max_event_len, const float *d_ambient, float *d_out,
+                       int64_t n_samples, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,374 @@
+"""Labelled SELD scenes rendered on the GPU: isolated events convolved with multichannel room impulse
+responses of known directions, the DCASE data generator's recipe, so that audio exists whose labels mean something.  The reference
+has no such code; the definition is this project's.
+
+A scene is the item list of one clip; item i is (event e_i, rir r_i, onset o_i, gain g_i, class c_i, track t_i).
+
+    audio[b, c, n] = ambient[b, c, n] + sum_i g_i (h[r_i, c, :] * s[e_i])[n - o_i]          0 <= n < N
+
+with `*` the full linear convolution.  Item i is active in label frame f iff its DRY extent [o_i, o_i + len) meets
+[hop f, hop (f + 1)), hop = fs / label_rate; its row is (f, c_i, t_i, azimuth[r_i], elevation[r_i]) in integer degrees, a DCASE
+metadata CSV's row.  The convolutions run in salsa_amd/csrc/scene_render.hip (include/salsa_hip.h: salsa_scene_*); SALSA_HIP_SCENE=0
+sends render_scenes to a composed torch.fft evaluation of the same definition, for A/B runs."""
+import ctypes as C
+import io
+import os
+
+import numpy as np
+
+from . import _lib
+
+HIP_SCENE = os.environ.get('SALSA_HIP_SCENE', '1') != '0'   # 0: render_scenes composes torch.fft calls, for A/B runs and bisecting
+FS = 24000
+MAX_CHANNELS, MAX_RIR_LEN, MAX_ITEMS_PER_CLIP = 16, 16384, 256          # the launchers' limits (include/salsa_hip.h)
+SOUND_SPEED = 343.0
+MIC_RADIUS = 0.042
+MIC_DIRECTIONS = ((45, 35), (-45, -35), (135, -35), (-135, 35))          # the TNSSE tetrahedron (azimuth, elevation), degrees
+SINC_HALF = 16                                                           # half width of the Hann-windowed sinc, samples
+
+
+def _unit(az_deg, el_deg):
+    az, el = np.deg2rad(np.asarray(az_deg, np.float64)), np.deg2rad(np.asarray(el_deg, np.float64))
+    return np.stack([np.cos(az) * np.cos(el), np.sin(az) * np.cos(el), np.sin(el)], axis=-1)          # (x, y, z)
+
+
+class RirBank:
+    """rirs float32 (R, C, L) with the integer-degree direction of each response.  Measured SRIRs (TAU-SRIR, ...) enter here as plain
+    arrays; make_rir_bank builds synthetic ones.  The partition spectra are made once per device, on first use there."""
+
+    def __init__(self, rirs, azimuth, elevation, audio_format='foa'):
+        rirs = np.ascontiguousarray(rirs, np.float32)
+        if rirs.ndim != 3 or not (1 <= rirs.shape[1] <= MAX_CHANNELS and 1 <= rirs.shape[2] <= MAX_RIR_LEN) or rirs.shape[0] < 1:
+            raise ValueError('rirs must be (R, C, L) with 1 <= C <= %d and 1 <= L <= %d, got %s' % (MAX_CHANNELS, MAX_RIR_LEN, rirs.shape))
+        if audio_format not in _lib.FORMAT:
+            raise ValueError('audio_format must be foa or mic')
+        self.rirs, self.audio_format = rirs, audio_format
+        self.azimuth, self.elevation = np.asarray(azimuth, np.int64).reshape(-1), np.asarray(elevation, np.int64).reshape(-1)
+        if len(self.azimuth) != rirs.shape[0] or len(self.elevation) != rirs.shape[0]:
+            raise ValueError('one azimuth and one elevation per response')
+        self._spectra = {}
+
+    n_rirs = property(lambda self: self.rirs.shape[0])
+    n_channels = property(lambda self: self.rirs.shape[1])
+    length = property(lambda self: self.rirs.shape[2])
+
+    def rirs_on(self, device):
+        import torch
+        return torch.from_numpy(self.rirs).to(device)
+
+    def spectra(self, device):
+        import torch
+        device = torch.device(device)
+        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        if key not in self._spectra:
+            L = _lib.load()
+            R, Cn, Ln = self.rirs.shape
+            n = L.salsa_scene_rir_spectra_bytes(R, Cn, Ln)
+            spec = torch.empty(n // 4, dtype=torch.float32, device=device)
+            d_rirs = self.rirs_on(device)
+            with torch.cuda.device(device):
+                rc = L.salsa_scene_rir_spectra(C.c_void_p(d_rirs.data_ptr()), R, Cn, Ln, C.c_void_p(spec.data_ptr()),
+                                               C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+            if rc:
+                raise RuntimeError('salsa_scene_rir_spectra failed (%d): %s' % (rc, _lib.last_error()))
+            torch.cuda.current_stream(device).synchronize()                   # d_rirs may go now; once per bank and device
+            self._spectra[key] = spec
+        return self._spectra[key]
+
+
+def make_rir_bank(audio_format, directions, length, rt60=None, drr_db=6.0, seed=0, fs=FS):
+    """Synthetic responses for `directions` = [(azimuth, elevation), ...] in integer degrees, float64 -> float32.
+    foa: channels W, Y, Z, X (the order the reference's FOA transform documents); the direct path is ONE tap (index 0) with the gains
+    (1, sin az cos el, sin el, cos az cos el).  mic: the TNSSE tetrahedron, a plane wave from the direction; microphone m hears it
+    p_m . d / c seconds early, a Hann-windowed-sinc fractional delay around tap SINC_HALF (length >= 2 SINC_HALF + 1).
+    rt60 (seconds): adds a diffuse tail after the direct path, Gaussian noise independent per channel decaying by 60 dB per rt60, whose
+    energy per channel is the first channel's direct energy / 10^(drr_db / 10); RandomState(seed) stream, frozen by numpy."""
+    directions = np.asarray(directions, np.int64).reshape(-1, 2)
+    d = _unit(directions[:, 0], directions[:, 1])                             # (R, 3)
+    R = len(d)
+    h = np.zeros((R, 4, length), np.float64)
+    if audio_format == 'foa':
+        h[:, 0, 0], h[:, 1, 0], h[:, 2, 0], h[:, 3, 0] = 1.0, d[:, 1], d[:, 2], d[:, 0]
+        t0 = 0
+    elif audio_format == 'mic':
+        if length < 2 * SINC_HALF + 1:
+            raise ValueError('a mic response needs at least %d taps' % (2 * SINC_HALF + 1))
+        mics = MIC_RADIUS * _unit([m[0] for m in MIC_DIRECTIONS], [m[1] for m in MIC_DIRECTIONS])     # (4, 3)
+        centre = SINC_HALF - (d @ mics.T) * fs / SOUND_SPEED                  # (R, 4): an advance moves the peak earlier
+        n = np.arange(2 * SINC_HALF + 1, dtype=np.float64)
+        x = n[None, None, :] - centre[:, :, None]
+        win = np.where(np.abs(x) <= SINC_HALF, 0.5 * (1.0 + np.cos(np.pi * x / SINC_HALF)), 0.0)
+        h[:, :, :2 * SINC_HALF + 1] = np.sinc(x) * win
+        t0 = 2 * SINC_HALF
+    else:
+        raise ValueError('audio_format must be foa or mic')
+    if rt60 is not None and length > t0 + 1:
+        rng = np.random.RandomState(seed)
+        t = np.arange(length - t0 - 1, dtype=np.float64)
+        tail = rng.randn(R, 4, len(t)) * 10.0 ** (-3.0 * t / (rt60 * fs))
+        direct = np.sum(h[:, :1] ** 2, axis=-1, keepdims=True)
+        tail *= np.sqrt(direct / 10.0 ** (drr_db / 10.0) / np.sum(tail ** 2, axis=-1, keepdims=True))
+        h[:, :, t0 + 1:] += tail
+    return RirBank(h.astype(np.float32), directions[:, 0], directions[:, 1], audio_format)
+
+
+class EventPool:
+    """signals: 1-D float arrays (the dry, isolated events); classes: one sound class index each."""
+
+    def __init__(self, signals, classes):
+        self.signals = [np.ascontiguousarray(s, np.float32).reshape(-1) for s in signals]
+        self.classes = np.asarray(classes, np.int64).reshape(-1)
+        if not self.signals or len(self.signals) != len(self.classes) or min(len(s) for s in self.signals) < 1:
+            raise ValueError('one class per signal, every signal at least one sample')
+        self.lengths = np.array([len(s) for s in self.signals], np.int64)
+        self.offset = np.concatenate(([0], np.cumsum(self.lengths))).astype(np.int64)
+        self.flat = np.concatenate(self.signals)
+        self.max_len = int(self.lengths.max())
+        self._dev = {}
+
+    def __len__(self):
+        return len(self.signals)
+
+    def on(self, device):
+        import torch
+        key = str(torch.device(device))
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.flat).to(device)
+        return self._dev[key]
+
+
+def synth_event_pool(n_classes=12, per_class=4, seed=0, fs=FS, min_s=0.4, max_s=2.0):
+    """Class-distinct synthetic sounds, so that classes are learnable: class k owns a band around f_k (log-spaced 250 Hz .. 7 kHz) and one
+    of three kinds by k % 3 -- band-limited noise, a harmonic stack on a class-specific fundamental, an up or down chirp across the band
+    -- under a class-specific envelope (attack and decay times).  Instances differ in length, phase and noise.  RandomState streams
+    (frozen by numpy), one per (seed, class, instance); peak-normalised to 0.5."""
+    signals, classes = [], []
+    fk = 250.0 * (7000.0 / 250.0) ** (np.arange(n_classes) / max(1, n_classes - 1))
+    for k in range(n_classes):
+        for j in range(per_class):
+            rng = np.random.RandomState((seed * 1009 + k) * 1013 + j)
+            n = int(rng.uniform(min_s, max_s) * fs)
+            t = np.arange(n) / fs
+            lo, hi = fk[k] / 1.25, fk[k] * 1.25
+            if k % 3 == 0:                                                     # band-limited noise: a Gaussian band cut from white noise
+                spec = np.fft.rfft(rng.randn(n))
+                f = np.fft.rfftfreq(n, 1.0 / fs)
+                x = np.fft.irfft(spec * np.exp(-0.5 * ((f - fk[k]) / (0.1 * fk[k])) ** 2), n)
+            elif k % 3 == 1:                                                   # harmonic stack
+                f0 = fk[k] / 3.0
+                x = sum(np.sin(2 * np.pi * f0 * h * t + rng.uniform(0, 2 * np.pi)) / h for h in range(1, 7) if f0 * h < 0.45 * fs)
+                x = x + 0.02 * rng.randn(n)
+            else:                                                              # chirp across the band, direction by class
+                a, b = (lo, hi) if (k // 3) % 2 == 0 else (hi, lo)
+                x = np.sin(2 * np.pi * (a * t + 0.5 * (b - a) * t * t / t[-1] if n > 1 else a * t) + rng.uniform(0, 2 * np.pi))
+                x = x + 0.02 * rng.randn(n)
+            attack, decay = 0.005 * (1 + k % 4), 0.05 * (1 + (k * 5) % 7)
+            env = np.minimum(1.0, t / attack) * np.minimum(1.0, (t[-1] - t) / decay + 1e-3)
+            if k % 2:
+                env = env * (0.6 + 0.4 * np.cos(2 * np.pi * (2 + k) * t))      # a class-specific tremolo
+            x = x * env
+            signals.append((0.5 * x / max(np.abs(x).max(), 1e-12)).astype(np.float32))
+            classes.append(k)
+    return EventPool(signals, classes)
+
+
+class Scenes:
+    """The item tables of n_clips clips: clip b owns items clip_start[b] .. clip_start[b + 1] - 1.  Per item: event (index into the
+    pool), rir (index into the bank), onset (samples), gain (linear), cls, track, length (of the dry event), azimuth and elevation
+    (integer degrees of its response).  scenes[b] is clip b alone."""
+    FIELDS = ('event', 'rir', 'onset', 'gain', 'cls', 'track', 'length', 'azimuth', 'elevation')
+
+    def __init__(self, n_samples, clip_start, **items):
+        self.n_samples = int(n_samples)
+        self.clip_start = np.asarray(clip_start, np.int32).reshape(-1)
+        for f in self.FIELDS:
+            setattr(self, f, np.asarray(items[f], np.float32 if f == 'gain' else np.int64).reshape(-1))
+        n = len(self.event)
+        if any(len(getattr(self, f)) != n for f in self.FIELDS) or len(self.clip_start) < 2 or self.clip_start[0] != 0 \
+                or self.clip_start[-1] != n or np.any(np.diff(self.clip_start) < 0):
+            raise ValueError('inconsistent scene tables')
+
+    n_clips = property(lambda self: len(self.clip_start) - 1)
+    n_items = property(lambda self: len(self.event))
+
+    def __len__(self):
+        return self.n_clips
+
+    def clips(self, lo, hi):
+        """clips lo .. hi - 1 as Scenes of their own"""
+        if not 0 <= lo <= hi <= self.n_clips:
+            raise IndexError((lo, hi))
+        sl = slice(self.clip_start[lo], self.clip_start[hi])
+        return Scenes(self.n_samples, self.clip_start[lo:hi + 1] - self.clip_start[lo], **{f: getattr(self, f)[sl] for f in self.FIELDS})
+
+    def __getitem__(self, b):
+        if not 0 <= b < self.n_clips:
+            raise IndexError(b)
+        return self.clips(b, b + 1)
+
+    @classmethod
+    def from_items(cls, n_samples, clips, pool, bank):
+        """clips: per clip a list of (event, rir, onset, gain, track) -- class, length and direction come from the pool and the bank."""
+        rows = [it for clip in clips for it in clip]
+        ev = np.array([r[0] for r in rows], np.int64)
+        rir = np.array([r[1] for r in rows], np.int64)
+        return cls(n_samples, np.concatenate(([0], np.cumsum([len(c) for c in clips]))), event=ev, rir=rir,
+                   onset=[r[2] for r in rows], gain=[r[3] for r in rows], cls=pool.classes[ev] if len(ev) else [],
+                   track=[r[4] for r in rows], length=pool.lengths[ev] if len(ev) else [],
+                   azimuth=bank.azimuth[rir] if len(ev) else [], elevation=bank.elevation[rir] if len(ev) else [])
+
+
+def draw_scenes(n_clips, pool, bank, n_samples, seed, max_polyphony=2, allow_same_class=False, gain_db=(-12.0, 0.0),
+                gap_s=(0.5, 4.0), fs=FS, label_rate=10):
+    """Seeded scenes: clip b draws from numpy's Generator default_rng([seed, b]).  Every track (0 .. max_polyphony - 1) is a sequence of
+    events that never share a label frame, so at most max_polyphony items are active in any label frame; unless allow_same_class, an
+    event whose class is active on another track in one of its label frames is drawn again (20 tries, then the place stays empty).
+    Events start at a uniform gap (gap_s seconds) after the frame in which the previous one of the track ended and must fit the clip
+    dry; gains are uniform in dB."""
+    hop = fs // label_rate
+    clips = []
+    for b in range(n_clips):
+        rng = np.random.default_rng([seed, b])
+        items, busy = [], []                                                   # busy: (first frame, last frame, class) of every item so far
+        for track in range(max_polyphony):
+            cursor = int(rng.uniform(0.0, gap_s[1]) * fs)
+            while True:
+                placed = None
+                for _ in range(20):
+                    e = int(rng.integers(len(pool)))
+                    ln = int(pool.lengths[e])
+                    if cursor + ln > n_samples:
+                        continue
+                    f0, f1, k = cursor // hop, (cursor + ln - 1) // hop, int(pool.classes[e])
+                    if allow_same_class or not any(c == k and f0 <= b1 and b0 <= f1 for b0, b1, c in busy):
+                        placed = (e, f0, f1, k, ln)
+                        break
+                if placed is None:
+                    if cursor + int(pool.lengths.min()) > n_samples:
+                        break
+                    cursor += hop
+                    continue
+                e, f0, f1, k, ln = placed
+                g = 10.0 ** (rng.uniform(gain_db[0], gain_db[1]) / 20.0)
+                items.append((e, int(rng.integers(bank.n_rirs)), cursor, g, track))
+                busy.append((f0, f1, k))
+                cursor = (f1 + 1) * hop + int(rng.uniform(gap_s[0], gap_s[1]) * fs)
+                if cursor >= n_samples:
+                    break
+        items.sort(key=lambda it: (it[2], it[4]))
+        clips.append(items)
+    return Scenes.from_items(n_samples, clips, pool, bank)
+
+
+def scene_rows(scene, label_rate=10, fs=FS):
+    """The DCASE metadata rows (frame, class, track, azimuth, elevation) of ONE clip, int64 (n_rows, 5), sorted by frame then item."""
+    if scene.n_clips != 1:
+        raise ValueError('scene_rows takes one clip: scenes[b]')
+    hop = fs // label_rate
+    rows = []
+    for i in range(scene.n_items):
+        o, end = int(scene.onset[i]), min(int(scene.onset[i] + scene.length[i]), scene.n_samples)
+        for f in range(o // hop, (end - 1) // hop + 1):
+            rows.append((f, int(scene.cls[i]), int(scene.track[i]), int(scene.azimuth[i]), int(scene.elevation[i]), i))
+    rows.sort(key=lambda r: (r[0], r[5]))
+    return np.array([r[:5] for r in rows], np.int64).reshape(-1, 5)
+
+
+def scene_labels(scene, n_frames, n_classes, label_format='classwise', label_rate=10, fs=FS):
+    """Training targets of one clip over n_frames LABEL frames (rows at or past n_frames are dropped): what load_classwise_gt /
+    load_trackwise_gt read from a CSV of scene_rows, by those very readers on the rows' text, hence bit for bit.  -> (sed, doa):
+    classwise (n_frames, n_classes) and (n_frames, 3 n_classes); trackwise three slots per class."""
+    from .dataset import LABEL_FORMATS, load_classwise_gt, load_trackwise_gt
+    if label_format not in LABEL_FORMATS:
+        raise ValueError('invalid label_format %r' % (label_format,))
+    rows = scene_rows(scene, label_rate, fs)
+    rows = rows[rows[:, 0] < n_frames]
+    width = n_classes * (3 if label_format == 'trackwise' else 1)
+    if not len(rows):
+        return np.zeros((n_frames, width), np.float32), np.zeros((n_frames, 3 * width), np.float32)
+    text = io.StringIO(''.join('%d,%d,%d,%d,%d\n' % tuple(r) for r in rows))
+    if label_format == 'trackwise':
+        return load_trackwise_gt(text, n_frames, n_classes, 1)[:2]
+    return load_classwise_gt(text, n_frames, n_classes, 1)
+
+
+def _tables(scenes, pool, bank):
+    if scenes.n_items and (scenes.event.min() < 0 or scenes.event.max() >= len(pool)):
+        raise ValueError('an item names no event of the pool')
+    items = np.ascontiguousarray(np.stack([pool.offset[scenes.event], scenes.onset, pool.lengths[scenes.event], scenes.rir]), np.int64) \
+        if scenes.n_items else np.zeros((4, 0), np.int64)
+    return np.ascontiguousarray(scenes.clip_start, np.int32), items, np.ascontiguousarray(scenes.gain, np.float32)
+
+
+def _render_torch_fft(scenes, pool, bank, n_samples, ambient, out):
+    """the same definition composed from torch.fft calls, one per item (SALSA_HIP_SCENE=0)"""
+    import torch
+    dev = out.device
+    ev, h = pool.on(dev), bank.rirs_on(dev)
+    L = bank.length
+    wet = torch.zeros_like(out)
+    inside = torch.zeros((scenes.n_clips, 1, n_samples), dtype=torch.bool, device=dev)
+    for b in range(scenes.n_clips):
+        for i in range(scenes.clip_start[b], scenes.clip_start[b + 1]):
+            e, o, ln = int(scenes.event[i]), int(scenes.onset[i]), int(pool.lengths[scenes.event[i]])
+            full = ln + L - 1
+            n_fft = 1 << (full - 1).bit_length()
+            s = ev[int(pool.offset[e]):int(pool.offset[e]) + ln]
+            y = torch.fft.irfft(torch.fft.rfft(s, n_fft)[None] * torch.fft.rfft(h[int(scenes.rir[i])], n_fft), n_fft)[:, :full]
+            keep = min(full, n_samples - o)
+            wet[b, :, o:o + keep] += float(scenes.gain[i]) * y[:, :keep]
+            inside[b, :, o:o + keep] = True
+    base = ambient if ambient is not None else torch.zeros_like(out)
+    out.copy_(torch.where(inside, base + wet, base))
+    return out
+
+
+def render_scenes(scenes, pool, bank, n_samples=None, ambient=None, out=None, device=None):
+    """-> CUDA float32 (B, C, n_samples).  ambient: CUDA (B, C, n_samples) or None; out may be given (and may be the ambient)."""
+    import torch
+    n_samples = scenes.n_samples if n_samples is None else int(n_samples)
+    B, Cn = scenes.n_clips, bank.n_channels
+    if ambient is not None:
+        device = ambient.device
+    elif out is not None:
+        device = out.device
+    device = torch.device('cuda' if device is None else device)
+    if out is None:
+        out = torch.empty((B, Cn, n_samples), dtype=torch.float32, device=device)
+    for t in (out, ambient):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (B, Cn, n_samples) and t.is_contiguous()):
+            raise ValueError('render_scenes: contiguous float32 CUDA (%d, %d, %d) expected' % (B, Cn, n_samples))
+    if scenes.n_items and scenes.onset.max() >= n_samples:
+        raise ValueError('an onset lies outside the clip')
+    if np.diff(scenes.clip_start).max() > MAX_ITEMS_PER_CLIP:
+        raise ValueError('a clip holds at most %d items' % MAX_ITEMS_PER_CLIP)
+    if not HIP_SCENE:
+        return _render_torch_fft(scenes, pool, bank, n_samples, ambient, out)
+    L = _lib.load()
+    clip_start, items, gains = _tables(scenes, pool, bank)
+    n_items = scenes.n_items
+    ws_bytes = L.salsa_scene_workspace_bytes(n_samples, pool.max_len, n_items)
+    ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=device)
+    d_clip, d_items, d_gains = (torch.from_numpy(a).to(device) for a in (clip_start, items, gains))
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    hp = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+    with torch.cuda.device(device):
+        rc = L.salsa_scene_render(ptr(pool.on(device)), len(pool.flat), ptr(bank.spectra(device)), bank.n_rirs, Cn, bank.length,
+                                  hp(clip_start), hp(items), hp(gains), ptr(d_clip), ptr(d_items), ptr(d_gains), B, n_items, pool.max_len,
+                                  ptr(ambient), ptr(out), n_samples, ptr(ws) if n_items else None, ws_bytes,
+                                  C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    if rc:
+        raise RuntimeError('salsa_scene_render failed (%d): %s' % (rc, _lib.last_error()))
+    return out
+
+
+def add_scenes(feature_bank, scenes, pool, bank, names=None, ambient=None, n_classes=None, label_rate=10, fs=FS):
+    """Render, then feature_bank.add_clips(audio, names, sed=, doa=) with the scenes' labels in the bank's label format.  -> the audio."""
+    audio = render_scenes(scenes, pool, bank, ambient=ambient, device=feature_bank.device)
+    fmt = feature_bank.label_format
+    n_classes = (feature_bank.n_classes // 3 if fmt == 'trackwise' else feature_bank.n_classes) if n_classes is None else n_classes
+    n_lab = -(-scenes.n_samples // (fs // label_rate))
+    labels = [scene_labels(scenes[b], n_lab, n_classes, fmt, label_rate, fs) for b in range(scenes.n_clips)]
+    names = ['scene_%04d' % b for b in range(scenes.n_clips)] if names is None else list(names)
+    feature_bank.add_clips(audio, names, sed=[lab[0] for lab in labels], doa=[lab[1] for lab in labels])
+    return audio

@@ -1,0 +1,92 @@
+#!/usr/bin/env python
+"""Does the training step learn to localise?  A record, not a test: FOA training scenes and held-out scenes are
+drawn from different seeds over ONE event pool and ONE response bank (salsa_amd/scenes.py), rendered on the device, extracted into
+GpuFeatureBanks, and Trainer.fit runs a few epochs.  The SELD 2021 scores on the held-out scenes are recorded before training and
+after every epoch.  No score is promised; the JSON lines say what was seen.
+
+    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--out profiles/scene_training.jsonl]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--train-clips', type=int, default=48)
+    ap.add_argument('--val-clips', type=int, default=8)
+    ap.add_argument('--clip-s', type=int, default=60)
+    ap.add_argument('--epochs', type=int, default=8)
+    ap.add_argument('--batch', type=int, default=32)
+    ap.add_argument('--rir-len', type=int, default=2400)
+    ap.add_argument('--rt60', type=float, default=0.3)
+    ap.add_argument('--seed', type=int, default=2021)
+    ap.add_argument('--out', default=None, help='append the JSON lines to this file too')
+    args = ap.parse_args()
+    import torch
+    from salsa_amd import scenes as sc
+    from salsa_amd.crnn.fit import validate
+    from salsa_amd.crnn.train import Trainer
+    from salsa_amd.dataset import GpuFeatureBank
+    from salsa_amd.extractor import SalsaExtractor
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, 'a') as f:
+                f.write(line + '\n')
+
+    dev = torch.device('cuda:0')
+    NC, n = 12, args.clip_s * sc.FS
+    pool = sc.synth_event_pool(NC, 4, 0)
+    rbank = sc.make_rir_bank('foa', [(a, e) for a in range(-180, 180, 30) for e in (-40, -10, 20, 50)], args.rir_len, rt60=args.rt60, seed=1)
+    ex = SalsaExtractor(audio_format='foa', fmax_doa=9000, device=dev)
+    t0 = time.perf_counter()
+    banks, drawn = {}, {}
+    for name, clips, seed in (('train', args.train_clips, args.seed), ('val', args.val_clips, args.seed + 1000)):
+        scenes = sc.draw_scenes(clips, pool, rbank, n, seed)
+        bank = GpuFeatureBank(ex, n_classes=NC, max_clip_s=args.clip_s)
+        g = torch.Generator(dev).manual_seed(seed)
+        for lo in range(0, clips, 16):                                         # 16 clips of audio at a time
+            part = scenes.clips(lo, min(lo + 16, clips))
+            amb = 1e-3 * torch.randn(part.n_clips, 4, n, device=dev, generator=g)
+            sc.add_scenes(bank, part, pool, rbank, names=['%s_%04d' % (name, lo + i) for i in range(part.n_clips)], ambient=amb)
+        banks[name], drawn[name] = bank, scenes
+    banks['train'].fit_scaler()
+    mean, std = (t.cpu().numpy() if torch.is_tensor(t) else t for t in (banks['train'].mean, banks['train'].std))
+    banks['val'].set_scaler(mean, std)
+    for b in banks.values():
+        b.finalize()
+    torch.cuda.synchronize()
+    val_gt = [[(int(f), int(c), float(az), float(el), int(t)) for f, c, t, az, el in sc.scene_rows(drawn['val'][b])] for b in range(args.val_clips)]
+    emit(dict(record='scene_training', what='setup', train_clips=args.train_clips, val_clips=args.val_clips, clip_s=args.clip_s,
+              train_items=int(drawn['train'].n_items), val_items=int(drawn['val'].n_items), train_chunks=len(banks['train']), classes=NC,
+              responses=int(rbank.n_rirs), rir_len=args.rir_len, rt60=args.rt60, events_in_pool=len(pool), ambient_rms=1e-3,
+              seconds_to_render_extract_and_bank=round(time.perf_counter() - t0, 2), device=torch.cuda.get_device_name(0)))
+    tr = Trainer('cuda', seed=args.seed)
+    keys = ('valER', 'valF1', 'valLE', 'valLR', 'valSeld')
+    before = validate(tr, banks['val'], val_gt)
+    emit(dict(record='scene_training', what='held-out scores before training', **{k: round(before[k], 4) for k in keys}))
+    t0 = time.perf_counter()
+    hist = tr.fit(banks['train'], val_bank=banks['val'], val_gt=val_gt, batch_size=args.batch, max_epochs=args.epochs, seed=args.seed,
+                  audio_format='foa')
+    seconds = time.perf_counter() - t0
+    steps_per_epoch = len(hist['steps']) // max(1, args.epochs)
+    for v in hist['val']:
+        ep = [s for s in hist['steps'] if s[0] == v['epoch']]
+        emit(dict(record='scene_training', what='epoch', epoch=v['epoch'], mean_loss=round(sum(s[4] for s in ep) / len(ep), 5),
+                  **{k: round(v[k], 4) for k in keys}))
+    after = hist['val'][-1]
+    emit(dict(record='scene_training', what='held-out scores after training', epochs=args.epochs, steps=len(hist['steps']),
+              steps_per_epoch=steps_per_epoch, fit_seconds=round(seconds, 2), **{k: round(after[k], 4) for k in keys},
+              valSeld_before=round(before['valSeld'], 4), best_valSeld=round(hist['best']['valSeld'], 4) if hist['best'] else None))
+
+
+if __name__ == '__main__':
+    main()
