@@ -69,9 +69,9 @@ def conv_backend_note() -> str:
     if USE_HIP_CONV_WIDE:
         wrw = ('every 3x3 layer hand-written' if os.environ.get('SALSA_HIP_CONV_WIDE_WRW', '1') != '0'
                else '64->64 hand-written, the rest MIOpen')
-        return ('every 3x3 layer forward + data gradient on hand-written MFMA kernels (stem 7->64 and 64->64: conv_mfma.hip; 128/256/512 '
+        return ('every 3x3 layer forward + data gradient on hand-written MFMA kernels (stem 7->64: conv_stem.hip; 64->64: conv_mfma.hip; 128/256/512 '
                 'channels: conv_wide.hip); weight gradients: %s; 1x1 shortcuts: conv_1x1.hip (MIOpen: nothing)' % wrw)
-    return 'stem 7->64 and the five 64->64 3x3 layers on the hand-written MFMA kernels (conv_mfma.hip), the 128/256/512-channel layers on MIOpen through torch'
+    return 'stem 7->64 and the five 64->64 3x3 layers on the hand-written MFMA kernels (conv_stem.hip, conv_mfma.hip), the 128/256/512-channel layers on MIOpen through torch'
 
 
 class _AvgPool2x2(torch.autograd.Function):
@@ -574,7 +574,7 @@ def _conv64(x, w, add=None, stats_part=None):
 
 class _Conv3x3C64(torch.autograd.Function):
     """64 -> 64 channel 3x3 convolution on the matrix cores (salsa_amd/csrc/conv_mfma.hip): forward, data gradient (the same
-    kernel with the flipped / transposed filter) and weight gradient (float32, straight into the float32 parameter's grad)."""
+    kernel with the flipped / transposed filter) and weight gradient (conv_c64_wrw.hip; float32, straight into the float32 parameter's grad)."""
 
     @staticmethod
     def forward(ctx, x, weight, wb=None, wbt=None, skip=False, stats_part=None):

@@ -9,18 +9,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "nn_det.h"
+#include "conv_internal.h" // bf16x8, f32x16, pack_bf16, tr_frag / tr_value
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)
-{
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
-}
 
 // ---------------------------------------------------------------------------------------------- forward / data gradient
 // x [M][K], w [N][K] (both K-contiguous: an MFMA operand fragment is ONE 16-byte load per lane, no LDS), y [M][N].
@@ -79,23 +70,14 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(const unsigned short *__re
 // ------------------------------------------------------------------------------------------------------ weight gradient
 // dW[co][ci] += sum_p dy[p][co] x[p][ci]: the reduction runs over PIXELS, so both operands need 8 consecutive pixels of one
 // channel per lane while memory is pixel-major -- gfx950's transposing LDS read (ds_read_b64_tr_b16; lane mapping in
-// conv_mfma.hip, "weight gradient") builds such fragments from pixel-major LDS tiles.  A workgroup owns a 128 co x 64 ci block
+// conv_c64_wrw.hip) builds such fragments from pixel-major LDS tiles.  A workgroup owns a 128 co x 64 ci block
 // of dW and a contiguous share of the pixel tiles (64 pixels each; grid.z splits the pixels so that ~512 workgroups exist);
 // wave w owns co 32w.. x both ci halves = 2 accumulator tiles, added to the float32 result with atomics at the end.
 constexpr int WP = 64;                  // pixels per tile
 constexpr int ROW_G = 128 + 8, ROW_X = 64 + 8; // padded LDS rows (bf16 elements): 272- and 144-byte pitches
 
-struct tr_frag {
-    unsigned long long lo, hi;
-};
-__device__ __forceinline__ bf16x8 tr_value(const tr_frag &f)
-{
-    union { unsigned long long q[2]; bf16x8 v; } u;
-    u.q[0] = f.lo;
-    u.q[1] = f.hi;
-    return u.v;
-}
 // one fragment (16 pixels x 32 channels) = two transposing reads: pixel rows +0..3 and +4..7 of the lane's 8-pixel half
+// (tr_frag and tr_value are conv_internal.h's; this macro is not its LDS_TR_ISSUE, which has the 3x3 kernels' row pitch built in)
 #define TR_ISSUE(f, addr, imm, row_bytes)                                                                                  \
     asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4"                              \
                  : "=&v"((f).lo), "=&v"((f).hi)                                                                            \

@@ -24,14 +24,12 @@
 #include <stdint.h>
 #include <utility>
 #include "nn_det.h"
+#include "conv_internal.h" // bf16x8, f32x16, pack_bf16
 
 #ifndef WIDE_OUT_NT
 #define WIDE_OUT_NT 0
 #endif
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int KC = 32;                // input channels per chunk (2 MFMA k-steps)
 constexpr int MAX_XL_BYTES = 53248;   // input chunk: up to 832 slots of 64 bytes (a multiple of 1 KiB: whole wave-loads)
@@ -49,13 +47,6 @@ __device__ __forceinline__ const unsigned short *wide_zero_ptr()
     const unsigned short *z = (const unsigned short *)&wide_zero16;
     asm volatile("" : "+s"(z));
     return z;
-}
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)
-{
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
 }
 
 // byte offset of 16-byte piece q of 64-byte row `row` (XOR swizzle, see the header)
@@ -252,7 +243,7 @@ __global__ __launch_bounds__(64 * WV) void conv3x3_wide_kernel(const unsigned sh
     // Training (stats_part != NULL): the per-channel sum and sum of squares of this tile's bf16-ROUNDED outputs -- what the
     // BatchNorm that follows would otherwise read the whole tensor for (15 statistics passes, 0.17 ms per step) -- as ONE float64
     // row pair stats_part[blockIdx.x][sum | sum of squares][COUT] (this workgroup's TN channels of it), the layout of the
-    // BatchNorm kernels' own partial table.  Per wave like conv64_stats (conv_mfma.hip): two DPP quad permutes sum neighbouring
+    // BatchNorm kernels' own partial table.  Per wave like conv64_stats (conv_internal.h): two DPP quad permutes sum neighbouring
     // pixel columns, lane q of a quad keeps channel group g = q, three shuffles combine the 8 quads of a half-wave; the
     // workgroup's waves meet in LDS (the tile buffers are free by then).
     if (stats_part) {
@@ -495,7 +486,7 @@ extern "C" int salsa_nn_conv3x3_wide_bias_act(const void *x, const void *w, cons
 // ------------------------------------------------------------------------------------------------------------ weight gradient
 // dW[co][tap][ci] = sum over pixels p of dy[p][co] * x[p + off(tap)][ci] for the wide layers: a GEMM whose reduction runs over
 // PIXELS, so both MFMA operands need 8 consecutive pixels of ONE channel per lane while memory is pixel-major -- gfx950's
-// transposing LDS read (ds_read_b64_tr_b16, mapping in conv_mfma.hip "weight gradient") builds them from pixel-major tiles.
+// transposing LDS read (ds_read_b64_tr_b16, mapping in conv_c64_wrw.hip) builds them from pixel-major tiles.
 // Same flattened pixel axis and padded slot layout as the forward kernel, with two differences: the tiles are NOT swizzled (a
 // transposing read of 32 lanes covers four whole consecutive 64-byte slots = every bank once), and a workgroup walks MANY pixel
 // tiles, so the (n, h, w) arithmetic of the forward kernel's set-up is replaced by two small index tables built once per map

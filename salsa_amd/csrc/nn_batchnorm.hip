@@ -1,143 +1,14 @@
-// nn_ops.hip -- gfx950 kernels for the memory-bound layers of the SELD CRNN (C ABI: include/salsa_nn.h).
-// Everything here is a streaming pass: 16-byte accesses, channels-last so that a thread's vector is contiguous.
+// nn_batchnorm.hip -- gfx950 kernels for BatchNorm2d (+ residual add) (+ ReLU) (+ dropout) (+ 2x2 average pool) of the SELD CRNN,
+// training forward, inference forward and backward (C ABI: include/salsa_nn.h).  Streaming passes: 16-byte accesses,
+// channels-last so that a thread's vector is contiguous.
 #include "build_guard.h" // probe switches need -DSALSA_PROBE_BUILD; SALSA_BUILD_FLAGS (generated: tools/gen_build_guard.py)
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
 
 #include "../../include/salsa_nn.h"
-#include "nn_det.h"
 #include "nn_common.h"
+#include "nn_vec.h"
 
 namespace {
-
-struct f32x4 {
-    float v[4];
-};
-struct bf16x8 {
-    unsigned short v[8];
-};
-
-__device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
-// two float32 -> packed bf16 (low half = a), round to nearest even: one v_cvt_pk_bf16_f32 on gfx950
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)
-{
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
-}
-
-// Round-5 probes: the 16-byte vector loads / stores of the streaming passes (BatchNorm, pooling) as non-temporal accesses
-// (-DNN_NT_LD=1 / -DNN_NT_ST=1).  Every tensor these passes touch is read or written exactly once per launch.
-#ifndef NN_NT_LD
-#define NN_NT_LD 0
-#endif
-#ifndef NN_NT_ST
-#define NN_NT_ST 0
-#endif
-typedef unsigned nn_u4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 nn_ld16(const void *p)
-{
-    if (NN_NT_LD) {
-        const nn_u4v t = __builtin_nontemporal_load((const nn_u4v *)p);
-        return make_uint4(t.x, t.y, t.z, t.w);
-    }
-    return *(const uint4 *)p;
-}
-__device__ __forceinline__ void nn_st16(void *p, const uint4 v)
-{
-    if (NN_NT_ST) {
-        const nn_u4v t = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(t, (nn_u4v *)p);
-    } else
-        *(uint4 *)p = v;
-}
-
-template <typename V, int L> struct vec_io;
-template <> struct vec_io<f32x4, 4> {
-    typedef float4 raw_t;
-    static __device__ __forceinline__ raw_t load_raw(const void *p) { return *(const float4 *)p; }
-    static __device__ __forceinline__ void convert(const raw_t &t, float *f) { f[0] = t.x; f[1] = t.y; f[2] = t.z; f[3] = t.w; }
-    static __device__ __forceinline__ void load(const void *p, float *f)
-    {
-        const float4 t = *(const float4 *)p;
-        f[0] = t.x; f[1] = t.y; f[2] = t.z; f[3] = t.w;
-    }
-    static __device__ __forceinline__ void store(void *p, const float *f) { *(float4 *)p = make_float4(f[0], f[1], f[2], f[3]); }
-};
-template <> struct vec_io<bf16x8, 8> {
-    typedef uint4 raw_t;
-    static __device__ __forceinline__ raw_t load_raw(const void *p) { return nn_ld16(p); }
-    static __device__ __forceinline__ void convert(const raw_t &t, float *f)
-    {
-        const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            f[2 * i] = bf2f((unsigned short)(w[i] & 0xffffu));
-            f[2 * i + 1] = bf2f((unsigned short)(w[i] >> 16));
-        }
-    }
-    static __device__ __forceinline__ void load(const void *p, float *f) { convert(load_raw(p), f); }
-    static __device__ __forceinline__ void store(void *p, const float *f)
-    {
-        unsigned w[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) w[i] = pack_bf16(f[2 * i], f[2 * i + 1]);
-        nn_st16(p, make_uint4(w[0], w[1], w[2], w[3]));
-    }
-};
-
-// one thread = one output pixel x L channels (16 bytes); x, y channels-last
-template <typename V, int L>
-__global__ __launch_bounds__(256) void avgpool2x2_fwd_kernel(const char *__restrict__ x, char *__restrict__ y, long n_vec,
-                                                             int H, int W, int C)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_vec) return;
-    const int cv = C / L, Ho = H / 2, Wo = W / 2;
-    const int c = (int)(i % cv);
-    long r = i / cv;
-    const int wo = (int)(r % Wo);
-    r /= Wo;
-    const int ho = (int)(r % Ho);
-    const long n = r / Ho;
-    const long esz = 16 / L; // bytes per element
-    const char *p = x + (((n * H + 2 * ho) * W + 2 * wo) * C + (long)c * L) * esz;
-    float a[L], b[L], cc[L], d[L], o[L];
-    vec_io<V, L>::load(p, a);
-    vec_io<V, L>::load(p + (long)C * esz, b);
-    vec_io<V, L>::load(p + (long)W * C * esz, cc);
-    vec_io<V, L>::load(p + ((long)W * C + C) * esz, d);
-#pragma unroll
-    for (int k = 0; k < L; k++) o[k] = (((a[k] + b[k]) + cc[k]) + d[k]) / 4.0f; // the reference implementation's order
-    vec_io<V, L>::store(y + i * 16, o);
-}
-
-// one thread = one INPUT pixel x L channels: grad_x = grad_y[h/2][w/2] / 4, zero in a dropped odd row / column
-template <typename V, int L>
-__global__ __launch_bounds__(256) void avgpool2x2_bwd_kernel(const char *__restrict__ gy, char *__restrict__ gx, long n_vec,
-                                                             int H, int W, int C)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_vec) return;
-    const int cv = C / L, Ho = H / 2, Wo = W / 2;
-    const int c = (int)(i % cv);
-    long r = i / cv;
-    const int w = (int)(r % W);
-    r /= W;
-    const int h = (int)(r % H);
-    const long n = r / H;
-    float g[L];
-    if (h < 2 * Ho && w < 2 * Wo) {
-        vec_io<V, L>::load(gy + ((((n * Ho + h / 2) * Wo + w / 2) * cv + c) * 16), g);
-#pragma unroll
-        for (int k = 0; k < L; k++) g[k] = g[k] / 4.0f;
-    } else {
-#pragma unroll
-        for (int k = 0; k < L; k++) g[k] = 0.f;
-    }
-    vec_io<V, L>::store(gx + i * 16, g);
-}
-
 
 // ------------------------------------------------------------------------------------------------ BatchNorm2d (+ add) (+ ReLU)
 // x: [M][C] channels-last (M = N*H*W).  A thread owns one column group of L channels (16 bytes); a 256-thread block is
@@ -663,507 +534,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const char *__restric
     else bn_bwd_apply_rows<V, L, POOL, 0>(dy, y, x, dx, dres, M, cv, rpi, cx, ry, a, b, mu, kk, is, be, ga, mask_from_x, drop, PH, PW);
 }
 
-// ------------------------------------------------------------------------------------------------ convolution filter bank
-// Every step the hand-written convolutions need each float32 master filter (Cout, Cin, 3, 3) as bf16 in two layouts: the
-// forward kernel's [Cout][3][3][Cin] and the data-gradient kernel's flipped / transposed [Cin][3][3][Cout].  Through torch
-// that was four small kernels per layer per step (cast, permute copy, flip, permute copy: 68 launches, ~0.5 ms); here ONE
-// launch does all layers.  A block = one layer's 32 x 32 (co, ci) tile with its nine taps: the 32 x 288 floats go through LDS
-// (row pitch 289: both read patterns below are bank-conflict-free) and leave as 64-byte runs in either layout.
-// desc: 11 x int64 per layer = src, fwd, bwd pointers, Cout, Cin, element strides of src (co, ci, ky, kx), first block, taps
-// (9, or 1 for the 1x1 shortcut filters: forward [Cout][Cin], data-gradient [Cin][Cout]).
-__global__ __launch_bounds__(256) void conv_filter_bank_kernel(const long long *__restrict__ desc, int n_layers)
-{
-    __shared__ float tile[32][289];
-    int l = 0;
-    while (l + 1 < n_layers && (long long)blockIdx.x >= desc[(l + 1) * 11 + 9]) l++;
-    const long long *d = desc + l * 11;
-    const float *src = (const float *)d[0];
-    __hip_bfloat16 *fwd = (__hip_bfloat16 *)d[1], *bwd = (__hip_bfloat16 *)d[2];
-    const int Cout = (int)d[3], Cin = (int)d[4], taps = (int)d[10], rw = 32 * taps; // taps = 9 or 1
-    const long s_co = d[5], s_ci = d[6], s_ky = d[7], s_kx = d[8];
-    const int t = (int)(blockIdx.x - d[9]), tiles_ci = Cin / 32, co0 = (t / tiles_ci) * 32, ci0 = (t % tiles_ci) * 32;
-    if (s_ci == 1 && !(s_co & 3) && !(s_ky & 3) && !(s_kx & 3)) { // channels-last master filter (the trainer's): 16-byte loads along ci
-        for (int e = threadIdx.x; e < 8 * rw; e += 256) {
-            const int co = e / (8 * taps), q = e % (8 * taps), ci = (q % 8) * 4, tap = q / 8;
-            const float4 v = *(const float4 *)(src + (co0 + co) * s_co + (ci0 + ci) + (tap / 3) * s_ky + (tap % 3) * s_kx);
-            tile[co][ci * taps + tap] = v.x;
-            tile[co][(ci + 1) * taps + tap] = v.y;
-            tile[co][(ci + 2) * taps + tap] = v.z;
-            tile[co][(ci + 3) * taps + tap] = v.w;
-        }
-    } else {
-        for (int e = threadIdx.x; e < 32 * rw; e += 256) { // consecutive threads walk the source's contiguous axis: ci when the
-            // master filter is channels-last (s_ci == 1), the taps when it is torch's default (co, ci, ky, kx)
-            const int co = e / rw, q = e % rw;
-            const int ci = s_ci == 1 ? q % 32 : q / taps, tap = s_ci == 1 ? q / 32 : q % taps;
-            tile[co][ci * taps + tap] = src[(co0 + co) * s_co + (ci0 + ci) * s_ci + (tap / 3) * s_ky + (tap % 3) * s_kx];
-        }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 16 * rw; e += 256) { // two neighbouring channels per thread: 4-byte stores, 64-byte runs per 16 lanes
-        const int a = (e % 16) * 2, tap = (e / 16) % taps, b = e / (16 * taps);
-        *(unsigned *)(fwd + ((long)(co0 + b) * taps + tap) * Cin + ci0 + a) = pack_bf16(tile[b][a * taps + tap], tile[b][(a + 1) * taps + tap]); // (co = b, ci = a)
-        if (bwd)
-            *(unsigned *)(bwd + ((long)(ci0 + b) * taps + (taps - 1 - tap)) * Cout + co0 + a) = pack_bf16(tile[a][b * taps + tap], tile[a + 1][b * taps + tap]); // (ci = b, co = a)
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------ frequency mean
-// The decoder's first step (models/decoders.py: x.mean(dim=3), then (B, C, T) -> (B, T, C)): x bf16 channels-last [N][H][W][C]
-// -> float32 [H][N][C] (time-major, the GRU's order) or [N][H][C]; torch's reduction over the strided axis ran at 0.4 TB/s.
-__global__ __launch_bounds__(256) void freq_mean_fwd_kernel(const unsigned short *__restrict__ x, float *__restrict__ y, long rows,
-                                                            int N, int H, int W, int C, int time_major)
-{
-    const int cv = C / 8;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * cv) return;
-    const long r = i / cv;
-    const int c8 = (int)(i - r * cv);
-    const uint4 *p = (const uint4 *)(x + (r * W) * C + c8 * 8);
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int w = 0; w < W; w++) {
-        const uint4 v = p[(long)w * cv];
-        const unsigned u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            acc[2 * k] += __uint_as_float(u[k] << 16);
-            acc[2 * k + 1] += __uint_as_float(u[k] & 0xFFFF0000u);
-        }
-    }
-    const float inv = 1.f / (float)W;
-    const long n = r / H, h = r - n * H;
-    float *o = y + ((time_major ? h * N + n : r) * C + c8 * 8);
-    *(float4 *)o = make_float4(acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
-    *(float4 *)(o + 4) = make_float4(acc[4] * inv, acc[5] * inv, acc[6] * inv, acc[7] * inv);
-}
-
-// dx[n][h][w][c] = g[row(n, h)][c] / W, bf16 channels-last
-__global__ __launch_bounds__(256) void freq_mean_bwd_kernel(const float *__restrict__ g, unsigned short *__restrict__ dx, long rows,
-                                                            int N, int H, int W, int C, int time_major)
-{
-    const int cv = C / 8;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * W * cv) return;
-    const long rw = i / cv;
-    const int c8 = (int)(i - rw * cv);
-    const long r = rw / W;
-    const long n = r / H, h = r - n * H;
-    const float *src = g + ((time_major ? h * N + n : r) * C + c8 * 8);
-    const float4 a = *(const float4 *)src, b = *(const float4 *)(src + 4);
-    const float inv = 1.f / (float)W;
-    uint4 o;
-    o.x = pack_bf16(a.x * inv, a.y * inv);
-    o.y = pack_bf16(a.z * inv, a.w * inv);
-    o.z = pack_bf16(b.x * inv, b.y * inv);
-    o.w = pack_bf16(b.z * inv, b.w * inv);
-    *(uint4 *)(dx + rw * C + c8 * 8) = o;
-}
-
-// ------------------------------------------------------------------------------------------- frequency max / avg + max pool
-// The decoder's freq_pool 'max' and 'avg_max' (models/decoders.py: torch.max(x, dim=3), mean + max) in one pass, laid out like
-// freq_mean_fwd_kernel (8 channels per thread).  mode 1: y = max; mode 2: y = mean + max, the mean accumulated in w order as
-// freq_mean does.  argmax (uint8, W <= 255) is the LOWEST w holding the maximum; a NaN wins over every number and the first NaN
-// is kept, so NaN propagates with its own index.
-__global__ __launch_bounds__(256) void freq_pool_fwd_kernel(const unsigned short *__restrict__ x, float *__restrict__ y,
-                                                            uint8_t *__restrict__ argmax, long rows, int N, int H, int W, int C,
-                                                            int mode, int time_major)
-{
-    const int cv = C / 8;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * cv) return;
-    const long r = i / cv;
-    const int c8 = (int)(i - r * cv);
-    const uint4 *p = (const uint4 *)(x + (r * W) * C + c8 * 8);
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, mx[8];
-    int am[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int w = 0; w < W; w++) {
-        const uint4 v = p[(long)w * cv];
-        const unsigned u[4] = {v.x, v.y, v.z, v.w};
-        float e[8];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            e[2 * k] = __uint_as_float(u[k] << 16);
-            e[2 * k + 1] = __uint_as_float(u[k] & 0xFFFF0000u);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            acc[k] += e[k];
-            const bool take = w == 0 || e[k] > mx[k] || (e[k] != e[k] && mx[k] == mx[k]); // strictly greater, or the first NaN
-            mx[k] = take ? e[k] : mx[k];
-            am[k] = take ? w : am[k];
-        }
-    }
-    const float inv = 1.f / (float)W;
-    float out[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) out[k] = mode == 2 ? __fadd_rn(__fmul_rn(acc[k], inv), mx[k]) : mx[k]; // (mean rounded, then added: no fma)
-    const long n = r / H, h = r - n * H;
-    const long row = time_major ? h * N + n : r;
-    float *o = y + (row * C + c8 * 8);
-    *(float4 *)o = make_float4(out[0], out[1], out[2], out[3]);
-    *(float4 *)(o + 4) = make_float4(out[4], out[5], out[6], out[7]);
-    uint2 a;
-    a.x = (unsigned)am[0] | ((unsigned)am[1] << 8) | ((unsigned)am[2] << 16) | ((unsigned)am[3] << 24);
-    a.y = (unsigned)am[4] | ((unsigned)am[5] << 8) | ((unsigned)am[6] << 16) | ((unsigned)am[7] << 24);
-    *(uint2 *)(argmax + row * C + c8 * 8) = a;
-}
-
-// dx[n][h][w][c] = g[row][c] / W (mode 2 only) + g[row][c] * (w == argmax[row][c]), bf16 channels-last
-__global__ __launch_bounds__(256) void freq_pool_bwd_kernel(const float *__restrict__ g, const uint8_t *__restrict__ argmax,
-                                                            unsigned short *__restrict__ dx, long rows, int N, int H, int W, int C,
-                                                            int mode, int time_major)
-{
-    const int cv = C / 8;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * W * cv) return;
-    const long rw = i / cv;
-    const int c8 = (int)(i - rw * cv);
-    const long r = rw / W;
-    const int w = (int)(rw - r * W);
-    const long n = r / H, h = r - n * H;
-    const long row = time_major ? h * N + n : r;
-    const float *src = g + (row * C + c8 * 8);
-    const float4 a = *(const float4 *)src, b = *(const float4 *)(src + 4);
-    const uint2 am = *(const uint2 *)(argmax + row * C + c8 * 8);
-    const float gv[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const float inv = mode == 2 ? 1.f / (float)W : 0.f;
-    float d[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const int idx = (int)(((k < 4 ? am.x : am.y) >> (8 * (k & 3))) & 0xFFu);
-        d[k] = __fadd_rn(__fmul_rn(gv[k], inv), idx == w ? gv[k] : 0.f);
-    }
-    uint4 o;
-    o.x = pack_bf16(d[0], d[1]);
-    o.y = pack_bf16(d[2], d[3]);
-    o.z = pack_bf16(d[4], d[5]);
-    o.w = pack_bf16(d[6], d[7]);
-    *(uint4 *)(dx + rw * C + c8 * 8) = o;
-}
-
-// ------------------------------------------------------------------------------------------------ deterministic reductions
-// dw[i] += sum over the slabs of ws[slab][i], in a FIXED order (what makes the result reproducible; it need not be slab order): a
-// workgroup owns 4 * 256 / SL consecutive elements and its SL slab lanes each add every SL-th slab in ascending order, then the SL
-// partial sums are added in lane order.  (First version: one thread per four elements walking all slabs -- 4 to 36
-// workgroups for the first layer's 1280 slabs and the 64 -> 64 layers' 384: 138 / 33 us per call.)
-template <int SL> // slab lanes per workgroup (16: many slabs -- the 64 -> 64 and first-layer gradients; 4: the wide layers' 4 - 64 slabs)
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float *__restrict__ ws, int slabs, long n, float *__restrict__ dw)
-{
-    constexpr int EX = 256 / SL;
-    __shared__ float4 red[SL][EX];
-    const int ex = threadIdx.x % EX, sl = threadIdx.x / EX;
-    const long i = ((long)blockIdx.x * EX + ex) * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i + 3 < n) {
-        int s = sl;
-        for (; s + 3 * SL < slabs; s += 4 * SL) { // four loads in flight; the additions keep their order
-            const float4 a = *(const float4 *)(ws + (long)s * n + i), b = *(const float4 *)(ws + (long)(s + SL) * n + i);
-            const float4 c = *(const float4 *)(ws + (long)(s + 2 * SL) * n + i), d = *(const float4 *)(ws + (long)(s + 3 * SL) * n + i);
-            acc.x = (((acc.x + a.x) + b.x) + c.x) + d.x; acc.y = (((acc.y + a.y) + b.y) + c.y) + d.y;
-            acc.z = (((acc.z + a.z) + b.z) + c.z) + d.z; acc.w = (((acc.w + a.w) + b.w) + c.w) + d.w;
-        }
-        for (; s < slabs; s += SL) {
-            const float4 a = *(const float4 *)(ws + (long)s * n + i);
-            acc.x += a.x; acc.y += a.y; acc.z += a.z; acc.w += a.w;
-        }
-    } else if (i < n) { // (n not a multiple of 4: the last elements one by one)
-        float t[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int s = sl; s < slabs; s += SL)
-            for (int k = 0; k < 4 && i + k < n; k++) t[k] += ws[(long)s * n + i + k];
-        acc = make_float4(t[0], t[1], t[2], t[3]);
-    }
-    red[sl][ex] = acc;
-    __syncthreads();
-    if (sl == 0 && i < n) {
-        float4 t = red[0][ex];
-#pragma unroll
-        for (int k = 1; k < SL; k++) {
-            const float4 v = red[k][ex];
-            t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
-        }
-        const float o[4] = {t.x, t.y, t.z, t.w};
-        for (int k = 0; k < 4 && i + k < n; k++) dw[i + k] += o[k];
-    }
-}
-
-__global__ __launch_bounds__(256) void slab_reduce_strided_kernel(const float *__restrict__ ws, int slabs, int C, float *__restrict__ oa,
-                                                                  float *__restrict__ ob)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    float acc = 0.f;
-    for (int s = 0; s < slabs; s++) acc += ws[((long)s * 2 + blockIdx.y) * C + c];
-    (blockIdx.y ? ob : oa)[c] += acc;
-}
-
-// out[c] += sum over rows of x[row][c] for up to two float32 matrices of one shape (the GRU's two bias gradients: rows = T * B,
-// C = D * 3H); out must hold zeros.  Workgroup = 64 columns x 4 row lanes over a slice of the rows; one float atomic per column.
-__global__ __launch_bounds__(256) void colsum2_kernel(const float *__restrict__ xa, const float *__restrict__ xb, float *__restrict__ oa,
-                                                      float *__restrict__ ob, long M, int C, int rows_per_block,
-                                                      float *__restrict__ part /* deterministic mode: [gridDim.y][2][C] */)
-{
-    __shared__ float red[4][64];
-    const float *x = blockIdx.z ? xb : xa;
-    float *o = blockIdx.z ? ob : oa;
-    const int col = blockIdx.x * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
-    const long r0 = (long)blockIdx.y * rows_per_block, r1 = r0 + rows_per_block < M ? r0 + rows_per_block : M;
-    float acc = 0.f;
-    if (col < C) {
-        long r = r0 + rl;
-        for (; r + 12 < r1; r += 16) { // four rows in flight
-            const float v0 = x[r * C + col], v1 = x[(r + 4) * C + col], v2 = x[(r + 8) * C + col], v3 = x[(r + 12) * C + col];
-            acc += (v0 + v1) + (v2 + v3);
-        }
-        for (; r < r1; r += 4) acc += x[r * C + col];
-    }
-    red[rl][threadIdx.x & 63] = acc;
-    __syncthreads();
-    if (rl == 0 && col < C) {
-        const float v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-        if (part) part[((long)blockIdx.y * 2 + blockIdx.z) * C + col] = v;
-        else atomicAdd(o + col, v);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------ SELD loss
-// models/interfaces.py:304-355: sed = mean BCE-with-logits(logit, sed_gt); doa = sum over the x / y / z blocks of
-// sum(|p - t| m) / sum(m) with m = sed_gt (the three blocks share sum(m)); loss = w_sed sed + w_doa doa -- and the gradients of
-// sed w.r.t. logit and of doa w.r.t. the predictions (unweighted: the backward launch scales them by what flows in).
-// Two launches of SELD_BLOCKS workgroups (a single 1024-thread workgroup took 64 us for the 123 k elements of a training step):
-// partial sums per workgroup in float64, fixed order = deterministic; the second launch adds the partials (every workgroup for
-// itself), writes the three values and the gradients of its slice.
-constexpr int SELD_BLOCKS = 64;
-__global__ __launch_bounds__(256) void seld_loss_partial_kernel(const float *__restrict__ logit, const float *__restrict__ doa,
-                                                                const float *__restrict__ sed_gt, const float *__restrict__ doa_gt,
-                                                                long rows, int nc, double *__restrict__ partial /* [SELD_BLOCKS][3] */)
-{
-    __shared__ double red[3][256];
-    const long n = rows * nc;
-    double s_bce = 0.0, s_mask = 0.0, s_abs = 0.0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)SELD_BLOCKS * 256) {
-        const long r = i / nc;
-        const int c = (int)(i - r * nc);
-        const float x = logit[i], z = sed_gt[i];
-        // max(x, 0) - x z + log1p(exp(-|x|))  (torch's binary_cross_entropy_with_logits)
-        s_bce += (double)(fmaxf(x, 0.f) - x * z + log1pf(expf(-fabsf(x))));
-        s_mask += (double)z;
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; k++) a += fabsf(doa[r * 3 * nc + k * nc + c] - doa_gt[r * 3 * nc + k * nc + c]) * z;
-        s_abs += (double)a;
-    }
-    red[0][threadIdx.x] = s_bce;
-    red[1][threadIdx.x] = s_mask;
-    red[2][threadIdx.x] = s_abs;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int k = 0; k < 3; k++) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x < 3) partial[blockIdx.x * 3 + threadIdx.x] = red[threadIdx.x][0];
-}
-
-__global__ __launch_bounds__(256) void seld_loss_finish_kernel(const float *__restrict__ logit, const float *__restrict__ doa,
-                                                               const float *__restrict__ sed_gt, const float *__restrict__ doa_gt,
-                                                               long rows, int nc, float w_sed, float w_doa,
-                                                               const double *__restrict__ partial, float *__restrict__ out3,
-                                                               float *__restrict__ g_logit, float *__restrict__ g_doa)
-{
-    __shared__ double tot[3];
-    if (threadIdx.x < 3) {
-        double t = 0.0;
-        for (int b = 0; b < SELD_BLOCKS; b++) t += partial[b * 3 + threadIdx.x];
-        tot[threadIdx.x] = t;
-    }
-    __syncthreads();
-    const long n = rows * nc;
-    const float sed = (float)(tot[0] / (double)n);
-    const float msum = (float)tot[1];
-    const float d = (float)tot[2] / msum; // 0 / 0 = nan when no class is active anywhere, as in the reference
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        out3[0] = w_sed * sed + w_doa * d;
-        out3[1] = sed;
-        out3[2] = d;
-    }
-    const float inv_n = 1.f / (float)n, inv_m = 1.f / msum;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)SELD_BLOCKS * 256) {
-        const long r = i / nc;
-        const int c = (int)(i - r * nc);
-        const float x = logit[i], z = sed_gt[i];
-        g_logit[i] = (1.f / (1.f + expf(-x)) - z) * inv_n;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const long j = r * 3 * nc + k * nc + c;
-            const float e = doa[j] - doa_gt[j];
-            g_doa[j] = (e > 0.f ? 1.f : e < 0.f ? -1.f : 0.f) * z * inv_m;
-        }
-    }
-}
-
-// backward: g_logit *= g_loss w_sed + g_sed ; g_doa *= g_loss w_doa + g_doa_loss   (the incoming gradients are device scalars
-// or NULL = 0), out of place
-__global__ __launch_bounds__(256) void seld_loss_scale_kernel(const float *__restrict__ a, long na, const float *__restrict__ b,
-                                                              long nb, const float *__restrict__ g_loss,
-                                                              const float *__restrict__ g_sed, const float *__restrict__ g_d,
-                                                              float w_sed, float w_doa, float *__restrict__ oa,
-                                                              float *__restrict__ ob)
-{
-    const float gl = g_loss ? *g_loss : 0.f;
-    const float fa = gl * w_sed + (g_sed ? *g_sed : 0.f), fb = gl * w_doa + (g_d ? *g_d : 0.f);
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < na + nb; i += (long)gridDim.x * 256) {
-        if (i < na) oa[i] = a[i] * fa;
-        else ob[i - na] = b[i - na] * fb;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------ ACCDOA loss
-// models/interfaces.py:284-302 (compute_classwise_accdoa_loss, output_format 'accdoa'): doa = sum over (rows, class) of
-// ((p_x - t_x)^2 + (p_y - t_y)^2 + (p_z - t_z)^2) m / rows with m = sed_gt; loss = doa (the reference's "sed" term is discarded).
-// The gradient 2 (p - t) m / rows needs no sum: the first launch writes it (and zeros for the event logits, which the loss does
-// not read) next to a float64 partial sum per workgroup; the second, one wavefront, adds the partials in a fixed order.
-constexpr int ACCDOA_BLOCKS = 64;
-__global__ __launch_bounds__(256) void accdoa_loss_partial_kernel(const float *__restrict__ doa, const float *__restrict__ sed_gt,
-                                                                  const float *__restrict__ doa_gt, long rows, int nc,
-                                                                  float *__restrict__ g_logit, float *__restrict__ g_doa,
-                                                                  double *__restrict__ partial /* [ACCDOA_BLOCKS] */)
-{
-    __shared__ double red[256];
-    const long n = rows * nc;
-    const float scale = 2.f / (float)rows;
-    double s = 0.0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)ACCDOA_BLOCKS * 256) {
-        const long r = i / nc;
-        const int c = (int)(i - r * nc);
-        const float z = sed_gt[i];
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const long j = r * 3 * nc + k * nc + c;
-            const float e = doa[j] - doa_gt[j];
-            a += e * e;
-            g_doa[j] = e * z * scale;
-        }
-        s += (double)(a * z);
-        if (g_logit) g_logit[i] = 0.f;
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-__global__ __launch_bounds__(64) void accdoa_loss_finish_kernel(const double *__restrict__ partial, long rows, float *__restrict__ out3)
-{
-    if (threadIdx.x != 0) return;
-    double t = 0.0;
-    for (int b = 0; b < ACCDOA_BLOCKS; b++) t += partial[b];
-    const float d = (float)(t / (double)rows);
-    out3[0] = d;
-    out3[1] = 0.f;
-    out3[2] = d;
-}
-
-// SED of the ACCDOA output (models/interfaces.py:260-268): sed[r][c] = sqrt(x^2 + y^2 + z^2) of the class's (x, y, z) in
-// float32, rounded as numpy rounds it: each square, (x^2 + y^2) + z^2 and the square root correctly rounded, no fma
-__global__ __launch_bounds__(256) void accdoa_sed_kernel(const float *__restrict__ xyz, float *__restrict__ sed, long rows, int nc)
-{
-#pragma clang fp contract(off)
-    const long n = rows * nc;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long r = i / nc;
-        const int c = (int)(i - r * nc);
-        const float *p = xyz + r * 3 * nc + c;
-        const float x = p[0], y = p[nc], z = p[2 * nc];
-        sed[i] = sqrtf((x * x + y * y) + z * z); // (HIP's sqrtf is the correctly rounded one; __fsqrt_rn is native_sqrt here)
-    }
-}
-
 } // namespace
 
-// One workspace PER DEVICE (round-4 advice: a single process-global pointer, re-pointed by whichever device ran a forward last,
-// made the backward kernels of device A write their slabs through device B's pointer in any single-process multi-device pattern).
-// salsa_nn_set_deterministic registers the workspace for the device that is current at the call; the kernels' launchers look up
-// the device current at THEIR call, so a device without a workspace keeps the atomics instead of borrowing a neighbour's.
-constexpr int DET_MAX_DEV = 64;
-static float *g_det_ws[DET_MAX_DEV] = {};
-static size_t g_det_bytes[DET_MAX_DEV] = {};
-static int det_device()
-{
-    int d = -1;
-    return (hipGetDevice(&d) == hipSuccess && d >= 0 && d < DET_MAX_DEV) ? d : -1;
-}
-extern "C" int salsa_nn_set_deterministic(void *ws, size_t bytes)
-{
-    if (!ws) { // off, everywhere
-        for (int i = 0; i < DET_MAX_DEV; i++) g_det_ws[i] = nullptr, g_det_bytes[i] = 0;
-        return 0;
-    }
-    const int d = det_device();
-    if (d < 0) return -6;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, ws) == hipSuccess && at.type == hipMemoryTypeDevice && at.device != d) return -1; // not this device's memory
-    g_det_ws[d] = (float *)ws;
-    g_det_bytes[d] = bytes;
-    return 0;
-}
-extern "C" int salsa_nn_get_deterministic(void)
-{
-    const int d = det_device();
-    return d >= 0 && g_det_ws[d] != nullptr;
-}
-float *salsa_nn_det_begin(int slabs, long n, hipStream_t st, int *rc)
-{
-    *rc = 0;
-    const int d = det_device();
-    if (d < 0 || !g_det_ws[d]) return nullptr;
-    const size_t need = (size_t)slabs * (size_t)n * sizeof(float);
-    if (need > g_det_bytes[d]) {
-        *rc = -5;
-        return nullptr;
-    }
-    // (no clearing pass: every kernel's workgroups cover every element of their slabs -- grids are sized so that no workgroup is
-    // idle -- and the GPU test runs on a NaN-poisoned workspace; a 75-MB memset per call was most of this mode's cost)
-    (void)st;
-    return g_det_ws[d];
-}
-int salsa_nn_det_finish(const float *ws, int slabs, long n, float *dw, hipStream_t st)
-{
-    if (slabs > 16) hipLaunchKernelGGL(slab_reduce_kernel<16>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, ws, slabs, n, dw);
-    else hipLaunchKernelGGL(slab_reduce_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ws, slabs, n, dw);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
 extern "C" {
-
-int salsa_nn_avgpool2x2_fwd(const void *x, void *y, int dtype, int64_t N, int H, int W, int C, void *hip_stream)
-{
-    const int L = dtype == 1 ? 8 : 4;
-    if (!x || !y || N <= 0 || H < 2 || W < 2 || C <= 0 || C % L || (dtype != 0 && dtype != 1)) return -1;
-    const long n_vec = (long)N * (H / 2) * (W / 2) * (C / L);
-    const dim3 grid((unsigned)((n_vec + 255) / 256));
-    if (dtype == 1)
-        hipLaunchKernelGGL((avgpool2x2_fwd_kernel<bf16x8, 8>), grid, dim3(256), 0, (hipStream_t)hip_stream, (const char *)x, (char *)y, n_vec, H, W, C);
-    else
-        hipLaunchKernelGGL((avgpool2x2_fwd_kernel<f32x4, 4>), grid, dim3(256), 0, (hipStream_t)hip_stream, (const char *)x, (char *)y, n_vec, H, W, C);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
-int salsa_nn_avgpool2x2_bwd(const void *grad_y, void *grad_x, int dtype, int64_t N, int H, int W, int C, void *hip_stream)
-{
-    const int L = dtype == 1 ? 8 : 4;
-    if (!grad_y || !grad_x || N <= 0 || H < 2 || W < 2 || C <= 0 || C % L || (dtype != 0 && dtype != 1)) return -1;
-    const long n_vec = (long)N * H * W * (C / L);
-    const dim3 grid((unsigned)((n_vec + 255) / 256));
-    if (dtype == 1)
-        hipLaunchKernelGGL((avgpool2x2_bwd_kernel<bf16x8, 8>), grid, dim3(256), 0, (hipStream_t)hip_stream, (const char *)grad_y, (char *)grad_x, n_vec, H, W, C);
-    else
-        hipLaunchKernelGGL((avgpool2x2_bwd_kernel<f32x4, 4>), grid, dim3(256), 0, (hipStream_t)hip_stream, (const char *)grad_y, (char *)grad_x, n_vec, H, W, C);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
 
 static int bn_geometry_ok(int dtype, int64_t M, int C)
 {
@@ -1190,11 +563,6 @@ static unsigned bn_apply_blocks(int dtype, int64_t M, int C)
     const long per = (long)rpi * bn_apply_rows(M, rpi);
     return (unsigned)((M + per - 1) / per);
 }
-#define NN_LAUNCH(KERNEL, grid, block, ...)                                                               \
-    do {                                                                                                  \
-        if (dtype == 1) hipLaunchKernelGGL((KERNEL<bf16x8, 8>), grid, block, 0, st, __VA_ARGS__);          \
-        else hipLaunchKernelGGL((KERNEL<f32x4, 4>), grid, block, 0, st, __VA_ARGS__);                      \
-    } while (0)
 
 int salsa_nn_bn_supported(int dtype, int64_t M, int C) { return bn_geometry_ok(dtype, M, C); }
 /* bytes of the sums_ws scratch: 2*C float64 sums + one partial pair per reduction block (float64 forward, float32 backward) */
@@ -1432,179 +800,4 @@ int salsa_nn_bn_bwd_pool_bits(const void *dy_pooled, const void *x, const void *
                             sums_ws, coef_ws, hip_stream);
 }
 
-/* bf16 copies of all hand-written convolution layers' float32 filters in ONE launch: the forward layout [Cout][3][3][Cin] and
- * (when bwd != 0) the data-gradient layout [Cin][3][3][Cout] with the taps flipped.  desc (device): n_layers x 11 int64 =
- * {src, fwd, bwd, Cout, Cin, src element strides co / ci / ky / kx, first block, taps (9 | 1)}; layer l owns (Cout/32)*(Cin/32) blocks from
- * its first block on; n_blocks = their total.  Cout and Cin must be multiples of 32. */
-int salsa_nn_conv_filter_bank(const void *desc, int n_layers, int n_blocks, void *hip_stream)
-{
-    if (!desc || n_layers <= 0 || n_blocks <= 0) return -1;
-    hipLaunchKernelGGL(conv_filter_bank_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)hip_stream, (const long long *)desc,
-                       n_layers);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
-/* SELD training loss and its gradients (salsa_amd/crnn/loss.py; reference models/interfaces.py:304-355): logit, sed_gt
- * [rows][nc]; doa, doa_gt [rows][3 nc] float32 contiguous.  out3 = {loss, sed, doa}; g_logit / g_doa = d sed / d logit and
- * d doa / d prediction (unweighted); partial_ws: SALSA_SELD_LOSS_WS float64 values of scratch. */
-int salsa_nn_seld_loss(const float *logit, const float *doa, const float *sed_gt, const float *doa_gt, int64_t rows, int nc,
-                       float w_sed, float w_doa, float *out3, float *g_logit, float *g_doa, double *partial_ws, void *hip_stream)
-{
-    if (!logit || !doa || !sed_gt || !doa_gt || !out3 || !g_logit || !g_doa || !partial_ws || rows <= 0 || nc <= 0) return -1;
-    hipLaunchKernelGGL(seld_loss_partial_kernel, dim3(SELD_BLOCKS), dim3(256), 0, (hipStream_t)hip_stream, logit, doa, sed_gt, doa_gt,
-                       (long)rows, nc, partial_ws);
-    hipLaunchKernelGGL(seld_loss_finish_kernel, dim3(SELD_BLOCKS), dim3(256), 0, (hipStream_t)hip_stream, logit, doa, sed_gt, doa_gt,
-                       (long)rows, nc, w_sed, w_doa, partial_ws, out3, g_logit, g_doa);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
-/* out_a = a (g_loss w_sed + g_sed), out_b = b (g_loss w_doa + g_doa): the loss's backward; g_* are device scalars or NULL (= 0) */
-int salsa_nn_seld_loss_bwd(const float *a, int64_t na, const float *b, int64_t nb, const float *g_loss, const float *g_sed,
-                           const float *g_doa, float w_sed, float w_doa, float *out_a, float *out_b, void *hip_stream)
-{
-    if (!a || !b || !out_a || !out_b || na <= 0 || nb <= 0) return -1;
-    const long blocks = (na + nb + 255) / 256;
-    hipLaunchKernelGGL(seld_loss_scale_kernel, dim3((unsigned)(blocks < 512 ? blocks : 512)), dim3(256), 0, (hipStream_t)hip_stream, a,
-                       (long)na, b, (long)nb, g_loss, g_sed, g_doa, w_sed, w_doa, out_a, out_b);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
-/* ACCDOA training loss and its gradient (reference models/interfaces.py:273-302): sed_gt [rows][nc]; doa, doa_gt [rows][3 nc]
- * float32 contiguous.  out3 = {loss, 0, doa loss}; g_doa = d doa / d prediction; g_logit (NULL: none) [rows][nc] zero-filled;
- * partial_ws: SALSA_ACCDOA_LOSS_WS float64 values of scratch. */
-int salsa_nn_accdoa_loss(const float *doa, const float *sed_gt, const float *doa_gt, int64_t rows, int nc, float *out3, float *g_logit,
-                         float *g_doa, double *partial_ws, void *hip_stream)
-{
-    if (!doa || !sed_gt || !doa_gt || !out3 || !g_doa || !partial_ws || rows <= 0 || nc <= 0) return -1;
-    hipLaunchKernelGGL(accdoa_loss_partial_kernel, dim3(ACCDOA_BLOCKS), dim3(256), 0, (hipStream_t)hip_stream, doa, sed_gt, doa_gt,
-                       (long)rows, nc, g_logit, g_doa, partial_ws);
-    hipLaunchKernelGGL(accdoa_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, (const double *)partial_ws, (long)rows,
-                       out3);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
-/* sed [rows][nc] = sqrt(x^2 + y^2 + z^2) of xyz [rows][3 nc] (blocks x | y | z), float32, bit-equal to numpy's float32 */
-int salsa_nn_accdoa_sed(const float *xyz, float *sed, int64_t rows, int nc, void *hip_stream)
-{
-    if (!xyz || !sed || rows <= 0 || nc <= 0) return -1;
-    const long blocks = (rows * nc + 255) / 256;
-    hipLaunchKernelGGL(accdoa_sed_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)hip_stream, xyz,
-                       sed, (long)rows, nc);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
-/* mean over the frequency axis of a bf16 channels-last map x [N][H][W][C] -> float32 y, [H][N][C] when time_major else [N][H][C];
- * C % 8 == 0.  _bwd: dx = g / W broadcast over W, bf16 channels-last. */
-int salsa_nn_freq_mean_fwd(const void *x, float *y, int64_t N, int H, int W, int C, int time_major, void *hip_stream)
-{
-    if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) return -1;
-    const long rows = (long)N * H, n = rows * (C / 8);
-    hipLaunchKernelGGL(freq_mean_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream,
-                       (const unsigned short *)x, y, rows, (int)N, H, W, C, time_major);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
-int salsa_nn_freq_mean_bwd(const float *g, void *dx, int64_t N, int H, int W, int C, int time_major, void *hip_stream)
-{
-    if (!g || !dx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) return -1;
-    const long rows = (long)N * H, n = rows * W * (C / 8);
-    hipLaunchKernelGGL(freq_mean_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, g,
-                       (unsigned short *)dx, rows, (int)N, H, W, C, time_major);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
-/* frequency max (mode 1) / mean + max (mode 2) of a bf16 channels-last map x [N][H][W][C] -> float32 y and uint8 argmax, both
- * [H][N][C] when time_major else [N][H][C]; C % 8 == 0, W <= 255.  _bwd: dx = g / W (mode 2) + g at w == argmax, bf16 channels-last. */
-int salsa_nn_freq_pool_fwd(const void *x, float *y, uint8_t *argmax, int64_t N, int H, int W, int C, int mode, int time_major,
-                           void *hip_stream)
-{
-    if (!x || !y || !argmax || N <= 0 || H <= 0 || W <= 0 || W > 255 || C <= 0 || C % 8 || (mode != 1 && mode != 2)) return -1;
-    const long rows = (long)N * H, n = rows * (C / 8);
-    hipLaunchKernelGGL(freq_pool_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream,
-                       (const unsigned short *)x, y, argmax, rows, (int)N, H, W, C, mode, time_major);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
-int salsa_nn_freq_pool_bwd(const float *g, const uint8_t *argmax, void *dx, int64_t N, int H, int W, int C, int mode, int time_major,
-                           void *hip_stream)
-{
-    if (!g || !argmax || !dx || N <= 0 || H <= 0 || W <= 0 || W > 255 || C <= 0 || C % 8 || (mode != 1 && mode != 2)) return -1;
-    const long rows = (long)N * H, n = rows * W * (C / 8);
-    hipLaunchKernelGGL(freq_pool_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, g, argmax,
-                       (unsigned short *)dx, rows, (int)N, H, W, C, mode, time_major);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
-/* out_a[c] += sum_rows a[row][c] (and out_b from b when b != NULL): float32 [M][C] row-major, the outputs must hold zeros. */
-int salsa_nn_colsum2(const float *a, const float *b, float *out_a, float *out_b, int64_t M, int C, void *hip_stream)
-{
-    if (!a || !out_a || (b && !out_b) || M <= 0 || C <= 0) return -1;
-    const int rpb = 64; // rows per workgroup: 16 per row lane
-    if (M > 65535L * rpb) return -1; // ceil(M / rpb) is grid y
-    const unsigned gy = (unsigned)((M + rpb - 1) / rpb);
-    int rc = 0;
-    float *part = salsa_nn_det_begin((int)gy, 2L * C, (hipStream_t)hip_stream, &rc);
-    if (rc) return rc;
-    hipLaunchKernelGGL(colsum2_kernel, dim3((unsigned)((C + 63) / 64), gy, b ? 2u : 1u), dim3(256), 0,
-                       (hipStream_t)hip_stream, a, b, out_a, out_b, (long)M, C, rpb, part);
-    if (part) { // slab row = [out_a | out_b]: two strided reductions (the outputs are separate arrays)
-        hipLaunchKernelGGL(slab_reduce_strided_kernel, dim3((unsigned)((C + 255) / 256), b ? 2u : 1u), dim3(256), 0, (hipStream_t)hip_stream,
-                           part, (int)gy, C, out_a, out_b);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-
 } // extern "C"
-
-// ------------------------------------------------------------------------------------------------------------ Adam, one launch
-namespace {
-struct AdamGrads {
-    const float *g[SALSA_NN_ADAM_MAX_TENSORS];
-};
-__global__ __launch_bounds__(256) void adam_step_kernel(const salsa_nn_adam_entry *__restrict__ table, const AdamGrads grads,
-                                                        const int2 *__restrict__ chunks, float w1 /* 1 - beta1 */, float beta2,
-                                                        float w2 /* 1 - beta2 */, float step_size, float bc2_sqrt, float eps, float wd)
-{
-    const int2 ch = chunks[blockIdx.x];
-    const salsa_nn_adam_entry e = table[ch.x];
-    const float *__restrict__ g = grads.g[ch.x];
-    const long first = (long)ch.y * SALSA_NN_ADAM_CHUNK;
-    const long last = first + SALSA_NN_ADAM_CHUNK < e.n ? first + SALSA_NN_ADAM_CHUNK : e.n;
-    auto update = [&](float &p, float &m, float &v, float gr) {
-        if (wd != 0.f) gr += p * wd;
-        m = m + w1 * (gr - m);                       // lerp(m, g, 1 - beta1), weight < 0.5
-        v = beta2 * v + w2 * gr * gr;
-        const float denom = sqrtf(v) / bc2_sqrt + eps;
-        p -= step_size * m / denom;
-    };
-    const bool vec = ((((uintptr_t)e.p | (uintptr_t)e.m | (uintptr_t)e.v | (uintptr_t)g) & 15) == 0) && (e.n & 3) == 0;
-    if (vec) {
-        for (long i = first + 4 * threadIdx.x; i < last; i += 4 * 256) {
-            float4 p = *(float4 *)(e.p + i), m = *(float4 *)(e.m + i), v = *(float4 *)(e.v + i);
-            const float4 gr = *(const float4 *)(g + i);
-            update(p.x, m.x, v.x, gr.x); update(p.y, m.y, v.y, gr.y); update(p.z, m.z, v.z, gr.z); update(p.w, m.w, v.w, gr.w);
-            *(float4 *)(e.p + i) = p; *(float4 *)(e.m + i) = m; *(float4 *)(e.v + i) = v;
-        }
-    } else {
-        for (long i = first + threadIdx.x; i < last; i += 256) update(e.p[i], e.m[i], e.v[i], g[i]);
-    }
-}
-} // namespace
-
-extern "C" int salsa_nn_adam_step(const salsa_nn_adam_entry *table, const float *const *grads, int n_tensors, const int *chunks, int n_chunks,
-                                  double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, void *hip_stream)
-{
-    if (!table || !grads || !chunks || n_tensors <= 0 || n_tensors > SALSA_NN_ADAM_MAX_TENSORS || n_chunks <= 0 || step < 1) return -1;
-    AdamGrads ga;
-    for (int i = 0; i < n_tensors; i++) {
-        if (!grads[i]) return -1;
-        ga.g[i] = grads[i];
-    }
-    for (int i = n_tensors; i < SALSA_NN_ADAM_MAX_TENSORS; i++) ga.g[i] = nullptr;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)hip_stream, table, ga, (const int2 *)chunks,
-                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1), (float)sqrt(bc2), (float)eps,
-                       (float)weight_decay); // (the hyper-parameters combine in double, as torch's kernel does per element)
-    return hipGetLastError() == hipSuccess ? 0 : -6;
-}
-

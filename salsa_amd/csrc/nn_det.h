@@ -1,5 +1,5 @@
 // nn_det.h -- internal: the deterministic-reduction hooks shared by the weight-gradient translation units (include/salsa_nn.h:
-// salsa_nn_set_deterministic).  Implemented in nn_ops.hip.
+// salsa_nn_set_deterministic).  Implemented in nn_reduce.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

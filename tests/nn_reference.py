@@ -1,4 +1,4 @@
-"""Float64 references for the CRNN kernels (conv_wide.hip, conv_mfma.hip, conv_1x1.hip, nn_ops.hip, gru_scan.hip) and the
+"""Float64 references for the CRNN kernels (conv_wide.hip, conv_mfma.hip, conv_1x1.hip, nn_pool.hip, nn_batchnorm.hip, gru_scan.hip) and the
 per-element error bounds the tests hold them to.
 
 Every reference takes the operands the kernel saw (bf16 values cast up exactly) and evaluates in float64 on their device,
@@ -107,7 +107,7 @@ def pooled_conv_c(n_terms):
 
 
 def avgpool_bound(x):
-    """(ref, bound) of salsa_nn_avgpool2x2_fwd on bf16 input: avgpool2x2_fwd_kernel in nn_ops.hip forms (((a + b) + c) + d) / 4
+    """(ref, bound) of salsa_nn_avgpool2x2_fwd on bf16 input: avgpool2x2_fwd_kernel in nn_pool.hip forms (((a + b) + c) + d) / 4
     in float32 -- three additions, each within u of a partial sum <= sum|x|, an exact division by 4 -- and rounds once to
     bf16: |y - ref| <= 2^-8 |ref| + (1 + 2^-8) 3 u mean|x|."""
     xd = x.double()
@@ -202,7 +202,7 @@ def check(got, ref, bound, what):
 
 # ------------------------------------------------------------------------------------------------------------ BatchNorm
 def bn_rows_per_thread(M, C, bf16):
-    """upper bound of the float32 chain of one thread in nn_ops.hip's reductions: a thread covers <= BN_RPT = 32 rows of a
+    """upper bound of the float32 chain of one thread in nn_batchnorm.hip's reductions: a thread covers <= BN_RPT = 32 rows of a
     chunk, and with the grid capped at BN_MAX_BLOCKS = 1024 blocks of rpi = 256 / (C / L) rows it walks several chunks"""
     rpi = 256 // (C // (8 if bf16 else 4))
     return max(32, math.ceil(M / (rpi * 1024))) + int(math.log2(rpi)) + 2

@@ -1,5 +1,5 @@
 """High-precision restatements, seeded input builders and the checks (with their bounds) for the small kernels beside the hot
-path: salsa_nn_seld_loss / _bwd, salsa_nn_colsum2 (csrc/nn_ops.hip), salsa_scaler_accumulate, salsa_normalize_batch and
+path: salsa_nn_seld_loss / _bwd (csrc/nn_loss.hip), salsa_nn_colsum2 (csrc/nn_reduce.hip), salsa_scaler_accumulate, salsa_normalize_batch and
 salsa_to_freq_major (csrc/feature_utils.hip).  numpy only, no torch: tests/test_small_kernels_gpu.py hands the kernels' outputs to
 the check_* functions below, tests/test_small_kernels_cpu.py hands them a float32 emulation of the kernels' arithmetic on the SAME
 inputs -- so what is shown to be satisfiable on the host is exactly what is asked of the device.

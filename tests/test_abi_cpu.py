@@ -163,3 +163,17 @@ def test_hand_issued_residual_loads_are_not_touched_before_their_wait():
     for touch in ('v_mov_b32_e32 v40, v10', 'scratch_store_dwordx2 off, v[10:11], s32 offset:16', 'v_add_f32_e32 v11, v1, v2'):
         n, bad = chk.check_lines(good[:5] + [touch] + good[5:])
         assert n == 1 and len(bad) == 1 and bad[0][4] == touch
+
+
+def test_shared_kernel_helpers_are_defined_once():
+    """The bf16 helpers were once copied by hand into four units.  pack_bf16 (the rounding every bf16 store shares) and bf2f each have ONE
+    definition among the sources, and tr_frag -- the transposing LDS read's fragment -- is defined by no unit: conv_c64_wrw.hip,
+    conv_stem_wrw.hip and conv_1x1.hip all take conv_internal.h's."""
+    csrc = os.path.join(ROOT, 'salsa_amd', 'csrc')
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(('.hip', '.h'))}
+    for name, home in (('pack_bf16', 'nn_common.h'), ('bf2f', 'nn_vec.h')):
+        definition = re.compile(r'^[ \t]*(?:[\w*&:<>]+[ \t]+)+[*&]?%s[ \t]*\([^;()]*\)[ \t]*(?://.*)?\n?[ \t]*\{' % name, re.M)   # `type name(params) {`
+        assert [f for f, t in text.items() if definition.search(t)] == [home], name
+        assert sum(len(definition.findall(t)) for t in text.values()) == 1, name
+        assert sum(len(re.findall(r'\b%s\s*\(' % name, t)) for t in text.values()) > 1, name      # ... and it is called
+    assert [f for f, t in text.items() if re.search(r'\bstruct\s+tr_frag\b[^;]*\{', t)] == ['conv_internal.h']

@@ -295,8 +295,8 @@ def test_c64_statistics_finalize_and_transforming_convolutions(shape):
     and invstd by 0.5 invstd^3 of that (+ u invstd); the running statistics: the 8 u of
     test_batchnorm_train_forward_backward_at_bench_size plus momentum times those.
 
-    The transforming kernels' operand: conv_mfma.hip rewrites each landed 16-byte piece in LDS (`transform` in
-    conv3x3_c64_fwd_async_kernel; in registers between the global load and the LDS write in conv3x3_c64_wrw_kernel<true>) as
+    The transforming kernels' operand: each landed 16-byte piece is rewritten in LDS (`transform` in conv_mfma.hip's
+    conv3x3_c64_fwd_async_kernel; in registers between the global load and the LDS write in conv_c64_wrw.hip's conv3x3_c64_wrw_kernel<true>) as
     a = max(x1 * sc + sh, 0) in float32 with sc = fl(invstd * gamma), sh = fl(beta - mean * sc) (both fused multiply-adds),
     and rounds a to bf16 THERE, once, before any product (pack_bf16).  The reference forms a in float64 from the stored bf16
     x1, the kernel's own mean / invstd and that float32 sc / sh, rounds it to float32 and to bf16 the same way, and is a plain

@@ -61,7 +61,7 @@ WRW_IMMEDIATE_W = (50, 25, 12)          # conv_wide.hip: widths with their own w
 
 
 def c64_plan(n, h, w, th=4, tw=32):
-    """conv_mfma.hip's c64_plan restated: (tiles, transposed) -- the map is handed over with its axes swapped when that needs
+    """conv_internal.h's c64_plan restated: (tiles, transposed) -- the map is handed over with its axes swapped when that needs
     fewer than 95 % of the tiles (TH x TW = 4 x 32 for the forward and the weight gradient alike)"""
     tn = n * -(-h // th) * -(-w // tw)
     tt = n * -(-w // th) * -(-h // tw)

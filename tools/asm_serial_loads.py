@@ -12,7 +12,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 srcs = sys.argv[1:] or [os.path.join(ROOT, 'salsa_amd', 'csrc', f) for f in
-                        ('salsa_kernels.hip', 'conv_mfma.hip', 'conv_wide.hip', 'conv_1x1.hip', 'nn_ops.hip', 'gru_scan.hip')]
+                        ('salsa_kernels.hip', 'conv_mfma.hip', 'conv_stem.hip', 'conv_c64_wrw.hip', 'conv_stem_wrw.hip', 'conv_wide.hip',
+                         'conv_1x1.hip', 'nn_pool.hip', 'nn_batchnorm.hip', 'nn_reduce.hip', 'nn_loss.hip', 'nn_optim.hip', 'gru_scan.hip')]
 for src in srcs:
     out = os.path.join(tempfile.mkdtemp(), 'k.s')
     subprocess.check_call(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-S', '--cuda-device-only', '-o', out, src],

@@ -5,7 +5,7 @@ full drain inside the tile loop means the pipeline is being emptied once per ite
 scratch in front of a global_load_lds cost the 64 -> 64 statistics kernel 70 us of 440)."""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-srcs = sys.argv[1:] or [os.path.join(ROOT, 'salsa_amd', 'csrc', f) for f in ('conv_mfma.hip', 'conv_wide.hip', 'conv_1x1.hip', 'salsa_kernels.hip')]
+srcs = sys.argv[1:] or [os.path.join(ROOT, 'salsa_amd', 'csrc', f) for f in ('conv_mfma.hip', 'conv_stem.hip', 'conv_c64_wrw.hip', 'conv_stem_wrw.hip', 'conv_wide.hip', 'conv_1x1.hip', 'salsa_kernels.hip')]
 for src in srcs:
     out = os.path.join(tempfile.mkdtemp(), 'k.s')
     subprocess.check_call(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-S', '--cuda-device-only', '-o', out, src], stderr=subprocess.DEVNULL)
