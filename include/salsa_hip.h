@@ -318,6 +318,38 @@ int salsa_scene_render(const float *d_events, int64_t n_event_samples, const flo
                        const float *d_gains, int n_clips, int n_items, int max_event_len, const float *d_ambient, float *d_out,
                        int64_t n_samples, void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
+/* Moving sources.  An item with a trajectory of responses, one node every S samples of its dry time, is cut by
+ * the caller into SEGMENTS, one per node: node k covers the dry samples ((k - 1) S, (k + 1) S) of the event, weighted by the window
+ * (float)(S - |n - k S|) / (float)S, the windowed sample rounded once, and convolved with node k's response; the windows of neighbouring
+ * nodes sum to one, so the input is cross-faded linearly from response to response.  The call renders
+ *     audio[b, c, n] = ambient[b, c, n] + sum_s gain_s (h[rir_s, c, :] * (w_s . x_s))[n - onset_s],   0 <= n < n_samples,
+ * over the segments s of clip b, with the properties of salsa_scene_render (the ambient's bits outside every segment's support
+ * [onset, onset + length + rir_len - 1), equal bits from two calls, a clip independent of its batch, two launches on hip_stream,
+ * nothing allocated or synchronised).  A segment of step 0 has no window: a static item is ONE such segment, and a call whose segments
+ * are all of that kind gives the bits of salsa_scene_render on the same items.
+ *
+ * The tables are given twice with equal contents, on the host (checked entry by entry before the first device call) and on the device.
+ * clip_start int [n_clips + 1] (host only): clip b owns segments clip_start[b] .. clip_start[b + 1] - 1, at most 65536 of them,
+ * accumulated in that order.  segments int64 [6][n_segments]: the segment's first sample in d_events, its onset in the clip (0 <= onset
+ * < n_samples: the item's onset plus the segment's start in the event; a segment that would start at or past n_samples is left out by
+ * the caller), its length (1 .. max_segment_len), the response's index, the ramp's centre counted from the segment's first sample, and
+ * the ramp step S: 0 (no window) or 240 .. 16777216, with |q - centre| < S for every sample 0 <= q < length, so that no weight is zero
+ * or negative.  gains float32 [n_segments].  block_table int [n_clips][ceil(n_samples / 512)][2]: for output block m of clip b (samples
+ * [512 m, 512 m + 512)) the first and the one-past-last segment the render kernel visits; it visits only these, so the range must hold
+ * every segment of the clip that reaches the block, i.e. with onset / 512 <= m <= min((onset + length - 1) / 512 + 1, M - 1) +
+ * ceil(rir_len / 512) - 1, and lie inside the clip's segments.  The host checks that no reaching segment is left out.
+ * d_workspace: 16-byte aligned, salsa_scene_moving_workspace_bytes(n_samples, max_segment_len, n_segments) = n_segments x min(
+ * (max_segment_len + 510) / 512 + 2, ceil(n_samples / 512)) x 4096 bytes: sized by the longest SEGMENT (2 S - 1 samples when every
+ * item moves), not by the longest event; not needed for n_segments = 0 (the block table is).  Limits on channels, response length and
+ * clips as above.  Returns -1 for an argument outside these limits or tables that contradict each other, -5 for a workspace too
+ * small; the size query returns 0 for arguments the call would refuse. */
+size_t salsa_scene_moving_workspace_bytes(int64_t n_samples, int max_segment_len, int n_segments);
+int salsa_scene_render_moving(const float *d_events, int64_t n_event_samples, const float *d_rir_spectra, int n_rirs, int n_channels,
+                              int rir_len, const int *clip_start, const int64_t *segments, const float *gains, const int *block_table,
+                              const int64_t *d_segments, const float *d_gains, const int *d_block_table, int n_clips, int n_segments,
+                              int max_segment_len, const float *d_ambient, float *d_out, int64_t n_samples, void *d_workspace,
+                              size_t workspace_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,148 @@ __global__ __launch_bounds__(SC_THREADS) void render_kernel(const scene_tables t
     }
 }
 
+// ---- moving sources: the host has cut every item into segments, one per trajectory node; a segment is an
+// item of its own response whose dry samples are weighted by a linear ramp while they are loaded.  A static item is ONE segment of
+// step 0, loaded as it is, so a batch of static items goes through the arithmetic of the kernels above in the same order.
+struct moving_tables {
+    const int *block_tab;       // (B, M, 2): first and one-past-last segment that can reach output block m of clip b
+    const int64_t *segs;        // (6, n_segs): source offset in `events`, onset, length, rir, ramp centre from the segment's start, ramp step
+    const float *gains;         // (n_segs)
+    int n_segs;
+};
+
+__global__ __launch_bounds__(SC_THREADS) void segment_spectra_kernel(const float *__restrict__ events, const moving_tables tb, int slots,
+                                                                      int64_t M, const cf *__restrict__ tw, cf *__restrict__ ws)
+{
+    __shared__ cf zs[SC_WAVES][Z_LEN];
+    const int lane = (int)threadIdx.x & 63, w = (int)threadIdx.x >> 6;
+    const int64_t i = blockIdx.x, n = tb.n_segs;
+    const int64_t src = tb.segs[i], o = tb.segs[n + i], len = tb.segs[2 * n + i], centre = tb.segs[4 * n + i], step = tb.segs[5 * n + i];
+    const int64_t j0 = o >> 9, j1 = min(((o + len - 1) >> 9) + 1, M - 1);
+    const int slot = (int)blockIdx.y * SC_WAVES + w;
+    const int64_t j = j0 + slot;
+    const bool on = slot < slots && j <= j1;
+    const float fstep = (float)step;
+    cf v[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int64_t e = FFT_N * (j - 1) + 2 * (lane + 64 * r) - o;      // index into the segment's dry samples
+        float x[2];
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const int64_t eq = e + q;
+            const bool in = on && eq >= 0 && eq < len;
+            x[q] = in ? events[src + eq] : 0.f;
+            if (in && step) {                                                // the window, then ONE rounding of the windowed sample
+                const int64_t d = eq >= centre ? eq - centre : centre - eq;
+                x[q] = x[q] * ((float)(step - d) / fstep);
+            }
+        }
+        v[r] = {x[0], x[1]};
+    }
+    wave_real_spectrum(v, zs[w], tw, lane);
+    if (!on) return;
+    cf *dst = ws + (i * slots + slot) * FFT_N;
+#pragma unroll
+    for (int r = 0; r < 8; r++) dst[lane + 64 * r] = v[r];
+}
+
+// render_kernel with the segments of the block table's range [first, last) in place of all items of the clip
+__global__ __launch_bounds__(SC_THREADS) void render_moving_kernel(const moving_tables tb, const cf *__restrict__ spectra, int C, int L,
+                                                                    int P, int slots, const cf *__restrict__ ws, const float *ambient,
+                                                                    float *out, int64_t N, int64_t M)
+{
+    __shared__ cf ys[SC_CH][Z_LEN];
+    __shared__ unsigned char inside[FFT_N];
+    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t m = blockIdx.x, b = blockIdx.y;
+    const int i_lo = tb.block_tab[2 * (b * M + m)], i_hi = tb.block_tab[2 * (b * M + m) + 1];
+    const int64_t *t_on = tb.segs + tb.n_segs, *t_len = tb.segs + 2 * (int64_t)tb.n_segs, *t_rir = tb.segs + 3 * (int64_t)tb.n_segs;
+    const int64_t n0 = FFT_N * m;
+
+    // which samples of the block lie in some segment's support (a support never reaches further than the range covers)
+    bool in0 = false, in1 = false;
+    for (int i = i_lo; i < i_hi; i++) {
+        const int64_t lo = t_on[i], hi = lo + t_len[i] + L - 1;
+        in0 = in0 || (n0 + tid >= lo && n0 + tid < hi);
+        in1 = in1 || (n0 + tid + 256 >= lo && n0 + tid + 256 < hi);
+    }
+    inside[tid] = in0;
+    inside[tid + 256] = in1;
+    if (!__syncthreads_or(in0 || in1)) {                       // a silent block: the ambient as it is
+        for (int c = 0; c < C; c++)
+            for (int q = 0; q < 2; q++) {
+                const int64_t n = n0 + tid + 256 * q, idx = (b * C + c) * N + n;
+                if (n < N) out[idx] = ambient ? ambient[idx] : 0.f;
+            }
+        return;
+    }
+
+    const cf *tw = spectra, *H = spectra + SC_TW;
+    for (int c0 = 0; c0 < C; c0 += SC_CH) {
+        const int nc = min(SC_CH, C - c0);
+        cf acc[SC_CH][2];
+#pragma unroll
+        for (int c = 0; c < SC_CH; c++) acc[c][0] = acc[c][1] = {0.f, 0.f};
+        for (int i = i_lo; i < i_hi; i++) {
+            const int64_t o = t_on[i], len = t_len[i];
+            const int64_t j0 = o >> 9, j1 = min(((o + len - 1) >> 9) + 1, M - 1);
+            const int64_t p_lo = max((int64_t)0, m - j1), p_hi = min((int64_t)P - 1, m - j0);
+            if (p_lo > p_hi) continue;
+            const float g = tb.gains[i];
+            const cf *Hi = H + (t_rir[i] * C + c0) * P * FFT_N + 2 * tid;
+            const cf *Xi = ws + (int64_t)i * slots * FFT_N + 2 * tid;
+            for (int64_t p = p_lo; p <= p_hi; p++) {
+                const float4 xr = *reinterpret_cast<const float4 *>(Xi + (m - p - j0) * FFT_N);
+                const cf x0 = {g * xr.x, g * xr.y}, x1 = {g * xr.z, g * xr.w};
+#pragma unroll
+                for (int c = 0; c < SC_CH; c++)
+                    if (c < nc) {
+                        const float4 hr = *reinterpret_cast<const float4 *>(Hi + ((int64_t)c * P + p) * FFT_N);
+                        acc[c][0] = scene::spec_mac(acc[c][0], cf{hr.x, hr.y}, x0, tid == 0);
+                        acc[c][1] = scene::spec_mac(acc[c][1], cf{hr.z, hr.w}, x1, false);
+                    }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < SC_CH; c++) {
+            ys[c][zpad(2 * tid)] = acc[c][0];
+            ys[c][zpad(2 * tid + 1)] = acc[c][1];
+        }
+        __syncthreads();
+        for (int rd = 0; rd * SC_WAVES < nc; rd++) {           // a wave per channel, the inverse transform by conjugation
+            const int c = w + SC_WAVES * rd;
+            const bool on = c < nc;
+            cf *z = ys[c];
+            cf v[8];
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                const int k = lane + 64 * r;
+                v[r] = salsa::cconj(scene::real_pack(z[zpad(k)], z[zpad((FFT_N - k) & (FFT_N - 1))], k, tw));
+            }
+            __syncthreads();
+            wave_fft(v, z, tw, lane);
+            if (on) {
+                const int64_t row = (b * C + c0 + c) * N;
+#pragma unroll
+                for (int r = 4; r < 8; r++) {                  // samples 512 .. 1023 of the transform are block m
+                    const int nl = 2 * (lane + 64 * r) - FFT_N;
+#pragma unroll
+                    for (int q = 0; q < 2; q++) {
+                        const int64_t n = n0 + nl + q;
+                        if (n < N) {
+                            const float y = (q ? -v[r].im : v[r].re) * (1.f / FFT_N);
+                            const float a = ambient ? ambient[row + n] : 0.f;
+                            out[row + n] = inside[nl + q] ? a + y : a;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
 int sfail(int code, const char *msg)
 {
     salsa_set_last_error_(msg);
@@ -306,4 +448,77 @@ extern "C" int salsa_scene_render(const float *events, int64_t n_event_samples, 
     hipLaunchKernelGGL(render_kernel, dim3((unsigned)M, (unsigned)n_clips), dim3(SC_THREADS), 0, (hipStream_t)hip_stream, tb, spectra,
                        n_channels, rir_len, P, slots, (const cf *)workspace, ambient, out, n_samples, M);
     return hipGetLastError() == hipSuccess ? 0 : sfail(-6, "salsa_scene_render: launch failed");
+}
+
+// ---- moving sources: segments and a block table in place of items
+namespace {
+constexpr int SC_MAX_SEGS = 65536;                  // segments per clip
+constexpr int64_t SC_MIN_STEP = 240, SC_MAX_STEP = 1 << 24;   // ramp steps; up to 2^24 the window's numerator is exact in float32
+} // namespace
+
+extern "C" size_t salsa_scene_moving_workspace_bytes(int64_t n_samples, int max_segment_len, int n_segments)
+{
+    if (n_samples < 1 || blocks_of(n_samples) > 0x7fffffff || max_segment_len < 1 || n_segments < 0) return 0;
+    return (size_t)n_segments * (size_t)slots_of(n_samples, max_segment_len) * FFT_N * sizeof(cf);
+}
+
+extern "C" int salsa_scene_render_moving(const float *events, int64_t n_event_samples, const float *rir_spectra, int n_rirs, int n_channels,
+                                         int rir_len, const int *clip_start, const int64_t *segments, const float *gains,
+                                         const int *block_table, const int64_t *segments_dev, const float *gains_dev,
+                                         const int *block_table_dev, int n_clips, int n_segments, int max_segment_len,
+                                         const float *ambient, float *out, int64_t n_samples, void *workspace, size_t workspace_bytes,
+                                         void *hip_stream)
+{
+    // as salsa_scene_render: every table entry is checked on the host before the first device call
+    if (!rir_spectra || ((uintptr_t)rir_spectra & 15) || !out || !clip_start || !block_table || !block_table_dev)
+        return sfail(-1, "salsa_scene_render_moving: null or unaligned pointer");
+    if (!shape_ok(n_rirs, n_channels, rir_len))
+        return sfail(-1, "salsa_scene_render_moving: 1 <= channels <= 16 and 1 <= rir length <= 16384");
+    if (n_clips < 1 || n_clips > 65535 || n_segments < 0 || n_samples < 1 || blocks_of(n_samples) > 0x7fffffff || max_segment_len < 1)
+        return sfail(-1, "salsa_scene_render_moving: bad sizes");
+    if (n_segments > 0 && (!events || !segments || !gains || !segments_dev || !gains_dev || !workspace || ((uintptr_t)workspace & 15) || n_event_samples < 1))
+        return sfail(-1, "salsa_scene_render_moving: null or unaligned pointer");
+    if (clip_start[0] != 0 || clip_start[n_clips] != n_segments)
+        return sfail(-1, "salsa_scene_render_moving: clip_start does not span the segments");
+    for (int b = 0; b < n_clips; b++)
+        if (clip_start[b + 1] < clip_start[b] || clip_start[b + 1] - clip_start[b] > SC_MAX_SEGS)
+            return sfail(-1, "salsa_scene_render_moving: clip_start must not decrease, and a clip holds at most 65536 segments");
+    const int64_t M = blocks_of(n_samples), ns = n_segments;
+    const int P = partitions(rir_len);
+    for (int b = 0; b < n_clips; b++) {
+        const int *bt = block_table + 2 * (int64_t)b * M;
+        for (int64_t m = 0; m < M; m++)
+            if (bt[2 * m] < clip_start[b] || bt[2 * m] > bt[2 * m + 1] || bt[2 * m + 1] > clip_start[b + 1])
+                return sfail(-1, "salsa_scene_render_moving: a block's segment range lies outside its clip");
+        for (int i = clip_start[b]; i < clip_start[b + 1]; i++) {
+            const int64_t src = segments[i], o = segments[ns + i], len = segments[2 * ns + i], r = segments[3 * ns + i],
+                          centre = segments[4 * ns + i], step = segments[5 * ns + i];
+            if (len < 1 || len > max_segment_len || src < 0 || src > n_event_samples - len)
+                return sfail(-1, "salsa_scene_render_moving: a segment's samples lie outside the pool");
+            if (o < 0 || o >= n_samples) return sfail(-1, "salsa_scene_render_moving: an onset lies outside the clip");
+            if (r < 0 || r >= n_rirs) return sfail(-1, "salsa_scene_render_moving: a segment names no response of the bank");
+            if (!(fabsf(gains[i]) <= 3.4e38f)) return sfail(-1, "salsa_scene_render_moving: a gain is not finite");
+            if (step != 0 && (step < SC_MIN_STEP || step > SC_MAX_STEP))
+                return sfail(-1, "salsa_scene_render_moving: a ramp step is 0 (no window) or 240 .. 16777216 samples");
+            // |q - centre| < step for every sample 0 <= q < len: the ramp stays above zero inside the segment
+            if (step != 0 && (centre <= -step || centre >= step || len - 1 - centre >= step))
+                return sfail(-1, "salsa_scene_render_moving: a ramp reaches zero or below inside its segment");
+            const int64_t j0 = o >> 9, m_hi = std::min(std::min(((o + len - 1) >> 9) + 1, M - 1) + P - 1, M - 1);
+            for (int64_t m = j0; m <= m_hi; m++)
+                if (i < bt[2 * m] || i >= bt[2 * m + 1])
+                    return sfail(-1, "salsa_scene_render_moving: the block table leaves out a segment that reaches the block");
+        }
+    }
+    if (workspace_bytes < salsa_scene_moving_workspace_bytes(n_samples, max_segment_len, n_segments))
+        return sfail(-5, "salsa_scene_render_moving: workspace too small");
+    const int slots = (int)slots_of(n_samples, max_segment_len);
+    if ((slots + SC_WAVES - 1) / SC_WAVES > 65535) return sfail(-1, "salsa_scene_render_moving: segment too long");
+    const moving_tables tb = {block_table_dev, segments_dev, gains_dev, n_segments};
+    const cf *spectra = (const cf *)rir_spectra;
+    if (n_segments > 0)
+        hipLaunchKernelGGL(segment_spectra_kernel, dim3((unsigned)n_segments, (unsigned)((slots + SC_WAVES - 1) / SC_WAVES)), dim3(SC_THREADS),
+                           0, (hipStream_t)hip_stream, events, tb, slots, M, spectra, (cf *)workspace);
+    hipLaunchKernelGGL(render_moving_kernel, dim3((unsigned)M, (unsigned)n_clips), dim3(SC_THREADS), 0, (hipStream_t)hip_stream, tb, spectra,
+                       n_channels, rir_len, P, slots, (const cf *)workspace, ambient, out, n_samples, M);
+    return hipGetLastError() == hipSuccess ? 0 : sfail(-6, "salsa_scene_render_moving: launch failed");
 }

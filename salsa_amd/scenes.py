@@ -9,7 +9,13 @@ A scene is the item list of one clip; item i is (event e_i, rir r_i, onset o_i, 
 with `*` the full linear convolution.  Item i is active in label frame f iff its DRY extent [o_i, o_i + len) meets
 [hop f, hop (f + 1)), hop = fs / label_rate; its row is (f, c_i, t_i, azimuth[r_i], elevation[r_i]) in integer degrees, a DCASE
 metadata CSV's row.  The convolutions run in salsa_amd/csrc/scene_render.hip (include/salsa_hip.h: salsa_scene_*); SALSA_HIP_SCENE=0
-sends render_scenes to a composed torch.fft evaluation of the same definition, for A/B runs."""
+sends render_scenes to a composed torch.fft evaluation of the same definition, for A/B runs.
+
+Moving sources: an item may carry a trajectory of responses r_{i,0} .. r_{i,K-1}, node k at dry time k S (S =
+Scenes.traj_step samples, K = ceil((len - 1) / S) + 1).  With the windows w_k(n) = max(0, 1 - |n - k S| / S), which sum to one on
+[0, len), the item contributes g_i sum_k (h[r_{i,k}, c, :] * (w_k . s_i))[n - o_i]: the input is cross-faded linearly from response to
+response.  It is active in the frames its dry extent meets, as before; frame f carries the direction of the node nearest the frame's
+centre, a tie going to the later one.  Scenes with a trajectory are rendered by salsa_scene_render_moving from a segment table."""
 import ctypes as C
 import io
 import os
@@ -21,6 +27,8 @@ from . import _lib
 HIP_SCENE = os.environ.get('SALSA_HIP_SCENE', '1') != '0'   # 0: render_scenes composes torch.fft calls, for A/B runs and bisecting
 FS = 24000
 MAX_CHANNELS, MAX_RIR_LEN, MAX_ITEMS_PER_CLIP = 16, 16384, 256          # the launchers' limits (include/salsa_hip.h)
+MAX_SEGMENTS_PER_CLIP, MIN_TRAJ_STEP, MAX_TRAJ_STEP = 65536, 240, 1 << 24  # salsa_scene_render_moving's
+PART = 512                                                               # the renderer's partition, samples
 SOUND_SPEED = 343.0
 MIC_RADIUS = 0.042
 MIC_DIRECTIONS = ((45, 35), (-45, -35), (135, -35), (-135, 35))          # the TNSSE tetrahedron (azimuth, elevation), degrees
@@ -55,6 +63,12 @@ class RirBank:
     def rirs_on(self, device):
         import torch
         return torch.from_numpy(self.rirs).to(device)
+
+    def nearest(self, azimuth, elevation):
+        """index of the response at the least great-circle angle from (azimuth, elevation) in degrees; the lowest index on a tie"""
+        cosine = np.clip(_unit(self.azimuth, self.elevation) @ _unit(azimuth, elevation).T, -1.0, 1.0)    # (R,) or (R, n) for arrays
+        idx = np.argmin(np.arccos(cosine), axis=0)
+        return int(idx) if np.ndim(idx) == 0 else idx.astype(np.int64)
 
     def spectra(self, device):
         import torch
@@ -177,8 +191,13 @@ class Scenes:
     pool), rir (index into the bank), onset (samples), gain (linear), cls, track, length (of the dry event), azimuth and elevation
     (integer degrees of its response).  scenes[b] is clip b alone."""
     FIELDS = ('event', 'rir', 'onset', 'gain', 'cls', 'track', 'length', 'azimuth', 'elevation')
+    TRAJ_FIELDS = ('traj_rir', 'traj_azimuth', 'traj_elevation')              # flat, one entry per trajectory node
 
-    def __init__(self, n_samples, clip_start, **items):
+    def __init__(self, n_samples, clip_start, traj_start=None, traj_rir=None, traj_azimuth=None, traj_elevation=None, traj_step=2400,
+                 **items):
+        """Trajectories (optional): item i owns nodes traj_start[i] .. traj_start[i + 1] - 1 of traj_rir (and of traj_azimuth /
+        traj_elevation, the nodes' directions in integer degrees): none for a static item, exactly K = ceil((length - 1) / traj_step)
+        + 1 for a moving one, whose rir / azimuth / elevation fields are those of node 0."""
         self.n_samples = int(n_samples)
         self.clip_start = np.asarray(clip_start, np.int32).reshape(-1)
         for f in self.FIELDS:
@@ -187,9 +206,29 @@ class Scenes:
         if any(len(getattr(self, f)) != n for f in self.FIELDS) or len(self.clip_start) < 2 or self.clip_start[0] != 0 \
                 or self.clip_start[-1] != n or np.any(np.diff(self.clip_start) < 0):
             raise ValueError('inconsistent scene tables')
+        self.traj_step = int(traj_step)
+        self.traj_start = np.zeros(n + 1, np.int64) if traj_start is None else np.asarray(traj_start, np.int64).reshape(-1)
+        for f, v in zip(self.TRAJ_FIELDS, (traj_rir, traj_azimuth, traj_elevation)):
+            setattr(self, f, np.asarray([] if v is None else v, np.int64).reshape(-1))
+        if len(self.traj_start) != n + 1 or self.traj_start[0] != 0 or self.traj_start[-1] != len(self.traj_rir) \
+                or any(len(getattr(self, f)) != len(self.traj_rir) for f in self.TRAJ_FIELDS):
+            raise ValueError('inconsistent trajectory tables')
+        nodes = np.diff(self.traj_start)
+        if np.any(nodes < 0):
+            raise ValueError('inconsistent trajectory tables')
+        if len(self.traj_rir):
+            if not MIN_TRAJ_STEP <= self.traj_step <= MAX_TRAJ_STEP:
+                raise ValueError('traj_step must lie in %d .. %d samples' % (MIN_TRAJ_STEP, MAX_TRAJ_STEP))
+            if np.any((nodes != 0) & (nodes != traj_nodes(self.length, self.traj_step))):
+                raise ValueError('a moving item has exactly ceil((length - 1) / traj_step) + 1 trajectory nodes, a static one none')
 
     n_clips = property(lambda self: len(self.clip_start) - 1)
     n_items = property(lambda self: len(self.event))
+    has_trajectories = property(lambda self: len(self.traj_rir) > 0)
+
+    def nodes(self, i):
+        """trajectory nodes of item i as a slice of the traj_* arrays (empty for a static item)"""
+        return slice(int(self.traj_start[i]), int(self.traj_start[i + 1]))
 
     def __len__(self):
         return self.n_clips
@@ -199,7 +238,10 @@ class Scenes:
         if not 0 <= lo <= hi <= self.n_clips:
             raise IndexError((lo, hi))
         sl = slice(self.clip_start[lo], self.clip_start[hi])
-        return Scenes(self.n_samples, self.clip_start[lo:hi + 1] - self.clip_start[lo], **{f: getattr(self, f)[sl] for f in self.FIELDS})
+        t_lo, t_hi = (int(self.traj_start[self.clip_start[k]]) for k in (lo, hi))
+        return Scenes(self.n_samples, self.clip_start[lo:hi + 1] - self.clip_start[lo],
+                      traj_start=self.traj_start[sl.start:sl.stop + 1] - t_lo, traj_step=self.traj_step,
+                      **{f: getattr(self, f)[t_lo:t_hi] for f in self.TRAJ_FIELDS}, **{f: getattr(self, f)[sl] for f in self.FIELDS})
 
     def __getitem__(self, b):
         if not 0 <= b < self.n_clips:
@@ -207,24 +249,39 @@ class Scenes:
         return self.clips(b, b + 1)
 
     @classmethod
-    def from_items(cls, n_samples, clips, pool, bank):
-        """clips: per clip a list of (event, rir, onset, gain, track) -- class, length and direction come from the pool and the bank."""
+    def from_items(cls, n_samples, clips, pool, bank, traj_step=2400):
+        """clips: per clip a list of (event, rir, onset, gain, track) -- class, length and direction come from the pool and the bank.
+        `rir` is one response index, or for a moving item the list of its K trajectory nodes' indices."""
         rows = [it for clip in clips for it in clip]
         ev = np.array([r[0] for r in rows], np.int64)
-        rir = np.array([r[1] for r in rows], np.int64)
+        trajs = [np.asarray(r[1], np.int64).reshape(-1) if np.ndim(r[1]) else np.zeros(0, np.int64) for r in rows]
+        if any(np.ndim(r[1]) and not len(t) for r, t in zip(rows, trajs)):
+            raise ValueError('a trajectory holds at least one node')
+        rir = np.array([t[0] if len(t) else r[1] for r, t in zip(rows, trajs)], np.int64)
+        flat = np.concatenate(trajs) if trajs else np.zeros(0, np.int64)
         return cls(n_samples, np.concatenate(([0], np.cumsum([len(c) for c in clips]))), event=ev, rir=rir,
                    onset=[r[2] for r in rows], gain=[r[3] for r in rows], cls=pool.classes[ev] if len(ev) else [],
                    track=[r[4] for r in rows], length=pool.lengths[ev] if len(ev) else [],
-                   azimuth=bank.azimuth[rir] if len(ev) else [], elevation=bank.elevation[rir] if len(ev) else [])
+                   azimuth=bank.azimuth[rir] if len(ev) else [], elevation=bank.elevation[rir] if len(ev) else [],
+                   traj_start=np.concatenate(([0], np.cumsum([len(t) for t in trajs]))), traj_rir=flat,
+                   traj_azimuth=bank.azimuth[flat], traj_elevation=bank.elevation[flat], traj_step=traj_step)
+
+
+def traj_nodes(length, step):
+    """K = ceil((length - 1) / step) + 1: trajectory nodes of a moving event of `length` samples (a one-sample event has one)"""
+    return -(-(np.asarray(length, np.int64) - 1) // int(step)) + 1
 
 
 def draw_scenes(n_clips, pool, bank, n_samples, seed, max_polyphony=2, allow_same_class=False, gain_db=(-12.0, 0.0),
-                gap_s=(0.5, 4.0), fs=FS, label_rate=10):
+                gap_s=(0.5, 4.0), fs=FS, label_rate=10, moving=0.0, speed_deg_s=(10.0, 40.0), traj_step=2400):
     """Seeded scenes: clip b draws from numpy's Generator default_rng([seed, b]).  Every track (0 .. max_polyphony - 1) is a sequence of
     events that never share a label frame, so at most max_polyphony items are active in any label frame; unless allow_same_class, an
     event whose class is active on another track in one of its label frames is drawn again (20 tries, then the place stays empty).
     Events start at a uniform gap (gap_s seconds) after the frame in which the previous one of the track ended and must fit the clip
-    dry; gains are uniform in dB."""
+    dry; gains are uniform in dB.
+    moving: the probability that an item moves, in azimuth at its drawn response's elevation, at a speed of uniform magnitude in
+    speed_deg_s (degrees per second) and either sign; node k of its trajectory is bank.nearest of the ideal point azimuth + speed k
+    traj_step / fs.  With moving = 0.0 not one more random number is drawn, so every field is what it was without the keyword."""
     hop = fs // label_rate
     clips = []
     for b in range(n_clips):
@@ -250,26 +307,38 @@ def draw_scenes(n_clips, pool, bank, n_samples, seed, max_polyphony=2, allow_sam
                     continue
                 e, f0, f1, k, ln = placed
                 g = 10.0 ** (rng.uniform(gain_db[0], gain_db[1]) / 20.0)
-                items.append((e, int(rng.integers(bank.n_rirs)), cursor, g, track))
+                r = int(rng.integers(bank.n_rirs))
+                if moving > 0.0 and rng.random() < moving:
+                    speed = rng.uniform(speed_deg_s[0], speed_deg_s[1]) * (1.0 if rng.random() < 0.5 else -1.0)
+                    az = bank.azimuth[r] + speed * np.arange(int(traj_nodes(ln, traj_step))) * traj_step / fs
+                    r = list(bank.nearest((az + 180.0) % 360.0 - 180.0, np.full(len(az), float(bank.elevation[r]))))
+                items.append((e, r, cursor, g, track))
                 busy.append((f0, f1, k))
                 cursor = (f1 + 1) * hop + int(rng.uniform(gap_s[0], gap_s[1]) * fs)
                 if cursor >= n_samples:
                     break
         items.sort(key=lambda it: (it[2], it[4]))
         clips.append(items)
-    return Scenes.from_items(n_samples, clips, pool, bank)
+    return Scenes.from_items(n_samples, clips, pool, bank, traj_step=traj_step)
 
 
 def scene_rows(scene, label_rate=10, fs=FS):
-    """The DCASE metadata rows (frame, class, track, azimuth, elevation) of ONE clip, int64 (n_rows, 5), sorted by frame then item."""
+    """The DCASE metadata rows (frame, class, track, azimuth, elevation) of ONE clip, int64 (n_rows, 5), sorted by frame then item.
+    A moving item's row carries the direction of the trajectory node nearest the frame's centre."""
     if scene.n_clips != 1:
         raise ValueError('scene_rows takes one clip: scenes[b]')
     hop = fs // label_rate
     rows = []
     for i in range(scene.n_items):
         o, end = int(scene.onset[i]), min(int(scene.onset[i] + scene.length[i]), scene.n_samples)
+        nodes, S = scene.nodes(i), scene.traj_step
+        K = nodes.stop - nodes.start
         for f in range(o // hop, (end - 1) // hop + 1):
-            rows.append((f, int(scene.cls[i]), int(scene.track[i]), int(scene.azimuth[i]), int(scene.elevation[i]), i))
+            az, el = int(scene.azimuth[i]), int(scene.elevation[i])
+            if K:                                                              # the node nearest the frame's centre, a tie to the later one
+                k = nodes.start + min(max((2 * (hop * f + hop // 2 - o) + S) // (2 * S), 0), K - 1)
+                az, el = int(scene.traj_azimuth[k]), int(scene.traj_elevation[k])
+            rows.append((f, int(scene.cls[i]), int(scene.track[i]), az, el, i))
     rows.sort(key=lambda r: (r[0], r[5]))
     return np.array([r[:5] for r in rows], np.int64).reshape(-1, 5)
 
@@ -323,8 +392,109 @@ def _render_torch_fft(scenes, pool, bank, n_samples, ambient, out):
     return out
 
 
-def render_scenes(scenes, pool, bank, n_samples=None, ambient=None, out=None, device=None):
-    """-> CUDA float32 (B, C, n_samples).  ambient: CUDA (B, C, n_samples) or None; out may be given (and may be the ambient)."""
+def segment_tables(scenes, pool, bank, n_samples=None):
+    """The tables salsa_scene_render_moving takes (include/salsa_hip.h).  Node k of a moving item becomes the segment of its dry samples
+    ((k - 1) S, (k + 1) S) with the ramp centre k S and step S; a static item is one segment of step 0; a segment that would start at
+    or past n_samples is left out.  -> (clip_start int32 (B + 1) over segments, segments int64 (6, n): source offset, onset, length,
+    rir, centre from the segment's start, step; gains float32 (n); block_table int32 (B, M, 2): the first and one-past-last segment
+    that reaches output block m; the longest segment)."""
+    n_samples = scenes.n_samples if n_samples is None else int(n_samples)
+    if scenes.n_items and (scenes.event.min() < 0 or scenes.event.max() >= len(pool)):
+        raise ValueError('an item names no event of the pool')
+    S = scenes.traj_step
+    K = np.diff(scenes.traj_start)                                             # nodes per item, 0 for a static one
+    per_item = np.maximum(K, 1)
+    item = np.repeat(np.arange(scenes.n_items), per_item)                      # the item of every segment, then its node
+    k = np.arange(len(item)) - np.repeat(np.cumsum(per_item) - per_item, per_item)
+    moves = K[item] > 0
+    ln = pool.lengths[scenes.event[item]] if len(item) else np.zeros(0, np.int64)
+    a = np.where(moves, np.maximum(0, (k - 1) * S + 1), 0)
+    end = np.where(moves, np.minimum(ln, (k + 1) * S), ln)
+    rir = np.where(moves, scenes.traj_rir[np.where(moves, scenes.traj_start[item] + k, 0)], scenes.rir[item]) \
+        if scenes.has_trajectories else scenes.rir[item]
+    segs = np.stack([pool.offset[scenes.event[item]] + a, scenes.onset[item] + a, end - a, rir, np.where(moves, k * S - a, 0),
+                     np.where(moves, S, 0)]).astype(np.int64) if len(item) else np.zeros((6, 0), np.int64)
+    keep = segs[1] < n_samples
+    segs, gains = np.ascontiguousarray(segs[:, keep]), np.ascontiguousarray(scenes.gain[item][keep], np.float32)
+    first_of_item = np.concatenate(([0], np.cumsum(np.bincount(item[keep], minlength=scenes.n_items))))
+    clip_start = np.ascontiguousarray(first_of_item[scenes.clip_start], np.int32)
+    B, M, P, n = scenes.n_clips, -(-n_samples // PART), -(-bank.length // PART), segs.shape[1]
+    first = np.repeat(clip_start[:-1].astype(np.int64), M)                     # an empty range at the clip's first segment
+    last = first.copy()
+    if n:
+        clip_of = np.repeat(np.arange(B), np.diff(clip_start))
+        m_lo = segs[1] // PART
+        m_hi = np.minimum(np.minimum((segs[1] + segs[2] - 1) // PART + 1, M - 1) + P - 1, M - 1)
+        # Segment s reaches blocks m_lo[s] .. m_hi[s].  Every segment reaching block m lies in [min {s: m_hi[s] >= m}, 1 + max {s: m_lo[s]
+        # <= m}): two running extrema per clip instead of one entry per (segment, block); with onsets in ascending order the range is
+        # tight but for segments nested inside a longer one's reach, which the kernel skips.
+        s = np.arange(n)
+        lo, hi = np.full((B, M), n, np.int64), np.zeros((B, M), np.int64)
+        np.minimum.at(lo, (clip_of, m_hi), s)
+        np.maximum.at(hi, (clip_of, m_lo), s + 1)
+        lo = np.minimum.accumulate(lo[:, ::-1], axis=1)[:, ::-1].reshape(-1)
+        hi = np.maximum.accumulate(hi, axis=1).reshape(-1)
+        first, last = np.where(lo < hi, lo, first), np.where(lo < hi, hi, last)
+    block_table = np.ascontiguousarray(np.stack([first, last], axis=-1).reshape(B, M, 2), np.int32)
+    return clip_start, segs, gains, block_table, int(segs[2].max()) if n else 1
+
+
+def _render_torch_fft_segments(tables, pool, bank, n_samples, ambient, out):
+    """the moving definition composed from torch.fft calls, one per segment, each on its windowed samples (SALSA_HIP_SCENE=0)"""
+    import torch
+    clip_start, segs, gains = tables[:3]
+    dev = out.device
+    ev, h = pool.on(dev), bank.rirs_on(dev)
+    L = bank.length
+    wet = torch.zeros_like(out)
+    inside = torch.zeros((len(clip_start) - 1, 1, n_samples), dtype=torch.bool, device=dev)
+    for b in range(len(clip_start) - 1):
+        for i in range(clip_start[b], clip_start[b + 1]):
+            src, o, ln, r, centre, step = (int(v) for v in segs[:, i])
+            s = ev[src:src + ln]
+            if step:                                                           # (float)(S - |q - centre|) / (float)S, one rounding of the product
+                q = torch.arange(ln, device=dev)
+                s = s * ((step - (q - centre).abs()).to(torch.float32) / float(step))
+            full = ln + L - 1
+            n_fft = 1 << (full - 1).bit_length()
+            y = torch.fft.irfft(torch.fft.rfft(s, n_fft)[None] * torch.fft.rfft(h[r], n_fft), n_fft)[:, :full]
+            keep = min(full, n_samples - o)
+            wet[b, :, o:o + keep] += float(gains[i]) * y[:, :keep]
+            inside[b, :, o:o + keep] = True
+    base = ambient if ambient is not None else torch.zeros_like(out)
+    out.copy_(torch.where(inside, base + wet, base))
+    return out
+
+
+def _render_segments(scenes, pool, bank, n_samples, ambient, out, device):
+    import torch
+    tables = segment_tables(scenes, pool, bank, n_samples)
+    clip_start, segs, gains, block_table, max_seg = tables
+    if np.diff(clip_start).max() > MAX_SEGMENTS_PER_CLIP:
+        raise ValueError('a clip holds at most %d segments' % MAX_SEGMENTS_PER_CLIP)
+    if not HIP_SCENE:
+        return _render_torch_fft_segments(tables, pool, bank, n_samples, ambient, out)
+    L = _lib.load()
+    B, Cn, n = scenes.n_clips, bank.n_channels, segs.shape[1]
+    ws_bytes = L.salsa_scene_moving_workspace_bytes(n_samples, max_seg, n)
+    ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=device)
+    d_segs, d_gains, d_block = (torch.from_numpy(a).to(device) for a in (segs, gains, block_table))
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    hp = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+    with torch.cuda.device(device):
+        rc = L.salsa_scene_render_moving(ptr(pool.on(device)), len(pool.flat), ptr(bank.spectra(device)), bank.n_rirs, Cn, bank.length,
+                                         hp(clip_start), hp(segs), hp(gains), hp(block_table), ptr(d_segs), ptr(d_gains), ptr(d_block),
+                                         B, n, max_seg, ptr(ambient), ptr(out), n_samples, ptr(ws) if n else None, ws_bytes,
+                                         C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    if rc:
+        raise RuntimeError('salsa_scene_render_moving failed (%d): %s' % (rc, _lib.last_error()))
+    return out
+
+
+def render_scenes(scenes, pool, bank, n_samples=None, ambient=None, out=None, device=None, segments=None):
+    """-> CUDA float32 (B, C, n_samples).  ambient: CUDA (B, C, n_samples) or None; out may be given (and may be the ambient).
+    Scenes without any trajectory go through salsa_scene_render, others through salsa_scene_render_moving; segments=True sends
+    static scenes through the latter too (same bits: tests and tools/bench_scenes_moving.py compare the two)."""
     import torch
     n_samples = scenes.n_samples if n_samples is None else int(n_samples)
     B, Cn = scenes.n_clips, bank.n_channels
@@ -340,6 +510,8 @@ def render_scenes(scenes, pool, bank, n_samples=None, ambient=None, out=None, de
             raise ValueError('render_scenes: contiguous float32 CUDA (%d, %d, %d) expected' % (B, Cn, n_samples))
     if scenes.n_items and scenes.onset.max() >= n_samples:
         raise ValueError('an onset lies outside the clip')
+    if scenes.has_trajectories or segments:
+        return _render_segments(scenes, pool, bank, n_samples, ambient, out, device)
     if np.diff(scenes.clip_start).max() > MAX_ITEMS_PER_CLIP:
         raise ValueError('a clip holds at most %d items' % MAX_ITEMS_PER_CLIP)
     if not HIP_SCENE:

@@ -4,7 +4,10 @@ drawn from different seeds over ONE event pool and ONE response bank (salsa_amd/
 GpuFeatureBanks, and Trainer.fit runs a few epochs.  The SELD 2021 scores on the held-out scenes are recorded before training and
 after every epoch.  No score is promised; the JSON lines say what was seen.
 
-    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--out profiles/scene_training.jsonl]"""
+    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--moving 0.5] [--out profiles/scene_training.jsonl]
+
+--moving FRACTION makes that share of the items move in azimuth in the training and the held-out scenes alike, so
+the ground truth's directions change inside events; 0 (the default) leaves the run as it was."""
 import argparse
 import json
 import os
@@ -26,8 +29,10 @@ def main():
     ap.add_argument('--rir-len', type=int, default=2400)
     ap.add_argument('--rt60', type=float, default=0.3)
     ap.add_argument('--seed', type=int, default=2021)
+    ap.add_argument('--moving', type=float, default=0.0, help='fraction of items that move (DESIGN.md section 9l); 0: the run as it was')
     ap.add_argument('--out', default=None, help='append the JSON lines to this file too')
     args = ap.parse_args()
+    import numpy as np
     import torch
     from salsa_amd import scenes as sc
     from salsa_amd.crnn.fit import validate
@@ -42,6 +47,10 @@ def main():
             with open(args.out, 'a') as f:
                 f.write(line + '\n')
 
+    def static_view(scene):
+        """the same items without their trajectories: every row carries node 0's direction"""
+        return sc.Scenes(scene.n_samples, scene.clip_start, **{f: getattr(scene, f) for f in sc.Scenes.FIELDS})
+
     dev = torch.device('cuda:0')
     NC, n = 12, args.clip_s * sc.FS
     pool = sc.synth_event_pool(NC, 4, 0)
@@ -50,7 +59,7 @@ def main():
     t0 = time.perf_counter()
     banks, drawn = {}, {}
     for name, clips, seed in (('train', args.train_clips, args.seed), ('val', args.val_clips, args.seed + 1000)):
-        scenes = sc.draw_scenes(clips, pool, rbank, n, seed)
+        scenes = sc.draw_scenes(clips, pool, rbank, n, seed, **(dict(moving=args.moving) if args.moving else {}))
         bank = GpuFeatureBank(ex, n_classes=NC, max_clip_s=args.clip_s)
         g = torch.Generator(dev).manual_seed(seed)
         for lo in range(0, clips, 16):                                         # 16 clips of audio at a time
@@ -68,7 +77,13 @@ def main():
     emit(dict(record='scene_training', what='setup', train_clips=args.train_clips, val_clips=args.val_clips, clip_s=args.clip_s,
               train_items=int(drawn['train'].n_items), val_items=int(drawn['val'].n_items), train_chunks=len(banks['train']), classes=NC,
               responses=int(rbank.n_rirs), rir_len=args.rir_len, rt60=args.rt60, events_in_pool=len(pool), ambient_rms=1e-3,
-              seconds_to_render_extract_and_bank=round(time.perf_counter() - t0, 2), device=torch.cuda.get_device_name(0)))
+              seconds_to_render_extract_and_bank=round(time.perf_counter() - t0, 2), device=torch.cuda.get_device_name(0),
+              **(dict(moving=args.moving, traj_step=int(drawn['train'].traj_step), speed_deg_s=[10.0, 40.0],
+                      train_moving_items=int((np.diff(drawn['train'].traj_start) > 0).sum()), train_trajectory_nodes=len(drawn['train'].traj_rir),
+                      val_moving_items=int((np.diff(drawn['val'].traj_start) > 0).sum()),
+                      val_rows_whose_direction_differs_from_the_items_first=int(sum(
+                          (sc.scene_rows(drawn['val'][b])[:, 3] != sc.scene_rows(static_view(drawn['val'][b]))[:, 3]).sum()
+                          for b in range(args.val_clips)))) if args.moving else {})))
     tr = Trainer('cuda', seed=args.seed)
     keys = ('valER', 'valF1', 'valLE', 'valLR', 'valSeld')
     before = validate(tr, banks['val'], val_gt)
