@@ -369,29 +369,6 @@ def _tables(scenes, pool, bank):
     return np.ascontiguousarray(scenes.clip_start, np.int32), items, np.ascontiguousarray(scenes.gain, np.float32)
 
 
-def _render_torch_fft(scenes, pool, bank, n_samples, ambient, out):
-    """the same definition composed from torch.fft calls, one per item (SALSA_HIP_SCENE=0)"""
-    import torch
-    dev = out.device
-    ev, h = pool.on(dev), bank.rirs_on(dev)
-    L = bank.length
-    wet = torch.zeros_like(out)
-    inside = torch.zeros((scenes.n_clips, 1, n_samples), dtype=torch.bool, device=dev)
-    for b in range(scenes.n_clips):
-        for i in range(scenes.clip_start[b], scenes.clip_start[b + 1]):
-            e, o, ln = int(scenes.event[i]), int(scenes.onset[i]), int(pool.lengths[scenes.event[i]])
-            full = ln + L - 1
-            n_fft = 1 << (full - 1).bit_length()
-            s = ev[int(pool.offset[e]):int(pool.offset[e]) + ln]
-            y = torch.fft.irfft(torch.fft.rfft(s, n_fft)[None] * torch.fft.rfft(h[int(scenes.rir[i])], n_fft), n_fft)[:, :full]
-            keep = min(full, n_samples - o)
-            wet[b, :, o:o + keep] += float(scenes.gain[i]) * y[:, :keep]
-            inside[b, :, o:o + keep] = True
-    base = ambient if ambient is not None else torch.zeros_like(out)
-    out.copy_(torch.where(inside, base + wet, base))
-    return out
-
-
 def segment_tables(scenes, pool, bank, n_samples=None):
     """The tables salsa_scene_render_moving takes (include/salsa_hip.h).  Node k of a moving item becomes the segment of its dry samples
     ((k - 1) S, (k + 1) S) with the ramp centre k S and step S; a static item is one segment of step 0; a segment that would start at
@@ -440,7 +417,8 @@ def segment_tables(scenes, pool, bank, n_samples=None):
 
 
 def _render_torch_fft_segments(tables, pool, bank, n_samples, ambient, out):
-    """the moving definition composed from torch.fft calls, one per segment, each on its windowed samples (SALSA_HIP_SCENE=0)"""
+    """the definition composed from torch.fft calls, one per segment, each on its windowed samples (SALSA_HIP_SCENE=0); a static item is
+    a segment of step 0, taken as it is"""
     import torch
     clip_start, segs, gains = tables[:3]
     dev = out.device
@@ -466,28 +444,22 @@ def _render_torch_fft_segments(tables, pool, bank, n_samples, ambient, out):
     return out
 
 
-def _render_segments(scenes, pool, bank, n_samples, ambient, out, device):
+def _launch(entry, query, host, dev, n, max_len, pool, bank, n_samples, ambient, out, device):
+    """One call of the render entry point `entry`, its workspace sized by `query` for n rows of at most max_len samples.  host: the
+    entry's host tables in the order of its arguments (clip_start first), dev: those of them it takes again on the device, in order."""
     import torch
-    tables = segment_tables(scenes, pool, bank, n_samples)
-    clip_start, segs, gains, block_table, max_seg = tables
-    if np.diff(clip_start).max() > MAX_SEGMENTS_PER_CLIP:
-        raise ValueError('a clip holds at most %d segments' % MAX_SEGMENTS_PER_CLIP)
-    if not HIP_SCENE:
-        return _render_torch_fft_segments(tables, pool, bank, n_samples, ambient, out)
     L = _lib.load()
-    B, Cn, n = scenes.n_clips, bank.n_channels, segs.shape[1]
-    ws_bytes = L.salsa_scene_moving_workspace_bytes(n_samples, max_seg, n)
+    ws_bytes = getattr(L, query)(n_samples, max_len, n)
     ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=device)
-    d_segs, d_gains, d_block = (torch.from_numpy(a).to(device) for a in (segs, gains, block_table))
+    d_tables = [torch.from_numpy(a).to(device) for a in dev]
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
     hp = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
     with torch.cuda.device(device):
-        rc = L.salsa_scene_render_moving(ptr(pool.on(device)), len(pool.flat), ptr(bank.spectra(device)), bank.n_rirs, Cn, bank.length,
-                                         hp(clip_start), hp(segs), hp(gains), hp(block_table), ptr(d_segs), ptr(d_gains), ptr(d_block),
-                                         B, n, max_seg, ptr(ambient), ptr(out), n_samples, ptr(ws) if n else None, ws_bytes,
-                                         C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+        rc = getattr(L, entry)(ptr(pool.on(device)), len(pool.flat), ptr(bank.spectra(device)), bank.n_rirs, bank.n_channels, bank.length,
+                               *[hp(a) for a in host], *[ptr(t) for t in d_tables], len(host[0]) - 1, n, max_len, ptr(ambient), ptr(out),
+                               n_samples, ptr(ws) if n else None, ws_bytes, C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
     if rc:
-        raise RuntimeError('salsa_scene_render_moving failed (%d): %s' % (rc, _lib.last_error()))
+        raise RuntimeError('%s failed (%d): %s' % (entry, rc, _lib.last_error()))
     return out
 
 
@@ -510,28 +482,21 @@ def render_scenes(scenes, pool, bank, n_samples=None, ambient=None, out=None, de
             raise ValueError('render_scenes: contiguous float32 CUDA (%d, %d, %d) expected' % (B, Cn, n_samples))
     if scenes.n_items and scenes.onset.max() >= n_samples:
         raise ValueError('an onset lies outside the clip')
-    if scenes.has_trajectories or segments:
-        return _render_segments(scenes, pool, bank, n_samples, ambient, out, device)
-    if np.diff(scenes.clip_start).max() > MAX_ITEMS_PER_CLIP:
+    as_segments = scenes.has_trajectories or bool(segments)
+    if not as_segments and np.diff(scenes.clip_start).max() > MAX_ITEMS_PER_CLIP:
         raise ValueError('a clip holds at most %d items' % MAX_ITEMS_PER_CLIP)
-    if not HIP_SCENE:
-        return _render_torch_fft(scenes, pool, bank, n_samples, ambient, out)
-    L = _lib.load()
-    clip_start, items, gains = _tables(scenes, pool, bank)
-    n_items = scenes.n_items
-    ws_bytes = L.salsa_scene_workspace_bytes(n_samples, pool.max_len, n_items)
-    ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=device)
-    d_clip, d_items, d_gains = (torch.from_numpy(a).to(device) for a in (clip_start, items, gains))
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-    hp = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
-    with torch.cuda.device(device):
-        rc = L.salsa_scene_render(ptr(pool.on(device)), len(pool.flat), ptr(bank.spectra(device)), bank.n_rirs, Cn, bank.length,
-                                  hp(clip_start), hp(items), hp(gains), ptr(d_clip), ptr(d_items), ptr(d_gains), B, n_items, pool.max_len,
-                                  ptr(ambient), ptr(out), n_samples, ptr(ws) if n_items else None, ws_bytes,
-                                  C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc:
-        raise RuntimeError('salsa_scene_render failed (%d): %s' % (rc, _lib.last_error()))
-    return out
+    if as_segments or not HIP_SCENE:                                           # the torch.fft leg takes static items as segments of step 0
+        tables = segment_tables(scenes, pool, bank, n_samples)
+        clip_start, segs, gains, block_table, max_seg = tables
+        if as_segments and np.diff(clip_start).max() > MAX_SEGMENTS_PER_CLIP:
+            raise ValueError('a clip holds at most %d segments' % MAX_SEGMENTS_PER_CLIP)
+        if not HIP_SCENE:
+            return _render_torch_fft_segments(tables, pool, bank, n_samples, ambient, out)
+        return _launch('salsa_scene_render_moving', 'salsa_scene_moving_workspace_bytes', (clip_start, segs, gains, block_table),
+                       (segs, gains, block_table), segs.shape[1], max_seg, pool, bank, n_samples, ambient, out, device)
+    tables = _tables(scenes, pool, bank)
+    return _launch('salsa_scene_render', 'salsa_scene_workspace_bytes', tables, tables, scenes.n_items, pool.max_len, pool, bank,
+                   n_samples, ambient, out, device)
 
 
 def add_scenes(feature_bank, scenes, pool, bank, names=None, ambient=None, n_classes=None, label_rate=10, fs=FS):
