@@ -350,6 +350,32 @@ int salsa_scene_render_moving(const float *d_events, int64_t n_event_samples, co
                               int max_segment_len, const float *d_ambient, float *d_out, int64_t n_samples, void *d_workspace,
                               size_t workspace_bytes, void *hip_stream);
 
+/* Shoebox room responses by the image-source method (salsa_amd/rooms.py; the reference has no counterpart: the
+ * definition is this project's).  The caller has enumerated the room's images once, for all sources: image i mirrors a source s to
+ * p = sign_i o s + shift_i (sign = 1 - 2 q, shift = 2 n o L) with the amplitude A_i (the walls' reflection coefficients to the powers
+ * of their reflection counts; the order limit already applied).  For source r and receiver point rho:
+ *     d = |p - rho|,  tau = d fs_over_c - t0_r,  out[r, c, k] += g_r (A_i / d) gain_c w(k - tau),   0 <= k < rir_len,
+ * w(x) = sinc(x) (1 + cos(pi x / 16)) / 2 for |x| < 16 and 0 otherwise.  SALSA_ROOM_OMNI: channel c is receiver c, gain 1.
+ * SALSA_ROOM_FOA: ONE receiver, four channels W, Y, Z, X with the gains (1, u_y, u_z, u_x), u = (p - rho) / d.  Positions, distances,
+ * delays and the fractional part of tau are float64; from the tap argument on the arithmetic is float32, each tap summed over the
+ * images in TABLE ORDER: two calls give equal bits, a source's response does not depend on the other sources of the call, and a tap
+ * that no image's support reaches is +0.0.  Every element of out is written.
+ *
+ * The tables are given twice with equal contents, on the host (checked entry by entry before the first device call) and on the device.
+ * images double [7][n_images]: the rows sign x, y, z (each +1 or -1), shift x, y, z, amplitude (0 < A <= 1); 1 <= n_images <=
+ * salsa_room_max_images() = 4194304.  sources double [n_sources][5]: position x, y, z, the time origin t0 (a whole number >= 0) and the
+ * gain g > 0; 1 <= n_sources <= 65535.  receivers double [n_receivers][3], HOST only, 1 .. 4 of them.  1 <= rir_len <= 16384.
+ * d_out float32 [n_sources][C][rir_len], C = n_receivers (omni) or 4 (FOA).  One launch on hip_stream, nothing allocated or
+ * synchronised; a workgroup owns salsa_room_tap_block() = 256 consecutive taps of one (source, receiver).  Returns -1 for a null
+ * pointer or an argument outside these limits, before any device call; -6 when the launch fails. */
+#define SALSA_ROOM_OMNI 0
+#define SALSA_ROOM_FOA 1
+int salsa_room_max_images(void);
+int salsa_room_tap_block(void);
+int salsa_room_rirs(const double *images, const double *d_images, int n_images, const double *sources, const double *d_sources,
+                    int n_sources, const double *receivers, int n_receivers, int mode, double fs_over_c, int rir_len, float *d_out,
+                    void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

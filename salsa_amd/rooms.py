@@ -1,0 +1,228 @@
+"""Shoebox room responses by the image-source method of Allen & Berkley, generated on the GPU and handed to the
+scene renderer as a RirBank.  The reference has no such code; the definition is this project's.
+
+Room: size L = (Lx, Ly, Lz) metres, walls at x = 0, x = Lx, ...; amplitude reflection coefficients beta = (bx0, bx1, by0, by1, bz0,
+bz1) in [0, 1].  Array centre a.  foa: one receiver point a; mic: four open omnidirectional capsules a + MIC_RADIUS unit(
+MIC_DIRECTIONS[m]).  Source r: s_r = a + dist_r unit(az_r, el_r); its label is the direction seen from the array centre.
+
+Image (n, q), n in Z^3, q in {0, 1}^3: position p = (1 - 2 q) o s + 2 n o L, amplitude A = prod_axis beta_axis,0^|n - q| beta_axis,1^|n|
+(beta^0 = 1 also for beta = 0), order sum_axis (|n - q| + |n|).  For a receiver point rho: d = |p - rho|, tau = d fs / c - t0_r, and the
+image adds g_r (A / d) w(k - tau) to tap k, w(x) = sinc(x) (1 + cos(pi x / H)) / 2 for |x| < H = SINC_HALF and 0 otherwise (the kernel of
+make_rir_bank('mic')).  foa: the channels W, Y, Z, X get the gains (1, u_y, u_z, u_x), u = (p - a) / d; mic: channel m is receiver m.
+align_direct: t0_r = max(0, floor(|s_r - a| fs / c) - H), the direct peak near tap H at any distance (else t0_r = 0);
+normalize_direct: g_r = |s_r - a|, a unit direct W gain as in make_rir_bank (else g_r = 1).  Every image with A > 0 and order <=
+max_order whose support meets [0, length) is included, supports are cut at 0 and at length, a tap no support reaches is +0.0, and
+each tap is summed over the images in the order of room_images' table.
+
+Precision: positions, distances, delays and tau's fractional part are float64, the coefficient g A / d (times u_c) is formed in float64
+and rounded once; from the tap argument x on everything is float32.  The sums run in salsa_amd/csrc/room_rir.hip (include/salsa_hip.h:
+salsa_room_rirs); SALSA_HIP_ROOM=0, or a device that is no GPU, sends room_rir_bank to a composed torch evaluation of the same
+definition and the same split."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+from .scenes import (FS, MAX_RIR_LEN, MIC_DIRECTIONS, MIC_RADIUS, SINC_HALF, SOUND_SPEED, RirBank, _unit, rir_spectra)
+
+HIP_ROOM = os.environ.get('SALSA_HIP_ROOM', '1') != '0'     # 0: room_rir_bank composes torch calls, for A/B runs and bisecting
+MAX_IMAGES = 1 << 22                                        # salsa_room_max_images()
+MAX_SOURCES = 65535
+TAP_BLOCK = 256                                             # salsa_room_tap_block(): taps of one workgroup
+MIN_DISTANCE = 1e-3                                         # metres between a source and a receiver point
+
+
+def eyring_beta(size, rt60, c=SOUND_SPEED):
+    """The uniform amplitude reflection coefficient beta = sqrt(1 - alpha) of Eyring's alpha = 1 - exp(-24 ln 10 V / (c S rt60))."""
+    lx, ly, lz = (float(v) for v in size)
+    volume, surface = lx * ly * lz, 2.0 * (lx * ly + ly * lz + lx * lz)
+    return float(np.exp(-12.0 * np.log(10.0) * volume / (c * surface * float(rt60))))      # sqrt(exp(-24 ...)) = exp(-12 ...)
+
+
+class ShoeboxRoom:
+    """size (Lx, Ly, Lz) in metres; exactly one of beta -- the six amplitude reflection coefficients (x0, x1, y0, y1, z0, z1), or one
+    number for all walls -- and rt60, seconds, which stands for the uniform beta of Eyring's formula (eyring_beta).  array: the array
+    centre, None for the room's centre.
+    rt60 is a nominal figure: the decay an image-source shoebox realises is LONGER than Eyring's (a float64 prototype gave a T20-based
+    0.46 s on W for a nominal 0.3 s in a 6 x 5 x 3.2 m room, one run, not checked otherwise); nothing here asserts a realised RT60."""
+
+    def __init__(self, size, beta=None, rt60=None, array=None, fs=FS, c=SOUND_SPEED):
+        self.size = np.asarray(size, np.float64).reshape(-1)
+        if self.size.shape != (3,) or not np.all(np.isfinite(self.size)) or not np.all(self.size > 0):
+            raise ValueError('size is (Lx, Ly, Lz), positive metres')
+        if (beta is None) == (rt60 is None):
+            raise ValueError('give exactly one of beta and rt60')
+        self.fs, self.c = float(fs), float(c)
+        if not (self.fs > 0 and self.c > 0):
+            raise ValueError('fs and c are positive')
+        if rt60 is not None:
+            if not float(rt60) > 0:
+                raise ValueError('rt60 is positive seconds')
+            beta = eyring_beta(self.size, rt60, self.c)
+        self.rt60 = None if rt60 is None else float(rt60)
+        self.beta = np.broadcast_to(np.asarray(beta, np.float64), (6,)).copy() if np.ndim(beta) == 0 else np.asarray(beta, np.float64).reshape(-1)
+        if self.beta.shape != (6,) or not np.all((self.beta >= 0) & (self.beta <= 1)):
+            raise ValueError('beta is six reflection coefficients in [0, 1]')
+        self.array = 0.5 * self.size if array is None else np.asarray(array, np.float64).reshape(-1)
+        if self.array.shape != (3,) or not np.all((self.array > 0) & (self.array < self.size)):
+            raise ValueError('the array centre lies strictly inside the room')
+
+    def receivers(self, audio_format):
+        """the receiver points (M, 3) of the format: the centre (foa), the four capsules (mic)"""
+        if audio_format == 'foa':
+            return self.array[None].copy()
+        if audio_format == 'mic':
+            return self.array + MIC_RADIUS * _unit([m[0] for m in MIC_DIRECTIONS], [m[1] for m in MIC_DIRECTIONS])
+        raise ValueError('audio_format must be foa or mic')
+
+
+class RoomImages:
+    """The image table of a room, N images in canonical order: n and q int64 (N, 3), sign = 1 - 2 q and shift = 2 n o L float64 (N, 3),
+    amplitude float64 (N), order int64 (N)."""
+
+    def __init__(self, n, q, size, amplitude, order):
+        self.n, self.q, self.amplitude, self.order = n, q, amplitude, order
+        self.sign = (1 - 2 * q).astype(np.float64)
+        self.shift = 2.0 * n * np.asarray(size, np.float64)
+
+    def __len__(self):
+        return len(self.amplitude)
+
+    def table(self):
+        """float64 (7, N), what salsa_room_rirs takes: the rows sign x, y, z, shift x, y, z, amplitude"""
+        return np.ascontiguousarray(np.concatenate([self.sign.T, self.shift.T, self.amplitude[None]]), np.float64)
+
+
+def room_images(room, d_max, max_order=None):
+    """The host-side image table, shared by every source and receiver of the room.  Canonical order: ascending (n_x, n_y, n_z, q_x, q_y,
+    q_z), n_x the slowest.  Images with A = 0 or an order above max_order (None: no limit) are absent.  The table is cut by distance,
+    conservatively: with the source and the receiver ANYWHERE in the room, the image's offset along an axis is at least max(0, |2 n -
+    q| - 1) L, and an image is kept iff the norm of these three least offsets is at most d_max.  Everything is float64."""
+    L, b = room.size, room.beta
+    if not (np.isfinite(d_max) and d_max >= 0):
+        raise ValueError('d_max is a distance in metres')
+    reach = [int(np.ceil(d_max / (2.0 * L[ax]))) + 1 for ax in range(3)]
+    if max_order is not None:
+        if int(max_order) != max_order or max_order < 0:
+            raise ValueError('max_order is a whole number >= 0, or None')
+        reach = [min(r, int(max_order) // 2 + 1) for r in reach]
+    if 8 * np.prod([2.0 * r + 1 for r in reach]) > 4 * MAX_IMAGES:               # (the kept ball is about half of the enumerated box)
+        raise ValueError('the room has too many images within %g m (the limit is %d)' % (d_max, MAX_IMAGES))
+    ns = [np.arange(-r, r + 1, dtype=np.int64) for r in reach]
+    grid = np.stack(np.meshgrid(ns[0], ns[1], ns[2], [0, 1], [0, 1], [0, 1], indexing='ij'), axis=-1).reshape(-1, 6)   # C order: canonical
+    n, q = grid[:, :3], grid[:, 3:]
+    low, high = np.abs(n - q), np.abs(n)                                       # reflections at the walls 0 and at the walls L, per axis
+    order = (low + high).sum(axis=1)
+    amplitude = np.prod(b[0::2][None] ** low * b[1::2][None] ** high, axis=1)  # numpy: 0.0 ** 0 = 1.0
+    least = np.maximum(0, np.abs(2 * n - q) - 1) * L[None]
+    keep = (amplitude > 0) & (np.sqrt((least ** 2).sum(axis=1)) <= d_max)
+    if max_order is not None:
+        keep &= order <= int(max_order)
+    return RoomImages(np.ascontiguousarray(n[keep]), np.ascontiguousarray(q[keep]), L, amplitude[keep], order[keep])
+
+
+def room_geometry(audio_format, room, directions, distance, length, align_direct=True, normalize_direct=True):
+    """-> (directions int64 (R, 2), sources float64 (R, 5): position, t0, g; receivers float64 (M, 3); d_max: the distance past which no
+    image reaches a tap below `length`).  Raises ValueError unless every source and receiver lies strictly inside the room and every
+    source is at least 1 mm from every receiver."""
+    directions = np.asarray(directions, np.int64).reshape(-1, 2)
+    R = len(directions)
+    if not 1 <= R <= MAX_SOURCES:
+        raise ValueError('1 .. %d directions' % MAX_SOURCES)
+    if int(length) != length or not 1 <= length <= MAX_RIR_LEN:
+        raise ValueError('1 <= length <= %d' % MAX_RIR_LEN)
+    dist = np.broadcast_to(np.asarray(distance, np.float64), (R,)) if np.ndim(distance) == 0 else np.asarray(distance, np.float64).reshape(-1)
+    if dist.shape != (R,) or not np.all(np.isfinite(dist)) or not np.all(dist >= 0):
+        raise ValueError('distance is one number, or one per direction')
+    rec = room.receivers(audio_format)
+    pos = room.array[None] + dist[:, None] * _unit(directions[:, 0], directions[:, 1])
+    for what, pts in (('source', pos), ('receiver', rec)):
+        if not np.all((pts > 0) & (pts < room.size[None])):
+            raise ValueError('a %s lies outside the room' % what)
+    if np.sqrt(((pos[:, None] - rec[None]) ** 2).sum(axis=-1)).min() < MIN_DISTANCE:
+        raise ValueError('a source lies within %g m of a receiver' % MIN_DISTANCE)
+    centre = np.sqrt(((pos - room.array[None]) ** 2).sum(axis=-1))            # |s_r - a|
+    t0 = np.maximum(0.0, np.floor(centre * room.fs / room.c) - SINC_HALF) if align_direct else np.zeros(R)
+    g = centre if normalize_direct else np.ones(R)
+    if not np.all(g > 0):
+        raise ValueError('normalize_direct needs every source away from the array centre')
+    d_max = (int(length) + SINC_HALF + float(t0.max())) * room.c / room.fs * (1.0 + 1e-9)
+    return directions, np.ascontiguousarray(np.concatenate([pos, t0[:, None], g[:, None]], axis=1)), np.ascontiguousarray(rec), d_max
+
+
+def _rirs_torch(table, sources, receivers, foa, fs_over_c, length, device):
+    """The definition composed from torch calls with the kernel's precision split (SALSA_HIP_ROOM=0, and any device that is no GPU):
+    per (source, receiver) the images' 2 H taps as one (images, 2 H) array, float64 up to the tap argument, float32 from it on, added
+    into the response by index_add_ in float32 (in table order on the CPU; a GPU adds them in no promised order)."""
+    import torch
+    H = SINC_HALF
+    tb = torch.from_numpy(table).to(device)
+    sign, shift, amp = tb[0:3].T, tb[3:6].T, tb[6]
+    src, rec = torch.from_numpy(sources).to(device), torch.from_numpy(receivers).to(device)
+    R, M = len(sources), len(receivers)
+    out = torch.zeros((R, 4 if foa else M, length), dtype=torch.float32, device=device)
+    j = torch.arange(1 - H, H + 1, device=device)
+    for r in range(R):
+        p = sign * src[r, :3] + shift
+        for m in range(M):
+            delta = p - rec[m]
+            d = torch.sqrt((delta * delta).sum(dim=1))
+            tau = d * fs_over_c - src[r, 3]
+            tf = torch.floor(tau)
+            sel = torch.nonzero((tf >= -H) & (tf <= length + H - 2)).reshape(-1)      # the support meets [0, length)
+            if not len(sel):
+                continue
+            k = tf[sel].to(torch.int64)[:, None] + j[None]
+            x = (j[None].to(torch.float64) - (tau[sel] - tf[sel])[:, None]).to(torch.float32)
+            w = torch.sinc(x) * (0.5 * (1.0 + torch.cos(x * (np.pi / H))))
+            w = torch.where((x.abs() < H) & (k >= 0) & (k < length), w, torch.zeros_like(w))
+            a = src[r, 4] * amp[sel] / d[sel]
+            gains = [a] if not foa else [a, a * (delta[sel, 1] / d[sel]), a * (delta[sel, 2] / d[sel]), a * (delta[sel, 0] / d[sel])]
+            kk = k.clamp(0, length - 1).reshape(-1)
+            for c, gc in enumerate(gains):
+                out[r, c if foa else m].index_add_(0, kk, (gc.to(torch.float32)[:, None] * w).reshape(-1))
+    return out
+
+
+def _rirs_hip(table, sources, receivers, foa, fs_over_c, length, device):
+    import torch
+    L = _lib.load()
+    R, M = len(sources), len(receivers)
+    out = torch.empty((R, 4 if foa else M, length), dtype=torch.float32, device=device)
+    d_table, d_sources = torch.from_numpy(table).to(device), torch.from_numpy(sources).to(device)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    with torch.cuda.device(device):
+        rc = L.salsa_room_rirs(hp(table), C.c_void_p(d_table.data_ptr()), table.shape[1], hp(sources), C.c_void_p(d_sources.data_ptr()), R,
+                               hp(receivers), M, 1 if foa else 0, fs_over_c, length, C.c_void_p(out.data_ptr()),
+                               C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    if rc:
+        raise RuntimeError('salsa_room_rirs failed (%d): %s' % (rc, _lib.last_error()))
+    torch.cuda.current_stream(device).synchronize()                           # the tables may go now
+    return out
+
+
+def room_rirs(audio_format, room, directions, distance, length, max_order=None, align_direct=True, normalize_direct=True, device=None):
+    """The responses as a float32 tensor (R, C, length) on `device` (None: 'cuda'), and the directions: what room_rir_bank wraps."""
+    import torch
+    directions, sources, receivers, d_max = room_geometry(audio_format, room, directions, distance, length, align_direct, normalize_direct)
+    images = room_images(room, d_max, max_order)
+    if not 1 <= len(images) <= MAX_IMAGES:
+        raise ValueError('the room has %d images within reach of %d taps; 1 .. %d are supported' % (len(images), length, MAX_IMAGES))
+    device = torch.device('cuda' if device is None else device)
+    run = _rirs_hip if HIP_ROOM and device.type == 'cuda' else _rirs_torch
+    return run(images.table(), sources, receivers, audio_format == 'foa', room.fs / room.c, int(length), device), directions
+
+
+def room_rir_bank(audio_format, room, directions, distance, length, max_order=None, align_direct=True, normalize_direct=True, device=None):
+    """-> RirBank of the image-source responses of `room` for `directions` = [(azimuth, elevation), ...] in integer degrees, each at
+    `distance` metres (one number, or one per direction) from the array centre.  max_order: the highest reflection order, None for
+    every image that reaches a tap below `length`.  device: where the responses are generated, None for 'cuda'; on a GPU the
+    bank's partition spectra for that device are made there too, before the download, so the renderer does not upload them again.
+    device='cpu' (the torch path) needs no GPU.  A room given by rt60 realises a LONGER decay than the nominal one (ShoeboxRoom)."""
+    h, directions = room_rirs(audio_format, room, directions, distance, length, max_order, align_direct, normalize_direct, device)
+    spec = rir_spectra(h) if h.is_cuda else None                              # on the device, from the very values the bank will hold
+    bank = RirBank(h.cpu().numpy(), directions[:, 0], directions[:, 1], audio_format)
+    if spec is not None:
+        bank._spectra[RirBank.device_key(h.device)] = spec
+    return bank

@@ -70,24 +70,35 @@ class RirBank:
         idx = np.argmin(np.arccos(cosine), axis=0)
         return int(idx) if np.ndim(idx) == 0 else idx.astype(np.int64)
 
-    def spectra(self, device):
+    @staticmethod
+    def device_key(device):
         import torch
         device = torch.device(device)
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        return (device.type, device.index if device.index is not None else torch.cuda.current_device())
+
+    def spectra(self, device):
+        key = self.device_key(device)
         if key not in self._spectra:
-            L = _lib.load()
-            R, Cn, Ln = self.rirs.shape
-            n = L.salsa_scene_rir_spectra_bytes(R, Cn, Ln)
-            spec = torch.empty(n // 4, dtype=torch.float32, device=device)
-            d_rirs = self.rirs_on(device)
-            with torch.cuda.device(device):
-                rc = L.salsa_scene_rir_spectra(C.c_void_p(d_rirs.data_ptr()), R, Cn, Ln, C.c_void_p(spec.data_ptr()),
-                                               C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-            if rc:
-                raise RuntimeError('salsa_scene_rir_spectra failed (%d): %s' % (rc, _lib.last_error()))
-            torch.cuda.current_stream(device).synchronize()                   # d_rirs may go now; once per bank and device
-            self._spectra[key] = spec
+            self._spectra[key] = rir_spectra(self.rirs_on(device))            # once per bank and device
         return self._spectra[key]
+
+
+def rir_spectra(d_rirs):
+    """The partition spectra (salsa_scene_rir_spectra) of contiguous float32 CUDA responses (R, C, L), on their device.  A bank whose
+    responses were generated on a device (rooms.room_rir_bank) gets its spectra from here before the download."""
+    import torch
+    L = _lib.load()
+    R, Cn, Ln = d_rirs.shape
+    device = d_rirs.device
+    n = L.salsa_scene_rir_spectra_bytes(R, Cn, Ln)
+    spec = torch.empty(n // 4, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        rc = L.salsa_scene_rir_spectra(C.c_void_p(d_rirs.data_ptr()), R, Cn, Ln, C.c_void_p(spec.data_ptr()),
+                                       C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    if rc:
+        raise RuntimeError('salsa_scene_rir_spectra failed (%d): %s' % (rc, _lib.last_error()))
+    torch.cuda.current_stream(device).synchronize()                           # d_rirs may go now
+    return spec
 
 
 def make_rir_bank(audio_format, directions, length, rt60=None, drr_db=6.0, seed=0, fs=FS):
@@ -509,3 +520,15 @@ def add_scenes(feature_bank, scenes, pool, bank, names=None, ambient=None, n_cla
     names = ['scene_%04d' % b for b in range(scenes.n_clips)] if names is None else list(names)
     feature_bank.add_clips(audio, names, sed=[lab[0] for lab in labels], doa=[lab[1] for lab in labels])
     return audio
+
+
+_ROOMS = ('ShoeboxRoom', 'RoomImages', 'room_images', 'room_rirs', 'room_rir_bank', 'eyring_beta')
+
+
+def __getattr__(name):
+    """rooms.py (image-source responses of a shoebox room as a RirBank) builds on this module, so its public names
+    are re-exported on first use, not at import"""
+    if name in _ROOMS:
+        from . import rooms
+        return getattr(rooms, name)
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -1,0 +1,119 @@
+#!/usr/bin/env python
+"""Time of the shoebox image-source generator.  Three legs in ONE process, one sample of each per round so that
+drift hits them alike, medians after warm-up, a host clock around WHOLE calls of room_rir_bank (each ends in the download of the
+responses, a device synchronise): the image table, the uploads, the sums, on a GPU the bank's partition spectra, and the download --
+what a user's call costs.
+    a  HIP               salsa_room_rirs on the device
+    b  torch, device     the composed torch evaluation on the device (SALSA_HIP_ROOM=0)
+    c  torch, host       the same on the CPU (device='cpu'), --host-rounds samples
+Shapes: FOA and MIC banks of 72 directions (azimuth every 5 degrees) and one FOA bank of 360 (every degree), 7200 taps, sources at
+1.5 m in a 6 x 5 x 3.2 m room with rt60 = 0.3 s (uniform beta by Eyring).  The largest difference between the legs' responses is
+recorded with each shape, and so is the time of salsa_room_rirs' launch alone (device events, tables already uploaded; it includes the
+launcher's host-side check of the table).  One JSON line per record; whatever is seen is reported, a leg that loses included.
+
+    python tools/bench_rooms.py [--rounds 5] [--host-rounds 2] [--warmup 1] [--out profiles/room_rir_bench.jsonl]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, ROOT)
+
+
+def launch_ms(table, sources, receivers, foa, fs_over_c, length, dev, warmup, rounds):
+    """salsa_room_rirs alone, its tables already on the device: device events around one launch per sample -> ms per sample"""
+    import ctypes as C
+    import torch
+    from salsa_amd import _lib
+    L = _lib.load()
+    d_table, d_sources = torch.from_numpy(table).to(dev), torch.from_numpy(sources).to(dev)
+    out = torch.empty((len(sources), 4 if foa else len(receivers), length), dtype=torch.float32, device=dev)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    ms = []
+    for r in range(warmup + rounds):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        rc = L.salsa_room_rirs(hp(table), C.c_void_p(d_table.data_ptr()), table.shape[1], hp(sources), C.c_void_p(d_sources.data_ptr()),
+                               len(sources), hp(receivers), len(receivers), int(foa), fs_over_c, length, C.c_void_p(out.data_ptr()),
+                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        b.record()
+        torch.cuda.synchronize()
+        if rc:
+            raise RuntimeError(_lib.last_error())
+        if r >= warmup:
+            ms.append(a.elapsed_time(b))
+    return ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--host-rounds', type=int, default=2, help='samples of leg c')
+    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--rir-len', type=int, default=7200)
+    ap.add_argument('--distance', type=float, default=1.5)
+    ap.add_argument('--out', default=None, help='append the JSON lines to this file too')
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    from salsa_amd import rooms
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_rooms.py measures on cuda:0; there is none')
+    dev = torch.device('cuda:0')
+    room = rooms.ShoeboxRoom((6.0, 5.0, 3.2), rt60=0.3)
+    shapes = [('foa', 72), ('mic', 72), ('foa', 360)]
+    legs = {'a HIP': (True, dev), 'b torch, device': (False, dev), 'c torch, host': (False, 'cpu')}
+    for fmt, n_dir in shapes:
+        recs = []
+        directions = [(az, 0) for az in range(-180, 180, 360 // n_dir)]
+        _, sources, receivers, d_max = rooms.room_geometry(fmt, room, directions, args.distance, args.rir_len)
+        table_ms = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            images = rooms.room_images(room, d_max)
+            table_ms.append((time.perf_counter() - t0) * 1e3)
+        n_images, table_ms = len(images), min(table_ms)
+        times, last = {k: [] for k in legs}, {}
+        for r in range(args.warmup + max(args.rounds, args.host_rounds)):
+            for leg, (hip, where) in legs.items():
+                host = where == 'cpu'
+                if r >= (args.host_rounds if host else args.warmup + args.rounds):
+                    continue
+                rooms.HIP_ROOM = hip
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                bank = rooms.room_rir_bank(fmt, room, directions, args.distance, args.rir_len, device=where)
+                torch.cuda.synchronize()
+                if host or r >= args.warmup:
+                    times[leg].append((time.perf_counter() - t0) * 1e3)
+                last[leg] = bank.rirs
+        rooms.HIP_ROOM = True
+        kernel_ms = launch_ms(images.table(), sources, receivers, fmt == 'foa', room.fs / room.c, args.rir_len, dev, args.warmup, args.rounds)
+        top = float(np.abs(last['a HIP']).max())
+        for leg in legs:
+            t = np.array(times[leg])
+            recs.append(dict(bench='room_rir', format=fmt, directions=n_dir, rir_len=args.rir_len, room=[6.0, 5.0, 3.2], rt60_nominal=0.3,
+                             beta=round(float(room.beta[0]), 6), distance=args.distance, images=n_images, leg=leg,
+                             ms_median=round(float(np.median(t)), 2), ms_min=round(float(t.min()), 2), ms_max=round(float(t.max()), 2),
+                             samples=len(t), host_ms_to_build_the_image_table=round(table_ms, 2),
+                             max_abs_difference_from_leg_a=float(np.abs(last[leg] - last['a HIP']).max()), max_abs_response=round(top, 4),
+                             device=torch.cuda.get_device_name(0)))
+        med = {leg: float(np.median(times[leg])) for leg in legs}
+        recs.append(dict(bench='room_rir', format=fmt, directions=n_dir, rir_len=args.rir_len,
+                         launch_alone_ms_median=round(float(np.median(kernel_ms)), 3), launch_alone_ms_min=round(min(kernel_ms), 3),
+                         launch_alone_ms_max=round(max(kernel_ms), 3), launch_alone_samples=len(kernel_ms),
+                         b_over_a=round(med['b torch, device'] / med['a HIP'], 2), c_over_a=round(med['c torch, host'] / med['a HIP'], 2)))
+        for rec in recs:
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, 'a') as f:
+                    f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()

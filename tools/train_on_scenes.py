@@ -4,10 +4,13 @@ drawn from different seeds over ONE event pool and ONE response bank (salsa_amd/
 GpuFeatureBanks, and Trainer.fit runs a few epochs.  The SELD 2021 scores on the held-out scenes are recorded before training and
 after every epoch.  No score is promised; the JSON lines say what was seen.
 
-    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--moving 0.5] [--out profiles/scene_training.jsonl]
+    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--moving 0.5] [--room] [--out profiles/scene_training.jsonl]
 
 --moving FRACTION makes that share of the items move in azimuth in the training and the held-out scenes alike, so
-the ground truth's directions change inside events; 0 (the default) leaves the run as it was."""
+the ground truth's directions change inside events; 0 (the default) leaves the run as it was.
+--room takes the responses from room_rir_bank instead of make_rir_bank: the same 48 directions, sources at
+--distance metres from the centre of a 6 x 5 x 3.2 m shoebox whose uniform reflection coefficient is Eyring's for --rt60 (a nominal
+figure: the realised decay is longer), generated on the device."""
 import argparse
 import json
 import os
@@ -30,6 +33,8 @@ def main():
     ap.add_argument('--rt60', type=float, default=0.3)
     ap.add_argument('--seed', type=int, default=2021)
     ap.add_argument('--moving', type=float, default=0.0, help='fraction of items that move (DESIGN.md section 9l); 0: the run as it was')
+    ap.add_argument('--room', action='store_true', help='image-source responses of a shoebox room (DESIGN.md section 9m) instead of make_rir_bank')
+    ap.add_argument('--distance', type=float, default=1.5, help='--room: metres from the array centre to every source')
     ap.add_argument('--out', default=None, help='append the JSON lines to this file too')
     args = ap.parse_args()
     import numpy as np
@@ -54,7 +59,17 @@ def main():
     dev = torch.device('cuda:0')
     NC, n = 12, args.clip_s * sc.FS
     pool = sc.synth_event_pool(NC, 4, 0)
-    rbank = sc.make_rir_bank('foa', [(a, e) for a in range(-180, 180, 30) for e in (-40, -10, 20, 50)], args.rir_len, rt60=args.rt60, seed=1)
+    directions = [(a, e) for a in range(-180, 180, 30) for e in (-40, -10, 20, 50)]
+    room_rec = {}
+    if args.room:
+        room = sc.ShoeboxRoom((6.0, 5.0, 3.2), rt60=args.rt60)
+        t0 = time.perf_counter()
+        rbank = sc.room_rir_bank('foa', room, directions, args.distance, args.rir_len, device=dev)
+        room_rec = dict(room=[6.0, 5.0, 3.2], beta=round(float(room.beta[0]), 6), rt60_is='nominal (Eyring); the realised decay is longer',
+                        distance=args.distance, seconds_to_generate_the_bank=round(time.perf_counter() - t0, 3),
+                        response_energy_after_the_first_50_taps=round(float((rbank.rirs[:, 0, 50:] ** 2).sum() / (rbank.rirs[:, 0] ** 2).sum()), 4))
+    else:
+        rbank = sc.make_rir_bank('foa', directions, args.rir_len, rt60=args.rt60, seed=1)
     ex = SalsaExtractor(audio_format='foa', fmax_doa=9000, device=dev)
     t0 = time.perf_counter()
     banks, drawn = {}, {}
@@ -77,7 +92,7 @@ def main():
     emit(dict(record='scene_training', what='setup', train_clips=args.train_clips, val_clips=args.val_clips, clip_s=args.clip_s,
               train_items=int(drawn['train'].n_items), val_items=int(drawn['val'].n_items), train_chunks=len(banks['train']), classes=NC,
               responses=int(rbank.n_rirs), rir_len=args.rir_len, rt60=args.rt60, events_in_pool=len(pool), ambient_rms=1e-3,
-              seconds_to_render_extract_and_bank=round(time.perf_counter() - t0, 2), device=torch.cuda.get_device_name(0),
+              seconds_to_render_extract_and_bank=round(time.perf_counter() - t0, 2), device=torch.cuda.get_device_name(0), **room_rec,
               **(dict(moving=args.moving, traj_step=int(drawn['train'].traj_step), speed_deg_s=[10.0, 40.0],
                       train_moving_items=int((np.diff(drawn['train'].traj_start) > 0).sum()), train_trajectory_nodes=len(drawn['train'].traj_rir),
                       val_moving_items=int((np.diff(drawn['val'].traj_start) > 0).sum()),
