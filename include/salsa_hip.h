@@ -376,6 +376,46 @@ int salsa_room_rirs(const double *images, const double *d_images, int n_images, 
                     int n_sources, const double *receivers, int n_receivers, int mode, double fs_over_c, int rir_len, float *d_out,
                     void *hip_stream);
 
+/* Energy decay and room-acoustic parameters of a bank of impulse responses (salsa_amd/rooms.py: rir_acoustics, calibrate_room;
+ * DESIGN.md section 9n; the reference has no counterpart: the definition is this project's).  d_rirs float32 [n_rirs][n_channels]
+ * [rir_len], finite.  Per (response, channel), in float64 throughout:
+ *     e[n] = h[n]^2,  EDC[n] = sum_{m >= n} e[m] (Schroeder's backward integral),  E = EDC[0],  n_d = the FIRST index of the largest |h|,
+ *     i(x) = the first n with EDC[n] <= E 10^(x / 10), decided on energies with the host's five factors (x = 0, -5, -10, -25, -35 dB),
+ *     EDT, T20, T30 = -60 / slope of the least-squares line through (n / fs, 10 log10(EDC[n] / E)) over n in [i(lo), i(hi)], both
+ *         included, (lo, hi) = (0, -10), (-5, -25), (-5, -35) dB, centred sums; NaN when i(hi) does not exist, EDC[i(hi)] = 0 or the
+ *         range has fewer than two points,
+ *     headroom = -(slope per tap) (rir_len - 1 - i(hi)) dB: the decay the fitted line predicts between the range's end and the cut,
+ *     DRR = 10 log10(E_dir / E_rest): the taps within direct_halfwidth of n_d against all others (+inf when E_rest = 0),
+ *     C50 = 10 log10(E_early / E_late): the taps n < n_d + round(0.05 fs) against the others (+inf when E_late = 0).
+ * A silent response (E = 0) has energy 0, peak 0 and NaN everywhere else; its curve is 0.  d_params double [n_rirs][n_channels]
+ * [SALSA_DECAY_PARAMS], indexed by the enum below (the crossings as whole numbers, NaN where there is none); d_edc double [n_rirs]
+ * [n_channels][rir_len] receives the curve, or NULL: the parameters' bits are the same either way.  One launch on hip_stream, one
+ * workgroup per (response, channel), no atomics, every sum in a fixed order: two calls give equal bits and a response's result does
+ * not depend on the rest of the batch.  Nothing is allocated or synchronised.  1 <= n_rirs <= 65535, 1 <= n_channels <= 16, 1 <=
+ * rir_len <= 16384, 0 < fs <= 1e9, 0 <= direct_halfwidth <= 16384.  Returns -1 for a null pointer or an argument outside these
+ * limits, before any device call; -6 when the launch fails. */
+enum {
+    SALSA_DECAY_ENERGY = 0,
+    SALSA_DECAY_PEAK = 1,
+    SALSA_DECAY_EDT = 2,
+    SALSA_DECAY_T20 = 3,
+    SALSA_DECAY_T30 = 4,
+    SALSA_DECAY_HEADROOM_EDT = 5,
+    SALSA_DECAY_HEADROOM_T20 = 6,
+    SALSA_DECAY_HEADROOM_T30 = 7,
+    SALSA_DECAY_DRR_DB = 8,
+    SALSA_DECAY_C50_DB = 9,
+    SALSA_DECAY_CROSS_0DB = 10,
+    SALSA_DECAY_CROSS_5DB = 11,
+    SALSA_DECAY_CROSS_10DB = 12,
+    SALSA_DECAY_CROSS_25DB = 13,
+    SALSA_DECAY_CROSS_35DB = 14,
+    SALSA_DECAY_PARAMS = 15
+};
+int salsa_rir_decay_params(void);
+int salsa_rir_decay(const float *d_rirs, int n_rirs, int n_channels, int rir_len, double fs, int direct_halfwidth, double *d_params,
+                    double *d_edc, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

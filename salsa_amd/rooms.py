@@ -17,7 +17,13 @@ each tap is summed over the images in the order of room_images' table.
 Precision: positions, distances, delays and tau's fractional part are float64, the coefficient g A / d (times u_c) is formed in float64
 and rounded once; from the tap argument x on everything is float32.  The sums run in salsa_amd/csrc/room_rir.hip (include/salsa_hip.h:
 salsa_room_rirs); SALSA_HIP_ROOM=0, or a device that is no GPU, sends room_rir_bank to a composed torch evaluation of the same
-definition and the same split."""
+definition and the same split.
+
+Decay: rir_acoustics measures any response array (R, C, L) -- Schroeder's energy decay curve, EDT, T20, T30 with
+the headroom of each fit, DRR, C50 -- in float64, in salsa_amd/csrc/rir_decay.hip (include/salsa_hip.h: salsa_rir_decay, where the
+definition is written out); SALSA_HIP_DECAY=0, or a device that is no GPU, sends it to a composed torch evaluation of the same
+definition.  calibrate_room searches the walls' reflection coefficients for which the MEASURED decay of the generated responses is the
+one asked for."""
 import ctypes as C
 import os
 
@@ -31,6 +37,13 @@ MAX_IMAGES = 1 << 22                                        # salsa_room_max_ima
 MAX_SOURCES = 65535
 TAP_BLOCK = 256                                             # salsa_room_tap_block(): taps of one workgroup
 MIN_DISTANCE = 1e-3                                         # metres between a source and a receiver point
+HIP_DECAY = os.environ.get('SALSA_HIP_DECAY', '1') != '0'   # 0: rir_acoustics composes torch calls, for A/B runs and bisecting
+DECAY_LEVELS_DB = (0.0, -5.0, -10.0, -25.0, -35.0)          # the crossings salsa_rir_decay finds
+DECAY_FITS = {'edt': (0, 2), 't20': (1, 3), 't30': (1, 4)}  # measure -> (lo, hi) as indices into DECAY_LEVELS_DB
+DECAY_PARAMS = ('energy', 'peak', 'edt', 't20', 't30', 'headroom_edt', 'headroom_t20', 'headroom_t30', 'drr_db', 'c50_db',
+                'cross_0db', 'cross_5db', 'cross_10db', 'cross_25db', 'cross_35db')   # the enum SALSA_DECAY_* of include/salsa_hip.h
+TRUNCATION_HEADROOM_DB = 15.0                               # below it a fit counts as truncated (rir_acoustics)
+DEFAULT_PROBES = ((0, 0), (90, 20), (200, -10), (-60, 0))   # calibrate_room's probe directions
 
 
 def eyring_beta(size, rt60, c=SOUND_SPEED):
@@ -44,8 +57,11 @@ class ShoeboxRoom:
     """size (Lx, Ly, Lz) in metres; exactly one of beta -- the six amplitude reflection coefficients (x0, x1, y0, y1, z0, z1), or one
     number for all walls -- and rt60, seconds, which stands for the uniform beta of Eyring's formula (eyring_beta).  array: the array
     centre, None for the room's centre.
-    rt60 is a nominal figure: the decay an image-source shoebox realises is LONGER than Eyring's (a float64 prototype gave a T20-based
-    0.46 s on W for a nominal 0.3 s in a 6 x 5 x 3.2 m room, one run, not checked otherwise); nothing here asserts a realised RT60."""
+    rt60 is a nominal figure: the decay an image-source shoebox realises is LONGER than Eyring's, by 30 - 55 % in a 6 x 5 x 3.2 m room
+    (a T20 of 0.42 - 0.45 s on W for a nominal 0.3 s).  rir_acoustics measures what a bank realises, and calibrate_room returns the
+    room whose measured decay IS the figure asked for; such a room carries the record of the search in `.calibration`."""
+
+    calibration = None
 
     def __init__(self, size, beta=None, rt60=None, array=None, fs=FS, c=SOUND_SPEED):
         self.size = np.asarray(size, np.float64).reshape(-1)
@@ -219,10 +235,195 @@ def room_rir_bank(audio_format, room, directions, distance, length, max_order=No
     `distance` metres (one number, or one per direction) from the array centre.  max_order: the highest reflection order, None for
     every image that reaches a tap below `length`.  device: where the responses are generated, None for 'cuda'; on a GPU the
     bank's partition spectra for that device are made there too, before the download, so the renderer does not upload them again.
-    device='cpu' (the torch path) needs no GPU.  A room given by rt60 realises a LONGER decay than the nominal one (ShoeboxRoom)."""
+    device='cpu' (the torch path) needs no GPU.  A room given by rt60 realises a LONGER decay than the nominal one (ShoeboxRoom):
+    bank.acoustics() measures it, and calibrate_room gives the room that realises a wanted decay."""
     h, directions = room_rirs(audio_format, room, directions, distance, length, max_order, align_direct, normalize_direct, device)
     spec = rir_spectra(h) if h.is_cuda else None                              # on the device, from the very values the bank will hold
     bank = RirBank(h.cpu().numpy(), directions[:, 0], directions[:, 1], audio_format)
     if spec is not None:
         bank._spectra[RirBank.device_key(h.device)] = spec
     return bank
+
+
+# ---- decay measurement (DESIGN.md section 9n) ----------------------------------------------------------------------------------------
+class RirAcoustics:
+    """What rir_acoustics measured, float64 numpy arrays (R, C): energy, peak (the direct path's tap), edt, t20, t30 in seconds (NaN
+    where the response does not decay far enough to fit), headroom_edt, headroom_t20, headroom_t30 in dB, drr_db, c50_db, and
+    crossings (R, C, 5), the taps at which the curve passes DECAY_LEVELS_DB (NaN: never).  edc (R, C, L), the energy decay curve, or
+    None when it was not asked for.  A silent response has energy 0, peak 0 and NaN elsewhere."""
+
+    def __init__(self, params, edc, fs, length, direct_halfwidth):
+        params = np.asarray(params, np.float64)
+        for i, name in enumerate(DECAY_PARAMS[:10]):
+            setattr(self, name, np.ascontiguousarray(params[..., i]))
+        self.crossings = np.ascontiguousarray(params[..., 10:15])
+        self.params, self.edc, self.fs, self.length, self.direct_halfwidth = params, edc, float(fs), int(length), int(direct_halfwidth)
+
+    def headroom(self, measure):
+        if measure not in DECAY_FITS:
+            raise ValueError('measure is one of %s' % ', '.join(sorted(DECAY_FITS)))
+        return getattr(self, 'headroom_' + measure)
+
+    def truncated(self, measure):
+        """True where the fit of `measure` has less than TRUNCATION_HEADROOM_DB = 15 dB of predicted decay left between the end of its
+        range and the response's cut (the cut then bends the curve inside the range by more than 0.14 dB), and where there is no fit."""
+        return ~(self.headroom(measure) >= TRUNCATION_HEADROOM_DB)
+
+
+def _decay_factors():
+    return [10.0 ** (x / 10.0) for x in DECAY_LEVELS_DB]
+
+
+def _decay_torch(h, fs, halfwidth, want_edc):
+    """The definition composed from torch calls in float64 (SALSA_HIP_DECAY=0, and any device that is no GPU) -> params (R, C, 15), edc"""
+    import torch
+    R, Cn, L = h.shape
+    dev, f64, nan = h.device, torch.float64, float('nan')
+    e = h.to(f64) ** 2
+    edc = torch.flip(torch.cumsum(torch.flip(e, (-1,)), -1), (-1,))
+    E = edc[..., :1]
+    n = torch.arange(L, device=dev)
+    mag = h.abs()
+    n_d = torch.where(mag == mag.max(dim=-1, keepdim=True).values, n, L).min(dim=-1, keepdim=True).values     # the first of the largest
+    n_d = torch.where(E > 0, n_d, torch.zeros_like(n_d))
+    cross = torch.stack([(edc > E * f).sum(-1) for f in _decay_factors()], -1)                                    # counts (R, C, 5)
+    positive = (edc > 0).sum(-1)
+    level = 10.0 * torch.log10(torch.where(edc > 0, edc, torch.ones_like(edc)) / torch.where(E > 0, E, torch.ones_like(E)))
+    out = torch.full((R, Cn, len(DECAY_PARAMS)), nan, dtype=f64, device=dev)
+    out[..., 0], out[..., 1] = E[..., 0], n_d[..., 0].to(f64)
+    nf = n.to(f64)
+    for k, measure in enumerate(('edt', 't20', 't30')):
+        lo, hi = DECAY_FITS[measure]
+        i0, i1 = cross[..., lo:lo + 1], cross[..., hi:hi + 1]
+        valid = ((i1 < L) & (i1 < positive[..., None]) & (i1 - i0 + 1 >= 2))[..., 0]
+        inside = ((n >= i0) & (n <= i1)).to(f64)
+        count = (i1 - i0 + 1).to(f64)[..., 0].clamp(min=1.0)
+        x = nf - 0.5 * (i0 + i1).to(f64)
+        y = level - ((level * inside).sum(-1) / count)[..., None]
+        sxx = (x * x * inside).sum(-1)
+        slope = (x * y * inside).sum(-1) / torch.where(sxx > 0, sxx, torch.ones_like(sxx))                        # dB per tap
+        out[..., 2 + k] = torch.where(valid, -60.0 / (slope * fs), torch.full_like(slope, nan))
+        out[..., 5 + k] = torch.where(valid, -slope * (L - 1 - i1[..., 0]).to(f64), torch.full_like(slope, nan))
+    direct = ((n >= n_d - halfwidth) & (n <= n_d + halfwidth)).to(f64)
+    early = (n < n_d + int(np.floor(0.05 * fs + 0.5))).to(f64)
+    inf = torch.full_like(E[..., 0], float('inf'))
+    for col, part in ((8, direct), (9, early)):
+        a, b = (e * part).sum(-1), (e * (1.0 - part)).sum(-1)
+        out[..., col] = torch.where(b > 0, 10.0 * torch.log10(a / torch.where(b > 0, b, torch.ones_like(b))), inf)
+    out[..., 10:15] = torch.where(cross < L, cross.to(f64), torch.full_like(cross, nan, dtype=f64))
+    silent = ~(E[..., 0] > 0)
+    out[..., 2:][silent] = nan
+    return out, (edc if want_edc else None)
+
+
+def _decay_hip(h, fs, halfwidth, want_edc):
+    import torch
+    L = _lib.load()
+    R, Cn, Ln = h.shape
+    device = h.device
+    n_params = L.salsa_rir_decay_params()
+    if n_params != len(DECAY_PARAMS):
+        raise RuntimeError('libsalsa_hip.so reports %d decay parameters, this module knows %d' % (n_params, len(DECAY_PARAMS)))
+    out = torch.empty((R, Cn, n_params), dtype=torch.float64, device=device)
+    edc = torch.empty((R, Cn, Ln), dtype=torch.float64, device=device) if want_edc else None
+    with torch.cuda.device(device):
+        rc = L.salsa_rir_decay(C.c_void_p(h.data_ptr()), R, Cn, Ln, float(fs), int(halfwidth), C.c_void_p(out.data_ptr()),
+                               C.c_void_p(edc.data_ptr() if want_edc else None), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    if rc:
+        raise RuntimeError('salsa_rir_decay failed (%d): %s' % (rc, _lib.last_error()))
+    return out, edc
+
+
+def rir_acoustics(rirs, fs=FS, direct_halfwidth=None, edc=False, device=None):
+    """Measure responses `rirs`, a float32 array or tensor (R, C, L) with R <= 65535, C <= 16, L <= 16384 -> RirAcoustics (its docstring
+    lists the quantities; include/salsa_hip.h: salsa_rir_decay states the definition).  direct_halfwidth: the taps on either side of
+    the peak that count as the direct path for DRR, None for round(0.0025 fs) = 60 at 24 kHz, which covers the generators' windowed
+    sinc (half width 16).  edc=True also returns the energy decay curve.  device: where to measure, None for the tensor's own device,
+    or 'cuda' for an array; the kernel runs on a GPU unless SALSA_HIP_DECAY=0, a composed torch evaluation of the same definition on
+    any other device (device='cpu' needs no GPU)."""
+    import torch
+    fs = float(fs)
+    if not (fs > 0 and fs <= 1e9):
+        raise ValueError('fs is positive')
+    if direct_halfwidth is None:
+        direct_halfwidth = int(np.floor(0.0025 * fs + 0.5))
+    if int(direct_halfwidth) != direct_halfwidth or not 0 <= direct_halfwidth <= MAX_RIR_LEN:
+        raise ValueError('0 <= direct_halfwidth <= %d taps' % MAX_RIR_LEN)
+    if isinstance(rirs, torch.Tensor):
+        if rirs.dtype != torch.float32:
+            raise ValueError('rirs are float32')
+        h = rirs.detach()
+        device = h.device if device is None else torch.device(device)
+    else:
+        h = np.ascontiguousarray(rirs, np.float32)
+        h = torch.from_numpy(h if h.flags.writeable else h.copy())
+        device = torch.device('cuda' if device is None else device)
+    if h.dim() != 3 or not (1 <= h.shape[0] <= MAX_SOURCES and 1 <= h.shape[1] <= 16 and 1 <= h.shape[2] <= MAX_RIR_LEN):
+        raise ValueError('rirs must be (R, C, L) with R <= %d, C <= 16 and 1 <= L <= %d, got %s' % (MAX_SOURCES, MAX_RIR_LEN, tuple(h.shape)))
+    h = h.to(device).contiguous()
+    run = _decay_hip if HIP_DECAY and device.type == 'cuda' else _decay_torch
+    params, curve = run(h, fs, int(direct_halfwidth), bool(edc))
+    return RirAcoustics(params.cpu().numpy(), None if curve is None else curve.cpu().numpy(), fs, h.shape[2], direct_halfwidth)   # (.cpu() waits)
+
+
+def _length_for(measure, seconds, fs):
+    """taps after which a decay of `seconds` per 60 dB has passed the fit range of `measure` and TRUNCATION_HEADROOM_DB more, the
+    direct path near tap SINC_HALF; 5 % on top for the early part of the curve, which is not a straight line"""
+    depth = -DECAY_LEVELS_DB[DECAY_FITS[measure][1]] + TRUNCATION_HEADROOM_DB
+    return int(np.ceil(1.05 * depth / 60.0 * seconds * fs)) + 2 * SINC_HALF
+
+
+def calibrate_room(size, rt60, measure='t20', array=None, audio_format='foa', directions=None, distance=1.0, length=None,
+                   absorption_ratio=None, rtol=0.01, max_iter=8, max_order=None, device=None, fs=FS, c=SOUND_SPEED):
+    """-> ShoeboxRoom(size, beta=...) whose MEASURED decay is rt60 seconds: the mean of `measure` ('edt', 't20' or 't30') on channel 0
+    over probe responses generated by room_rirs on `device` (None: 'cuda'; 'cpu' needs no GPU) is within rtol of rt60.
+    The walls are beta_w = exp(-s a_w), a = absorption_ratio, six weights >= 0 in the order of beta (None: all one, a uniform beta),
+    scaled to a mean of one.  The search starts at Eyring's s = -ln eyring_beta(size, rt60); every step generates the probes
+    (directions: (azimuth, elevation) pairs, None for DEFAULT_PROBES, at `distance` metres; length taps, None for min(MAX_RIR_LEN,
+    ceil(rt60 fs))), measures them with rir_acoustics and, since a decay time is close to proportional to 1 / s, sets s <- s T / rt60.
+    Three or four evaluations are typical.  ValueError when max_iter evaluations do not reach rtol, when the accepted step has a
+    probe without a fit or with a truncated one (RirAcoustics.truncated; the message names a length that would do -- a truncated fit
+    at an earlier step only slows the search), and when a beta would leave [0, 1) on every absorbing wall: a lossless room has no
+    decay time.  The room's .rt60 stays None (that attribute is the nominal figure of Eyring's formula); .calibration is a dict:
+    measure, target, realised (the mean), probes (the per-probe values), headroom_db (per probe), beta_history (one array of six per
+    evaluation), evaluations, directions, distance, length."""
+    if measure not in DECAY_FITS:
+        raise ValueError('measure is one of %s' % ', '.join(sorted(DECAY_FITS)))
+    target, fs = float(rt60), float(fs)
+    if not (target > 0 and np.isfinite(target)):
+        raise ValueError('rt60 is positive seconds')
+    if not (rtol > 0 and max_iter >= 1):
+        raise ValueError('rtol is positive and max_iter at least 1')
+    a = np.ones(6) if absorption_ratio is None else np.asarray(absorption_ratio, np.float64).reshape(-1)
+    if a.shape != (6,) or not np.all(np.isfinite(a)) or not np.all(a >= 0) or not a.sum() > 0:
+        raise ValueError('absorption_ratio is six weights >= 0, not all zero')
+    a = a / a.mean()
+    directions = DEFAULT_PROBES if directions is None else directions
+    length = min(MAX_RIR_LEN, int(np.ceil(target * fs))) if length is None else int(length)
+    s = -np.log(eyring_beta(size, target, c))
+    history = []
+    for evaluation in range(1, int(max_iter) + 1):
+        beta = np.exp(-s * a)
+        if not np.isfinite(s) or not s > 0 or not np.all((beta >= 0) & (beta[a > 0] < 1)):
+            raise ValueError('a reflection coefficient would leave [0, 1) (s = %g): no absorbing room decays in %g s' % (s, target))
+        history.append(beta)
+        room = ShoeboxRoom(size, beta=beta, array=array, fs=fs, c=c)
+        h, _ = room_rirs(audio_format, room, directions, distance, length, max_order, device=device)
+        got = rir_acoustics(h, fs=fs)
+        T, bad = getattr(got, measure)[:, 0], got.truncated(measure)[:, 0]
+        mean = float(T.mean())
+        if not np.isfinite(mean):
+            raise ValueError('%d of %d probe responses of %d taps do not decay far enough for %s (evaluation %d); about %d taps would do%s'
+                             % (int(np.isnan(T).sum()), len(T), length, measure, evaluation, _length_for(measure, target, fs),
+                                '' if _length_for(measure, target, fs) <= MAX_RIR_LEN else ', more than the %d supported' % MAX_RIR_LEN))
+        if abs(mean / target - 1.0) <= rtol:
+            if bad.any():
+                raise ValueError('%s reached %g s, but %d of %d probe fits have less than %g dB of headroom in %d taps: the cut biases '
+                                 'them; about %d taps would do' % (measure, mean, int(bad.sum()), len(T), TRUNCATION_HEADROOM_DB, length,
+                                                                  _length_for(measure, target, fs)))
+            room.calibration = dict(measure=measure, target=target, realised=mean, probes=T.copy(), headroom_db=got.headroom(measure)[:, 0].copy(),
+                                    beta_history=history, evaluations=evaluation, directions=[tuple(d) for d in np.asarray(directions).tolist()],
+                                    distance=distance, length=length)
+            return room
+        s *= mean / target
+    raise ValueError('%s is %g s after %d evaluations, not within %g of %g s' % (measure, mean, int(max_iter), rtol, target))

@@ -82,6 +82,11 @@ class RirBank:
             self._spectra[key] = rir_spectra(self.rirs_on(device))            # once per bank and device
         return self._spectra[key]
 
+    def acoustics(self, device=None, **kw):
+        """rooms.rir_acoustics of the bank's responses: decay times, DRR, C50 per (response, channel)"""
+        from . import rooms
+        return rooms.rir_acoustics(self.rirs, device=device, **kw)
+
 
 def rir_spectra(d_rirs):
     """The partition spectra (salsa_scene_rir_spectra) of contiguous float32 CUDA responses (R, C, L), on their device.  A bank whose
@@ -522,11 +527,12 @@ def add_scenes(feature_bank, scenes, pool, bank, names=None, ambient=None, n_cla
     return audio
 
 
-_ROOMS = ('ShoeboxRoom', 'RoomImages', 'room_images', 'room_rirs', 'room_rir_bank', 'eyring_beta')
+_ROOMS = ('ShoeboxRoom', 'RoomImages', 'room_images', 'room_rirs', 'room_rir_bank', 'eyring_beta', 'RirAcoustics', 'rir_acoustics',
+          'calibrate_room')
 
 
 def __getattr__(name):
-    """rooms.py (image-source responses of a shoebox room as a RirBank) builds on this module, so its public names
+    """rooms.py (DESIGN.md sections 9m, 9n: image-source responses of a shoebox room as a RirBank, their decay) builds on this module, so its public names
     are re-exported on first use, not at import"""
     if name in _ROOMS:
         from . import rooms
