@@ -1,9 +1,10 @@
 """A float64 restatement of the shoebox image-source definition, for the tests of salsa_amd/rooms.py and
 salsa_amd/csrc/room_rir.hip.  It shares no code with either: the images are enumerated by six nested loops, and a response is
-summed image by image, every image over exactly the taps of its support.
+summed image by image, every image over exactly the taps of its support.  response_of_table is the same sum on the public (7, n)
+table of salsa_room_rirs, for tables that no room gives.
 
     image (n, q): p = (1 - 2 q) o s + 2 n o L,  A = prod_axis b_axis,0^|n - q| b_axis,1^|n| (b^0 = 1),  order = sum_axis |n - q| + |n|
-    tap k of receiver rho: d = |p - rho|, tau = d fs / c - t0, h[k] += g (A / d) gain_c w(k - tau),
+    tap k of receiver rho: d = |p - rho|, tau = d (fs / c) - t0, h[k] += g (A / d) gain_c w(k - tau),
     w(x) = sinc(x) (1 + cos(pi x / H)) / 2 for |x| < H = 16, else 0;  foa: gains (1, u_y, u_z, u_x), u = (p - rho) / d
 
 The float32 YARDSTICK is the same loop with float64 geometry (p, d, tau, the coefficient g A / d gain_c, and k - tau, each rounded to
@@ -69,19 +70,17 @@ def d_max_of(length, t0, fs=FS, c=SOUND_SPEED):
     return (length + H + t0) * c / fs * (1.0 + 1e-9)
 
 
-def response(image_list, size, src, recs, foa, length, f32=False, reverse=False, fs=FS, c=SOUND_SPEED):
-    """-> (h (C, length), reached bool (C, length): the taps inside some image's support).  src = (position, t0, g).  f32: the yardstick."""
-    s, t0, g = src
-    L = np.asarray(size, np.float64)
+def _sum_images(points, src, recs, foa, length, fs_over_c, f32):
+    """the one per-image tap code: points yields (p (3,), A) in the order of the sum -> (h (C, length), reached bool (C, length))"""
+    _, t0, g = src
     C = 4 if foa else len(recs)
     h = np.zeros((C, length), np.float32 if f32 else np.float64)
     reached = np.zeros((C, length), bool)
-    for n, q, amp, _ in (reversed(image_list) if reverse else image_list):
-        p = (1.0 - 2.0 * np.asarray(q, np.float64)) * s + 2.0 * np.asarray(n, np.float64) * L
+    for p, amp in points:
         for m, rho in enumerate(recs):
             v = p - rho
             d = math.sqrt(float(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]))
-            tau = d * fs / c - t0
+            tau = d * fs_over_c - t0
             k_lo, k_hi = max(0, math.floor(tau - H) + 1), min(length - 1, math.ceil(tau + H) - 1)     # tau - H < k < tau + H
             if k_lo > k_hi:
                 continue
@@ -103,6 +102,35 @@ def response(image_list, size, src, recs, foa, length, f32=False, reverse=False,
                 h[row, k_lo:k_hi + 1] += (np.float32(gc) * w) if f32 else gc * w
                 reached[row, k_lo:k_hi + 1] = True
     return h, reached
+
+
+def response(image_list, size, src, recs, foa, length, f32=False, reverse=False, fs=FS, c=SOUND_SPEED):
+    """-> (h (C, length), reached bool (C, length): the taps inside some image's support).  src = (position, t0, g).  f32: the yardstick.
+    The delay is d (fs / c) - t0, fs / c one float64 number: what the table-level interface takes."""
+    s, L = src[0], np.asarray(size, np.float64)
+    points = (((1.0 - 2.0 * np.asarray(q, np.float64)) * s + 2.0 * np.asarray(n, np.float64) * L, amp)
+              for n, q, amp, _ in (reversed(image_list) if reverse else image_list))
+    return _sum_images(points, src, recs, foa, length, fs / c, f32)
+
+
+def response_of_table(table, src, recs, foa, length, fs_over_c, f32=False, reverse=False):
+    """`response` on the public (7, n) table of salsa_room_rirs (rows: sign x, y, z, shift x, y, z, amplitude): image i lies at
+    sign_i o s + shift_i.  The table need not come from a room: the tests of the compaction build theirs by hand."""
+    table = np.asarray(table, np.float64)
+    assert table.ndim == 2 and table.shape[0] == 7
+    s = np.asarray(src[0], np.float64)
+    order = range(table.shape[1] - 1, -1, -1) if reverse else range(table.shape[1])
+    points = ((table[0:3, i] * s + table[3:6, i], float(table[6, i])) for i in order)
+    return _sum_images(points, src, recs, foa, length, fs_over_c, f32)
+
+
+def table_reference(table, src, recs, foa, length, fs_over_c):
+    """-> (ref64, [yardstick in table order, reversed], reached) of a table, each (C, length), read-only: shared, never written"""
+    ref, reached = response_of_table(table, src, recs, foa, length, fs_over_c)
+    yards = [response_of_table(table, src, recs, foa, length, fs_over_c, f32=True, reverse=rev)[0] for rev in (False, True)]
+    for a in [ref, reached] + yards:
+        a.setflags(write=False)
+    return ref, yards, reached
 
 
 def reference_and_yardstick(image_list, size, src, recs, foa, length):

@@ -1,10 +1,13 @@
 """GPU tests of the decay measurement (salsa_amd/csrc/rir_decay.hip through its C entry point salsa_rir_decay, salsa_amd/rooms.py:
 rir_acoustics, calibrate_room) against the float64 reference of tests/decay_reference.py.
 
-Shapes: response lengths 1, 2, both sides of the kernel's 256 threads, 7200 (a run of 29 taps per thread), and both sides of the
-longest (runs of 64, the 65-dword LDS rows), each as a bank of 3 x 4 responses of twelve families (decay_reference.FAMILIES: geometric
+Shapes: response lengths 1, 2, both sides of the kernel's 256 threads, 7200 (a run of 29 taps per thread), the switch between the
+kernel's two instantiations -- 8192 (a run of 32, LDS row stride 33: the last even run of the 33-dword rows), 8193 and 8448 (a run of
+33: stride = run, rows that abut without a pad, at 8448 the last row ending at the array's end), 8449 (a run of 34: the first of the
+65-dword rows) -- and both sides of the longest (runs of 64), each as a bank of 3 x 4 responses of twelve families (decay_reference.FAMILIES: geometric
 and two-slope decays, silence, an impulse at either end, a decay cut to exact zeros inside the fit ranges, make_rir_bank noise tails,
-image-source responses of the CPU path, a largest |h| that occurs twice); one channel and sixteen channels at one length each.
+image-source responses of the CPU path, a largest |h| that occurs twice); one channel and sixteen channels at one length each; one
+bank of 2^31 + 262144 input floats.
 Every output lies inside NaN guard bands, the input 4-byte aligned only.
 
 Held (decay_reference.holds): the peak, the five crossings and the NaN / inf pattern exactly; the energy and the curve within L 2^-53
@@ -24,7 +27,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
 GUARD = 67                                                                     # elements on either side of every buffer: odd
-LENGTHS = [1, 2, 255, 256, 257, 7200, 16383, 16384]
+LENGTHS = [1, 2, 255, 256, 257, 7200, 8192, 8193, 8448, 8449, 16383, 16384]
 SIZE = (6.0, 5.0, 3.2)
 MEASURED = """largest ratio (error) / Y per quantity over every kept case of every shape above, on one MI355X (the bound is 4 Y + 1e-12 |ref|)
   quantity       kernel    torch leg on the device (L = 7200 only)
@@ -39,6 +42,12 @@ MEASURED = """largest ratio (error) / Y per quantity over every kept case of eve
   (* and one case with Y = 0: image_source_y at L = 256, DRR 6.8999 dB, both yardsticks on the reference's very value, the kernel
   8.9e-16 = one ulp away; the floor of 6.9e-12 admits it.  The errors themselves: times and headrooms at most 10 ulp of the value
   (the largest error of a time is 1.4e-16 s), DRR and C50 at most 3.8e-15 dB, which is 272 ulp for a DRR of 0.079 dB.)
+  the kernel at the switch between its instantiations (runs of 32, 33, 33, 34 taps; LDS row strides 33, 33, 33, 35), none above the table:
+  L       edt    t20    t30    headroom_edt   headroom_t20   headroom_t30   drr_db   c50_db
+  8192    0.50   0.60   0.11   1.00           0.50           0.12           0.26     1.00
+  8193    1.00   0.60   0.25   1.00           2.00           0.17           0.20     0.00
+  8448    1.00   1.00   0.17   1.00           1.00           0.22           0.15     0.11
+  8449    0.43   1.50   0.12   0.50           1.00           0.22           0.15     1.00
   No case was dropped for its knife-edge margin.  energy and curve: within L 2^-53 everywhere.
   calibrate_room((6, 5, 3.2), 0.3) on the device: beta 0.8206 -> 0.7488 -> 0.7653 -> 0.7619, 4 evaluations, mean T20 0.298921 s by
   the kernel; the reference gives 0.298921 s on the device generator's responses and on the CPU generator's alike: the two generators'
@@ -113,7 +122,7 @@ def test_direct_halfwidth_and_fs_reach_the_kernel():
 
 
 # ---- exact properties ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('L', [257, 7200, 16384])
+@pytest.mark.parametrize('L', [257, 7200, 8448, 8449, 16384])
 def test_exact_properties(L):
     h = dr.case(L)[1]
     params, edc = _run(h)
@@ -125,6 +134,41 @@ def test_exact_properties(L):
         'a response alone gives the bits it has in a batch'
     without, none = _run(h, want_edc=False)
     assert none is None and np.array_equal(without.view(np.uint64), params.view(np.uint64)), 'the parameters do not depend on the curve\'s store'
+
+
+def test_offsets_past_two_to_the_31():
+    """8193 responses x 16 channels x 16384 taps = 2^31 + 262144 input floats (8.6 GB), no curve: the last response's offset rc x L does
+    not fit 32 bits.  All are silent but the last, which carries the families: its parameters are those of the same response measured
+    alone, bit for bit; every silent response gives energy 0, peak 0 and NaN elsewhere."""
+    R, Cn, L = 8193, 16, 16384
+    n = R * Cn * L
+    assert n == (1 << 31) + 262144
+    free = torch.cuda.mem_get_info()[0]
+    assert free > 10 * 2 ** 30, 'this test wants 10 GB of device memory'
+    lib = _lib.load()
+    P = lib.salsa_rir_decay_params()
+    _, h = dr.bank(L, 1, Cn)
+    src = torch.full((n + 2 * GUARD,), float('nan'), dtype=torch.float32, device=DEV)
+    src[GUARD:GUARD + n].zero_()
+    src[GUARD + n - Cn * L:GUARD + n] = torch.from_numpy(h.reshape(-1)).to(DEV)
+    n_p = R * Cn * P
+    out = torch.full((n_p + 2 * GUARD,), float('nan'), dtype=torch.float64, device=DEV)
+    out[GUARD:GUARD + n_p] = -7.0
+    rc = lib.salsa_rir_decay(C.c_void_p(src[GUARD:].data_ptr()), R, Cn, L, dr.FS, dr.halfwidth(), C.c_void_p(out[GUARD:].data_ptr()), None,
+                             C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream))
+    assert rc == 0, _lib.last_error()
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out[:GUARD]).all()) and bool(torch.isnan(out[GUARD + n_p:]).all()), 'a guard band was written'
+    params = out[GUARD:GUARD + n_p].view(R, Cn, P).cpu().numpy()
+    del src, out
+    torch.cuda.empty_cache()
+    assert not np.any(params == -7.0), 'a parameter was not written'
+    silent, zero = params[:-1], [dr.IDX['energy'], dr.IDX['peak']]
+    assert not silent[..., zero].view(np.uint64).any(), 'a silent response has energy +0.0 and peak +0.0'
+    assert np.isnan(np.delete(silent, zero, axis=-1)).all(), 'a silent response has NaN elsewhere'
+    alone, _ = _run(h, want_edc=False)
+    assert np.array_equal(params[-1].view(np.uint64), alone[0].view(np.uint64)), 'the last response, past 2^31, is not what it is alone'
+    assert np.isfinite(params[-1][:, dr.IDX['t20']]).sum() >= 8 and params[-1][:, dr.IDX['energy']].max() > 1.0
 
 
 # ---- the public path -----------------------------------------------------------------------------------------------------------------

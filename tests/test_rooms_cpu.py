@@ -1,6 +1,7 @@
 """CPU tests of the shoebox image-source responses (salsa_amd/rooms.py): the definition's analytic cases on the
 float64 restatement of tests/room_reference.py, the host-side image table, the public path on the CPU (the composed torch evaluation)
-against that restatement, the Eyring conversion as a formula, the refusals -- the launcher's before any device call -- and the ABI."""
+against that restatement, the Eyring conversion as a formula, the refusals -- the launcher's before any device call --, the table-level
+reference against the room-level one, the hand-built tables of tests/room_tables.py (what they claim; the launcher takes them) and the ABI."""
 import ctypes as C
 import math
 import os
@@ -282,6 +283,81 @@ def test_the_launcher_refuses_before_any_device_call():
         assert _launch(**over) == _lib.E_INVAL, over
         assert 'salsa_room_rirs' in _lib.last_error()
     assert _launch(n_receivers=2, receivers=np.ones((2, 3)), mode=1) == _lib.E_INVAL and 'FOA' in _lib.last_error()
+
+
+# ---- the table-level reference and the built tables of tests/room_tables.py ----------------------------------------------------
+@pytest.mark.parametrize('fmt', ['foa', 'mic'])
+def test_response_of_table_gives_the_bits_of_response_on_a_rooms_table(fmt):
+    from salsa_amd import rooms
+    length = 300
+    room = rooms.ShoeboxRoom(SIZE, beta=BETA, array=ARRAY)
+    _, sources, receivers, d_max = rooms.room_geometry(fmt, room, DIRECTIONS[:1], 0.7, length)
+    tab = rooms.room_images(room, d_max)
+    image_list = list(zip(map(tuple, tab.n.tolist()), map(tuple, tab.q.tolist()), tab.amplitude.tolist(), tab.order.tolist()))
+    assert len(image_list) > 100
+    src = rr.source(ARRAY, DIRECTIONS[0], 0.7)
+    assert np.array_equal(src[0], sources[0, :3]) and src[1] == sources[0, 3] and src[2] == sources[0, 4]
+    recs = rr.receivers(fmt, ARRAY)
+    for kw in (dict(), dict(f32=True), dict(f32=True, reverse=True), dict(reverse=True)):
+        h, reached = rr.response(image_list, SIZE, src, recs, fmt == 'foa', length, **kw)
+        ht, reached_t = rr.response_of_table(tab.table(), src, recs, fmt == 'foa', length, rr.FS / rr.SOUND_SPEED, **kw)
+        assert h.dtype == ht.dtype == (np.float32 if kw.get('f32') else np.float64) and np.abs(h).max() > 0.5
+        assert np.array_equal(h.view(np.uint8), ht.view(np.uint8)) and np.array_equal(reached, reached_t), kw
+    fwd = rr.response_of_table(tab.table(), src, recs, fmt == 'foa', length, rr.FS / rr.SOUND_SPEED, f32=True)[0]
+    rev = rr.response_of_table(tab.table(), src, recs, fmt == 'foa', length, rr.FS / rr.SOUND_SPEED, f32=True, reverse=True)[0]
+    assert not np.array_equal(fwd, rev), 'the order of the float32 sum shows'
+
+
+def _accepted(table, src_row, mode=1, fs_over_c=None, rir_len=None):
+    """the launcher's host checks pass the table and the source: its LAST check, the receivers', is the one that refuses (no device call)"""
+    import room_tables as rt
+    rc = _launch(images=table, n_images=table.shape[1], sources=src_row, mode=mode, fs_over_c=fs_over_c or rt.FS_OVER_C,
+                 rir_len=rir_len or rt.LENGTH, receivers=np.array([[float('nan'), 1.0, 1.0]]))
+    return rc == _lib.E_INVAL and 'a receiver position is not finite' in _lib.last_error()
+
+
+def _tau(table, t0=0.0):
+    """the delays of a built table at the point it was built around"""
+    import room_tables as rt
+    p = table[0:3] * rt.SOURCE[:, None] + table[3:6]
+    return np.sqrt(((p - rt.RECEIVER[:, None]) ** 2).sum(axis=0)) * rt.FS_OVER_C - t0
+
+
+def test_the_built_tables_are_what_they_claim_and_the_launcher_takes_them():
+    import room_tables as rt
+    H, src = rr.H, rt.source()
+    for name, mask in rt.MASKS.items():
+        table = rt.built_table(mask)
+        assert table.shape == (7, len(mask)) and table.dtype == np.float64 and _accepted(table, rt.source_row(src)), name
+        tf = np.floor(_tau(table))
+        kept = (tf >= -H) & (tf <= 256 + H - 2)                                 # what block 0 of the kernel keeps, by its header
+        assert np.array_equal(kept, mask) and np.all(tf[mask] >= 20) and np.all(tf[~mask] > 1e7), name
+        assert np.all((table[6] > 0.05) & (table[6] <= 1.0))
+        full = rt.built_table(np.ones(len(mask), bool))
+        assert np.array_equal(table[:, mask], full[:, mask]), 'an image does not depend on the mask'
+    waves = rt.MASKS['waves_0_2'].reshape(4, 4, 64).sum(axis=2)
+    assert np.array_equal(waves, [[64, 0, 64, 0]] * 4) and rt.MASKS['chunk1_miss'].reshape(4, 256).sum(axis=1).tolist() == [256, 0, 256, 256]
+    assert np.nonzero(rt.MASKS['last_only'])[0].tolist() == [1023] and not rt.MASKS['none'].any()
+    assert (np.floor(_tau(rt.built_table(rt.MASKS['all_1024']))) >= 256 - H).sum() > 50, 'block 1 keeps images too'
+    # negative delays: t0 > 0, every floor(tau) in [-16, 3]
+    neg, nsrc = rt.negative_delay_table(), rt.source(t0=40.0)
+    assert _accepted(neg, rt.source_row(nsrc))
+    tau = _tau(neg, 40.0)
+    assert neg.shape[1] > 256 and tau.min() > -16.0 and tau.max() < 4.0 and (tau < 0).sum() > 200
+    # the exact tables, and the two closed forms of the order check by a sequential float32 sum
+    big = rt.big_first_table()
+    assert big.shape == (7, 4097) and _accepted(big, rt.source_row(rt.exact_source(rt.BIG_TAP)), fs_over_c=1.0)
+    assert rt.sequential_float32(big, float(rt.BIG_TAP), rt.LENGTH)[0, rt.BIG_TAP] == np.float32(1.0)
+    assert rt.sequential_float32(big[:, ::-1], float(rt.BIG_TAP), rt.LENGTH)[0, rt.BIG_TAP] == np.float32(1.0 + 2.0 ** -13)
+    table, d = rt.random_exact_table()
+    assert table.shape == (7, 1000) and _accepted(table, rt.source_row(rt.exact_source(29.0)), fs_over_c=1.0)
+    assert sorted(set(d.tolist())) == [29, 33, 45, 261, 290] and np.bincount(d)[[29, 33, 45, 261, 290]].min() > 100
+    seq, rev = rt.sequential_float32(table, 29.0, rt.LENGTH), rt.sequential_float32(table[:, ::-1], 29.0, rt.LENGTH)
+    assert (seq != 0).any(axis=1).all() and (seq < 0).any() and not np.array_equal(seq, rev), 'every channel is used, and the order shows'
+    # a control: the same call with a table that is out of order is refused by the table's check, not the receivers'
+    bad = table.copy()
+    bad[6, 999] = 0.0
+    assert not _accepted(bad, rt.source_row(rt.exact_source(29.0)), fs_over_c=1.0) and 'amplitude' in _lib.last_error()
 
 
 # ---- ABI -----------------------------------------------------------------------------------------------------------------------
