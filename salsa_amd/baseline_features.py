@@ -17,7 +17,6 @@ reference's mel types accept other sizes; this port refuses them).  There is no 
 """
 import ctypes as C
 import os
-import shutil
 import sys
 from timeit import default_timer as timer
 
@@ -26,19 +25,13 @@ import yaml
 
 from . import _lib
 from . import io as sio
+from .features import _cli, _extract_serial, _rmtree_parallel, _torch
 
 import logging  # noqa: E402
 _log = logging.getLogger('salsa_amd.baseline_features')
 
 FEATURE_TYPES = tuple(_lib.BASELINE_FEATURE)
 PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))       # GCC channels 4..9: gcc_phat(sig=audio[m], refsig=audio[n])
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError('salsa_amd needs an MI355X (torch.cuda.is_available() is False); there is no CPU fallback')
-    return torch
 
 
 def _raise(rc):
@@ -305,7 +298,6 @@ def extract_features(data_config: str = 'configs/tnsse2021_feature_config.yml', 
     """:597-693: features of every clip of <format>_dev and <format>_eval into
     <feature_dir>/<feature_type>/<fs>fs_<n_fft>nfft_<hop>nhop_<n>nfreqs|nmels/<split>/ (cleared first; sorted file order;
     a (C, T, F) float32 'feature' per clip), then the scaler.  ``batch_size`` (clips per device call) is the only extra argument."""
-    from .features import feature_name
     with open(data_config, 'r') as stream:
         cfg = yaml.safe_load(stream)
     d = cfg['data']
@@ -318,42 +310,21 @@ def extract_features(data_config: str = 'configs/tnsse2021_feature_config.yml', 
         raise NotImplementedError('Feature type {} is not implemented!'.format(feature_type))
     if audio_format not in ('foa', 'mic'):
         raise ValueError('Unknown audio format {}'.format(audio_format))
-    splits = [audio_format + '_dev', audio_format + '_eval']
     if task in ['feature_scaler', 'feature']:
-        torch = _torch()
         ex = BaselineExtractor(feature_type=feature_type, fs=fs, n_fft=n_fft, hop_len=hop_length, win_len=win_length,
                                n_mels=n_mels, fmin=fmin, fmax=float(fmax), is_compressed_freq=is_compressed_freq)
-        for split in splits:
+        for split in (audio_format + '_dev', audio_format + '_eval'):
             start_time = timer()
             audio_dir = os.path.join(cfg['data_dir'], split)
             feature_dir = os.path.join(cfg['feature_dir'], feature_type, desc, split)
-            shutil.rmtree(feature_dir, ignore_errors=True)
+            _rmtree_parallel(feature_dir)
             os.makedirs(feature_dir, exist_ok=True)
-            pending = {}                                      # n_samples -> [(file name, audio)]
-
-            def flush(items):
-                batch = torch.from_numpy(np.stack([a for _, a in items])).to(ex.device)
-                feats = ex.extract(batch).cpu().numpy()
-                for (fn, _), f in zip(items, feats):
-                    sio.save_arrays(os.path.join(feature_dir, feature_name(fn)), feature=f)
-
-            for audio_fn in sorted(os.listdir(audio_dir)):
-                audio = sio.load_audio(os.path.join(audio_dir, audio_fn), sr=fs)
-                assert audio.shape[0] == 4, '{}: expected a 4-channel clip'.format(audio_fn)
-                lst = pending.setdefault(audio.shape[1], [])
-                lst.append((audio_fn, audio))
-                if len(lst) == batch_size:
-                    flush(lst)
-                    lst.clear()
-            for lst in pending.values():
-                if lst:
-                    flush(lst)
+            _extract_serial(ex, list(enumerate(sorted(os.listdir(audio_dir)))), audio_dir, feature_dir, fs, batch_size)
             _log.info('split %s: %.3f s', split, timer() - start_time)
     if task in ['feature_scaler', 'scaler']:
         compute_scaler(feature_dir=os.path.join(cfg['feature_dir'], feature_type, desc), audio_format=audio_format)
 
 
 if __name__ == '__main__':
-    from .features import _cli
     logging.basicConfig(level=logging.INFO, format='%(message)s')
     _cli(extract_features, sys.argv[1:])

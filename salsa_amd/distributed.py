@@ -68,53 +68,40 @@ def extract_features_sharded(data_config: str, cond_num: float = 5, n_hopframes:
     import torch.distributed as dist
     from . import io as sio
     from .extractor import SalsaExtractor
-    from .features import _extract_split, _parse
+    from .features import _extract_splits, _parse, tree_layout
 
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
     cfg, audio_format, fs, n_fft, hop_length, win_length, fmin_doa, fmax_doa = _parse(data_config)
     fmax_doa = int(np.min((fmax_doa, fs // 2)))
     if feature_type == 'salsa':
-        desc = '{}fs_{}nfft_{}nhop_{}cond_{}fmaxdoa'.format(fs, n_fft, hop_length, int(cond_num), int(fmax_doa))
-        desc += '' if is_tracking else '_notracking'
-        desc += '' if is_compress_high_freq else '_nocompress'
         if audio_format not in ('foa', 'mic'):
             raise ValueError('Unknown audio format {}'.format(audio_format))
     else:
         assert feature_type in ['salsa_lite', 'salsa_ipd'], 'Invalid feature type {}'.format(feature_type)
         assert audio_format == 'mic', 'SALSA-Lite and SALSA-IPD are only for MIC format!'
-        desc = '{}fs_{}nfft_{}nhop_{}fmaxdoa'.format(fs, n_fft, hop_length, int(fmax_doa))
+    desc, splits = tree_layout(feature_type, audio_format, fs, n_fft, hop_length, cond_num, fmax_doa, is_tracking, is_compress_high_freq)
     root = os.path.join(cfg['feature_dir'], feature_type, audio_format, desc)
     if task in ['feature_scaler', 'feature']:
         ex = SalsaExtractor(fs=fs, n_fft=n_fft, hop_len=hop_length, win_len=win_length, fmin_doa=fmin_doa,
                             fmax_doa=fmax_doa, cond_num=cond_num, n_hopframes=n_hopframes, is_tracking=is_tracking,
                             is_compress_high_freq=is_compress_high_freq, audio_format=audio_format,
                             feature_type=feature_type)
-        from . import features as _f
-        fused = {} if (task == 'feature_scaler' and _f.FUSED_SCALER) else None   # this rank's scaler statistics, taken on its device
-        for split in (audio_format + '_dev', audio_format + '_eval'):
-            feature_dir = os.path.join(root, split)
-            if rank == 0:
-                _f._rmtree_parallel(feature_dir)
-                os.makedirs(feature_dir, exist_ok=True)
-            if world > 1:
-                dist.barrier()
-            _extract_split(ex, os.path.join(cfg['data_dir'], split), feature_dir, fs, batch_size,
-                           shard=(rank, world), clear=False, scaler=fused if split.endswith('_dev') else None)
+        fused = _extract_splits(ex, cfg, root, splits, task, batch_size, shard=(rank, world))   # this rank's scaler statistics, taken on its device
         if world > 1:
             dist.barrier()
         if fused is not None:
             # every rank must take the same branch: a rank with an empty shard (or on the serial loop) has no sums of its own
-            ok = torch.tensor([0 if fused.get('unavailable') else 1], dtype=torch.int32)
+            ok = torch.tensor([1 if fused.available else 0], dtype=torch.int32)
             if world > 1:
                 okd = ok.to(ex.device) if dist.get_backend() == 'nccl' else ok
                 dist.all_reduce(okd, op=dist.ReduceOp.MIN)
                 ok = okd.cpu()
             if int(ok.item()) == 1:
                 F = ex.output_shape(ex.params.n_fft)[2]
-                h = fused['sums'].detach().cpu().numpy() if fused.get('sums') is not None else np.zeros((2, 4, F))
+                h = fused.sums.detach().cpu().numpy() if fused.sums is not None else np.zeros((2, 4, F))
                 device = ex.device if (dist.is_initialized() and dist.get_backend() == 'nccl') else None
-                mean, std = scaler_allreduce(fused.get('n', 0), h[0], h[1], F, device=device)
+                mean, std = scaler_allreduce(fused.n_frames, h[0], h[1], F, device=device)
                 if rank == 0:
                     sio.save_arrays(os.path.join(root, audio_format + '_feature_scaler.h5'), mean=mean, std=std)
                 if world > 1:

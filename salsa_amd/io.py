@@ -22,6 +22,12 @@ from . import _hdf5   # noqa: E402  (round 6: the HDF5 C library itself through 
 HAVE_HDF5 = HAVE_H5PY or _hdf5.available()    # real .h5 files are written / read; False: the numpy twins
 
 
+def feature_name(audio_fn: str) -> str:
+    """The reference names the feature file ``audio_fn.replace('wav', 'h5')`` (:379, every occurrence)."""
+    out = audio_fn.replace('wav', 'h5')
+    return out if out != audio_fn else os.path.splitext(audio_fn)[0] + '.h5'
+
+
 def load_audio(path: str, sr: int, device=None) -> np.ndarray:
     """-> (n_channels, n_samples) float32 in [-1, 1), like librosa.load(path, sr=sr, mono=False, dtype=float32)
     (salsa_feature_extraction.py:353).  A WAV file whose native rate is not ``sr`` is RESAMPLED as librosa does ('kaiser_best',

@@ -499,14 +499,14 @@ def test_file_pipeline_raises_instead_of_hanging(dev, tmp_path):
     ex = SalsaExtractor(device=dev)
     pipe = features._FilePipeline(ex)
     calls = [0]
-    real = pipe.slots[0]['ex'].extract
+    real = pipe.slots[0].ex.extract
     def bad_extract(*a, **k):
         calls[0] += 1
         if calls[0] == 3:
             raise Boom('device issue failed')
         return real(*a, **k)
     for sl in pipe.slots:
-        sl['ex'].extract = bad_extract
+        sl.ex.extract = bad_extract
     with pytest.raises(Boom):
         pipe.run(todo, str(adir), str(fdir), 24000, 2)
     # (ii) the writer fails
@@ -527,6 +527,76 @@ def test_file_pipeline_raises_instead_of_hanging(dev, tmp_path):
         pipe.run(todo + [(99, 'missing.npy')], str(adir), str(fdir), 24000, 2)
     pipe.run(todo, str(adir), str(fdir), 24000, 2)
     assert len(os.listdir(fdir)) == 12
+
+
+def _npy_tree(d, seed0, lengths, peak=None):
+    """clip00.npy ... in directory d (created): synth_clip(seed0 + i, lengths[i]), scaled to ``peak`` if given -> the pipeline's todo list"""
+    os.makedirs(d)
+    for i, n in enumerate(lengths):
+        y = synth_clip(seed0 + i, n)
+        np.save(os.path.join(d, 'clip%02d.npy' % i), y if peak is None else (y * (peak / np.abs(y).max())).astype(np.float32))
+    return list(enumerate(sorted(os.listdir(d))))
+
+
+def test_file_pipeline_failed_run_leaves_no_scaler_statistics(dev, tmp_path):
+    """A run with scaler= that fails midway must leave nothing behind in the (process-wide cached) pipeline: the statistics of the next
+    run over another tree are that tree's alone.  Tree A is 40 dB above tree B, so one stale batch moves the mean by many dB; the bound is
+    the one the fused scaler is held to against compute_scaler in test_extract_features_harness_reproduces_reference_tree."""
+    from salsa_amd import features, io as sio
+    from salsa_amd.extractor import SalsaExtractor
+    a_todo = _npy_tree(str(tmp_path / 'a_audio'), 400, [24000] * 6, peak=0.5)
+    b_todo = _npy_tree(str(tmp_path / 'b_audio'), 410, [24000] * 6, peak=0.005)
+    b_root = tmp_path / 'b'
+    os.makedirs(tmp_path / 'a_feat'), os.makedirs(b_root / 'foa_dev')
+
+    class Boom(RuntimeError):
+        pass
+
+    pipe = features._FilePipeline(SalsaExtractor(device=dev))
+    calls = [0]
+    real = [sl.ex.extract for sl in pipe.slots]
+    for sl, fn in zip(pipe.slots, real):
+        def bad_extract(*a, _fn=fn, **k):
+            calls[0] += 1
+            if calls[0] == 2:
+                raise Boom('second batch failed')
+            return _fn(*a, **k)
+        sl.ex.extract = bad_extract
+    with pytest.raises(Boom):
+        pipe.run(a_todo, str(tmp_path / 'a_audio'), str(tmp_path / 'a_feat'), 24000, 2, scaler=features.ScalerSums())
+    for sl, fn in zip(pipe.slots, real):
+        sl.ex.extract = fn
+    sums = features.ScalerSums()
+    pipe.run(b_todo, str(tmp_path / 'b_audio'), str(b_root / 'foa_dev'), 24000, 2, scaler=sums)
+    files = sio.feature_files(str(b_root / 'foa_dev'))
+    assert len(files) == 6
+    assert sums.n_frames == sum(sio.load_arrays(str(b_root / 'foa_dev' / f))['feature'].shape[1] for f in files) == 6 * 81
+    features.write_scaler_from_sums(str(b_root), 'foa', sums.sums, sums.n_frames)
+    fused = sio.load_arrays(str(b_root / 'foa_feature_scaler.h5'))
+    features.compute_scaler(feature_dir=str(b_root), audio_format='foa')
+    from_files = sio.load_arrays(str(b_root / 'foa_feature_scaler.h5'))
+    for k in ('mean', 'std'):
+        print(k, 'max |fused - files| =', np.abs(fused[k].astype(np.float64) - from_files[k]).max())
+        np.testing.assert_allclose(fused[k], from_files[k], rtol=2e-6, atol=2e-6)
+
+
+def test_file_pipeline_depth_3_writes_the_same_files(dev, tmp_path):
+    """depth = 3 is the smallest pipeline (one length bucket open at a time; the constructor refuses less): a tree whose two clip
+    lengths alternate comes out file for file, bit for bit, as from the default depth of 4."""
+    from salsa_amd import features, io as sio
+    from salsa_amd.extractor import SalsaExtractor
+    todo = _npy_tree(str(tmp_path / 'audio'), 420, [24000, 18000, 24000, 18000, 24000])
+    out = {}
+    for depth in (3, 4):
+        fdir = tmp_path / ('feat%d' % depth)
+        fdir.mkdir()
+        features._FilePipeline(SalsaExtractor(device=dev), depth=depth).run(todo, str(tmp_path / 'audio'), str(fdir), 24000, 2)
+        names = sio.feature_files(str(fdir))
+        assert len(names) == 5
+        out[depth] = {n: sio.load_arrays(str(fdir / n))['feature'] for n in names}
+    assert sorted(out[3]) == sorted(out[4])
+    for n, f in out[3].items():
+        assert f.dtype == np.float32 and f.shape == out[4][n].shape and np.array_equal(f, out[4][n]), n
 
 
 def test_lite_harness_and_python_surface(dev, tmp_path):

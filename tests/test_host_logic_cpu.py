@@ -17,6 +17,35 @@ def test_feature_name_follows_reference_replace_quirk():
     assert feature_name('clip.npy') == 'clip.h5'
 
 
+@pytest.mark.parametrize('fixture', ['g3_salsa_foa', 'g3_salsa_mic', 'g3_salsa_foa_nfft256', 'g3_salsa_foa_notrack_nocompress',
+                                     'g4_salsa_lite', 'g4_salsa_ipd'])
+def test_tree_layout_gives_the_reference_directories(fixture):
+    """features.tree_layout (the one place the directory-name formats are written) against the trees the reference wrote: every
+    golden key is feature_type|format|description|split|file|dataset or ...|description|scaler file|dataset."""
+    from conftest import load_golden
+    from salsa_amd.features import tree_layout
+    meta, a = load_golden(fixture)
+    feature_type = meta.get('feature_type', 'salsa')
+    desc, splits = tree_layout(feature_type, meta['format'], meta['fs'], meta['n_fft'], meta['hop'], meta.get('cond_num'),
+                               meta['fmax_doa'], **meta.get('kw', {}))
+    assert splits == (meta['format'] + '_dev', meta['format'] + '_eval')
+    seen = set()
+    for key in a:
+        parts = key.split('|')
+        assert parts[:3] == [feature_type, meta['format'], desc], key
+        if len(parts) == 6:
+            assert parts[3] in splits, key
+            seen.add(parts[3])
+    assert seen and seen <= set(splits)
+
+
+def test_file_pipeline_refuses_depth_below_3():
+    """the reader keeps depth - 2 length buckets open; the check comes before anything touches the device"""
+    from salsa_amd.features import _FilePipeline
+    with pytest.raises(ValueError):
+        _FilePipeline(None, depth=2)
+
+
 def test_wav_reader_matches_float_and_int16_conventions(tmp_path):
     from scipy.io import wavfile
     rng = np.random.RandomState(0)
