@@ -115,6 +115,37 @@ def avgpool_bound(x):
     return ref, BF16_REL * ref.abs() + (1 + BF16_REL) * 3 * U32 * F.avg_pool2d(xd.abs(), 2)
 
 
+def avgpool_bwd_ref(gy, H, W):
+    """float64 gradient of a floor-mode 2x2 average pool's (N, C, H, W) input for the pooled gradient gy: gy / 4 at the four
+    pixels of a window, 0 in the last row of an odd H and the last column of an odd W.  avgpool2x2_bwd_kernel in nn_pool.hip
+    forms g / 4.0f in float32 and rounds once: a division by 2^2 of a bf16 (or float32) value is exact in both formats (no
+    rounding count; only a subnormal result could round), so the kernel's output EQUALS this reference cast to its dtype."""
+    g = F.interpolate(gy.double(), scale_factor=2, mode='nearest') / 4
+    return F.pad(g, (0, W - g.shape[3], 0, H - g.shape[2]))
+
+
+def assert_dropped_plus_zero(g, what):
+    """the (N, C, H, W) gradient of a floor-mode 2x2 pool's input holds +0.0 BIT FOR BIT in the last row of an odd H and the last
+    column of an odd W: not -0.0, not the NaN the buffer was filled with (an element left unwritten), not a neighbour's value"""
+    assert g.dtype in (torch.bfloat16, torch.float32)
+    bits = g.view(torch.int16 if g.dtype == torch.bfloat16 else torch.int32)
+    H, W = g.shape[2], g.shape[3]
+    assert H % 2 or W % 2, what + ': the pool drops nothing at an even map'
+    if W % 2:
+        n = int((bits[:, :, :, W - 1] != 0).sum())
+        assert n == 0, '%s: %d elements of the dropped last column are not +0.0' % (what, n)
+    if H % 2:
+        n = int((bits[:, :, H - 1, :] != 0).sum())
+        assert n == 0, '%s: %d elements of the dropped last row are not +0.0' % (what, n)
+
+
+def any_order_wgrad_bound(ref, absum, n_terms):
+    """bound of a bf16 weight gradient whose float32 accumulation order is unknown (the torch / MIOpen fallback of a map the wide
+    weight-gradient kernel refuses): ANY order of adding n_terms float32 products is within (n_terms - 1) u sum|term| of the
+    exact sum (Higham 4.2 holds for every summation tree), then one rounding to bf16 as in bf16_bound."""
+    return bf16_bound(ref, absum, (1 + BF16_REL) * (n_terms - 1) * U32)
+
+
 def conv_wgrad_ref(x, gy, k=3):
     """(ref, absum) float64 (Cout, Cin, k, k): ref = sum over pixels of gy * x(shifted), absum = the same of |gy| |x|."""
     N, Cin, H, W = x.shape
@@ -230,6 +261,22 @@ def bn_train_ref(x, gamma, beta, eps, residual=None, relu=True, pool=False):
     if pool:
         y = F.avg_pool2d(y, 2)
     return dict(y=y, pre=pre, mean=mean, var=var, unbiased=var * M / (M - 1), invstd=invstd, xhat=xhat, fwd_abs=fwd_abs, M=M)
+
+
+def bn_eval_ref(x, gamma, beta, mean, invstd, residual=None, relu=True):
+    """(ref, absum) float64 of salsa_nn_bn_eval_fwd: [relu]((x - mean) invstd gamma + beta [+ residual]) on the operands the
+    kernel is handed (invstd is an operand: BatchNormAct2d.forward forms rsqrt(running_var + eps) in float32).  bn_apply_kernel in
+    nn_batchnorm.hip evaluates ((x - mean) * invstd) * gamma + beta, + residual in float32: five roundings, each within u of a
+    partial result <= absum = |gamma| invstd (|x| + |mean|) + |beta| + |residual|, so 5 u absum -- inside the 16 u the training
+    forward (the same kernel, after its statistics) is held to; a bf16 output adds one rounding (bf16_bound)."""
+    v = lambda t: t.double().view(1, -1, 1, 1)
+    a = v(gamma) * v(invstd)
+    ref = (x.double() - v(mean)) * a + v(beta)
+    absum = a.abs() * (x.double().abs() + v(mean).abs()) + v(beta).abs()
+    if residual is not None:
+        ref = ref + residual.double()
+        absum = absum + residual.double().abs()
+    return (ref.clamp_(min=0) if relu else ref), absum
 
 
 def bn_bwd_ref(r, gamma, gy, relu=True, pool=False, fwd_c=16 * U32, bf16=False):

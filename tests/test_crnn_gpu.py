@@ -332,12 +332,19 @@ def test_stem_conv_kernel_matches_torch():
         torch.testing.assert_close(fused.float(), want, rtol=2.0 ** -8, atol=2e-3)
 
 
-def test_whole_model_hip_layers_on_vs_off():
+def whole_model_hip_layers_on_vs_off(batch, label_margin=None):
     """The CRNN with every hand-written layer (MFMA convolutions, pools, fused BatchNorm, GRU scan) against the same weights
-    with those layers switched to torch / MIOpen: bf16-autocast eval forward and one training step's loss and gradients."""
+    with those layers switched to torch / MIOpen: bf16-autocast eval forward and one training step's loss and gradients.
+    batch: (x, sed, doa) on cuda:0 (tests/test_nn_kernels_lite_maps_gpu.py runs this at 191 and 382 frequency bins).
+
+    label_margin: the loss's DOA term is a masked L1, so its gradient is sign(pred - target) / (active labels): an active label
+    whose prediction lies within the bf16 forward noise of its target (the legs' outputs differ by up to 2e-2) takes one sign in
+    one leg and the other in another, and ONE such flip moves that leg's whole gradient by 2 / sqrt(active labels on that axis) --
+    0.21 at the 84 of a 2-clip batch, measured at 382 bins, where it alone put the HIP leg's median error at 0.168 against 0.099.
+    With a margin, active labels within it of their float32 prediction on any axis are switched off before any leg runs; every
+    bound below stays as it is."""
     from salsa_amd.crnn import model as M, nn_ops
     from salsa_amd.crnn.loss import seld_loss
-    from salsa_amd.crnn.train import synthetic_batch
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     net = M.SeldCRNN().to(dev).to(memory_format=torch.channels_last)
@@ -357,7 +364,7 @@ def test_whole_model_hip_layers_on_vs_off():
             mod.dropout_p = 0.0
     real_dropout = M.F.dropout
     M.F.dropout = lambda t, p=0.5, training=True, inplace=False: t
-    x, sed, doa = synthetic_batch(4, dev, seed=3)
+    x, sed, doa = batch
     x = x.contiguous(memory_format=torch.channels_last)
 
     def run(on, amp=True):
@@ -378,6 +385,17 @@ def test_whole_model_hip_layers_on_vs_off():
 
     try:
         bufs = {n: b.clone() for n, b in net.named_buffers()}
+        if label_margin is not None:
+            nn_ops.USE_HIP_POOL = nn_ops.USE_HIP_BN = nn_ops.USE_HIP_CONV = M.FUSED_GRU = False
+            net.train()
+            with torch.no_grad():
+                pred = net(x)['doa_frame_output'].float()                           # float32, torch layers
+            for n, b in net.named_buffers():
+                b.copy_(bufs[n])
+            near = ((pred - doa).abs() < label_margin).view(*sed.shape[:2], 3, sed.shape[2]).any(dim=2) & (sed > 0)
+            print('labels switched off within %g of their float32 prediction: %d of %d active' % (label_margin, int(near.sum()), int((sed > 0).sum())))
+            assert int(near.sum()) <= 0.25 * int((sed > 0).sum())
+            sed = sed * ~near
         ev_on, loss_on, g_on = run(True)
         for n, b in net.named_buffers():
             b.copy_(bufs[n])
@@ -400,6 +418,11 @@ def test_whole_model_hip_layers_on_vs_off():
     mid = len(e_on) // 2
     print('gradient error vs float32, median / max: hip %.3f / %.3f   torch-bf16 %.3f / %.3f' % (e_on[mid], e_on[-1], e_off[mid], e_off[-1]))
     assert e_on[mid] <= 1.25 * e_off[mid] + 2e-2 and e_on[-1] <= 1.5 * e_off[-1] + 5e-2
+
+
+def test_whole_model_hip_layers_on_vs_off():
+    from salsa_amd.crnn.train import synthetic_batch
+    whole_model_hip_layers_on_vs_off(synthetic_batch(4, torch.device('cuda:0'), seed=3))
 
 
 def test_register_resident_gru_inference_scan():
@@ -1130,12 +1153,12 @@ def test_config5_sub_batch_is_batch_invariant():
     np.testing.assert_allclose(d32[30:].cpu().numpy(), d_last.cpu().numpy(), rtol=0, atol=1e-6)
 
 
-def test_deterministic_mode_gives_bit_equal_weight_gradients():
+def deterministic_mode_gives_bit_equal_weight_gradients(n_freq=200):
     """nn_ops.set_deterministic (include/salsa_nn.h: salsa_nn_set_deterministic): with it on, every weight-gradient kernel (64 -> 64,
     first layer, wide, 1x1) and the GRU bias column sums write per-workgroup partial slabs that one launch adds in slab order,
     so two identical training passes -- same parameters, same batch, same dropout seeds -- leave BIT-EQUAL gradients on every
     parameter (round-3 review: float atomics summed the partials in arrival order).  The deterministic gradients agree with the
-    atomic ones to float32 rounding of differently ordered sums."""
+    atomic ones to float32 rounding of differently ordered sums.  -> grads (seed -> the gradients of one more pass)"""
     from salsa_amd.crnn import nn_ops
     from salsa_amd.crnn.loss import seld_loss
     from salsa_amd.crnn.train import Trainer, synthetic_batch
@@ -1144,7 +1167,7 @@ def test_deterministic_mode_gives_bit_equal_weight_gradients():
         for m in tr.raw_model.modules():                      # (zero-initialised bn2 weights would silence half the network)
             if isinstance(m, torch.nn.BatchNorm2d):
                 m.weight.uniform_(0.5, 1.5)
-    x, sed, doa = synthetic_batch(8, 'cuda:0', seed=3)
+    x, sed, doa = synthetic_batch(8, 'cuda:0', seed=3, n_freq=n_freq)
     params = [p for p in tr.raw_model.parameters()]
 
     def grads(seed):
@@ -1175,6 +1198,12 @@ def test_deterministic_mode_gives_bit_equal_weight_gradients():
         assert torch.equal(ga, gb), n                                            # bit-equal, run to run
         scale = float(g0.abs().max()) + 1e-12
         assert float((ga - g0).abs().max()) <= 2e-3 * scale, (n, float((ga - g0).abs().max()), scale)   # same gradient as the atomic path
+    return grads
+
+
+def test_deterministic_mode_gives_bit_equal_weight_gradients():
+    from salsa_amd.crnn import nn_ops
+    grads = deterministic_mode_gives_bit_equal_weight_gradients()
     # the library refuses a workspace that is too small for a shape instead of writing past it
     import ctypes as C
     from salsa_amd import _lib

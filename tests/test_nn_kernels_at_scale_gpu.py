@@ -396,7 +396,7 @@ def _stem_bn_ref(xq, wq, gam, bet, eps, gy):
 
 @pytest.mark.parametrize('kind', ['normalised', 'features'])
 @pytest.mark.parametrize('cin', [7, 10])
-def test_stem_batchnorm_backward_modes_at_mel_map(cin, kind):
+def test_stem_batchnorm_backward_modes_at_mel_map(cin, kind, shape=(32, 640, 128)):
     """The first layer's weight gradient with its BatchNorm (+ ReLU) backward folded in at 32 x Cin x 640 x 128, in both modes --
     _bnf (the BatchNorm backward's reduction in the same pass, the training default) and _bn (reduction launch + coefficient
     table) -- against a float64 evaluation of the layer: no further from it than the two-node path (plain stem weight gradient
@@ -406,7 +406,7 @@ def test_stem_batchnorm_backward_modes_at_mel_map(cin, kind):
     -- the same dx formed on load instead of stored -- must also stay within 2e-3 of the scale of the two-node path."""
     from salsa_amd.crnn import nn_ops
     from test_baseline_training_gpu import _bn_step
-    n, h, w = 32, 640, 128
+    n, h, w = shape                      # (tests/test_nn_kernels_lite_maps_gpu.py calls this at 640 x 191)
     assert _lib().salsa_nn_bn_supported(1, n * h * w, 64) and nn_ops._stem_wrw_hip(cin)
     x = _features(n, cin, h, w, 24 + cin, kind)
     gy = _act(n, 64, h, w, 25, offset=False)

@@ -1,5 +1,6 @@
-"""CPU checks behind tests/test_nn_kernels_at_scale_gpu.py: the wide convolution's dispatch (which instantiation every bench
-layer reaches, at the SALSA / lin maps and at the mel maps), the 64 -> 64 convolution's geometry, its weight-gradient index
+"""CPU checks behind tests/test_nn_kernels_at_scale_gpu.py, _full_res_gpu.py and _lite_maps_gpu.py: the wide convolution's dispatch
+(which instantiation every bench layer reaches, at the SALSA / lin maps, at the mel maps and at the odd-width SALSA-Lite / IPD
+maps), the 64 -> 64 convolution's geometry, its weight-gradient index
 tables against a numpy restatement of the padded layout, and the power of the float64 checker in tests/nn_reference.py -- it
 must reject small, realistic kernel bugs.  No GPU calls."""
 import ctypes as C
@@ -144,8 +145,14 @@ def test_c64_geometry_query(lib):
     assert c64_config(lib, 32, 640, 200) == c64_plan(32, 640, 200)
     for n in (1, 3, 32):
         for h in (1, 2, 3, 4, 5, 7, 8, 31, 32, 33, 40, 64, 100, 127, 128, 160, 320, 640):
-            for w in (1, 3, 4, 5, 8, 12, 16, 25, 31, 32, 33, 50, 64, 65, 100, 128, 200):
+            for w in (1, 3, 4, 5, 8, 11, 12, 16, 23, 25, 31, 32, 33, 47, 50, 64, 65, 95, 100, 128, 191, 200, 382):
                 assert c64_config(lib, n, h, w) == c64_plan(n, h, w), (n, h, w)
+    # the SALSA-Lite / IPD maps: 640 x 191 and 320 x 95 (n_fft 512) run untransposed -- every row ends in a 31-column partial tile
+    # (191 = 5 x 32 + 31, 95 = 2 x 32 + 31) -- while 320 x 47 (n_fft 256) runs transposed
+    assert c64_config(lib, 32, 640, 191) == (30720, 0) == c64_plan(32, 640, 191)
+    assert c64_config(lib, 32, 320, 95) == (7680, 0) == c64_plan(32, 320, 95)
+    assert c64_config(lib, 32, 320, 47) == (3840, 1) == c64_plan(32, 320, 47)
+    assert 191 % 32 == 31 and 95 % 32 == 31
     tr = C.c_int(-7)
     for bad in ((0, 8, 8), (1, 0, 8), (1, 8, 0), (-1, 8, 8), (1 << 24, 64, 64)):
         assert lib.salsa_nn_conv3x3_c64_config(*bad, C.byref(tr)) == -1, bad
@@ -182,7 +189,8 @@ def numpy_tables(n, h, w, tm=128):
     return vpos, inv, np.stack([first, last - first + w + 4], 1).reshape(-1)
 
 
-@pytest.mark.parametrize('shape', [(32, 160, 50), (32, 80, 25), (32, 40, 12), (3, 30, 33), (1, 5, 7), (5, 3, 40), (2, 64, 1)])
+@pytest.mark.parametrize('shape', [(32, 160, 50), (32, 80, 25), (32, 40, 12), (3, 30, 33), (1, 5, 7), (5, 3, 40), (2, 64, 1),
+                                   (32, 160, 47), (32, 80, 23), (32, 40, 11), (32, 160, 95)])        # (the last four: SALSA-Lite / IPD)
 def test_wide_wrw_tables_match_the_padded_layout(lib, shape):
     n, h, w = shape
     L = int(lib.salsa_nn_conv3x3_wide_table_len(n, h, w))
@@ -446,3 +454,259 @@ def test_python_eligibility_agrees_with_the_library_at_the_pixel_limit(lib):
         assert bool(nn_ops._c64_map_ok(n, h, w)) == ok, shape
         assert (lib.salsa_nn_conv3x3_c64_stats_blocks(n, h, w) > 0) == ok, shape
     assert 31 * 1801 * 601 == 33554431
+
+
+# ------------------------------------------------------------------------------------------------ the SALSA-Lite / IPD maps
+# SALSA-Lite and SALSA-IPD keep the bins lower_bin .. cutoff_bin - 1 of the spectrum (salsa_bin_limits): F = 191 at n_fft 512,
+# 382 at 1024, 95 at 256; full SALSA at n_fft 256 compresses to 100.  Every 2 x 2 pool halves the width rounding DOWN, so a
+# Lite width is odd at every stage: (T = 640) 640 x 191, 320 x 95, 160 x 47, 80 x 23, 40 x 11.
+LITE_F, LITE1024_F, LITE256_F, SALSA256_F = 191, 382, 95, 100
+WIDE_CHANNELS = [(64, 128), (128, 128), (128, 256), (256, 256), (256, 512), (512, 512)]
+WG_XL = 28672                           # conv_wide.hip: the weight gradient's input tile buffer (448 slots of 64 bytes)
+
+
+def family_widths(f):
+    """the frequency widths of the stem map and the four stages' maps: floor-halving"""
+    return [f >> k for k in range(5)]
+
+
+def wide_layers(f):
+    """(Cin, Cout, H, W) of the six wide 3x3 layers (stages 2 - 4) for F = f frequency bins and 640 frames"""
+    ws = family_widths(f)
+    return [(cin, cout, 160 >> (i // 2), ws[2 + i // 2]) for i, (cin, cout) in enumerate(WIDE_CHANNELS)]
+
+
+def stages(f):
+    """(C, H, W) of the four residual stages' BatchNorms"""
+    ws = family_widths(f)
+    return [(64 << k, 320 >> k, ws[1 + k]) for k in range(4)]
+
+
+LITE_WIDE, LITE1024_WIDE, LITE256_WIDE, SALSA256_WIDE = (wide_layers(f) for f in (LITE_F, LITE1024_F, LITE256_F, SALSA256_F))
+LITE_STAGES, LITE1024_STAGES, LITE256_STAGES, SALSA256_STAGES = (stages(f) for f in (LITE_F, LITE1024_F, LITE256_F, SALSA256_F))
+LITE_FAMILIES = {'lite512': LITE_F, 'lite1024': LITE1024_F, 'lite256': LITE256_F, 'salsa256': SALSA256_F}
+
+
+def wide_wrw_ok(h, w):
+    """salsa_nn_conv3x3_wide_wrw_supported's size condition restated: a 128-pixel tile's input rows fit the tile buffer"""
+    return wide_rows(128, h, w) * (w + 2) * 64 <= WG_XL
+
+
+def test_lite_map_lists_follow_the_extractor(lib):
+    from salsa_amd.extractor import bin_limits
+    from salsa_amd.torch_ops import output_shape
+    for n_fft, f in ((512, LITE_F), (1024, LITE1024_F), (256, LITE256_F)):
+        lo, _, cut = bin_limits(24000, n_fft, 50, 2000)
+        assert cut - lo == f, (n_fft, lo, cut)
+        for kind in ('salsa_lite', 'salsa_ipd'):
+            assert output_shape(8 * 24000, 'mic', kind, 24000, n_fft, 300, 50, 2000) == (7, 641, f)
+    assert output_shape(8 * 24000, 'mic', 'salsa', 24000, 256, 300, 50, 4000) == (7, 641, SALSA256_F)
+    assert output_shape(8 * 24000, 'mic', 'salsa', 24000, 512, 300, 50, 4000) == (7, 641, 200)
+    assert family_widths(191) == [191, 95, 47, 23, 11] and family_widths(382) == [382, 191, 95, 47, 23]
+    assert family_widths(95) == [95, 47, 23, 11, 5] and family_widths(100) == [100, 50, 25, 12, 6]
+    assert all(w % 2 for f in (191, 382, 95) for w in family_widths(f)[:5] if w != 382)       # odd at every stage (382: from stage 1 on)
+    assert LITE_WIDE == [(64, 128, 160, 47), (128, 128, 160, 47), (128, 256, 80, 23), (256, 256, 80, 23), (256, 512, 40, 11), (512, 512, 40, 11)]
+    assert LITE1024_WIDE[0] == (64, 128, 160, 95) and LITE1024_WIDE[2] == (128, 256, 80, 47) and LITE256_WIDE[4] == (256, 512, 40, 5)
+    assert LITE_STAGES == [(64, 320, 95), (128, 160, 47), (256, 80, 23), (512, 40, 11)]
+    assert wide_layers(200) == BENCH_WIDE and wide_layers(128) == MEL_WIDE and stages(128) == MEL_STAGES
+
+
+# what batch 32 reaches at every wide layer of a family: [(forward instantiation, data-gradient instantiation)] in layer order
+LITE_WIDE_INST = {
+    'lite512': [((512, 128), (512, 64)), ((512, 128), (512, 128)), ((512, 128), (256, 128)), ((512, 128), (512, 128)),
+                ((256, 128), (256, 64)), ((256, 128), (256, 128))],
+    # 160 x 95: a 512-pixel tile's chunk needs 68 608 B > MAX_XL_BYTES, so (256, 128) where the other families run (512, 128);
+    # 80 x 47 with 128 channels out (the data gradient of 128 -> 256): (512, 128), a pairing no 200- or 128-bin map reaches
+    'lite1024': [((256, 128), (256, 64)), ((256, 128), (256, 128)), ((512, 128), (512, 128)), ((512, 128), (512, 128)),
+                 ((512, 128), (256, 128)), ((512, 128), (512, 128))],
+    'lite256': [((512, 128), (512, 64)), ((512, 128), (512, 128)), ((256, 128), (256, 64)), ((256, 128), (256, 128)),
+                ((256, 64), (256, 64)), ((256, 64), (256, 64))],
+    'salsa256': [((512, 128), (512, 64)), ((512, 128), (512, 128)), ((256, 128), (256, 64)), ((256, 128), (256, 128)),
+                 ((256, 64), (256, 64)), ((256, 64), (256, 64))]}
+
+
+@pytest.mark.parametrize('family', sorted(LITE_FAMILIES))
+def test_wide_dispatch_at_every_lite_layer(lib, family):
+    f = LITE_FAMILIES[family]
+    layers = wide_layers(f)
+    _assert_wide_dispatch(lib, layers)
+    for (cin, cout, h, w), (fwd, dgrad) in zip(layers, LITE_WIDE_INST[family]):
+        assert config(lib, 32, h, w, cout) == fwd == wide_tile(32, h, w, cout), (family, 'fwd', cin, cout, h, w)
+        assert config(lib, 32, h, w, cin) == dgrad == wide_tile(32, h, w, cin), (family, 'dgrad', cin, cout, h, w)
+        # the weight gradient.  Only full SALSA's widths 50 / 25 / 12 have an instantiation of their own (salsa256 meets 25 and
+        # 12); every Lite width takes the generic (W2C = 0) kernel.  The kernel takes a map when a 128-pixel tile's input rows
+        # fit its 28 672-byte tile buffer -- W <= 62 at these heights -- and then all of these maps run on three tile buffers
+        # (wrw3).  160 x 95 does NOT fit (7 rows x 97 slots x 64 B = 43 456 B): salsa_nn_conv3x3_wide_wrw_supported refuses it,
+        # the entry point returns -1 and _Conv3x3Wide.backward hands that weight gradient to torch.  wrw3(160, 95) is false as
+        # well, but the two-buffer kernel is not what production runs there: nothing of the library is.
+        ok = bool(lib.salsa_nn_conv3x3_wide_wrw_supported(32, h, w, cin, cout))
+        assert ok == wide_wrw_ok(h, w) == (w <= 62), (family, cin, cout, h, w)
+        assert ok == wrw3(h, w), (family, h, w)
+        assert (w in WRW_IMMEDIATE_W) == (family == 'salsa256' and w in (25, 12)), (family, w)
+    assert not wrw3(160, 95) and not wide_wrw_ok(160, 95) and wide_rows(128, 160, 95) * 97 * 64 == 43456
+    assert [l for l in layers if not wide_wrw_ok(l[2], l[3])] == (layers[:2] if family == 'lite1024' else [])
+    assert wide_xl_bytes(512, 160, 95) == 68608 > MAX_XL_BYTES
+    # the 1 x 1 shortcuts of the three stride-2 blocks: forward, data gradient, weight gradient
+    for cin, cout, h, w in (layers[0], layers[2], layers[4]):
+        M = 32 * h * w
+        assert lib.salsa_nn_conv1x1_supported(M, cin, cout) and lib.salsa_nn_conv1x1_supported(M, cout, cin)
+        assert lib.salsa_nn_conv1x1_wrw_supported(M, cin, cout)
+
+
+@pytest.mark.parametrize('family', sorted(LITE_FAMILIES))
+def test_batchnorm_takes_every_lite_stage(lib, family):
+    for n in (2, 8, 16, 32):
+        for c, h, w in stages(LITE_FAMILIES[family]) + [(64, 640, LITE_FAMILIES[family])]:
+            for dtype in (0, 1):
+                assert lib.salsa_nn_bn_supported(dtype, n * h * w, c), (n, c, h, w, dtype)
+
+
+# ------------------------------------------------------------------------------------------------ the GPU cases' batch sizes
+def smallest_batch(answers):
+    """the smallest N in 1 .. 32 at which answers(N) == answers(32): the host queries then pick for the test what they pick for
+    the bench batch; 2 where they do not depend on N at all"""
+    want = answers(32)
+    n = min(k for k in range(1, 33) if answers(k) == want)
+    assert all(answers(k) == want for k in range(n, 33)), n          # (and nothing changes between there and 32)
+    return max(n, 2) if n == 1 else n
+
+
+def wide_answers(lib, cin, cout, h, w):
+    return lambda n: (config(lib, n, h, w, cout), config(lib, n, h, w, cin), bool(lib.salsa_nn_conv3x3_wide_supported(n, h, w, cin, cout)),
+                      bool(lib.salsa_nn_conv3x3_wide_supported(n, h, w, cout, cin)),
+                      bool(lib.salsa_nn_conv3x3_wide_wrw_supported(n, h, w, cin, cout)))
+
+
+def c64_answers(lib, h, w):
+    """the 64 -> 64 kernels' plan: transposed or not, the forward grid (salsa_nn_conv3x3_c64_stats_blocks: 512, or 1024 from
+    16384 tiles up) and the weight gradient's grid as c64_wgrad_c restates it (128 / 256 / 512 workgroups)"""
+    def grid(n):
+        tiles, tr = c64_config(lib, n, h, w)
+        return tr, lib.salsa_nn_conv3x3_c64_stats_blocks(n, h, w), 512 if tiles >= 16384 else 256 if tiles >= 4096 else 128 if tiles >= 128 else tiles
+    return grid
+
+
+# (Cin, Cout, H, W) -> N of the wide GPU cases: every LITE_WIDE layer and the three layers only another family reaches
+LITE_GPU_WIDE = LITE_WIDE + [LITE1024_WIDE[0], LITE1024_WIDE[2], LITE256_WIDE[4]]
+LITE_BATCH = {(64, 128, 160, 47): 14, (128, 128, 160, 47): 14, (128, 256, 80, 23): 27, (256, 256, 80, 23): 27, (256, 512, 40, 11): 28,
+              (512, 512, 40, 11): 28, (64, 128, 160, 95): 4, (128, 256, 80, 47): 27, (256, 512, 40, 5): 2}
+# (H, W) -> N of the 64 -> 64 cases: 320 x 95 (256-workgroup weight gradient from 4096 tiles), 640 x 191 (1024 / 512 grids from
+# 16384 tiles), 320 x 47 (transposed); the 60-s inference maps: the smallest N on the 1024-workgroup grid
+LITE_C64_BATCH = {(320, 95): 18, (640, 191): 18, (320, 47): 5, (4800, 191): 3, (2400, 95): 10}
+LITE_STEM_BATCH = 3                     # 7 -> 64 at 640 x 191: salsa_nn_conv3x3_stem_stats_blocks reaches its 1024 rows
+
+
+def test_lite_gpu_batches_answer_the_host_queries_as_batch_32_does(lib):
+    assert set(LITE_BATCH) == set(LITE_GPU_WIDE)
+    for layer, n in LITE_BATCH.items():
+        assert smallest_batch(wide_answers(lib, *layer)) == n, layer
+    for (h, w), n in LITE_C64_BATCH.items():
+        assert smallest_batch(c64_answers(lib, h, w)) == n, (h, w)
+    assert smallest_batch(lambda n: lib.salsa_nn_conv3x3_stem_stats_blocks(n, 640, 191)) == LITE_STEM_BATCH
+    assert c64_answers(lib, 4800, 191)(3)[1] == 1024 == c64_answers(lib, 2400, 95)(10)[1]
+    # nothing else the GPU cases ask depends on N: 2
+    for cin, cout, h, w in (LITE_WIDE[0], LITE_WIDE[2], LITE_WIDE[4]):
+        assert smallest_batch(lambda n: (lib.salsa_nn_conv1x1_supported(n * h * w, cin, cout), lib.salsa_nn_conv1x1_supported(n * h * w, cout, cin),
+                                         lib.salsa_nn_conv1x1_wrw_supported(n * h * w, cin, cout))) == 2
+    for c, h, w in LITE_STAGES + [(128, 159, 47)]:
+        assert smallest_batch(lambda n: (lib.salsa_nn_bn_supported(0, n * h * w, c), lib.salsa_nn_bn_supported(1, n * h * w, c))) == 2
+
+
+# ------------------------------------------------------------------------------------------------ the checker at an odd width
+def test_checker_accepts_float32_evaluations_of_the_pool_gradient_and_the_any_order_bound():
+    """avgpool_bwd_ref is exact in float32 and in bf16 (a division by 4); a float32 evaluation of a weight gradient in torch's
+    own summation order stays inside any_order_wgrad_bound"""
+    g = torch.Generator().manual_seed(12)
+    gy = torch.randn(2, 8, 4, 5, generator=g).to(torch.bfloat16)
+    ref = nr.avgpool_bwd_ref(gy, 9, 11)
+    assert ref.shape == (2, 8, 9, 11) and torch.equal(ref.to(torch.bfloat16).double(), ref) and torch.equal(ref.float().double(), ref)
+    assert not bool(ref[:, :, 8].any()) and not bool(ref[:, :, :, 10].any())
+    x = torch.randn(2, 8, 9, 11, generator=g, dtype=torch.float64).requires_grad_(True)
+    torch.nn.functional.avg_pool2d(x, 2).backward(gy.double())
+    assert torch.equal(x.grad, ref)
+    nr.assert_dropped_plus_zero(ref.to(torch.bfloat16), 'bf16')
+    nr.assert_dropped_plus_zero(ref.float(), 'float32')
+    xq, wt = _small_conv(13, n=4, cin=16, cout=8, h=9, w=11)
+    gyq = _bf16(torch.randn(4, 8, 9, 11, generator=g))
+    wref, wabs = nr.conv_wgrad_ref(xq, gyq)
+    w32 = torch.nn.grad.conv2d_weight(xq.float(), (8, 16, 3, 3), gyq.float(), padding=1)
+    assert nr.check(_bf16(w32), wref, nr.any_order_wgrad_bound(wref, wabs, 4 * 9 * 11), 'dW') <= 1
+    with pytest.raises(AssertionError):                                  # and it is no free pass: one pixel's products missing
+        keep = torch.ones(4, 1, 9, 11, dtype=torch.float64)
+        keep[2, 0, 8, 10] = 0
+        nr.check(_bf16(nr.conv_wgrad_ref(xq, gyq * keep)[0].float()), wref, nr.any_order_wgrad_bound(wref, wabs, 4 * 9 * 11), 'dW')
+
+
+def test_checker_accepts_a_float32_evaluation_of_the_eval_batchnorm():
+    """bn_eval_ref against torch's eval-mode batch_norm, and the kernel's float32 statement order inside 16 u absum (+ bf16)"""
+    g = torch.Generator().manual_seed(16)
+    x = _bf16(torch.randn(2, 16, 9, 11, generator=g) * 2 + torch.linspace(-3, 3, 16).view(1, -1, 1, 1)).float()
+    res = _bf16(torch.randn(2, 16, 9, 11, generator=g)).float()
+    gamma, beta = torch.rand(16, generator=g) + 0.5, torch.randn(16, generator=g)
+    rm, rv = torch.randn(16, generator=g), torch.rand(16, generator=g) + 0.5
+    invstd = torch.rsqrt(rv + 1e-5)
+    ref, absum = nr.bn_eval_ref(x, gamma, beta, rm, invstd, residual=res, relu=True)
+    want = torch.relu(torch.nn.functional.batch_norm(x.double(), rm.double(), rv.double(), gamma.double(), beta.double(), False, 0.1, 1e-5)
+                      + res.double())
+    assert torch.allclose(ref, want, rtol=1e-6, atol=1e-6)               # (invstd is float32 in ref, float64 in torch's)
+    v = lambda t: t.view(1, -1, 1, 1)
+    y32 = torch.relu(((x - v(rm)) * v(invstd)) * v(gamma) + v(beta) + res)
+    assert nr.check(y32, ref, 16 * nr.U32 * absum, 'bn eval fp32') <= 5 / 16 + 1e-3
+    assert nr.check(_bf16(y32), ref, 16 * nr.U32 * absum + nr.BF16_REL * ref.abs(), 'bn eval bf16') <= 1
+    with pytest.raises(AssertionError):                                  # the residual of the pixel to the left
+        bad = torch.relu(((x - v(rm)) * v(invstd)) * v(gamma) + v(beta) + torch.roll(res, 1, dims=3))
+        nr.check(_bf16(bad), ref, 16 * nr.U32 * absum + nr.BF16_REL * ref.abs(), 'bn eval bf16')
+
+
+def test_checker_rejects_a_dropped_column_gradient_left_unwritten():
+    """a pool backward over a 9 x 11 map that never stores the column (and row) the pool drops: in a NaN-filled buffer those
+    elements stay NaN, in a recycled one they hold stale values or -0.0 -- none of them may pass"""
+    g = torch.Generator().manual_seed(14)
+    gy = torch.randn(2, 8, 4, 5, generator=g).to(torch.bfloat16)
+    ref = nr.avgpool_bwd_ref(gy, 9, 11)
+    good = ref.to(torch.bfloat16)
+    assert nr.check(good, ref, 0 * ref, 'pool bwd') == 0
+    nr.assert_dropped_plus_zero(good, 'pool bwd')
+    for stale in (float('nan'), -0.0, 2.0 ** -20):
+        for cut in ((slice(None), slice(10, 11)), (slice(8, 9), slice(None))):       # the last column / the last row
+            bad = good.clone()
+            bad[:, :, cut[0], cut[1]] = stale
+            with pytest.raises(AssertionError):
+                nr.assert_dropped_plus_zero(bad, 'pool bwd')
+            if stale != 0:                                                           # (-0.0 == +0.0 to the value checker)
+                with pytest.raises(AssertionError):
+                    nr.check(bad, ref, 0 * ref, 'pool bwd')
+    # the BatchNorm + pool backward's dres at the same map, against bn_bwd_ref's own bound
+    x = torch.randn(2, 8, 9, 11, generator=g) + 0.5
+    res = torch.randn(2, 8, 9, 11, generator=g)
+    r = nr.bn_train_ref(x, torch.ones(8), torch.zeros(8), 1e-5, residual=res, relu=True, pool=True)
+    b = nr.bn_bwd_ref(r, torch.ones(8), gy, relu=True, pool=True, bf16=True)
+    assert not bool(b['dres'][:, :, :, 10].any()) and not bool(b['dres'][:, :, 8].any())
+    dres = b['dres'].to(torch.bfloat16)
+    keep = ~b['exempt']
+    assert nr.check(dres.double()[keep], b['dres'][keep], b['b_dres'][keep], 'dres') <= 1
+    dres[:, :, :, 10] = float('nan')
+    with pytest.raises(AssertionError):
+        nr.check(dres.double()[keep], b['dres'][keep], b['b_dres'][keep], 'dres')
+
+
+def test_checker_rejects_a_partial_tile_whose_last_column_reads_the_next_row():
+    """W = 47 = 32 + 15: the second tile of a row is partial.  A kernel that walks the map as one run of pixels takes, for the
+    right-hand taps of the row's LAST column, the first pixel of the next row where the padding's zero belongs."""
+    x, wt = _small_conv(15, n=2, cin=64, cout=32, h=5, w=47)
+    ref, absum = nr.conv_fwd_ref(x, wt)
+    assert _fwd_check(_bf16(ref.float()), ref, absum, 64) <= 1
+    n, h, w = x.shape[0], x.shape[2], x.shape[3]
+    bad = ref.clone()
+    flat = torch.nn.functional.pad(x, (0, 0, 1, 2)).reshape(n, 64, -1)               # rows -1 .. h + 1, one after the other
+    for r in range(3):                                                               # tap (r, 2) of pixel (hh, w - 1): row hh + r - 1, column w
+        for hh in range(h):
+            bad[:, :, hh, w - 1] += flat[:, :, (hh + r) * w + w] @ wt[:, :, r, 2].T
+    assert torch.equal(bad[:, :, :, :w - 1], ref[:, :, :, :w - 1])
+    with pytest.raises(AssertionError):
+        _fwd_check(_bf16(bad.float()), ref, absum, 64)
+    # one image, one row, one tap is enough
+    one = ref.clone()
+    one[1, :, 2, w - 1] += wt[:, :, 1, 2] @ x[1, :, 3, 0]
+    with pytest.raises(AssertionError):
+        _fwd_check(_bf16(one.float()), ref, absum, 64)
