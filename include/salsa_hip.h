@@ -376,6 +376,39 @@ int salsa_room_rirs(const double *images, const double *d_images, int n_images, 
                     int n_sources, const double *receivers, int n_receivers, int mode, double fs_over_c, int rir_len, float *d_out,
                     void *hip_stream);
 
+/* The MIC capsules of a shoebox room on a RIGID sphere (salsa_amd/rooms.py: baffle='rigid'; the reference has no
+ * counterpart: the definition is this project's).  The pressure of a plane wave from the unit direction u at a capsule at the unit
+ * direction m on a rigid sphere of radius R, relative to the free-field pressure at the sphere's centre, is the series
+ *     H(f, Theta) = sum_{n=0}^{N} i^n (2 n + 1) b_n(k R) P_n(cos Theta),   b_n(x) = j_n(x) - j_n'(x) / h_n^(2)'(x) h_n^(2)(x),
+ *     k = 2 pi f / c,  cos Theta = u . m,  H(0, Theta) = 1.
+ * The host (salsa_amd/rooms.py: SphereTable) turns it into a float32 table S[Q + 1][P + 1][lead + trail] of band-limited tap weights:
+ * S[q][p][j] = h_{q pi / Q}(j - (lead - 1) - p / P), h_Theta(x) = sum_n a_Theta[n] w(x - n), a_Theta the inverse real FFT of H times a
+ * raised-cosine taper, cut to a fixed support, w the Hann-windowed sinc of salsa_room_rirs; row P is row 0 one tap on.  This call only
+ * READS the table.  For source r, image i and capsule m, with d and tau measured to the array CENTRE (one distance and one delay for
+ * all four capsules: a far-field, plane-wave model),
+ *     v = sign_i o s_r + shift_i - centre,  d = |v|,  tau = d fs_over_c - t0_r,  k0 = floor(tau),  fr = tau - k0,
+ *     cos Theta_m = clamp((v . unit_m) / d, -1, 1),  qf = acos(cos Theta_m) Q / pi,  q = min(floor(qf), Q - 1),  wq = qf - q,
+ *     pf = fr P,  p = min(floor(pf), P - 1),  wp = pf - p,  j = k - k0 + lead - 1,
+ *     out[r, m, k] += g_r (A_i / d) ((1 - wq) ((1 - wp) S[q][p][j] + wp S[q][p + 1][j]) + wq ((1 - wp) S[q + 1][p][j] + wp S[q + 1][p + 1][j]))
+ * for 0 <= j < lead + trail and 0 <= k < rir_len: the image's taps are k0 - lead + 1 .. k0 + trail.  Theta = pi reads the rows Q - 1 and
+ * Q with the weights (0, 1), and no fraction reads a phase row past P.  Everything up to k0, fr, wq, wp and the coefficient g A / d is
+ * float64, each rounded once; from the table lookup on the arithmetic is float32, each tap summed over the images in TABLE ORDER: two
+ * calls give equal bits, a source's response does not depend on the other sources of the call, a capsule's row does not depend on
+ * the other capsules' directions, and a tap that no image's support reaches is +0.0.  Every element of out is written.
+ *
+ * images, sources (and their device copies) as for salsa_room_rirs.  centre double [3] and capsule_units double [4][3], HOST only, each
+ * unit of length 1 to within 1e-6.  table / d_table float32 [Q + 1][P + 1][lead + trail], host and device with equal contents; the
+ * host copy is checked entry by entry (finite) before the first device call.  salsa_room_sphere_limits writes the largest Q, P and
+ * lead + trail (4096, 1024, 512; each pointer may be NULL) and returns the largest number of table entries, 1 << 27.  1 <= Q, 1 <= P,
+ * 1 <= lead, 1 <= trail.  d_out float32 [n_sources][4][rir_len].  A source or an image AT the centre (d = 0) is the caller's to
+ * exclude.  One launch on hip_stream, nothing allocated or synchronised; a workgroup owns salsa_room_tap_block() = 256 consecutive
+ * taps of one source and all four capsules.  Returns -1 for a null pointer or an argument outside these limits, before any device
+ * call; -6 when the launch fails. */
+int salsa_room_sphere_limits(int *max_q, int *max_p, int *max_support);
+int salsa_room_rirs_sphere(const double *images, const double *d_images, int n_images, const double *sources, const double *d_sources,
+                           int n_sources, const double *centre, const double *capsule_units, const float *table, const float *d_table,
+                           int Q, int P, int lead, int trail, double fs_over_c, int rir_len, float *d_out, void *hip_stream);
+
 /* Energy decay and room-acoustic parameters of a bank of impulse responses (salsa_amd/rooms.py: rir_acoustics, calibrate_room;
  * DESIGN.md section 9n; the reference has no counterpart: the definition is this project's).  d_rirs float32 [n_rirs][n_channels]
  * [rir_len], finite.  Per (response, channel), in float64 throughout:

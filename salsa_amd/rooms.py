@@ -19,6 +19,17 @@ and rounded once; from the tap argument x on everything is float32.  The sums ru
 salsa_room_rirs); SALSA_HIP_ROOM=0, or a device that is no GPU, sends room_rir_bank to a composed torch evaluation of the same
 definition and the same split.
 
+Rigid sphere: baffle='rigid' (mic only; the default 'open' is everything above, bit for bit) puts the four
+capsules on a rigid sphere of MIC_RADIUS, the array the MIC features are written for.  sphere_response is the classical series H(f,
+Theta) = sum_n i^n (2 n + 1) b_n(k R) P_n(cos Theta) of a plane wave's pressure on the sphere; SphereTable turns it into band-limited tap
+weights h_Theta(x) = sum_n a_Theta[n] w(x - n) (a_Theta: the inverse real FFT of H times a raised-cosine taper above 9 kHz, cut to
+[-16, 32)) on a float32 table uniform in Theta (Q = 180) and in the sub-sample phase (P = 32), and a weight is the bilinear
+interpolation of four entries.  An image then adds g_r (A / d) interp(Theta_m, k - tau) to tap k of capsule m, with d and tau = d fs / c -
+t0_r measured to the array CENTRE (one distance and delay for the four capsules) and Theta_m the angle between the image's direction and
+capsule m: a plane-wave model, so a source nearer than 10 radii (0.42 m) is refused.  t0_r and d_max use the table's lead (32) for
+H.  float64 up to floor tau, the two interpolation weights and the coefficient, float32 from the table lookup on; the sums run in
+salsa_amd/csrc/room_sphere.hip (salsa_room_rirs_sphere), or in the composed torch path as above.
+
 Decay: rir_acoustics measures any response array (R, C, L) -- Schroeder's energy decay curve, EDT, T20, T30 with
 the headroom of each fit, DRR, C50 -- in float64, in salsa_amd/csrc/rir_decay.hip (include/salsa_hip.h: salsa_rir_decay, where the
 definition is written out); SALSA_HIP_DECAY=0, or a device that is no GPU, sends it to a composed torch evaluation of the same
@@ -44,6 +55,13 @@ DECAY_PARAMS = ('energy', 'peak', 'edt', 't20', 't30', 'headroom_edt', 'headroom
                 'cross_0db', 'cross_5db', 'cross_10db', 'cross_25db', 'cross_35db')   # the enum SALSA_DECAY_* of include/salsa_hip.h
 TRUNCATION_HEADROOM_DB = 15.0                               # below it a fit counts as truncated (rir_acoustics)
 DEFAULT_PROBES = ((0, 0), (90, 20), (200, -10), (-60, 0))   # calibrate_room's probe directions
+BAFFLES = ('open', 'rigid')                                 # the capsules in free space / on a rigid sphere
+SPHERE_ORDER = 48                                           # N of the series: its truncation is below float64 noise at k R = 9.3
+SPHERE_Q, SPHERE_P = 180, 32                                # the table's grid: Q steps over [0, pi], P over one sample
+SPHERE_NA, SPHERE_NB = 16, 32                               # the sphere filter's support n in [-NA, NB)
+SPHERE_NFFT = 1024                                          # the inverse real FFT that makes the sphere filter
+SPHERE_TAPER_START = 0.75                                   # of Nyquist: 9 kHz at 24 kHz, the largest fmax_doa of any feature
+FAR_FIELD_RADII = 10.0                                      # a source nearer than 10 R to the centre is refused: a plane-wave model
 
 
 def eyring_beta(size, rt60, c=SOUND_SPEED):
@@ -138,10 +156,123 @@ def room_images(room, d_max, max_order=None):
     return RoomImages(np.ascontiguousarray(n[keep]), np.ascontiguousarray(q[keep]), L, amplitude[keep], order[keep])
 
 
-def room_geometry(audio_format, room, directions, distance, length, align_direct=True, normalize_direct=True):
+# ---- the capsules on a rigid sphere -------------------------------------------------------------------------------
+def sphere_response(f, cos_theta, radius=MIC_RADIUS, c=SOUND_SPEED):
+    """H(f, Theta), complex128: the pressure of a plane wave of frequency f (Hz, >= 0) at a point of a rigid sphere of `radius` metres at
+    the angle Theta from the wave's direction of arrival, relative to the free-field pressure at the centre:
+        H = sum_{n=0}^{48} i^n (2 n + 1) b_n(k R) P_n(cos Theta),  b_n(x) = j_n(x) - j_n'(x) / h_n^(2)'(x) h_n^(2)(x),  H(0, .) = 1.
+    b_n is evaluated as -i / (x^2 h_n^(2)'(x)), the same number by the Wronskian j_n y_n' - j_n' y_n = 1 / x^2 (no cancellation, and an
+    order whose y_n' overflows contributes its limit, 0).  With numpy's irfft sign convention H is causal and an advance at Theta = 0."""
+    from scipy.special import eval_legendre, spherical_jn, spherical_yn
+    f, ct = np.asarray(f, np.float64), np.asarray(cos_theta, np.float64)
+    if not (np.all(f >= 0) and np.all(np.abs(ct) <= 1) and radius > 0 and c > 0):
+        raise ValueError('f >= 0, |cos_theta| <= 1, radius and c positive')
+    x = 2.0 * np.pi * f * (float(radius) / float(c))
+    live = x > 0
+    xs = np.where(live, x, 1.0)                                               # (b_n on f's own shape, P_n on cos_theta's)
+    out = np.zeros(np.broadcast(f, ct).shape, np.complex128)
+    with np.errstate(over='ignore', invalid='ignore', divide='ignore'):
+        for n in range(SPHERE_ORDER + 1):
+            jp, yp = spherical_jn(n, xs, derivative=True), spherical_yn(n, xs, derivative=True)
+            ok = np.isfinite(yp)
+            b = np.where(ok, -1j / (xs * xs * (jp - 1j * np.where(ok, yp, 1.0))), 0.0)
+            out = out + (1j ** n * (2 * n + 1)) * b * eval_legendre(n, ct)
+    return np.where(live, out, 1.0 + 0.0j)
+
+
+def _windowed_sinc(x):
+    """the project's w(x) = sinc(x) (1 + cos(pi x / H)) / 2 for |x| < H = SINC_HALF, else 0, float64"""
+    return np.where(np.abs(x) < SINC_HALF, np.sinc(x) * 0.5 * (1.0 + np.cos(np.pi * x / SINC_HALF)), 0.0)
+
+
+def sphere_filter(cos_theta, radius=MIC_RADIUS, fs=FS, c=SOUND_SPEED):
+    """a_Theta[n] PERIODIC over SPHERE_NFFT taps (index n mod SPHERE_NFFT), float64 (..., SPHERE_NFFT): the inverse real FFT of H(f_l,
+    Theta) T(f_l), T = 1 up to SPHERE_TAPER_START of Nyquist and a raised cosine down to 0 at Nyquist"""
+    ct = np.asarray(cos_theta, np.float64)
+    f = np.arange(SPHERE_NFFT // 2 + 1, dtype=np.float64) * (float(fs) / SPHERE_NFFT)
+    f0, f1 = SPHERE_TAPER_START * 0.5 * fs, 0.5 * fs
+    taper = np.where(f <= f0, 1.0, 0.5 * (1.0 + np.cos(np.pi * (f - f0) / (f1 - f0))))
+    taper[-1] = 0.0
+    return np.fft.irfft(sphere_response(f, ct[..., None], radius, c) * taper, SPHERE_NFFT, axis=-1)
+
+
+class SphereTable:
+    """The rigid sphere's band-limited tap weights as the table the kernel and the torch path read.
+    h_Theta(x) = sum_{n = -NA}^{NB - 1} a_Theta[n] w(x - n) vanishes outside (-lead, trail), lead = NA + SINC_HALF, trail = NB + SINC_HALF - 1.
+    .table float32 (Q + 1, P + 1, lead + trail): table[q, p, j] = h_{q pi / Q}(j - (lead - 1) - p / P), computed in float64 and rounded
+    once; row P is row 0 one tap on.  A weight is the bilinear interpolation of four entries: weights()."""
+
+    def __init__(self, radius=MIC_RADIUS, fs=FS, c=SOUND_SPEED):
+        self.radius, self.fs, self.c = float(radius), float(fs), float(c)
+        if not (self.radius > 0 and self.fs > 0 and self.c > 0):
+            raise ValueError('radius, fs and c are positive')
+        self.Q, self.P = SPHERE_Q, SPHERE_P
+        self.lead, self.trail = SPHERE_NA + SINC_HALF, SPHERE_NB + SINC_HALF - 1
+        a = sphere_filter(np.cos(np.arange(self.Q + 1) * (np.pi / self.Q)), self.radius, self.fs, self.c)
+        taps = np.arange(-SPHERE_NA, SPHERE_NB)
+        a = a[:, taps % SPHERE_NFFT]                                          # (Q + 1, NA + NB)
+        x = (np.arange(self.lead + self.trail) - (self.lead - 1))[None, :] - (np.arange(self.P + 1) / self.P)[:, None]
+        table = (a @ _windowed_sinc(x.reshape(-1)[None, :] - taps[:, None])).reshape(self.Q + 1, self.P + 1, -1)
+        table[:, self.P, 1:], table[:, self.P, 0] = table[:, 0, :-1], 0.0      # row P IS row 0 one tap on
+        self.table = np.ascontiguousarray(table, np.float32)
+        self.table.setflags(write=False)
+        self._device = {}
+
+    def weights(self, theta, x):
+        """The interpolated definition in float64: the weight of a tap at x = k - tau samples from an image's delay, at the angle theta
+        (radians, [0, pi]) -- the bilinear interpolation of the float32 table's four entries around (theta Q / pi, frac(tau) P)."""
+        theta, x = np.broadcast_arrays(np.asarray(theta, np.float64), np.asarray(x, np.float64))
+        if not (np.all(theta >= 0) and np.all(theta <= np.pi)):
+            raise ValueError('0 <= theta <= pi')
+        jp = np.ceil(x)                                                       # x = j' - frac, 0 <= frac < 1
+        qf, pf = theta * (self.Q / np.pi), (jp - x) * self.P
+        q, p = np.clip(np.floor(qf), 0, self.Q - 1).astype(np.int64), np.clip(np.floor(pf), 0, self.P - 1).astype(np.int64)
+        wq, wp = qf - q, pf - p
+        j = jp.astype(np.int64) + (self.lead - 1)
+        inside = (j >= 0) & (j < self.lead + self.trail)
+        j = np.clip(j, 0, self.lead + self.trail - 1)
+        t = self.table.astype(np.float64)
+        v = (1.0 - wq) * ((1.0 - wp) * t[q, p, j] + wp * t[q, p + 1, j]) + wq * ((1.0 - wp) * t[q + 1, p, j] + wp * t[q + 1, p + 1, j])
+        return np.where(inside, v, 0.0)
+
+    def on(self, device):
+        """the table as a tensor on `device`, uploaded once"""
+        import torch
+        key = str(torch.device(device))
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self.table.copy()).to(device)
+        return self._device[key]
+
+
+_SPHERE_TABLES = {}
+
+
+def sphere_table(radius=MIC_RADIUS, fs=FS, c=SOUND_SPEED):
+    """the SphereTable of (radius, fs, c), built once"""
+    key = (float(radius), float(fs), float(c))
+    if key not in _SPHERE_TABLES:
+        _SPHERE_TABLES[key] = SphereTable(*key)
+    return _SPHERE_TABLES[key]
+
+
+def _capsule_units():
+    return _unit([m[0] for m in MIC_DIRECTIONS], [m[1] for m in MIC_DIRECTIONS])
+
+
+def _check_baffle(audio_format, baffle):
+    if baffle not in BAFFLES:
+        raise ValueError("baffle is 'open' or 'rigid'")
+    if baffle == 'rigid' and audio_format != 'mic':
+        raise ValueError("baffle='rigid' is the mic format's: the foa format has one receiver point and no sphere")
+    return baffle == 'rigid'
+
+
+def room_geometry(audio_format, room, directions, distance, length, align_direct=True, normalize_direct=True, baffle='open'):
     """-> (directions int64 (R, 2), sources float64 (R, 5): position, t0, g; receivers float64 (M, 3); d_max: the distance past which no
     image reaches a tap below `length`).  Raises ValueError unless every source and receiver lies strictly inside the room and every
-    source is at least 1 mm from every receiver."""
+    source is at least 1 mm from every receiver.  baffle='rigid' (mic only): t0 and d_max take the sphere table's lead for SINC_HALF, and
+    a source nearer than FAR_FIELD_RADII = 10 sphere radii (0.42 m) to the centre is refused -- the limit of the plane-wave model."""
+    lead = sphere_table(MIC_RADIUS, room.fs, room.c).lead if _check_baffle(audio_format, baffle) else SINC_HALF
     directions = np.asarray(directions, np.int64).reshape(-1, 2)
     R = len(directions)
     if not 1 <= R <= MAX_SOURCES:
@@ -159,19 +290,65 @@ def room_geometry(audio_format, room, directions, distance, length, align_direct
     if np.sqrt(((pos[:, None] - rec[None]) ** 2).sum(axis=-1)).min() < MIN_DISTANCE:
         raise ValueError('a source lies within %g m of a receiver' % MIN_DISTANCE)
     centre = np.sqrt(((pos - room.array[None]) ** 2).sum(axis=-1))            # |s_r - a|
-    t0 = np.maximum(0.0, np.floor(centre * room.fs / room.c) - SINC_HALF) if align_direct else np.zeros(R)
+    if baffle == 'rigid' and centre.min() < FAR_FIELD_RADII * MIC_RADIUS:
+        raise ValueError('a source lies within %g m of the array centre: the rigid sphere is a plane-wave model' % (FAR_FIELD_RADII * MIC_RADIUS))
+    t0 = np.maximum(0.0, np.floor(centre * room.fs / room.c) - lead) if align_direct else np.zeros(R)
     g = centre if normalize_direct else np.ones(R)
     if not np.all(g > 0):
         raise ValueError('normalize_direct needs every source away from the array centre')
-    d_max = (int(length) + SINC_HALF + float(t0.max())) * room.c / room.fs * (1.0 + 1e-9)
+    d_max = (int(length) + lead + float(t0.max())) * room.c / room.fs * (1.0 + 1e-9)
     return directions, np.ascontiguousarray(np.concatenate([pos, t0[:, None], g[:, None]], axis=1)), np.ascontiguousarray(rec), d_max
 
 
-def _rirs_torch(table, sources, receivers, foa, fs_over_c, length, device):
+def _rirs_torch_sphere(table, sources, sphere, fs_over_c, length, device):
+    """_rirs_torch's rigid case, sphere = (SphereTable, centre (3,), capsule units (4, 3)): section 9o's definition with the kernel's
+    split -- float64 up to floor tau, the two interpolation weights and the coefficient, float32 from the table lookup on -- per
+    (source, capsule) the images' lead + trail taps as one array, added by index_add_."""
+    import torch
+    st, centre, units = sphere
+    Q, P, lead, trail = st.Q, st.P, st.lead, st.trail
+    S = st.on(device)
+    tb = torch.from_numpy(table).to(device)
+    sign, shift, amp = tb[0:3].T, tb[3:6].T, tb[6]
+    src, ctr, um = (torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(device) for a in (sources, centre, units))
+    out = torch.zeros((len(sources), 4, length), dtype=torch.float32, device=device)
+    j = torch.arange(1 - lead, trail + 1, device=device)
+    for r in range(len(sources)):
+        delta = sign * src[r, :3] + shift - ctr
+        d = torch.sqrt((delta * delta).sum(dim=1))
+        tau = d * fs_over_c - src[r, 3]
+        tf = torch.floor(tau)
+        sel = torch.nonzero((tf >= -trail) & (tf <= length + lead - 2)).reshape(-1)      # the support meets [0, length)
+        if not len(sel):
+            continue
+        delta, d = delta[sel], d[sel]
+        k = tf[sel].to(torch.int64)[:, None] + j[None]
+        pf = (tau[sel] - tf[sel]) * P
+        p = pf.floor().clamp(0, P - 1).to(torch.int64)
+        wp = (pf - p).to(torch.float32)[:, None]
+        co = (src[r, 4] * amp[sel] / d).to(torch.float32)[:, None]
+        inside = (k >= 0) & (k < length)
+        kk = k.clamp(0, length - 1).reshape(-1)
+        for m in range(4):
+            cos = ((delta[:, 0] * um[m, 0] + delta[:, 1] * um[m, 1] + delta[:, 2] * um[m, 2]) / d).clamp(-1.0, 1.0)
+            qf = torch.acos(cos) * (Q / np.pi)
+            q = qf.floor().clamp(0, Q - 1).to(torch.int64)
+            wq = (qf - q).to(torch.float32)[:, None]
+            e0 = (1.0 - wp) * S[q, p] + wp * S[q, p + 1]
+            e1 = (1.0 - wp) * S[q + 1, p] + wp * S[q + 1, p + 1]
+            v = torch.where(inside, co * ((1.0 - wq) * e0 + wq * e1), torch.zeros((), dtype=torch.float32, device=device))
+            out[r, m].index_add_(0, kk, v.reshape(-1))
+    return out
+
+
+def _rirs_torch(table, sources, receivers, foa, fs_over_c, length, device, sphere=None):
     """The definition composed from torch calls with the kernel's precision split (SALSA_HIP_ROOM=0, and any device that is no GPU):
     per (source, receiver) the images' 2 H taps as one (images, 2 H) array, float64 up to the tap argument, float32 from it on, added
-    into the response by index_add_ in float32 (in table order on the CPU; a GPU adds them in no promised order)."""
+    into the response by index_add_ in float32 (in table order on the CPU; a GPU adds them in no promised order).  sphere: the rigid
+    case, _rirs_torch_sphere."""
     import torch
+    if sphere is not None:
+        return _rirs_torch_sphere(table, sources, sphere, fs_over_c, length, device)
     H = SINC_HALF
     tb = torch.from_numpy(table).to(device)
     sign, shift, amp = tb[0:3].T, tb[3:6].T, tb[6]
@@ -201,8 +378,29 @@ def _rirs_torch(table, sources, receivers, foa, fs_over_c, length, device):
     return out
 
 
-def _rirs_hip(table, sources, receivers, foa, fs_over_c, length, device):
+def _rirs_hip_sphere(table, sources, sphere, fs_over_c, length, device):
     import torch
+    L = _lib.load()
+    st, centre, units = sphere
+    centre, units = np.ascontiguousarray(centre, np.float64), np.ascontiguousarray(units, np.float64)
+    R = len(sources)
+    out = torch.empty((R, 4, length), dtype=torch.float32, device=device)
+    d_table, d_sources, d_sphere = torch.from_numpy(table).to(device), torch.from_numpy(sources).to(device), st.on(device)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    with torch.cuda.device(device):
+        rc = L.salsa_room_rirs_sphere(hp(table), C.c_void_p(d_table.data_ptr()), table.shape[1], hp(sources), C.c_void_p(d_sources.data_ptr()), R,
+                                      hp(centre), hp(units), hp(st.table), C.c_void_p(d_sphere.data_ptr()), st.Q, st.P, st.lead, st.trail,
+                                      fs_over_c, length, C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    if rc:
+        raise RuntimeError('salsa_room_rirs_sphere failed (%d): %s' % (rc, _lib.last_error()))
+    torch.cuda.current_stream(device).synchronize()                           # the tables may go now
+    return out
+
+
+def _rirs_hip(table, sources, receivers, foa, fs_over_c, length, device, sphere=None):
+    import torch
+    if sphere is not None:
+        return _rirs_hip_sphere(table, sources, sphere, fs_over_c, length, device)
     L = _lib.load()
     R, M = len(sources), len(receivers)
     out = torch.empty((R, 4 if foa else M, length), dtype=torch.float32, device=device)
@@ -218,26 +416,37 @@ def _rirs_hip(table, sources, receivers, foa, fs_over_c, length, device):
     return out
 
 
-def room_rirs(audio_format, room, directions, distance, length, max_order=None, align_direct=True, normalize_direct=True, device=None):
-    """The responses as a float32 tensor (R, C, length) on `device` (None: 'cuda'), and the directions: what room_rir_bank wraps."""
+def room_rirs(audio_format, room, directions, distance, length, max_order=None, align_direct=True, normalize_direct=True, device=None,
+              baffle='open'):
+    """The responses as a float32 tensor (R, C, length) on `device` (None: 'cuda'), and the directions: what room_rir_bank wraps.
+    baffle='rigid' (mic only) puts the four capsules on a rigid sphere of MIC_RADIUS."""
     import torch
-    directions, sources, receivers, d_max = room_geometry(audio_format, room, directions, distance, length, align_direct, normalize_direct)
+    directions, sources, receivers, d_max = room_geometry(audio_format, room, directions, distance, length, align_direct, normalize_direct,
+                                                          baffle)
     images = room_images(room, d_max, max_order)
     if not 1 <= len(images) <= MAX_IMAGES:
         raise ValueError('the room has %d images within reach of %d taps; 1 .. %d are supported' % (len(images), length, MAX_IMAGES))
     device = torch.device('cuda' if device is None else device)
     run = _rirs_hip if HIP_ROOM and device.type == 'cuda' else _rirs_torch
+    if baffle == 'rigid':
+        sphere = (sphere_table(MIC_RADIUS, room.fs, room.c), room.array, _capsule_units())
+        return run(images.table(), sources, receivers, False, room.fs / room.c, int(length), device, sphere=sphere), directions
     return run(images.table(), sources, receivers, audio_format == 'foa', room.fs / room.c, int(length), device), directions
 
 
-def room_rir_bank(audio_format, room, directions, distance, length, max_order=None, align_direct=True, normalize_direct=True, device=None):
+def room_rir_bank(audio_format, room, directions, distance, length, max_order=None, align_direct=True, normalize_direct=True, device=None,
+                  baffle='open'):
     """-> RirBank of the image-source responses of `room` for `directions` = [(azimuth, elevation), ...] in integer degrees, each at
     `distance` metres (one number, or one per direction) from the array centre.  max_order: the highest reflection order, None for
     every image that reaches a tap below `length`.  device: where the responses are generated, None for 'cuda'; on a GPU the
     bank's partition spectra for that device are made there too, before the download, so the renderer does not upload them again.
     device='cpu' (the torch path) needs no GPU.  A room given by rt60 realises a LONGER decay than the nominal one (ShoeboxRoom):
-    bank.acoustics() measures it, and calibrate_room gives the room that realises a wanted decay."""
-    h, directions = room_rirs(audio_format, room, directions, distance, length, max_order, align_direct, normalize_direct, device)
+    bank.acoustics() measures it, and calibrate_room gives the room that realises a wanted decay.
+    baffle: 'open' -- the mic format's capsules are four points in free space -- or 'rigid' (mic only): they sit on a rigid sphere of
+    MIC_RADIUS, the array the MIC features are written for.  Each image then reaches all four capsules through
+    one distance and delay to the array centre and a direction-dependent filter per capsule, a plane-wave model that refuses a source
+    nearer than 0.42 m; the direct path then peaks between tap lead - 3 and lead + 5 (lead = 32), not at SINC_HALF."""
+    h, directions = room_rirs(audio_format, room, directions, distance, length, max_order, align_direct, normalize_direct, device, baffle)
     spec = rir_spectra(h) if h.is_cuda else None                              # on the device, from the very values the bank will hold
     bank = RirBank(h.cpu().numpy(), directions[:, 0], directions[:, 1], audio_format)
     if spec is not None:
@@ -374,7 +583,7 @@ def _length_for(measure, seconds, fs):
 
 
 def calibrate_room(size, rt60, measure='t20', array=None, audio_format='foa', directions=None, distance=1.0, length=None,
-                   absorption_ratio=None, rtol=0.01, max_iter=8, max_order=None, device=None, fs=FS, c=SOUND_SPEED):
+                   absorption_ratio=None, rtol=0.01, max_iter=8, max_order=None, device=None, fs=FS, c=SOUND_SPEED, baffle='open'):
     """-> ShoeboxRoom(size, beta=...) whose MEASURED decay is rt60 seconds: the mean of `measure` ('edt', 't20' or 't30') on channel 0
     over probe responses generated by room_rirs on `device` (None: 'cuda'; 'cpu' needs no GPU) is within rtol of rt60.
     The walls are beta_w = exp(-s a_w), a = absorption_ratio, six weights >= 0 in the order of beta (None: all one, a uniform beta),
@@ -386,7 +595,8 @@ def calibrate_room(size, rt60, measure='t20', array=None, audio_format='foa', di
     at an earlier step only slows the search), and when a beta would leave [0, 1) on every absorbing wall: a lossless room has no
     decay time.  The room's .rt60 stays None (that attribute is the nominal figure of Eyring's formula); .calibration is a dict:
     measure, target, realised (the mean), probes (the per-probe values), headroom_db (per probe), beta_history (one array of six per
-    evaluation), evaluations, directions, distance, length."""
+    evaluation), evaluations, directions, distance, length.  baffle: as for room_rirs; 'rigid' needs audio_format='mic'."""
+    _check_baffle(audio_format, baffle)
     if measure not in DECAY_FITS:
         raise ValueError('measure is one of %s' % ', '.join(sorted(DECAY_FITS)))
     target, fs = float(rt60), float(fs)
@@ -408,7 +618,7 @@ def calibrate_room(size, rt60, measure='t20', array=None, audio_format='foa', di
             raise ValueError('a reflection coefficient would leave [0, 1) (s = %g): no absorbing room decays in %g s' % (s, target))
         history.append(beta)
         room = ShoeboxRoom(size, beta=beta, array=array, fs=fs, c=c)
-        h, _ = room_rirs(audio_format, room, directions, distance, length, max_order, device=device)
+        h, _ = room_rirs(audio_format, room, directions, distance, length, max_order, device=device, baffle=baffle)
         got = rir_acoustics(h, fs=fs)
         T, bad = getattr(got, measure)[:, 0], got.truncated(measure)[:, 0]
         mean = float(T.mean())

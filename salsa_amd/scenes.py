@@ -106,18 +106,39 @@ def rir_spectra(d_rirs):
     return spec
 
 
-def make_rir_bank(audio_format, directions, length, rt60=None, drr_db=6.0, seed=0, fs=FS):
+def _rigid_direct(d, length, fs):
+    """make_rir_bank('mic', baffle='rigid'): the free-field direct path on the rigid sphere, float64 (R, 4, length) and the tail's start"""
+    from . import rooms
+    st = rooms.sphere_table(MIC_RADIUS, fs, SOUND_SPEED)
+    t0 = st.lead + st.trail
+    if length < t0 + 1:
+        raise ValueError('a rigid mic response needs at least %d taps' % (t0 + 1))
+    theta = np.arccos(np.clip(d @ _unit([m[0] for m in MIC_DIRECTIONS], [m[1] for m in MIC_DIRECTIONS]).T, -1.0, 1.0))      # (R, 4)
+    h = np.zeros((len(d), 4, length), np.float64)
+    h[:, :, :t0 + 1] = st.weights(theta[:, :, None], np.arange(t0 + 1, dtype=np.float64)[None, None, :] - st.lead)
+    return h, t0
+
+
+def make_rir_bank(audio_format, directions, length, rt60=None, drr_db=6.0, seed=0, fs=FS, baffle='open'):
     """Synthetic responses for `directions` = [(azimuth, elevation), ...] in integer degrees, float64 -> float32.
     foa: channels W, Y, Z, X (the order the reference's FOA transform documents); the direct path is ONE tap (index 0) with the gains
     (1, sin az cos el, sin el, cos az cos el).  mic: the TNSSE tetrahedron, a plane wave from the direction; microphone m hears it
     p_m . d / c seconds early, a Hann-windowed-sinc fractional delay around tap SINC_HALF (length >= 2 SINC_HALF + 1).
     rt60 (seconds): adds a diffuse tail after the direct path, Gaussian noise independent per channel decaying by 60 dB per rt60, whose
-    energy per channel is the first channel's direct energy / 10^(drr_db / 10); RandomState(seed) stream, frozen by numpy."""
+    energy per channel is the first channel's direct energy / 10^(drr_db / 10); RandomState(seed) stream, frozen by numpy.
+    baffle='rigid' (mic only): the capsules sit on a rigid sphere of MIC_RADIUS; the direct path is rooms.
+    SphereTable.weights at each capsule's angle from the direction, the array centre at tap `lead`, the tail after tap lead + trail."""
     directions = np.asarray(directions, np.int64).reshape(-1, 2)
     d = _unit(directions[:, 0], directions[:, 1])                             # (R, 3)
     R = len(d)
     h = np.zeros((R, 4, length), np.float64)
-    if audio_format == 'foa':
+    if baffle not in ('open', 'rigid'):
+        raise ValueError("baffle is 'open' or 'rigid'")
+    if baffle == 'rigid':
+        if audio_format != 'mic':
+            raise ValueError("baffle='rigid' is the mic format's")
+        h, t0 = _rigid_direct(d, length, fs)
+    elif audio_format == 'foa':
         h[:, 0, 0], h[:, 1, 0], h[:, 2, 0], h[:, 3, 0] = 1.0, d[:, 1], d[:, 2], d[:, 0]
         t0 = 0
     elif audio_format == 'mic':
@@ -528,11 +549,11 @@ def add_scenes(feature_bank, scenes, pool, bank, names=None, ambient=None, n_cla
 
 
 _ROOMS = ('ShoeboxRoom', 'RoomImages', 'room_images', 'room_rirs', 'room_rir_bank', 'eyring_beta', 'RirAcoustics', 'rir_acoustics',
-          'calibrate_room')
+          'calibrate_room', 'sphere_response', 'sphere_filter', 'SphereTable', 'sphere_table')
 
 
 def __getattr__(name):
-    """rooms.py (DESIGN.md sections 9m, 9n: image-source responses of a shoebox room as a RirBank, their decay) builds on this module, so its public names
+    """rooms.py (DESIGN.md sections 9m, 9n, 9o: image-source responses of a shoebox room as a RirBank, their decay, the rigid sphere) builds on this module, so its public names
     are re-exported on first use, not at import"""
     if name in _ROOMS:
         from . import rooms

@@ -11,7 +11,10 @@ Shapes: FOA and MIC banks of 72 directions (azimuth every 5 degrees) and one FOA
 recorded with each shape, and so is the time of salsa_room_rirs' launch alone (device events, tables already uploaded; it includes the
 launcher's host-side check of the table).  One JSON line per record; whatever is seen is reported, a leg that loses included.
 
-    python tools/bench_rooms.py [--rounds 5] [--host-rounds 2] [--warmup 1] [--out profiles/room_rir_bench.jsonl]"""
+--baffle rigid measures the MIC bank of 72 directions with the capsules on the rigid sphere instead: rigid(),
+whose docstring lists its legs; the two launches alone share one image table (the rigid geometry's).
+
+    python tools/bench_rooms.py [--baffle rigid] [--rounds 5] [--host-rounds 2] [--warmup 1] [--out profiles/room_rir_bench.jsonl]"""
 import argparse
 import json
 import os
@@ -49,8 +52,100 @@ def launch_ms(table, sources, receivers, foa, fs_over_c, length, dev, warmup, ro
     return ms
 
 
+def sphere_launch_ms(table, sources, room, length, dev, samples):
+    """salsa_room_rirs_sphere and salsa_room_rirs (open MIC) alone, ALTERNATING, their tables already on the device: device events
+    around one launch per sample (each includes its launcher's host-side checks) -> (rigid ms, open ms) per sample"""
+    import ctypes as C
+    import numpy as np
+    import torch
+    from salsa_amd import _lib, rooms
+    L = _lib.load()
+    st = rooms.sphere_table(rooms.MIC_RADIUS, room.fs, room.c)
+    centre, units, receivers = np.ascontiguousarray(room.array), np.ascontiguousarray(rooms._capsule_units()), room.receivers('mic')
+    d_table, d_sources, d_sphere = torch.from_numpy(table).to(dev), torch.from_numpy(sources).to(dev), st.on(dev)
+    out = torch.empty((len(sources), 4, length), dtype=torch.float32, device=dev)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    common = (hp(table), C.c_void_p(d_table.data_ptr()), table.shape[1], hp(sources), C.c_void_p(d_sources.data_ptr()), len(sources))
+    calls = (lambda: L.salsa_room_rirs_sphere(*common, hp(centre), hp(units), hp(st.table), C.c_void_p(d_sphere.data_ptr()), st.Q, st.P, st.lead,
+                                              st.trail, room.fs / room.c, length, C.c_void_p(out.data_ptr()), stream),
+             lambda: L.salsa_room_rirs(*common, hp(receivers), 4, 0, room.fs / room.c, length, C.c_void_p(out.data_ptr()), stream))
+    ms = ([], [])
+    for r in range(samples[0] + samples[1]):
+        for which, call in enumerate(calls):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            rc = call()
+            b.record()
+            torch.cuda.synchronize()
+            if rc:
+                raise RuntimeError(_lib.last_error())
+            if r >= samples[0]:
+                ms[which].append(a.elapsed_time(b))
+    return ms
+
+
+def rigid(args):
+    """--baffle rigid: the MIC bank of 72 directions with the capsules on the rigid sphere.  Legs, one sample of
+    each per round: a HIP rigid, a' HIP open (the same bank in free space, alternating with a), b the rigid torch path on the device,
+    c the same on the host.  Whole calls of room_rir_bank, and the two launches alone, alternating."""
+    import numpy as np
+    import torch
+    from salsa_amd import rooms
+    dev = torch.device('cuda:0')
+    room = rooms.ShoeboxRoom((6.0, 5.0, 3.2), rt60=0.3)
+    n_dir = 72
+    directions = [(az, 0) for az in range(-180, 180, 360 // n_dir)]
+    _, sources, _, d_max = rooms.room_geometry('mic', room, directions, args.distance, args.rir_len, baffle='rigid')
+    images = rooms.room_images(room, d_max)
+    st = rooms.sphere_table(rooms.MIC_RADIUS, room.fs, room.c)
+    legs = {'a HIP rigid': (True, dev, 'rigid'), "a' HIP open": (True, dev, 'open'), 'b torch rigid, device': (False, dev, 'rigid'),
+            'c torch rigid, host': (False, 'cpu', 'rigid')}
+    times, last = {k: [] for k in legs}, {}
+    for r in range(args.warmup + max(args.rounds, args.host_rounds)):
+        for leg, (hip, where, baffle) in legs.items():
+            host = where == 'cpu'
+            if r >= (args.host_rounds if host else args.warmup + args.rounds):
+                continue
+            rooms.HIP_ROOM = hip
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            bank = rooms.room_rir_bank('mic', room, directions, args.distance, args.rir_len, device=where, baffle=baffle)
+            torch.cuda.synchronize()
+            if host or r >= args.warmup:
+                times[leg].append((time.perf_counter() - t0) * 1e3)
+            last[leg] = bank.rirs
+    rooms.HIP_ROOM = True
+    rigid_ms, open_ms = sphere_launch_ms(images.table(), sources, room, args.rir_len, dev, (args.warmup, args.rounds))
+    recs = []
+    for leg, (_, _, baffle) in legs.items():
+        t = np.array(times[leg])
+        recs.append(dict(bench='room_rir_sphere', format='mic', baffle=baffle, directions=n_dir, rir_len=args.rir_len, room=[6.0, 5.0, 3.2],
+                         rt60_nominal=0.3, beta=round(float(room.beta[0]), 6), distance=args.distance, images=len(images), leg=leg,
+                         ms_median=round(float(np.median(t)), 2), ms_min=round(float(t.min()), 2), ms_max=round(float(t.max()), 2), samples=len(t),
+                         max_abs_difference_from_leg_a=None if baffle == 'open' else float(np.abs(last[leg] - last['a HIP rigid']).max()),
+                         max_abs_response=round(float(np.abs(last[leg]).max()), 4), device=torch.cuda.get_device_name(0)))
+    med = {leg: float(np.median(times[leg])) for leg in legs}
+    rm, om = float(np.median(rigid_ms)), float(np.median(open_ms))
+    recs.append(dict(bench='room_rir_sphere', format='mic', directions=n_dir, rir_len=args.rir_len, table=list(st.table.shape), lead=st.lead, trail=st.trail,
+                     rigid_launch_alone_ms_median=round(rm, 3), rigid_launch_alone_ms_min=round(min(rigid_ms), 3), rigid_launch_alone_ms_max=round(max(rigid_ms), 3),
+                     open_launch_alone_ms_median=round(om, 3), open_launch_alone_ms_min=round(min(open_ms), 3), open_launch_alone_ms_max=round(max(open_ms), 3),
+                     launch_alone_samples=len(rigid_ms), rigid_over_open_launch=round(rm / om, 2),
+                     taps_visited_per_image_rigid_over_open=round((st.lead + st.trail) / 32.0, 2),
+                     rigid_over_open_whole_call=round(med['a HIP rigid'] / med["a' HIP open"], 2),
+                     b_over_a=round(med['b torch rigid, device'] / med['a HIP rigid'], 2), c_over_a=round(med['c torch rigid, host'] / med['a HIP rigid'], 2)))
+    for rec in recs:
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, 'a') as f:
+                f.write(line + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--baffle', choices=['open', 'rigid'], default='open', help='rigid: the legs of the rigid-sphere MIC bank instead')
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--host-rounds', type=int, default=2, help='samples of leg c')
     ap.add_argument('--warmup', type=int, default=1)
@@ -63,6 +158,8 @@ def main():
     from salsa_amd import rooms
     if not torch.cuda.is_available():
         raise SystemExit('bench_rooms.py measures on cuda:0; there is none')
+    if args.baffle == 'rigid':
+        return rigid(args)
     dev = torch.device('cuda:0')
     room = rooms.ShoeboxRoom((6.0, 5.0, 3.2), rt60=0.3)
     shapes = [('foa', 72), ('mic', 72), ('foa', 360)]

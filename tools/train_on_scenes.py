@@ -4,13 +4,15 @@ drawn from different seeds over ONE event pool and ONE response bank (salsa_amd/
 GpuFeatureBanks, and Trainer.fit runs a few epochs.  The SELD 2021 scores on the held-out scenes are recorded before training and
 after every epoch.  No score is promised; the JSON lines say what was seen.
 
-    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--moving 0.5] [--room] [--out profiles/scene_training.jsonl]
+    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--moving 0.5] [--room] [--format mic --baffle rigid] [--out profiles/scene_training.jsonl]
 
 --moving FRACTION makes that share of the items move in azimuth in the training and the held-out scenes alike, so
 the ground truth's directions change inside events; 0 (the default) leaves the run as it was.
 --room takes the responses from room_rir_bank instead of make_rir_bank: the same 48 directions, sources at
 --distance metres from the centre of a 6 x 5 x 3.2 m shoebox whose uniform reflection coefficient is Eyring's for --rt60 (a nominal
-figure: the realised decay is longer), generated on the device."""
+figure: the realised decay is longer), generated on the device.
+--format mic renders the four capsules of the TNSSE tetrahedron and extracts SALSA-MIC (fmax_doa 4 kHz); --baffle rigid puts them on the
+rigid sphere, --baffle open (the default) leaves them in free space.  Each run is ONE run."""
 import argparse
 import json
 import os
@@ -35,8 +37,14 @@ def main():
     ap.add_argument('--moving', type=float, default=0.0, help='fraction of items that move (DESIGN.md section 9l); 0: the run as it was')
     ap.add_argument('--room', action='store_true', help='image-source responses of a shoebox room (DESIGN.md section 9m) instead of make_rir_bank')
     ap.add_argument('--distance', type=float, default=1.5, help='--room: metres from the array centre to every source')
+    ap.add_argument('--format', choices=['foa', 'mic'], default='foa', help='mic: the TNSSE tetrahedron, SALSA-MIC features up to 4 kHz')
+    ap.add_argument('--baffle', choices=['open', 'rigid'], default='open',
+                    help='--format mic: the capsules in free space, or on the rigid sphere of DESIGN.md section 9o')
     ap.add_argument('--out', default=None, help='append the JSON lines to this file too')
     args = ap.parse_args()
+    if args.baffle == 'rigid' and args.format != 'mic':
+        ap.error('--baffle rigid needs --format mic')
+    baffle = dict(baffle=args.baffle) if args.format == 'mic' else {}
     import numpy as np
     import torch
     from salsa_amd import scenes as sc
@@ -64,13 +72,13 @@ def main():
     if args.room:
         room = sc.ShoeboxRoom((6.0, 5.0, 3.2), rt60=args.rt60)
         t0 = time.perf_counter()
-        rbank = sc.room_rir_bank('foa', room, directions, args.distance, args.rir_len, device=dev)
+        rbank = sc.room_rir_bank(args.format, room, directions, args.distance, args.rir_len, device=dev, **baffle)
         room_rec = dict(room=[6.0, 5.0, 3.2], beta=round(float(room.beta[0]), 6), rt60_is='nominal (Eyring); the realised decay is longer',
                         distance=args.distance, seconds_to_generate_the_bank=round(time.perf_counter() - t0, 3),
                         response_energy_after_the_first_50_taps=round(float((rbank.rirs[:, 0, 50:] ** 2).sum() / (rbank.rirs[:, 0] ** 2).sum()), 4))
     else:
-        rbank = sc.make_rir_bank('foa', directions, args.rir_len, rt60=args.rt60, seed=1)
-    ex = SalsaExtractor(audio_format='foa', fmax_doa=9000, device=dev)
+        rbank = sc.make_rir_bank(args.format, directions, args.rir_len, rt60=args.rt60, seed=1, **baffle)
+    ex = SalsaExtractor(audio_format=args.format, fmax_doa=9000 if args.format == 'foa' else 4000, device=dev)
     t0 = time.perf_counter()
     banks, drawn = {}, {}
     for name, clips, seed in (('train', args.train_clips, args.seed), ('val', args.val_clips, args.seed + 1000)):
@@ -91,7 +99,7 @@ def main():
     val_gt = [[(int(f), int(c), float(az), float(el), int(t)) for f, c, t, az, el in sc.scene_rows(drawn['val'][b])] for b in range(args.val_clips)]
     emit(dict(record='scene_training', what='setup', train_clips=args.train_clips, val_clips=args.val_clips, clip_s=args.clip_s,
               train_items=int(drawn['train'].n_items), val_items=int(drawn['val'].n_items), train_chunks=len(banks['train']), classes=NC,
-              responses=int(rbank.n_rirs), rir_len=args.rir_len, rt60=args.rt60, events_in_pool=len(pool), ambient_rms=1e-3,
+              audio_format=args.format, **baffle, responses=int(rbank.n_rirs), rir_len=args.rir_len, rt60=args.rt60, events_in_pool=len(pool), ambient_rms=1e-3,
               seconds_to_render_extract_and_bank=round(time.perf_counter() - t0, 2), device=torch.cuda.get_device_name(0), **room_rec,
               **(dict(moving=args.moving, traj_step=int(drawn['train'].traj_step), speed_deg_s=[10.0, 40.0],
                       train_moving_items=int((np.diff(drawn['train'].traj_start) > 0).sum()), train_trajectory_nodes=len(drawn['train'].traj_rir),
@@ -105,7 +113,7 @@ def main():
     emit(dict(record='scene_training', what='held-out scores before training', **{k: round(before[k], 4) for k in keys}))
     t0 = time.perf_counter()
     hist = tr.fit(banks['train'], val_bank=banks['val'], val_gt=val_gt, batch_size=args.batch, max_epochs=args.epochs, seed=args.seed,
-                  audio_format='foa')
+                  audio_format=args.format)
     seconds = time.perf_counter() - t0
     steps_per_epoch = len(hist['steps']) // max(1, args.epochs)
     for v in hist['val']:
