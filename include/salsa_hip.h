@@ -449,6 +449,37 @@ int salsa_rir_decay_params(void);
 int salsa_rir_decay(const float *d_rirs, int n_rirs, int n_channels, int rir_len, double fs, int direct_halfwidth, double *d_params,
                     double *d_edc, void *hip_stream);
 
+/* Shoebox rooms whose walls differ per octave band (salsa_amd/rooms.py: ShoeboxRoom(bands=...); the reference has
+ * no counterpart: the definition is this project's).  A banded room has K amplitude rows over ONE image table, and K linear-phase
+ * filters h_b of 2 half + 1 taps, centre `half`, that sum to a unit impulse at `half` (rooms.octave_filters).  With r_b the response
+ * of salsa_room_rirs for the amplitude row of band b, evaluated on the taps -half .. L + half - 1, the banded response is
+ *     h[s, c, k] = sum_b sum_{j = 0}^{2 half} h_b[j] r_b[s, c, k + half - j],   0 <= k < L,
+ * and the band signals of a measured response x (zero outside [0, L)) are y_b[k] = sum_j h_b[j] x[k + half - j].
+ *
+ * salsa_room_rirs_bands: the r_b.  images double [6 + K][n_images]: the rows sign x, y, z, shift x, y, z of salsa_room_rirs, then one
+ * amplitude row per band, 0 <= A <= 1 (a band may be 0 where another is not); 1 <= K <= salsa_room_max_bands() = 8.  sources,
+ * receivers, mode and fs_over_c as for salsa_room_rirs.  The taps are first_tap .. first_tap + n_taps - 1, |first_tap| <= 4096 and 1 <=
+ * n_taps <= 16384 + 4096; d_out float32 [n_sources][C][K][n_taps], element t the tap first_tap + t.  An image's float64 geometry, its
+ * delay, fraction and windowed sinc are computed once and applied to K accumulators with K coefficients g A_b / d (times u_c), each
+ * formed in float64 and rounded once.  As for salsa_room_rirs: table-order sums without atomics, equal bits from two calls, a source
+ * independent of its batch, +0.0 where no support reaches, every element written; and a tap's bits depend neither on first_tap nor
+ * on n_taps.  With K = 1, first_tap = 0 and amplitudes > 0 the output is salsa_room_rirs's bit for bit.
+ *
+ * salsa_band_merge: d_bands float32 [n][K][L + 2 half] (element e of a row is tap e - half), d_filters float32 [K][2 half + 1] ->
+ * d_out float32 [n][L], the first sum.  salsa_band_split: d_x float32 [n][L] -> d_out float32 [n][K][L], the second.  Both run in
+ * float32, every output ONE chain acc = fma(h_b[j], x_b[k + half - j], acc) from +0.0, b ascending outside (merge), j ascending inside,
+ * a zero for an input outside its row: two calls give equal bits, a row does not depend on its batch, and an impulse in gives the
+ * filter's taps bit for bit.  Inputs are finite.  1 <= n <= 1048576, 1 <= L <= 16384, 1 <= half <= 2048.  A workgroup owns 2048
+ * outputs of a row (direct form from LDS).  One launch per 65535 rows on hip_stream, nothing allocated or synchronised.
+ * All three return -1 for a null pointer or an argument outside these limits, before any device call; -6 when a launch fails. */
+int salsa_room_max_bands(void);
+int salsa_room_rirs_bands(const double *images, const double *d_images, int n_images, int n_bands, const double *sources,
+                          const double *d_sources, int n_sources, const double *receivers, int n_receivers, int mode, double fs_over_c,
+                          int first_tap, int n_taps, float *d_out, void *hip_stream);
+int salsa_band_merge(const float *d_bands, const float *d_filters, int n, int n_bands, int length, int half, float *d_out,
+                     void *hip_stream);
+int salsa_band_split(const float *d_x, const float *d_filters, int n, int n_bands, int length, int half, float *d_out, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,15 @@ Decay: rir_acoustics measures any response array (R, C, L
 the headroom of each fit, DRR, C50 -- in float64, in salsa_amd/csrc/rir_decay.hip (include/salsa_hip.h: salsa_rir_decay, where the
 definition is written out); SALSA_HIP_DECAY=0, or a device that is no GPU, sends it to a composed torch evaluation of the same
 definition.  calibrate_room searches the walls' reflection coefficients for which the MEASURED decay of the generated responses is the
-one asked for."""
+one asked for.
+
+Octave-band walls: ShoeboxRoom(bands=OCTAVE_BANDS) gives the walls one set of coefficients per band.  The image
+table then carries one amplitude row per band, and the response is sum_b sum_j h_b[j] r_b[k + D - j]: r_b the definition above with
+band b's amplitudes on the taps -D .. length + D - 1, h_b = octave_filters (linear phase, 2 D + 1 taps, sum_b h_b a unit impulse at D,
+read as float32).  The r_b come from one launch of salsa_room_rirs_bands (salsa_amd/csrc/room_bands.hip: an image's geometry and
+windowed sinc once, K accumulators), the sum from salsa_band_merge; rir_acoustics(bands=) splits a response into its band signals
+(salsa_band_split) and measures each, and calibrate_room(bands=) fits one wall scale per band.  The switches above send all of it
+to composed torch paths (per-band _rirs_torch, conv1d)."""
 import ctypes as C
 import os
 
@@ -62,6 +70,11 @@ SPHERE_NA, SPHERE_NB = 16, 32                               # the sphere filter'
 SPHERE_NFFT = 1024                                          # the inverse real FFT that makes the sphere filter
 SPHERE_TAPER_START = 0.75                                   # of Nyquist: 9 kHz at 24 kHz, the largest fmax_doa of any feature
 FAR_FIELD_RADII = 10.0                                      # a source nearer than 10 R to the centre is refused: a plane-wave model
+OCTAVE_BANDS = (125, 250, 500, 1000, 2000, 4000, 8000)      # Hz: the bands of a banded room
+MAX_BANDS = 8                                               # salsa_room_max_bands()
+BAND_HALF = 1024                                            # D: a band filter has 2 D + 1 taps, centre D
+MAX_BAND_HALF = 2048                                        # salsa_band_merge / salsa_band_split
+BAND_NFFT = 8192                                            # the inverse real FFT that makes the band filters
 
 
 def eyring_beta(size, rt60, c=SOUND_SPEED):
@@ -71,17 +84,70 @@ def eyring_beta(size, rt60, c=SOUND_SPEED):
     return float(np.exp(-12.0 * np.log(10.0) * volume / (c * surface * float(rt60))))      # sqrt(exp(-24 ...)) = exp(-12 ...)
 
 
+def _check_bands(bands, fs):
+    """-> the K centre frequencies as a tuple of floats: 1 <= K <= MAX_BANDS, ascending, every edge f sqrt(2) below Nyquist"""
+    b = np.asarray(bands, np.float64).reshape(-1) if np.ndim(bands) <= 1 else None
+    if b is None or not 1 <= len(b) <= MAX_BANDS:
+        raise ValueError('bands is 1 .. %d centre frequencies in Hz' % MAX_BANDS)
+    if not (np.all(np.isfinite(b)) and np.all(b > 0) and np.all(np.diff(b) > 0) and (len(b) == 1 or b[-2] * np.sqrt(2.0) < 0.5 * fs)):
+        raise ValueError('bands are positive, ascending, and every edge f sqrt(2) between two of them lies below fs / 2')
+    return tuple(float(v) for v in b)
+
+
+def octave_filters(fs=FS, bands=OCTAVE_BANDS, half=BAND_HALF):
+    """The band filters of a banded room -> float64 (K, 2 half + 1), linear phase (symmetric about tap `half`) and
+    amplitude complementary: sum_b h_b = delta[n - half] to rounding, so a room whose bands are equal is the broadband room again.
+    Edges e_b = f_b sqrt(2); low_b(f) = 1 below e_b 2^(-1/4), 0 above e_b 2^(1/4) and a raised cosine in log2 f between them; G_0 =
+    low_0, G_b = low_b - low_(b-1), G_(K-1) = 1 - low_(K-2): the lowest band reaches down to DC, the highest up to Nyquist.  h_b is the
+    inverse real FFT of G_b on BAND_NFFT = 8192 points, rotated to the centre `half`, cut to 2 half + 1 taps and multiplied by the Hann
+    window np.hanning(2 half + 3)[1:-1], which is 1 at the centre and the same for every band."""
+    bands = _check_bands(bands, float(fs))
+    if int(half) != half or not 1 <= half <= MAX_BAND_HALF:
+        raise ValueError('1 <= half <= %d' % MAX_BAND_HALF)
+    half, K = int(half), len(bands)
+    f = np.arange(BAND_NFFT // 2 + 1, dtype=np.float64) * (float(fs) / BAND_NFFT)
+    low = np.empty((max(K - 1, 0), len(f)))
+    with np.errstate(divide='ignore'):
+        for b in range(K - 1):
+            u = np.log2(f / (bands[b] * np.sqrt(2.0)))                           # -inf at DC
+            low[b] = np.where(u <= -0.25, 1.0, np.where(u >= 0.25, 0.0, 0.5 * (1.0 + np.cos(np.pi * (np.clip(u, -0.25, 0.25) + 0.25) / 0.5))))
+    G = np.ones((K, len(f)))
+    if K > 1:
+        G[0], G[K - 1] = low[0], 1.0 - low[K - 2]
+        G[1:K - 1] = low[1:] - low[:-1]
+    h = np.fft.irfft(G, BAND_NFFT, axis=-1)[:, np.arange(-half, half + 1) % BAND_NFFT]
+    return np.ascontiguousarray(h * np.hanning(2 * half + 3)[1:-1][None])
+
+
+_BAND_FILTERS = {}
+
+
+def _band_filters32(fs, bands, half):
+    """octave_filters rounded to float32, what the kernels and the torch paths read; built once per (fs, bands, half)"""
+    key = (float(fs), tuple(bands), int(half))
+    if key not in _BAND_FILTERS:
+        h = octave_filters(*key).astype(np.float32)
+        h.setflags(write=False)
+        _BAND_FILTERS[key] = h
+    return _BAND_FILTERS[key]
+
+
 class ShoeboxRoom:
     """size (Lx, Ly, Lz) in metres; exactly one of beta -- the six amplitude reflection coefficients (x0, x1, y0, y1, z0, z1), or one
     number for all walls -- and rt60, seconds, which stands for the uniform beta of Eyring's formula (eyring_beta).  array: the array
     centre, None for the room's centre.
     rt60 is a nominal figure: the decay an image-source shoebox realises is LONGER than Eyring's, by 30 - 55 % in a 6 x 5 x 3.2 m room
     (a T20 of 0.42 - 0.45 s on W for a nominal 0.3 s).  rir_acoustics measures what a bank realises, and calibrate_room returns the
-    room whose measured decay IS the figure asked for; such a room carries the record of the search in `.calibration`."""
+    room whose measured decay IS the figure asked for; such a room carries the record of the search in `.calibration`.
+    bands: K <= 8 ascending centre frequencies in Hz (OCTAVE_BANDS) make the walls frequency dependent: beta is
+    then (K,) -- one coefficient per band for all walls -- or (K, 6), rt60 is K nominal figures (Eyring per band), and band_half is the
+    D of the band filters (octave_filters).  .bands is None for every other room, and nothing about such a room changes."""
 
     calibration = None
+    bands = None
+    band_half = None
 
-    def __init__(self, size, beta=None, rt60=None, array=None, fs=FS, c=SOUND_SPEED):
+    def __init__(self, size, beta=None, rt60=None, array=None, fs=FS, c=SOUND_SPEED, bands=None, band_half=BAND_HALF):
         self.size = np.asarray(size, np.float64).reshape(-1)
         if self.size.shape != (3,) or not np.all(np.isfinite(self.size)) or not np.all(self.size > 0):
             raise ValueError('size is (Lx, Ly, Lz), positive metres')
@@ -90,17 +156,40 @@ class ShoeboxRoom:
         self.fs, self.c = float(fs), float(c)
         if not (self.fs > 0 and self.c > 0):
             raise ValueError('fs and c are positive')
-        if rt60 is not None:
-            if not float(rt60) > 0:
-                raise ValueError('rt60 is positive seconds')
-            beta = eyring_beta(self.size, rt60, self.c)
-        self.rt60 = None if rt60 is None else float(rt60)
-        self.beta = np.broadcast_to(np.asarray(beta, np.float64), (6,)).copy() if np.ndim(beta) == 0 else np.asarray(beta, np.float64).reshape(-1)
-        if self.beta.shape != (6,) or not np.all((self.beta >= 0) & (self.beta <= 1)):
-            raise ValueError('beta is six reflection coefficients in [0, 1]')
+        if bands is not None:
+            self._init_bands(beta, rt60, bands, band_half)
+        else:
+            if rt60 is not None:
+                if not float(rt60) > 0:
+                    raise ValueError('rt60 is positive seconds')
+                beta = eyring_beta(self.size, rt60, self.c)
+            self.rt60 = None if rt60 is None else float(rt60)
+            self.beta = np.broadcast_to(np.asarray(beta, np.float64), (6,)).copy() if np.ndim(beta) == 0 else np.asarray(beta, np.float64).reshape(-1)
+            if self.beta.shape != (6,) or not np.all((self.beta >= 0) & (self.beta <= 1)):
+                raise ValueError('beta is six reflection coefficients in [0, 1]')
         self.array = 0.5 * self.size if array is None else np.asarray(array, np.float64).reshape(-1)
         if self.array.shape != (3,) or not np.all((self.array > 0) & (self.array < self.size)):
             raise ValueError('the array centre lies strictly inside the room')
+
+    def _init_bands(self, beta, rt60, bands, band_half):
+        """the banded room: .bands the K centre frequencies, .beta (K, 6), .rt60 (K,) or None, .band_half the filters' D"""
+        self.bands = _check_bands(bands, self.fs)
+        K = len(self.bands)
+        if int(band_half) != band_half or not 1 <= band_half <= MAX_BAND_HALF:
+            raise ValueError('1 <= band_half <= %d' % MAX_BAND_HALF)
+        self.band_half = int(band_half)
+        if rt60 is not None:
+            rt60 = np.asarray(rt60, np.float64)
+            if rt60.shape != (K,) or not np.all(rt60 > 0):
+                raise ValueError('rt60 is %d positive numbers of seconds, one per band' % K)
+            beta = np.array([eyring_beta(self.size, t, self.c) for t in rt60])
+        self.rt60 = None if rt60 is None else rt60.copy()
+        beta = np.asarray(beta, np.float64)
+        if beta.shape not in ((K,), (K, 6)):
+            raise ValueError('beta of a room with %d bands is (%d,) -- one coefficient per band -- or (%d, 6)' % (K, K, K))
+        self.beta = np.ascontiguousarray(np.broadcast_to(beta[:, None] if beta.ndim == 1 else beta, (K, 6)))
+        if not np.all((self.beta >= 0) & (self.beta <= 1)):
+            raise ValueError('beta is reflection coefficients in [0, 1]')
 
     def receivers(self, audio_format):
         """the receiver points (M, 3) of the format: the centre (foa), the four capsules (mic)"""
@@ -113,7 +202,7 @@ class ShoeboxRoom:
 
 class RoomImages:
     """The image table of a room, N images in canonical order: n and q int64 (N, 3), sign = 1 - 2 q and shift = 2 n o L float64 (N, 3),
-    amplitude float64 (N), order int64 (N)."""
+    amplitude float64 (N), order int64 (N).  Of a banded room: amplitude float64 (K, N), one row per band."""
 
     def __init__(self, n, q, size, amplitude, order):
         self.n, self.q, self.amplitude, self.order = n, q, amplitude, order
@@ -121,18 +210,26 @@ class RoomImages:
         self.shift = 2.0 * n * np.asarray(size, np.float64)
 
     def __len__(self):
-        return len(self.amplitude)
+        return len(self.order)
 
     def table(self):
         """float64 (7, N), what salsa_room_rirs takes: the rows sign x, y, z, shift x, y, z, amplitude"""
+        if self.amplitude.ndim != 1:
+            raise ValueError('a banded room has one amplitude row per band: band_table()')
         return np.ascontiguousarray(np.concatenate([self.sign.T, self.shift.T, self.amplitude[None]]), np.float64)
+
+    def band_table(self):
+        """float64 (6 + K, N), what salsa_room_rirs_bands takes: the rows sign x, y, z, shift x, y, z, then the amplitude of each band
+        (K = 1 for a room without bands: table())"""
+        return np.ascontiguousarray(np.concatenate([self.sign.T, self.shift.T, np.atleast_2d(self.amplitude)]), np.float64)
 
 
 def room_images(room, d_max, max_order=None):
     """The host-side image table, shared by every source and receiver of the room.  Canonical order: ascending (n_x, n_y, n_z, q_x, q_y,
     q_z), n_x the slowest.  Images with A = 0 or an order above max_order (None: no limit) are absent.  The table is cut by distance,
     conservatively: with the source and the receiver ANYWHERE in the room, the image's offset along an axis is at least max(0, |2 n -
-    q| - 1) L, and an image is kept iff the norm of these three least offsets is at most d_max.  Everything is float64."""
+    q| - 1) L, and an image is kept iff the norm of these three least offsets is at most d_max.  Everything is float64.
+    A banded room: one amplitude row per band, and an image is absent only when EVERY band's amplitude is 0."""
     L, b = room.size, room.beta
     if not (np.isfinite(d_max) and d_max >= 0):
         raise ValueError('d_max is a distance in metres')
@@ -148,12 +245,17 @@ def room_images(room, d_max, max_order=None):
     n, q = grid[:, :3], grid[:, 3:]
     low, high = np.abs(n - q), np.abs(n)                                       # reflections at the walls 0 and at the walls L, per axis
     order = (low + high).sum(axis=1)
-    amplitude = np.prod(b[0::2][None] ** low * b[1::2][None] ** high, axis=1)  # numpy: 0.0 ** 0 = 1.0
     least = np.maximum(0, np.abs(2 * n - q) - 1) * L[None]
-    keep = (amplitude > 0) & (np.sqrt((least ** 2).sum(axis=1)) <= d_max)
+    if room.bands is None:
+        amplitude = np.prod(b[0::2][None] ** low * b[1::2][None] ** high, axis=1)  # numpy: 0.0 ** 0 = 1.0
+        alive = amplitude > 0
+    else:                                                                      # one row per band; an image stays while ANY band carries it
+        amplitude = np.stack([np.prod(bk[0::2][None] ** low * bk[1::2][None] ** high, axis=1) for bk in b])
+        alive = (amplitude > 0).any(axis=0)
+    keep = alive & (np.sqrt((least ** 2).sum(axis=1)) <= d_max)
     if max_order is not None:
         keep &= order <= int(max_order)
-    return RoomImages(np.ascontiguousarray(n[keep]), np.ascontiguousarray(q[keep]), L, amplitude[keep], order[keep])
+    return RoomImages(np.ascontiguousarray(n[keep]), np.ascontiguousarray(q[keep]), L, np.ascontiguousarray(amplitude[..., keep]), order[keep])
 
 
 # ---- the capsules on a rigid sphere -------------------------------------------------------------------------------
@@ -271,8 +373,12 @@ def room_geometry(audio_format, room, directions, distance, length, align_direct
     """-> (directions int64 (R, 2), sources float64 (R, 5): position, t0, g; receivers float64 (M, 3); d_max: the distance past which no
     image reaches a tap below `length`).  Raises ValueError unless every source and receiver lies strictly inside the room and every
     source is at least 1 mm from every receiver.  baffle='rigid' (mic only): t0 and d_max take the sphere table's lead for SINC_HALF, and
-    a source nearer than FAR_FIELD_RADII = 10 sphere radii (0.42 m) to the centre is refused -- the limit of the plane-wave model."""
-    lead = sphere_table(MIC_RADIUS, room.fs, room.c).lead if _check_baffle(audio_format, baffle) else SINC_HALF
+    a source nearer than FAR_FIELD_RADII = 10 sphere radii (0.42 m) to the centre is refused -- the limit of the plane-wave model.
+    A banded room: d_max reaches room.band_half taps further, the band responses' extent; 'rigid' is refused."""
+    rigid = _check_baffle(audio_format, baffle)
+    if rigid and room.bands is not None:
+        raise ValueError("baffle='rigid' is not available for a room with bands")
+    lead = sphere_table(MIC_RADIUS, room.fs, room.c).lead if rigid else SINC_HALF
     directions = np.asarray(directions, np.int64).reshape(-1, 2)
     R = len(directions)
     if not 1 <= R <= MAX_SOURCES:
@@ -296,7 +402,8 @@ def room_geometry(audio_format, room, directions, distance, length, align_direct
     g = centre if normalize_direct else np.ones(R)
     if not np.all(g > 0):
         raise ValueError('normalize_direct needs every source away from the array centre')
-    d_max = (int(length) + lead + float(t0.max())) * room.c / room.fs * (1.0 + 1e-9)
+    reach = int(length) + (room.band_half if room.bands is not None else 0)    # a banded room's band responses run D taps past `length`
+    d_max = (reach + lead + float(t0.max())) * room.c / room.fs * (1.0 + 1e-9)
     return directions, np.ascontiguousarray(np.concatenate([pos, t0[:, None], g[:, None]], axis=1)), np.ascontiguousarray(rec), d_max
 
 
@@ -341,11 +448,11 @@ def _rirs_torch_sphere(table, sources, sphere, fs_over_c, length, device):
     return out
 
 
-def _rirs_torch(table, sources, receivers, foa, fs_over_c, length, device, sphere=None):
+def _rirs_torch(table, sources, receivers, foa, fs_over_c, length, device, sphere=None, first=0):
     """The definition composed from torch calls with the kernel's precision split (SALSA_HIP_ROOM=0, and any device that is no GPU):
     per (source, receiver) the images' 2 H taps as one (images, 2 H) array, float64 up to the tap argument, float32 from it on, added
     into the response by index_add_ in float32 (in table order on the CPU; a GPU adds them in no promised order).  sphere: the rigid
-    case, _rirs_torch_sphere."""
+    case, _rirs_torch_sphere.  first: the taps are first .. first + length - 1 (the band responses of a banded room start below 0)."""
     import torch
     if sphere is not None:
         return _rirs_torch_sphere(table, sources, sphere, fs_over_c, length, device)
@@ -363,10 +470,10 @@ def _rirs_torch(table, sources, receivers, foa, fs_over_c, length, device, spher
             d = torch.sqrt((delta * delta).sum(dim=1))
             tau = d * fs_over_c - src[r, 3]
             tf = torch.floor(tau)
-            sel = torch.nonzero((tf >= -H) & (tf <= length + H - 2)).reshape(-1)      # the support meets [0, length)
+            sel = torch.nonzero((tf >= first - H) & (tf <= first + length + H - 2)).reshape(-1)      # the support meets [first, first + length)
             if not len(sel):
                 continue
-            k = tf[sel].to(torch.int64)[:, None] + j[None]
+            k = tf[sel].to(torch.int64)[:, None] + (j[None] - first)
             x = (j[None].to(torch.float64) - (tau[sel] - tf[sel])[:, None]).to(torch.float32)
             w = torch.sinc(x) * (0.5 * (1.0 + torch.cos(x * (np.pi / H))))
             w = torch.where((x.abs() < H) & (k >= 0) & (k < length), w, torch.zeros_like(w))
@@ -416,10 +523,84 @@ def _rirs_hip(table, sources, receivers, foa, fs_over_c, length, device, sphere=
     return out
 
 
+# ---- octave-band walls ----------------------------------------------------------------------------------------
+def _band_call(name, *args):
+    rc = getattr(_lib.load(), name)(*args)
+    if rc:
+        raise RuntimeError('%s failed (%d): %s' % (name, rc, _lib.last_error()))
+
+
+def _band_rirs_hip(table, sources, receivers, foa, fs_over_c, first, n_taps, device):
+    """salsa_room_rirs_bands -> float32 (R, C, K, n_taps) on the device: the band responses on the taps first .. first + n_taps - 1"""
+    import torch
+    K, R, M = table.shape[0] - 6, len(sources), len(receivers)
+    out = torch.empty((R, 4 if foa else M, K, n_taps), dtype=torch.float32, device=device)
+    d_table, d_sources = torch.from_numpy(table).to(device), torch.from_numpy(sources).to(device)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    with torch.cuda.device(device):
+        _band_call('salsa_room_rirs_bands', hp(table), C.c_void_p(d_table.data_ptr()), table.shape[1], K, hp(sources),
+                   C.c_void_p(d_sources.data_ptr()), R, hp(receivers), M, 1 if foa else 0, fs_over_c, int(first), int(n_taps),
+                   C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    torch.cuda.current_stream(device).synchronize()                           # the tables may go now
+    return out
+
+
+def _band_merge_hip(r, filters):
+    """salsa_band_merge: r float32 (n, K, L + 2 D) on a GPU, filters float32 (K, 2 D + 1) on it -> (n, L)"""
+    import torch
+    n, K, ext = r.shape
+    half = (filters.shape[1] - 1) // 2
+    out = torch.empty((n, ext - 2 * half), dtype=torch.float32, device=r.device)
+    with torch.cuda.device(r.device):
+        _band_call('salsa_band_merge', C.c_void_p(r.data_ptr()), C.c_void_p(filters.data_ptr()), n, K, ext - 2 * half, half,
+                   C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(r.device).cuda_stream))
+    return out
+
+
+def _band_split_hip(x, filters):
+    """salsa_band_split: x float32 (n, L) on a GPU -> (n, K, L)"""
+    import torch
+    n, L = x.shape
+    K, half = filters.shape[0], (filters.shape[1] - 1) // 2
+    out = torch.empty((n, K, L), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _band_call('salsa_band_split', C.c_void_p(x.data_ptr()), C.c_void_p(filters.data_ptr()), n, K, L, half, C.c_void_p(out.data_ptr()),
+                   C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+    return out
+
+
+def _band_merge_torch(r, filters):
+    """the merge as one conv1d in float32 (a cross-correlation: the taps reversed): r (n, K, L + 2 D) -> (n, L)"""
+    import torch
+    return torch.nn.functional.conv1d(r, torch.flip(filters, (-1,))[None])[:, 0]
+
+
+def _band_split_torch(x, filters):
+    """the split as one conv1d in float32 with D zeros on either side: x (n, L) -> (n, K, L)"""
+    import torch
+    half = (filters.shape[1] - 1) // 2
+    return torch.nn.functional.conv1d(x[:, None], torch.flip(filters, (-1,))[:, None], padding=half)
+
+
+def _band_rirs(room, table, sources, receivers, foa, length, device, hip):
+    """the banded response (R, C, length): the K band responses on the taps -D .. length + D - 1, merged through the band filters"""
+    import torch
+    D = room.band_half
+    n_taps, fs_over_c = length + 2 * D, room.fs / room.c
+    filters = torch.from_numpy(_band_filters32(room.fs, room.bands, D).copy()).to(device)
+    if hip:
+        r = _band_rirs_hip(table, sources, receivers, foa, fs_over_c, -D, n_taps, device)
+        return _band_merge_hip(r.reshape(-1, r.shape[2], n_taps), filters).reshape(r.shape[0], r.shape[1], length)
+    r = torch.stack([_rirs_torch(np.ascontiguousarray(np.concatenate([table[:6], table[6 + b:7 + b]])), sources, receivers, foa, fs_over_c,
+                                 n_taps, device, first=-D) for b in range(table.shape[0] - 6)], dim=2)
+    return _band_merge_torch(r.reshape(-1, r.shape[2], n_taps), filters).reshape(r.shape[0], r.shape[1], length)
+
+
 def room_rirs(audio_format, room, directions, distance, length, max_order=None, align_direct=True, normalize_direct=True, device=None,
               baffle='open'):
     """The responses as a float32 tensor (R, C, length) on `device` (None: 'cuda'), and the directions: what room_rir_bank wraps.
-    baffle='rigid' (mic only) puts the four capsules on a rigid sphere of MIC_RADIUS."""
+    baffle='rigid' (mic only) puts the four capsules on a rigid sphere of MIC_RADIUS.  A banded room (DESIGN.md
+    section 9p; 'foa' and open 'mic') gives the sum over its bands of the band's response through the band's filter."""
     import torch
     directions, sources, receivers, d_max = room_geometry(audio_format, room, directions, distance, length, align_direct, normalize_direct,
                                                           baffle)
@@ -427,6 +608,9 @@ def room_rirs(audio_format, room, directions, distance, length, max_order=None, 
     if not 1 <= len(images) <= MAX_IMAGES:
         raise ValueError('the room has %d images within reach of %d taps; 1 .. %d are supported' % (len(images), length, MAX_IMAGES))
     device = torch.device('cuda' if device is None else device)
+    if room.bands is not None:
+        return _band_rirs(room, images.band_table(), sources, receivers, audio_format == 'foa', int(length), device,
+                          HIP_ROOM and device.type == 'cuda'), directions
     run = _rirs_hip if HIP_ROOM and device.type == 'cuda' else _rirs_torch
     if baffle == 'rigid':
         sphere = (sphere_table(MIC_RADIUS, room.fs, room.c), room.array, _capsule_units())
@@ -459,7 +643,8 @@ class RirAcoustics:
     """What rir_acoustics measured, float64 numpy arrays (R, C): energy, peak (the direct path's tap), edt, t20, t30 in seconds (NaN
     where the response does not decay far enough to fit), headroom_edt, headroom_t20, headroom_t30 in dB, drr_db, c50_db, and
     crossings (R, C, 5), the taps at which the curve passes DECAY_LEVELS_DB (NaN: never).  edc (R, C, L), the energy decay curve, or
-    None when it was not asked for.  A silent response has energy 0, peak 0 and NaN elsewhere."""
+    None when it was not asked for.  A silent response has energy 0, peak 0 and NaN elsewhere.  Measured per band (rir_acoustics(bands=))
+    every array has one more axis: (R, C, K), crossings (R, C, K, 5), edc (R, C, K, L)."""
 
     def __init__(self, params, edc, fs, length, direct_halfwidth):
         params = np.asarray(params, np.float64)
@@ -543,13 +728,17 @@ def _decay_hip(h, fs, halfwidth, want_edc):
     return out, edc
 
 
-def rir_acoustics(rirs, fs=FS, direct_halfwidth=None, edc=False, device=None):
+def rir_acoustics(rirs, fs=FS, direct_halfwidth=None, edc=False, device=None, bands=None, band_half=BAND_HALF):
     """Measure responses `rirs`, a float32 array or tensor (R, C, L) with R <= 65535, C <= 16, L <= 16384 -> RirAcoustics (its docstring
     lists the quantities; include/salsa_hip.h: salsa_rir_decay states the definition).  direct_halfwidth: the taps on either side of
     the peak that count as the direct path for DRR, None for round(0.0025 fs) = 60 at 24 kHz, which covers the generators' windowed
     sinc (half width 16).  edc=True also returns the energy decay curve.  device: where to measure, None for the tensor's own device,
     or 'cuda' for an array; the kernel runs on a GPU unless SALSA_HIP_DECAY=0, a composed torch evaluation of the same definition on
-    any other device (device='cpu' needs no GPU)."""
+    any other device (device='cpu' needs no GPU).
+    bands (None: the broadband measurement above): K <= 8 centre frequencies, OCTAVE_BANDS for the data sets' tables.
+    Each response is split into its band signals y_b[k] = sum_j h_b[j] x[k + D - j] (octave_filters(fs, bands, band_half); salsa_band_split,
+    or a conv1d on the torch path) and every band signal is measured as above: the arrays are then (R, C, K), edc (R, C, K, L); R C <=
+    65535.  The filters ring for D taps on either side of a tap, which the decay of a band signal includes."""
     import torch
     fs = float(fs)
     if not (fs > 0 and fs <= 1e9):
@@ -570,7 +759,19 @@ def rir_acoustics(rirs, fs=FS, direct_halfwidth=None, edc=False, device=None):
     if h.dim() != 3 or not (1 <= h.shape[0] <= MAX_SOURCES and 1 <= h.shape[1] <= 16 and 1 <= h.shape[2] <= MAX_RIR_LEN):
         raise ValueError('rirs must be (R, C, L) with R <= %d, C <= 16 and 1 <= L <= %d, got %s' % (MAX_SOURCES, MAX_RIR_LEN, tuple(h.shape)))
     h = h.to(device).contiguous()
-    run = _decay_hip if HIP_DECAY and device.type == 'cuda' else _decay_torch
+    hip = HIP_DECAY and device.type == 'cuda'
+    run = _decay_hip if hip else _decay_torch
+    if bands is not None:
+        bands = _check_bands(bands, fs)
+        R, Cn, L = h.shape
+        if R * Cn > MAX_SOURCES:
+            raise ValueError('a banded measurement takes R C <= %d responses, got %d' % (MAX_SOURCES, R * Cn))
+        filters = torch.from_numpy(octave_filters(fs, bands, band_half).astype(np.float32)).to(device)
+        y = (_band_split_hip if hip else _band_split_torch)(h.reshape(R * Cn, L), filters)
+        params, curve = run(y.contiguous(), fs, int(direct_halfwidth), bool(edc))
+        params = params.reshape(R, Cn, len(bands), -1)
+        curve = None if curve is None else curve.reshape(R, Cn, len(bands), L)
+        return RirAcoustics(params.cpu().numpy(), None if curve is None else curve.cpu().numpy(), fs, L, direct_halfwidth)
     params, curve = run(h, fs, int(direct_halfwidth), bool(edc))
     return RirAcoustics(params.cpu().numpy(), None if curve is None else curve.cpu().numpy(), fs, h.shape[2], direct_halfwidth)   # (.cpu() waits)
 
@@ -583,7 +784,8 @@ def _length_for(measure, seconds, fs):
 
 
 def calibrate_room(size, rt60, measure='t20', array=None, audio_format='foa', directions=None, distance=1.0, length=None,
-                   absorption_ratio=None, rtol=0.01, max_iter=8, max_order=None, device=None, fs=FS, c=SOUND_SPEED, baffle='open'):
+                   absorption_ratio=None, rtol=0.01, max_iter=8, max_order=None, device=None, fs=FS, c=SOUND_SPEED, baffle='open',
+                   bands=None, band_half=BAND_HALF):
     """-> ShoeboxRoom(size, beta=...) whose MEASURED decay is rt60 seconds: the mean of `measure` ('edt', 't20' or 't30') on channel 0
     over probe responses generated by room_rirs on `device` (None: 'cuda'; 'cpu' needs no GPU) is within rtol of rt60.
     The walls are beta_w = exp(-s a_w), a = absorption_ratio, six weights >= 0 in the order of beta (None: all one, a uniform beta),
@@ -595,10 +797,21 @@ def calibrate_room(size, rt60, measure='t20', array=None, audio_format='foa', di
     at an earlier step only slows the search), and when a beta would leave [0, 1) on every absorbing wall: a lossless room has no
     decay time.  The room's .rt60 stays None (that attribute is the nominal figure of Eyring's formula); .calibration is a dict:
     measure, target, realised (the mean), probes (the per-probe values), headroom_db (per probe), beta_history (one array of six per
-    evaluation), evaluations, directions, distance, length.  baffle: as for room_rirs; 'rigid' needs audio_format='mic'."""
-    _check_baffle(audio_format, baffle)
+    evaluation), evaluations, directions, distance, length.  baffle: as for room_rirs; 'rigid' needs audio_format='mic'.
+    bands (None: everything above, unchanged): K centre frequencies, rt60 then K targets, a data set's table.  One
+    wall scale s_b per band, each from Eyring; every evaluation generates the probes ONCE with all bands (a banded ShoeboxRoom with
+    band_half), measures them per band (rir_acoustics(bands=)) and sets s_b <- s_b T_b / rt60_b; it is accepted when EVERY band's mean
+    is within rtol, and the checks above are made per band.  target, realised are then (K,), probes and headroom_db (probes, K), each
+    entry of beta_history (K, 6), and .calibration also holds realised_history (the K means of every evaluation), bands and
+    band_half.  length None: from the longest target."""
+    rigid = _check_baffle(audio_format, baffle)
     if measure not in DECAY_FITS:
         raise ValueError('measure is one of %s' % ', '.join(sorted(DECAY_FITS)))
+    if bands is not None:
+        if rigid:
+            raise ValueError("baffle='rigid' is not available for a room with bands")
+        return _calibrate_bands(size, rt60, bands, band_half, measure, array, audio_format, directions, distance, length, absorption_ratio,
+                                rtol, max_iter, max_order, device, float(fs), c)
     target, fs = float(rt60), float(fs)
     if not (target > 0 and np.isfinite(target)):
         raise ValueError('rt60 is positive seconds')
@@ -637,3 +850,52 @@ def calibrate_room(size, rt60, measure='t20', array=None, audio_format='foa', di
             return room
         s *= mean / target
     raise ValueError('%s is %g s after %d evaluations, not within %g of %g s' % (measure, mean, int(max_iter), rtol, target))
+
+
+def _calibrate_bands(size, rt60, bands, band_half, measure, array, audio_format, directions, distance, length, absorption_ratio, rtol,
+                     max_iter, max_order, device, fs, c):
+    """calibrate_room against one target per band: the same proportional step, one wall scale per band, one set of probes per step"""
+    bands = _check_bands(bands, fs)
+    K = len(bands)
+    target = np.asarray(rt60, np.float64).reshape(-1) if np.ndim(rt60) <= 1 else np.zeros(0)
+    if target.shape != (K,) or not np.all(np.isfinite(target)) or not np.all(target > 0):
+        raise ValueError('rt60 is %d positive numbers of seconds, one per band' % K)
+    if not (rtol > 0 and max_iter >= 1):
+        raise ValueError('rtol is positive and max_iter at least 1')
+    a = np.ones(6) if absorption_ratio is None else np.asarray(absorption_ratio, np.float64).reshape(-1)
+    if a.shape != (6,) or not np.all(np.isfinite(a)) or not np.all(a >= 0) or not a.sum() > 0:
+        raise ValueError('absorption_ratio is six weights >= 0, not all zero')
+    a = a / a.mean()
+    directions = DEFAULT_PROBES if directions is None else directions
+    length = min(MAX_RIR_LEN, int(np.ceil(target.max() * fs))) if length is None else int(length)
+    s = np.array([-np.log(eyring_beta(size, t, c)) for t in target])
+    need = max(_length_for(measure, t, fs) for t in target) + int(band_half)
+    advice = 'about %d taps would do%s' % (need, '' if need <= MAX_RIR_LEN else ', more than the %d supported' % MAX_RIR_LEN)
+    history, realised = [], []
+    for evaluation in range(1, int(max_iter) + 1):
+        beta = np.exp(-s[:, None] * a[None])
+        if not np.all(np.isfinite(s)) or not np.all(s > 0) or not np.all((beta >= 0) & (beta[:, a > 0] < 1)):
+            raise ValueError('a reflection coefficient would leave [0, 1) (s = %s): no absorbing room decays in %s s' % (s.tolist(), target.tolist()))
+        history.append(beta)
+        room = ShoeboxRoom(size, beta=beta, array=array, fs=fs, c=c, bands=bands, band_half=band_half)
+        h, _ = room_rirs(audio_format, room, directions, distance, length, max_order, device=device)
+        got = rir_acoustics(h, fs=fs, bands=bands, band_half=band_half)
+        T, bad = getattr(got, measure)[:, 0], got.truncated(measure)[:, 0]                # (probes, K)
+        mean = T.mean(axis=0)
+        realised.append(mean)
+        if not np.all(np.isfinite(mean)):
+            raise ValueError('%d of %d probe band signals of %d taps do not decay far enough for %s (evaluation %d, bands %s); %s'
+                             % (int(np.isnan(T).sum()), T.size, length, measure, evaluation,
+                                [bands[b] for b in np.nonzero(~np.isfinite(mean))[0]], advice))
+        if np.all(np.abs(mean / target - 1.0) <= rtol):
+            if bad.any():
+                raise ValueError('%s reached %s s, but %d of %d probe fits (bands %s) have less than %g dB of headroom in %d taps: the cut '
+                                 'biases them; %s' % (measure, mean.tolist(), int(bad.sum()), T.size,
+                                                      [bands[b] for b in np.nonzero(bad.any(axis=0))[0]], TRUNCATION_HEADROOM_DB, length, advice))
+            room.calibration = dict(measure=measure, target=target.copy(), realised=mean, probes=T.copy(),
+                                    headroom_db=got.headroom(measure)[:, 0].copy(), beta_history=history, realised_history=realised,
+                                    evaluations=evaluation, directions=[tuple(d) for d in np.asarray(directions).tolist()],
+                                    distance=distance, length=length, bands=bands, band_half=int(band_half))
+            return room
+        s = s * mean / target
+    raise ValueError('%s is %s s after %d evaluations, not within %g of %s s' % (measure, mean.tolist(), int(max_iter), rtol, target.tolist()))

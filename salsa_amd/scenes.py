@@ -549,11 +549,11 @@ def add_scenes(feature_bank, scenes, pool, bank, names=None, ambient=None, n_cla
 
 
 _ROOMS = ('ShoeboxRoom', 'RoomImages', 'room_images', 'room_rirs', 'room_rir_bank', 'eyring_beta', 'RirAcoustics', 'rir_acoustics',
-          'calibrate_room', 'sphere_response', 'sphere_filter', 'SphereTable', 'sphere_table')
+          'calibrate_room', 'sphere_response', 'sphere_filter', 'SphereTable', 'sphere_table', 'OCTAVE_BANDS', 'octave_filters')
 
 
 def __getattr__(name):
-    """rooms.py (DESIGN.md sections 9m, 9n, 9o: image-source responses of a shoebox room as a RirBank, their decay, the rigid sphere) builds on this module, so its public names
+    """rooms.py (DESIGN.md sections 9m - 9p: image-source responses of a shoebox room as a RirBank, their decay, the rigid sphere, octave-band walls) builds on this module, so its public names
     are re-exported on first use, not at import"""
     if name in _ROOMS:
         from . import rooms

@@ -11,7 +11,11 @@ the largest difference of the legs' T20.  Then calibrate_room((6, 5, 3.2), 0.3) 
 the CPU; and the T20 on W that rooms of NOMINAL rt60 0.2 / 0.3 / 0.5 s realise in three directions, with the beta that calibrate_room
 finds for the same figure.  One JSON line per record; whatever is seen is reported, a leg that loses included.
 
-    python tools/bench_room_acoustics.py [--rounds 5] [--host-rounds 2] [--warmup 1] [--out profiles/room_acoustics_bench.jsonl]"""
+--bands measures per octave band instead: rir_acoustics(bands=OCTAVE_BANDS) on the FOA bank of 72 directions, HIP
+(salsa_band_split, then salsa_rir_decay on seven band signals per response) against the torch path on the device, alternating; the
+split's and the decay's launches alone; and calibrate_room against seven octave-band targets, 0.50 .. 0.20 s, 12000 taps.
+
+    python tools/bench_room_acoustics.py [--bands] [--rounds 5] [--host-rounds 2] [--warmup 1] [--out profiles/room_acoustics_bench.jsonl]"""
 import argparse
 import json
 import os
@@ -49,8 +53,62 @@ def launch_ms(d_h, want_edc, warmup, rounds):
     return ms
 
 
+def banded(args, emit, stats):
+    import ctypes as C
+    import numpy as np
+    import torch
+    from salsa_amd import _lib, rooms
+    dev, name = torch.device('cuda:0'), torch.cuda.get_device_name(0)
+    bands, K, D = rooms.OCTAVE_BANDS, len(rooms.OCTAVE_BANDS), rooms.BAND_HALF
+    directions = [(az, 0) for az in range(-180, 180, 5)]
+    d_h, _ = rooms.room_rirs('foa', rooms.ShoeboxRoom(SIZE, rt60=(0.3,) * K, bands=bands), directions, 1.5, 7200, device=dev)
+    legs = {'a HIP': True, 'b torch, device': False}
+    times, last = {k: [] for k in legs}, {}
+    for r in range(args.warmup + args.rounds):
+        for leg, hip in legs.items():
+            rooms.HIP_DECAY = hip
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = rooms.rir_acoustics(d_h, bands=bands)
+            torch.cuda.synchronize()
+            if r >= args.warmup:
+                times[leg].append((time.perf_counter() - t0) * 1e3)
+            last[leg] = got.t20
+    rooms.HIP_DECAY = True
+    for leg in legs:
+        emit(dict(bench='rir_acoustics_bands', responses=72, channels=4, bands=K, band_half=D, rir_len=7200, leg=leg, **stats(times[leg]),
+                  max_rel_t20_difference_from_leg_a=float(np.nanmax(np.abs(last[leg] / last['a HIP'] - 1.0))), device=name))
+    filters = torch.from_numpy(rooms.octave_filters(24000.0).astype(np.float32)).to(dev)
+    x = d_h.reshape(72 * 4, 7200)
+    split_ms = []
+    for r in range(args.warmup + args.rounds):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        y = rooms._band_split_hip(x, filters)
+        b.record()
+        torch.cuda.synchronize()
+        if r >= args.warmup:
+            split_ms.append(a.elapsed_time(b))
+    decay_ms = launch_ms(y, False, args.warmup, args.rounds)
+    emit(dict(bench='rir_acoustics_bands', responses=72, channels=4, bands=K, rir_len=7200, split_launch_alone=stats(split_ms),
+              decay_launch_alone=stats(decay_ms), b_over_a=round(float(np.median(times['b torch, device']) / np.median(times['a HIP'])), 2), device=name))
+    target = (0.50, 0.45, 0.40, 0.35, 0.30, 0.25, 0.20)
+    cal_ms = []
+    for r in range(args.warmup + args.rounds):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        cal = rooms.calibrate_room(SIZE, rt60=target, bands=bands, length=12000, device=dev).calibration
+        if r >= args.warmup:
+            cal_ms.append((time.perf_counter() - t0) * 1e3)
+    emit(dict(bench='calibrate_room_bands', room=list(SIZE), target=list(target), where='cuda', **stats(cal_ms), evaluations=cal['evaluations'],
+              relative_error_per_evaluation=[[round(float(v), 5) for v in m / np.array(target) - 1.0] for m in cal['realised_history']],
+              beta=[round(float(b), 6) for b in cal['beta_history'][-1][:, 0]], length=cal['length'], device=name))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--bands', action='store_true', help='per-band measurement and a seven-band calibration instead (DESIGN.md section 9p)')
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--host-rounds', type=int, default=2, help='samples of the host legs')
     ap.add_argument('--warmup', type=int, default=1)
@@ -73,6 +131,8 @@ def main():
 
     med = lambda t: round(float(np.median(t)), 3)
     stats = lambda t: dict(ms_median=med(t), ms_min=round(float(min(t)), 3), ms_max=round(float(max(t)), 3), samples=len(t))
+    if args.bands:
+        return banded(args, emit, stats)
     room = rooms.ShoeboxRoom(SIZE, rt60=0.3)
     legs = {'a HIP': (True, dev), 'b torch, device': (False, dev), 'c torch, host': (False, 'cpu')}
     for n_dir in (72, 360):

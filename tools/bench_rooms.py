@@ -12,9 +12,10 @@ recorded with each shape, and so is the time of salsa_room_rirs' launch alone (d
 launcher's host-side check of the table).  One JSON line per record; whatever is seen is reported, a leg that loses included.
 
 --baffle rigid measures the MIC bank of 72 directions with the capsules on the rigid sphere instead: rigid(),
-whose docstring lists its legs; the two launches alone share one image table (the rigid geometry's).
+whose docstring lists its legs; the two launches alone share one image table (the rigid geometry's).  --bands measures the FOA bank of
+72 directions in a room with seven octave bands: banded(), whose docstring lists its comparisons.
 
-    python tools/bench_rooms.py [--baffle rigid] [--rounds 5] [--host-rounds 2] [--warmup 1] [--out profiles/room_rir_bench.jsonl]"""
+    python tools/bench_rooms.py [--baffle rigid | --bands] [--rounds 5] [--host-rounds 2] [--warmup 1] [--out profiles/room_rir_bench.jsonl]"""
 import argparse
 import json
 import os
@@ -143,8 +144,116 @@ def rigid(args):
                 f.write(line + '\n')
 
 
+def _event_ms(calls, samples):
+    """device events around each call, the calls ALTERNATING, one sample of each per round -> one list of ms per call"""
+    import torch
+    ms = [[] for _ in calls]
+    for r in range(samples[0] + samples[1]):
+        for which, call in enumerate(calls):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            call()
+            b.record()
+            torch.cuda.synchronize()
+            if r >= samples[0]:
+                ms[which].append(a.elapsed_time(b))
+    return ms
+
+
+def banded(args):
+    """--bands: the FOA bank of 72 directions in a room with seven octave bands, every band at rt60 = 0.3 s so that
+    the table is the one of the broadband records.  Three comparisons, each with its legs alternating in one process:
+      launches   salsa_room_rirs_bands (K = 7, the taps -D .. L + D - 1) against seven launches of salsa_room_rirs over as many taps, one
+                 per band -- what the parent commit offers for the same rows (its taps start at 0; the work is the same);
+      filters    salsa_band_merge and salsa_band_split against torch's conv1d on the device, on the bank's own shapes;
+      whole      room_rir_bank of the banded room: HIP, the composed torch path on the device, and the broadband room's HIP call."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    from salsa_amd import _lib, rooms
+    L = _lib.load()
+    dev = torch.device('cuda:0')
+    K, D, length, n_dir = len(rooms.OCTAVE_BANDS), rooms.BAND_HALF, args.rir_len, 72
+    room = rooms.ShoeboxRoom((6.0, 5.0, 3.2), rt60=(0.3,) * K, bands=rooms.OCTAVE_BANDS)
+    plain = rooms.ShoeboxRoom((6.0, 5.0, 3.2), rt60=0.3)
+    directions = [(az, 0) for az in range(-180, 180, 360 // n_dir)]
+    _, sources, receivers, d_max = rooms.room_geometry('foa', room, directions, args.distance, length)
+    images = rooms.room_images(room, d_max)
+    table, n_taps, fs_over_c = images.band_table(), length + 2 * D, room.fs / room.c
+    single = np.ascontiguousarray(table[:7])
+    d_table, d_single, d_sources = (torch.from_numpy(a).to(dev) for a in (table, single, sources))
+    r = torch.empty((n_dir, 4, K, n_taps), dtype=torch.float32, device=dev)
+    one = torch.empty((n_dir, 4, n_taps), dtype=torch.float32, device=dev)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    dp = lambda t: C.c_void_p(t.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def ok(rc):
+        if rc:
+            raise RuntimeError(_lib.last_error())
+
+    def launch_banded():
+        ok(L.salsa_room_rirs_bands(hp(table), dp(d_table), table.shape[1], K, hp(sources), dp(d_sources), n_dir, hp(receivers), 1, 1, fs_over_c, -D,
+                                   n_taps, dp(r), stream))
+
+    def launch_k_single():
+        for _ in range(K):
+            ok(L.salsa_room_rirs(hp(single), dp(d_single), single.shape[1], hp(sources), dp(d_sources), n_dir, hp(receivers), 1, 1, fs_over_c, n_taps,
+                                 dp(one), stream))
+    banded_ms, single_ms = _event_ms((launch_banded, launch_k_single), (args.warmup, args.rounds))
+    # the filters, on the rows the launch left
+    filters = torch.from_numpy(rooms.octave_filters(room.fs).astype(np.float32)).to(dev)
+    rows = r.reshape(n_dir * 4, K, n_taps)
+    merged = rooms._band_merge_hip(rows, filters)
+    merge_diff = float((merged - rooms._band_merge_torch(rows, filters)).abs().max())
+    split_diff = float((rooms._band_split_hip(merged, filters) - rooms._band_split_torch(merged, filters)).abs().max())
+    filter_ms = _event_ms((lambda: rooms._band_merge_hip(rows, filters), lambda: rooms._band_merge_torch(rows, filters),
+                           lambda: rooms._band_split_hip(merged, filters), lambda: rooms._band_split_torch(merged, filters)), (args.warmup, args.rounds))
+    # whole calls
+    legs = {'a HIP banded': (True, room), 'b torch banded, device': (False, room), "a' HIP broadband": (True, plain)}
+    times, last = {k: [] for k in legs}, {}
+    for rnd in range(args.warmup + args.rounds):
+        for leg, (hip, which) in legs.items():
+            if not hip and rnd >= args.warmup + args.host_rounds:
+                continue
+            rooms.HIP_ROOM = hip
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            bank = rooms.room_rir_bank('foa', which, directions, args.distance, length, device=dev)
+            torch.cuda.synchronize()
+            if rnd >= args.warmup:
+                times[leg].append((time.perf_counter() - t0) * 1e3)
+            last[leg] = bank.rirs
+    rooms.HIP_ROOM = True
+    med = lambda v: round(float(np.median(v)), 3)
+    span = lambda v: [round(float(min(v)), 3), round(float(max(v)), 3)]
+    common = dict(bench='room_rir_bands', format='foa', directions=n_dir, rir_len=length, bands=K, band_half=D, room=[6.0, 5.0, 3.2], rt60_nominal=0.3,
+                  distance=args.distance, images=len(images), device=torch.cuda.get_device_name(0))
+    recs = [dict(common, what='launches alone', taps=n_taps, banded_launch_ms_median=med(banded_ms), banded_launch_ms_min_max=span(banded_ms),
+                 k_single_launches_ms_median=med(single_ms), k_single_launches_ms_min_max=span(single_ms), samples=len(banded_ms),
+                 banded_over_k_single=round(float(np.median(banded_ms) / np.median(single_ms)), 3)),
+            dict(common, what='filters', rows=n_dir * 4, merge_hip_ms_median=med(filter_ms[0]), merge_hip_ms_min_max=span(filter_ms[0]),
+                 merge_conv1d_ms_median=med(filter_ms[1]), merge_conv1d_ms_min_max=span(filter_ms[1]), split_hip_ms_median=med(filter_ms[2]),
+                 split_hip_ms_min_max=span(filter_ms[2]), split_conv1d_ms_median=med(filter_ms[3]), split_conv1d_ms_min_max=span(filter_ms[3]),
+                 samples=len(filter_ms[0]), merge_hip_over_conv1d=round(float(np.median(filter_ms[0]) / np.median(filter_ms[1])), 3),
+                 split_hip_over_conv1d=round(float(np.median(filter_ms[2]) / np.median(filter_ms[3])), 3),
+                 merge_max_abs_difference=merge_diff, split_max_abs_difference=split_diff)]
+    for leg in legs:
+        recs.append(dict(common, what='whole call', leg=leg, ms_median=med(times[leg]), ms_min_max=span(times[leg]), samples=len(times[leg]),
+                         max_abs_difference_from_leg_a=float(np.abs(last[leg] - last['a HIP banded']).max()),
+                         max_abs_response=round(float(np.abs(last[leg]).max()), 4)))
+    for rec in recs:
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, 'a') as f:
+                f.write(line + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--bands', action='store_true', help='the legs of the octave-band room instead (DESIGN.md section 9p)')
     ap.add_argument('--baffle', choices=['open', 'rigid'], default='open', help='rigid: the legs of the rigid-sphere MIC bank instead')
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--host-rounds', type=int, default=2, help='samples of leg c')
@@ -158,6 +267,8 @@ def main():
     from salsa_amd import rooms
     if not torch.cuda.is_available():
         raise SystemExit('bench_rooms.py measures on cuda:0; there is none')
+    if args.bands:
+        return banded(args)
     if args.baffle == 'rigid':
         return rigid(args)
     dev = torch.device('cuda:0')
