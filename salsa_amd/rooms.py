@@ -28,7 +28,8 @@ interpolation of four entries.  An image then adds g_r (A / d) interp(Theta_m, k
 t0_r measured to the array CENTRE (one distance and delay for the four capsules) and Theta_m the angle between the image's direction and
 capsule m: a plane-wave model, so a source nearer than 10 radii (0.42 m) is refused.  t0_r and d_max use the table's lead (32) for
 H.  float64 up to floor tau, the two interpolation weights and the coefficient, float32 from the table lookup on; the sums run in
-salsa_amd/csrc/room_sphere.hip (salsa_room_rirs_sphere), or in the composed torch path as above.
+salsa_amd/csrc/room_sphere.hip (salsa_room_rirs_sphere; the skeleton it shares with room_rir.hip is salsa_amd/csrc/room_gather.h), or
+in the composed torch path as above.
 
 Decay: rir_acoustics measures any response array (R, C, L) -- Schroeder's energy decay curve, EDT, T20, T30 with
 the headroom of each fit, DRR, C50 -- in float64, in salsa_amd/csrc/rir_decay.hip (include/salsa_hip.h: salsa_rir_decay, where the
@@ -39,10 +40,10 @@ one asked for.
 Octave-band walls: ShoeboxRoom(bands=OCTAVE_BANDS) gives the walls one set of coefficients per band.  The image
 table then carries one amplitude row per band, and the response is sum_b sum_j h_b[j] r_b[k + D - j]: r_b the definition above with
 band b's amplitudes on the taps -D .. length + D - 1, h_b = octave_filters (linear phase, 2 D + 1 taps, sum_b h_b a unit impulse at D,
-read as float32).  The r_b come from one launch of salsa_room_rirs_bands (salsa_amd/csrc/room_bands.hip: an image's geometry and
-windowed sinc once, K accumulators), the sum from salsa_band_merge; rir_acoustics(bands=) splits a response into its band signals
-(salsa_band_split) and measures each, and calibrate_room(bands=) fits one wall scale per band.  The switches above send all of it
-to composed torch paths (per-band _rirs_torch, conv1d)."""
+read as float32).  The r_b come from one launch of salsa_room_rirs_bands (salsa_amd/csrc/room_rir.hip, salsa_room_rirs's gather with K
+accumulators: an image's geometry and windowed sinc once), the sum from salsa_band_merge (salsa_amd/csrc/room_bands.hip);
+rir_acoustics(bands=) splits a response into its band signals (salsa_band_split) and measures each, and calibrate_room(bands=) fits
+one wall scale per band.  The switches above send all of it to composed torch paths (per-band _rirs_torch, conv1d)."""
 import ctypes as C
 import os
 
@@ -216,7 +217,7 @@ class RoomImages:
         """float64 (7, N), what salsa_room_rirs takes: the rows sign x, y, z, shift x, y, z, amplitude"""
         if self.amplitude.ndim != 1:
             raise ValueError('a banded room has one amplitude row per band: band_table()')
-        return np.ascontiguousarray(np.concatenate([self.sign.T, self.shift.T, self.amplitude[None]]), np.float64)
+        return self.band_table()
 
     def band_table(self):
         """float64 (6 + K, N), what salsa_room_rirs_bands takes: the rows sign x, y, z, shift x, y, z, then the amplitude of each band
@@ -485,64 +486,53 @@ def _rirs_torch(table, sources, receivers, foa, fs_over_c, length, device, spher
     return out
 
 
-def _rirs_hip_sphere(table, sources, sphere, fs_over_c, length, device):
-    import torch
-    L = _lib.load()
-    st, centre, units = sphere
-    centre, units = np.ascontiguousarray(centre, np.float64), np.ascontiguousarray(units, np.float64)
-    R = len(sources)
-    out = torch.empty((R, 4, length), dtype=torch.float32, device=device)
-    d_table, d_sources, d_sphere = torch.from_numpy(table).to(device), torch.from_numpy(sources).to(device), st.on(device)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
-    with torch.cuda.device(device):
-        rc = L.salsa_room_rirs_sphere(hp(table), C.c_void_p(d_table.data_ptr()), table.shape[1], hp(sources), C.c_void_p(d_sources.data_ptr()), R,
-                                      hp(centre), hp(units), hp(st.table), C.c_void_p(d_sphere.data_ptr()), st.Q, st.P, st.lead, st.trail,
-                                      fs_over_c, length, C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc:
-        raise RuntimeError('salsa_room_rirs_sphere failed (%d): %s' % (rc, _lib.last_error()))
-    torch.cuda.current_stream(device).synchronize()                           # the tables may go now
-    return out
-
-
-def _rirs_hip(table, sources, receivers, foa, fs_over_c, length, device, sphere=None):
-    import torch
-    if sphere is not None:
-        return _rirs_hip_sphere(table, sources, sphere, fs_over_c, length, device)
-    L = _lib.load()
-    R, M = len(sources), len(receivers)
-    out = torch.empty((R, 4 if foa else M, length), dtype=torch.float32, device=device)
-    d_table, d_sources = torch.from_numpy(table).to(device), torch.from_numpy(sources).to(device)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
-    with torch.cuda.device(device):
-        rc = L.salsa_room_rirs(hp(table), C.c_void_p(d_table.data_ptr()), table.shape[1], hp(sources), C.c_void_p(d_sources.data_ptr()), R,
-                               hp(receivers), M, 1 if foa else 0, fs_over_c, length, C.c_void_p(out.data_ptr()),
-                               C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc:
-        raise RuntimeError('salsa_room_rirs failed (%d): %s' % (rc, _lib.last_error()))
-    torch.cuda.current_stream(device).synchronize()                           # the tables may go now
-    return out
-
-
-# ---- octave-band walls ----------------------------------------------------------------------------------------
-def _band_call(name, *args):
+def _room_call(name, *args):
+    """the entry point `name` of the library; a nonzero return raises with the library's message"""
     rc = getattr(_lib.load(), name)(*args)
     if rc:
         raise RuntimeError('%s failed (%d): %s' % (name, rc, _lib.last_error()))
 
 
+def _hp(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def _gather_hip(name, table, sources, shape, device, head, tail):
+    """One launch of the gather entry point `name` -> float32 `shape` on the device.  The image table and the sources are uploaded; the
+    call is name(table, its copy, N, *head, sources, their copy, R, *tail, out, stream) on the device's current stream, which is
+    synchronised before the uploads go."""
+    import torch
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    d_table, d_sources = torch.from_numpy(table).to(device), torch.from_numpy(sources).to(device)
+    stream = torch.cuda.current_stream(device)
+    with torch.cuda.device(device):
+        _room_call(name, _hp(table), C.c_void_p(d_table.data_ptr()), table.shape[1], *head, _hp(sources), C.c_void_p(d_sources.data_ptr()),
+                   len(sources), *tail, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
+    stream.synchronize()                                                      # the tables may go now
+    return out
+
+
+def _rirs_hip_sphere(table, sources, sphere, fs_over_c, length, device):
+    st, centre, units = sphere
+    centre, units = np.ascontiguousarray(centre, np.float64), np.ascontiguousarray(units, np.float64)
+    tail = (_hp(centre), _hp(units), _hp(st.table), C.c_void_p(st.on(device).data_ptr()), st.Q, st.P, st.lead, st.trail, fs_over_c, length)
+    return _gather_hip('salsa_room_rirs_sphere', table, sources, (len(sources), 4, length), device, (), tail)
+
+
+def _rirs_hip(table, sources, receivers, foa, fs_over_c, length, device, sphere=None):
+    if sphere is not None:
+        return _rirs_hip_sphere(table, sources, sphere, fs_over_c, length, device)
+    R, M = len(sources), len(receivers)
+    tail = (_hp(receivers), M, 1 if foa else 0, fs_over_c, length)
+    return _gather_hip('salsa_room_rirs', table, sources, (R, 4 if foa else M, length), device, (), tail)
+
+
+# ---- octave-band walls (DESIGN.md section 9p) ----------------------------------------------------------------------------------------
 def _band_rirs_hip(table, sources, receivers, foa, fs_over_c, first, n_taps, device):
     """salsa_room_rirs_bands -> float32 (R, C, K, n_taps) on the device: the band responses on the taps first .. first + n_taps - 1"""
-    import torch
     K, R, M = table.shape[0] - 6, len(sources), len(receivers)
-    out = torch.empty((R, 4 if foa else M, K, n_taps), dtype=torch.float32, device=device)
-    d_table, d_sources = torch.from_numpy(table).to(device), torch.from_numpy(sources).to(device)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
-    with torch.cuda.device(device):
-        _band_call('salsa_room_rirs_bands', hp(table), C.c_void_p(d_table.data_ptr()), table.shape[1], K, hp(sources),
-                   C.c_void_p(d_sources.data_ptr()), R, hp(receivers), M, 1 if foa else 0, fs_over_c, int(first), int(n_taps),
-                   C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    torch.cuda.current_stream(device).synchronize()                           # the tables may go now
-    return out
+    tail = (_hp(receivers), M, 1 if foa else 0, fs_over_c, int(first), int(n_taps))
+    return _gather_hip('salsa_room_rirs_bands', table, sources, (R, 4 if foa else M, K, n_taps), device, (K,), tail)
 
 
 def _band_merge_hip(r, filters):
@@ -552,7 +542,7 @@ def _band_merge_hip(r, filters):
     half = (filters.shape[1] - 1) // 2
     out = torch.empty((n, ext - 2 * half), dtype=torch.float32, device=r.device)
     with torch.cuda.device(r.device):
-        _band_call('salsa_band_merge', C.c_void_p(r.data_ptr()), C.c_void_p(filters.data_ptr()), n, K, ext - 2 * half, half,
+        _room_call('salsa_band_merge', C.c_void_p(r.data_ptr()), C.c_void_p(filters.data_ptr()), n, K, ext - 2 * half, half,
                    C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(r.device).cuda_stream))
     return out
 
@@ -564,7 +554,7 @@ def _band_split_hip(x, filters):
     K, half = filters.shape[0], (filters.shape[1] - 1) // 2
     out = torch.empty((n, K, L), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _band_call('salsa_band_split', C.c_void_p(x.data_ptr()), C.c_void_p(filters.data_ptr()), n, K, L, half, C.c_void_p(out.data_ptr()),
+        _room_call('salsa_band_split', C.c_void_p(x.data_ptr()), C.c_void_p(filters.data_ptr()), n, K, L, half, C.c_void_p(out.data_ptr()),
                    C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
     return out
 

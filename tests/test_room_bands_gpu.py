@@ -1,5 +1,5 @@
-"""GPU tests of the octave-band rooms (salsa_amd/csrc/room_bands.hip) against the float64 restatement
-tests/room_bands_reference.py, on image tables built by hand (tests/room_tables.py).
+"""GPU tests of the octave-band rooms (the gather of salsa_amd/csrc/room_rir.hip, the filters of room_bands.hip)
+against the float64 restatement tests/room_bands_reference.py, on image tables built by hand (tests/room_tables.py).
 
   gather   salsa_room_rirs_bands on a 520-image table whose delays run from tap -1040 to tap 480, eight amplitude rows (row 1 all zero,
            single zeros elsewhere), FOA and one and four omni receivers.  ONE window, first_tap = -1024 and 1537 taps, is held to float64
@@ -7,7 +7,8 @@ tests/room_bands_reference.py, on image tables built by hand (tests/room_tables.
            order and reversed.  Every other window -- first_tap in {0, -1, -1024} x n_taps in {1, 255, 256, 257, 513} -- is held to that
            run BIT FOR BIT (a tap's bits depend neither on first_tap nor on n_taps), which is the same bound on each of them and more.
            K = 1 at first_tap = 0 is salsa_room_rirs bit for bit; a source alone is its row of a batch; two runs agree; the zero band and
-           every tap outside the supports are +0.0; table order is read from exact tables (1 then 4096 x 2^-25).
+           every tap outside the supports are +0.0; table order is read from exact tables (1 then 4096 x 2^-25).  The launchers' shared
+           checks (room_gather.h) refuse the same tables at all three gather entry points, each within its own limits.
   filters  salsa_band_merge and salsa_band_split at half in {1, 16, 1024} x L in {1, 255, 256, 257, 2049}: an impulse in gives the taps
            bit for bit, random rows hold the float64 bound (Y: the float32 chain in the definition's order and reversed), equal bands
            give the input back, two runs agree and a row does not depend on its batch.
@@ -161,6 +162,8 @@ def test_every_window_is_a_slice_bit_for_bit(K, fmt):
 
 @pytest.mark.parametrize('fmt', ['foa', 'omni1', 'omni4'])
 def test_one_band_from_tap_zero_is_salsa_room_rirs(fmt):
+    """salsa_room_rirs launches the K = 1 instantiation of the band gather from tap 0 (room_rir.hip): this holds the entry point's
+    mapping of its arguments -- one band, first_tap = 0, n_taps = rir_len, the output layout -- to salsa_room_rirs_bands's, bit for bit."""
     foa = fmt == 'foa'
     for name in ('all_257', 'alternating', 'lane63'):
         table = rt.built_table(rt.MASKS[name])
@@ -228,6 +231,80 @@ def test_the_gather_refuses_what_it_cannot_run():
         assert call(**kw) == -1, kw
     assert 'amplitude' in _lib.last_error()
     torch.cuda.synchronize()
+
+
+def test_the_three_gathers_share_their_checks_and_keep_their_limits():
+    """room_gather.h's host checks behind salsa_room_rirs, salsa_room_rirs_bands and salsa_room_rirs_sphere, on the 520-image table with one
+    source and one omni receiver: an amplitude of 0 and 16385 taps are refused by salsa_room_rirs and taken by salsa_room_rirs_bands; a
+    sign of 0.5, a NaN shift, a fractional t0 and a gain of 0 are refused by all three, and a refusal launches nothing (the output and
+    its guard bands stay NaN)."""
+    L = _lib.load()
+    table, rows, rec = np.array(_band_table()[:7]), _source_row(), np.ascontiguousarray(rt.RECEIVERS[:1])
+    units = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [-1.0, 0.0, 0.0]])
+    Q, P, lead, trail = 4, 2, 3, 5
+    sphere = np.ones((Q + 1) * (P + 1) * (lead + trail), np.float32)            # (the kernel only reads it, every index clamped)
+    d_rows, d_sphere = torch.from_numpy(rows).to(DEV), torch.from_numpy(sphere).to(DEV)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    dp = lambda t: C.c_void_p(t.data_ptr())
+    keep = []
+
+    def up(a):                                                                  # the device copy of the table a call is given
+        keep.append(torch.from_numpy(a).to(DEV))
+        return dp(keep[-1])
+
+    def rirs(buf, table=table, rows=rows, length=64):
+        return L.salsa_room_rirs(p(table), up(table), table.shape[1], p(rows), dp(d_rows), 1, p(rec), 1, 0, rt.FS_OVER_C, length,
+                                 dp(buf[GUARD:]), _stream())
+
+    def bands(buf, table=table, rows=rows, length=64):
+        return L.salsa_room_rirs_bands(p(table), up(table), table.shape[1], 1, p(rows), dp(d_rows), 1, p(rec), 1, 0, rt.FS_OVER_C, 0, length,
+                                       dp(buf[GUARD:]), _stream())
+
+    def rigid(buf, table=table, rows=rows, length=64):
+        return L.salsa_room_rirs_sphere(p(table), up(table), table.shape[1], p(rows), dp(d_rows), 1, p(rec), p(units), p(sphere), dp(d_sphere),
+                                        Q, P, lead, trail, rt.FS_OVER_C, length, dp(buf[GUARD:]), _stream())
+    # an amplitude of 0: refused where an image without amplitude has no place, taken where a band may carry nothing
+    tau = np.sqrt(((table[0:3] * rt.SOURCE[:, None] + table[3:6] - rec[0][:, None]) ** 2).sum(axis=0)) * rt.FS_OVER_C - T0
+    col = int(np.nonzero((tau > 100.0) & (tau < 200.0))[0][0])                 # an image in the middle of the taps 0 .. 299
+    zero = table.copy()
+    zero[6, col] = 0.0
+    buf = _guarded(64)
+    assert rirs(buf, table=zero) == -1 and 'amplitude' in _lib.last_error() and 'salsa_room_rirs:' in _lib.last_error()
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(buf).all())
+    full = _full_window(1, 'omni1')[0, 0]                                      # the taps -1024 .. 512 of the table as it is
+    buf = _guarded(300)
+    assert bands(buf, table=zero, length=300) == 0, _lib.last_error()
+    got = _unguard(buf, 300).cpu().numpy()
+    rest = np.ascontiguousarray(np.delete(table, col, axis=1))                 # the sums started at +0.0, so a term +-0 changes no bit of them:
+    buf = _guarded(300)                                                        # the response is the one of the table without that image
+    assert bands(buf, table=rest, length=300) == 0, _lib.last_error()
+    want = _unguard(buf, 300).cpu().numpy()
+    assert np.array_equal(_bits(got), _bits(want)) and not (_bits(got) == 0x80000000).any() and not np.array_equal(_bits(got), _bits(full[1024:1324]))
+    # 16385 taps
+    buf = _guarded(64)
+    assert rirs(buf, length=16385) == -1 and 'rir length' in _lib.last_error()
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(buf).all())
+    buf = _guarded(16385)
+    assert bands(buf, length=16385) == 0, _lib.last_error()
+    got = _unguard(buf, 16385).cpu().numpy()
+    assert np.array_equal(_bits(got[:513]), _bits(full[1024:])) and not _bits(got[513:]).any()      # (every delay lies below tap 480)
+    # what no gather takes
+    def changed(a, at, v):
+        a = a.copy()
+        a[at] = v
+        return a
+    refused = (dict(table=changed(table, (0, 5), 0.5)), dict(table=changed(table, (4, 5), float('nan'))), dict(rows=changed(rows, (0, 3), T0 + 0.5)),
+               dict(rows=changed(rows, (0, 4), 0.0)))
+    for call, n in ((rirs, 64), (bands, 64), (rigid, 256)):
+        buf = _guarded(n)
+        for kw in refused:
+            assert call(buf, **kw) == -1, (call.__name__, kw)
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(buf).all()), call.__name__
+        assert call(buf) == 0, _lib.last_error()                               # (a control: the same call with the tables in order runs)
+        _unguard(buf, n)
 
 
 # ---- merge and split -----------------------------------------------------------------------------------------------------------------
