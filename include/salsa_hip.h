@@ -350,6 +350,30 @@ int salsa_scene_render_moving(const float *d_events, int64_t n_event_samples, co
                               int max_segment_len, const float *d_ambient, float *d_out, int64_t n_samples, void *d_workspace,
                               size_t workspace_bytes, void *hip_stream);
 
+/* Spatially diffuse ambient noise (salsa_amd/ambient.py; the reference has no counterpart: the definition is this
+ * project's).  n_dirs uncorrelated plane-wave noises reach the four channels through the array's direct-path response, one colouring
+ * filter follows, and the result is added to the rendered audio at a per-clip scale:
+ *     m[c][t] = sum_{d < n_dirs} sum_{k < mix_taps} mix[d][c][k] white(seed_b, d, t - k)
+ *     y[c][n] = sum_{j < colour_taps} colour[j] m[c][n - j]
+ *     out[b][c][n] = fmaf(scale_b, y[c][n], in[b][c][n]),   without d_in: scale_b * y[c][n],   0 <= n < n_samples,
+ * all float32 fmaf chains from +0.0 in the order written (d outer, k inner, j, each ascending).  white(seed, d, n) is a counter hash, a
+ * pure function of its three integers defined from n = -1024 on (so the noise has no onset at sample 0), mean 0 and variance 1; it is
+ * stated in salsa_amd/csrc/scene_diffuse.hip's header and restated in tests/diffuse_reference.py.
+ * d_mix float32 [n_dirs][n_channels][mix_taps], d_colour float32 [colour_taps], d_seeds uint64 [n_clips], d_scales float32 [n_clips] --
+ * all on the device, so a scale computed there needs no synchronisation.  d_in float32 [n_clips][n_channels][n_samples] or NULL, and it
+ * may be d_out; d_out the same shape.  A clip whose scale is 0 gets d_in's bits (+0.0 without d_in).  A clip's bits depend on its seed,
+ * its scale and its input alone -- not on the batch, its place in it or n_samples (a shorter call gives the first samples' bits) --, and
+ * two calls give equal bits.  One launch on hip_stream, nothing allocated or synchronised; a workgroup owns
+ * salsa_scene_diffuse_block() = 2048 consecutive samples of one clip.
+ * Supported (salsa_scene_diffuse_supported, host only, 1 or 0): n_channels == 4, 1 <= n_dirs <= 256, 1 <= mix_taps <= 128, 1 <=
+ * colour_taps <= 513 and odd.  Further n_clips >= 1, 1 <= n_samples < 2^32 and at most 2^31 - 1 blocks in all.  Returns -1 for a shape
+ * outside these limits or a null pointer, before any device call, and -6 when the launch fails. */
+int salsa_scene_diffuse_block(void);
+int salsa_scene_diffuse_supported(int n_channels, int n_dirs, int mix_taps, int colour_taps);
+int salsa_scene_diffuse(const float *d_mix, int n_dirs, int n_channels, int mix_taps, const float *d_colour, int colour_taps,
+                        const uint64_t *d_seeds, const float *d_scales, const float *d_in, float *d_out, int n_clips, int64_t n_samples,
+                        void *hip_stream);
+
 /* Shoebox room responses by the image-source method (salsa_amd/rooms.py; the reference has no counterpart: the
  * definition is this project's).  The caller has enumerated the room's images once, for all sources: image i mirrors a source s to
  * p = sign_i o s + shift_i (sign = 1 - 2 q, shift = 2 n o L) with the amplitude A_i (the walls' reflection coefficients to the powers

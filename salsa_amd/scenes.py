@@ -536,9 +536,18 @@ def render_scenes(scenes, pool, bank, n_samples=None, ambient=None, out=None, de
                    n_samples, ambient, out, device)
 
 
-def add_scenes(feature_bank, scenes, pool, bank, names=None, ambient=None, n_classes=None, label_rate=10, fs=FS):
-    """Render, then feature_bank.add_clips(audio, names, sed=, doa=) with the scenes' labels in the bank's label format.  -> the audio."""
+def add_scenes(feature_bank, scenes, pool, bank, names=None, ambient=None, n_classes=None, label_rate=10, fs=FS, diffuse=None):
+    """Render, then feature_bank.add_clips(audio, names, sed=, doa=) with the scenes' labels in the bank's label format.  -> the audio.
+    diffuse: (DiffuseField, dict(snr_db= or level_db=, seed=)) adds spatially diffuse noise to the render (ambient.add_diffuse, DESIGN.md
+    section 9q; clip b gets the seed `seed` + b); None leaves the render as it is."""
     audio = render_scenes(scenes, pool, bank, ambient=ambient, device=feature_bank.device)
+    if diffuse is not None:
+        from . import ambient as _ambient
+        field, how = diffuse
+        if field.audio_format != bank.audio_format:
+            raise ValueError('a %s field on a %s bank' % (field.audio_format, bank.audio_format))
+        how = dict(how)
+        _ambient.add_diffuse(audio, field, seeds=how.pop('seed', None), out=audio, **how)
     fmt = feature_bank.label_format
     n_classes = (feature_bank.n_classes // 3 if fmt == 'trackwise' else feature_bank.n_classes) if n_classes is None else n_classes
     n_lab = -(-scenes.n_samples // (fs // label_rate))
@@ -550,6 +559,7 @@ def add_scenes(feature_bank, scenes, pool, bank, names=None, ambient=None, n_cla
 
 _ROOMS = ('ShoeboxRoom', 'RoomImages', 'room_images', 'room_rirs', 'room_rir_bank', 'eyring_beta', 'RirAcoustics', 'rir_acoustics',
           'calibrate_room', 'sphere_response', 'sphere_filter', 'SphereTable', 'sphere_table', 'OCTAVE_BANDS', 'octave_filters')
+_AMBIENT = ('DiffuseField', 'diffuse_noise', 'add_diffuse', 'colour_filter', 'fibonacci_sphere')
 
 
 def __getattr__(name):
@@ -558,4 +568,7 @@ def __getattr__(name):
     if name in _ROOMS:
         from . import rooms
         return getattr(rooms, name)
+    if name in _AMBIENT:                                                       # ambient.py (diffuse noise) likewise
+        from . import ambient
+        return getattr(ambient, name)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

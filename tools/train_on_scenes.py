@@ -4,7 +4,7 @@ drawn from different seeds over ONE event pool and ONE response bank (salsa_amd/
 GpuFeatureBanks, and Trainer.fit runs a few epochs.  The SELD 2021 scores on the held-out scenes are recorded before training and
 after every epoch.  No score is promised; the JSON lines say what was seen.
 
-    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--moving 0.5] [--room] [--format mic --baffle rigid] [--out profiles/scene_training.jsonl]
+    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--moving 0.5] [--room] [--format mic --baffle rigid] [--ambient diffuse --snr-db 20] [--out profiles/scene_training.jsonl]
 
 --moving FRACTION makes that share of the items move in azimuth in the training and the held-out scenes alike, so
 the ground truth's directions change inside events; 0 (the default) leaves the run as it was.
@@ -12,7 +12,10 @@ the ground truth's directions change inside events; 0 (the default) leaves the r
 --distance metres from the centre of a 6 x 5 x 3.2 m shoebox whose uniform reflection coefficient is Eyring's for --rt60 (a nominal
 figure: the realised decay is longer), generated on the device.
 --format mic renders the four capsules of the TNSSE tetrahedron and extracts SALSA-MIC (fmax_doa 4 kHz); --baffle rigid puts them on the
-rigid sphere, --baffle open (the default) leaves them in free space.  Each run is ONE run."""
+rigid sphere, --baffle open (the default) leaves them in free space.
+--ambient white (the default) renders the scenes over channel-independent white noise of rms 1e-3, the draw this tool has always made;
+--ambient diffuse adds the spatially diffuse field of DESIGN.md section 9q instead (64 directions, 'room' colour, the array of --format and
+--baffle) at --snr-db decibels below each clip's own mean square.  Each run is ONE run."""
 import argparse
 import json
 import os
@@ -24,7 +27,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--train-clips', type=int, default=48)
     ap.add_argument('--val-clips', type=int, default=8)
@@ -40,10 +43,27 @@ def main():
     ap.add_argument('--format', choices=['foa', 'mic'], default='foa', help='mic: the TNSSE tetrahedron, SALSA-MIC features up to 4 kHz')
     ap.add_argument('--baffle', choices=['open', 'rigid'], default='open',
                     help='--format mic: the capsules in free space, or on the rigid sphere of DESIGN.md section 9o')
+    ap.add_argument('--ambient', choices=['white', 'diffuse'], default='white',
+                    help='white: independent noise of rms 1e-3 per channel; diffuse: the diffuse field of DESIGN.md section 9q at --snr-db')
+    ap.add_argument('--snr-db', type=float, default=20.0, help='--ambient diffuse: each clip\'s mean square over the noise\'s expected one, dB')
     ap.add_argument('--out', default=None, help='append the JSON lines to this file too')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.baffle == 'rigid' and args.format != 'mic':
         ap.error('--baffle rigid needs --format mic')
+    return args
+
+
+def scene_ambient(args, field, n_clips, n, device, generator, first_seed):
+    """-> (ambient, diffuse) for add_scenes: --ambient white draws the ambient tensor from `generator` and adds no field; --ambient diffuse
+    renders over silence and hands `field` on, clip i seeded first_seed + i"""
+    import torch
+    if args.ambient == 'white':
+        return 1e-3 * torch.randn(n_clips, 4, n, device=device, generator=generator), None
+    return None, (field, dict(snr_db=args.snr_db, seed=first_seed))
+
+
+def main():
+    args = parse_args()
     baffle = dict(baffle=args.baffle) if args.format == 'mic' else {}
     import numpy as np
     import torch
@@ -79,6 +99,9 @@ def main():
     else:
         rbank = sc.make_rir_bank(args.format, directions, args.rir_len, rt60=args.rt60, seed=1, **baffle)
     ex = SalsaExtractor(audio_format=args.format, fmax_doa=9000 if args.format == 'foa' else 4000, device=dev)
+    field = sc.DiffuseField(args.format, **baffle) if args.ambient == 'diffuse' else None
+    noise_rec = dict(ambient_rms=1e-3) if field is None else dict(ambient='diffuse', snr_db=args.snr_db, diffuse_directions=field.n_directions,
+                                                                  diffuse_colour='room')
     t0 = time.perf_counter()
     banks, drawn = {}, {}
     for name, clips, seed in (('train', args.train_clips, args.seed), ('val', args.val_clips, args.seed + 1000)):
@@ -87,8 +110,8 @@ def main():
         g = torch.Generator(dev).manual_seed(seed)
         for lo in range(0, clips, 16):                                         # 16 clips of audio at a time
             part = scenes.clips(lo, min(lo + 16, clips))
-            amb = 1e-3 * torch.randn(part.n_clips, 4, n, device=dev, generator=g)
-            sc.add_scenes(bank, part, pool, rbank, names=['%s_%04d' % (name, lo + i) for i in range(part.n_clips)], ambient=amb)
+            amb, diffuse = scene_ambient(args, field, part.n_clips, n, dev, g, seed * 65536 + lo)
+            sc.add_scenes(bank, part, pool, rbank, names=['%s_%04d' % (name, lo + i) for i in range(part.n_clips)], ambient=amb, diffuse=diffuse)
         banks[name], drawn[name] = bank, scenes
     banks['train'].fit_scaler()
     mean, std = (t.cpu().numpy() if torch.is_tensor(t) else t for t in (banks['train'].mean, banks['train'].std))
@@ -99,7 +122,7 @@ def main():
     val_gt = [[(int(f), int(c), float(az), float(el), int(t)) for f, c, t, az, el in sc.scene_rows(drawn['val'][b])] for b in range(args.val_clips)]
     emit(dict(record='scene_training', what='setup', train_clips=args.train_clips, val_clips=args.val_clips, clip_s=args.clip_s,
               train_items=int(drawn['train'].n_items), val_items=int(drawn['val'].n_items), train_chunks=len(banks['train']), classes=NC,
-              audio_format=args.format, **baffle, responses=int(rbank.n_rirs), rir_len=args.rir_len, rt60=args.rt60, events_in_pool=len(pool), ambient_rms=1e-3,
+              audio_format=args.format, **baffle, responses=int(rbank.n_rirs), rir_len=args.rir_len, rt60=args.rt60, events_in_pool=len(pool), **noise_rec,
               seconds_to_render_extract_and_bank=round(time.perf_counter() - t0, 2), device=torch.cuda.get_device_name(0), **room_rec,
               **(dict(moving=args.moving, traj_step=int(drawn['train'].traj_step), speed_deg_s=[10.0, 40.0],
                       train_moving_items=int((np.diff(drawn['train'].traj_start) > 0).sum()), train_trajectory_nodes=len(drawn['train'].traj_rir),
