@@ -119,9 +119,7 @@ size_t salsa_multichannel_workspace_bytes(const salsa_plan *pl, int n_channels, 
 {
     if (!pl || batch <= 0 || n_samples <= 0 || n_channels < 4 || n_channels > SALSA_MAX_MICS || (n_channels & 1)) return 0;
     if (pl->p.feature_type != SALSA_FEATURE_SALSA) return 256;
-    const size_t T = 1 + n_samples / pl->p.hop_len;
-    return align256((size_t)batch * T * n_channels * pl->nd * sizeof(float2)) +
-           align256((size_t)batch * ((pl->nd + TR_BINS - 1) / TR_BINS) * T * sizeof(unsigned)) + 256;
+    return workspace_layout(batch, (size_t)(1 + n_samples / pl->p.hop_len), pl->nd, n_channels, MASK_TIGHT).total;
 }
 
 int salsa_extract_multichannel(salsa_plan *pl, const float *d_audio, int n_channels, int batch, int64_t n_samples, float *d_out,
@@ -132,17 +130,13 @@ int salsa_extract_multichannel(salsa_plan *pl, const float *d_audio, int n_chann
         return fail(SALSA_EINVAL, "salsa_extract_multichannel is the contrib (SALSA_FLAG_FLEX) surface, planar audio%s");
     if (n_channels < 6 || n_channels > SALSA_MAX_MICS || (n_channels & 1))
         return fail(SALSA_EINVAL, "salsa_extract_multichannel takes an even number of channels from 6 to 16 (pad an odd count with a silent channel; <= 4: salsa_extract_batch)%s");
-    if (n_samples <= pl->p.n_fft / 2) return fail(SALSA_EINVAL, "clip shorter than n_fft/2 samples cannot be reflect-padded%s");
+    if (const int rc = refuse_short_clip(pl, n_samples)) return rc;
     const int64_t T64 = 1 + n_samples / pl->p.hop_len;
     const int OC = 2 * n_channels - 1;
     if (n_samples * 4 * n_channels >= INT32_MAX || T64 * OC * pl->F >= INT32_MAX / 2 || T64 * n_channels * (pl->nd > 0 ? pl->nd : 1) >= INT32_MAX / 16 ||
         T64 > 65535 * 16)
         return fail(SALSA_EINVAL, "clip too long for 32-bit per-clip indexing (split it)%s");
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != pl->device)
-            return fail(SALSA_EINVAL, "the plan's tables live on the device that was current at salsa_plan_create; make it current%s");
-    }
+    if (const int rc = refuse_other_device(pl)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     KParams kp = make_kparams(pl, batch, n_samples);
     kp.nch = n_channels;
@@ -151,11 +145,10 @@ int salsa_extract_multichannel(salsa_plan *pl, const float *d_audio, int n_chann
     const bool full = pl->p.feature_type == SALSA_FEATURE_SALSA;
     float4 *Xs = nullptr;
     unsigned *valid = nullptr;
-    if (full) {
-        const size_t need = salsa_multichannel_workspace_bytes(pl, n_channels, batch, n_samples);
-        if (!d_workspace || workspace_bytes < need) return fail(SALSA_EWORKSPACE, "workspace too small%s (need %ld bytes)", "", (long)need);
-        Xs = (float4 *)d_workspace;
-        valid = (unsigned *)((unsigned char *)d_workspace + align256((size_t)batch * kp.T * n_channels * kp.nd * sizeof(float2)));
+    if (full) { // (this path has no doubt mask: cov_eig_n_kernel decides its gate in float64)
+        const WorkspaceLayout lay = workspace_layout(batch, (size_t)kp.T, kp.nd, n_channels, MASK_TIGHT);
+        if (const int rc = refuse_workspace(d_workspace, workspace_bytes, lay.total)) return rc;
+        bind_workspace(lay, d_workspace, 0, false, Xs, valid, kp);
     }
     int rc = n_channels == 6 ? launch_stft_multi<3>(pl, kp, d_audio, d_out, Xs, s)
            : n_channels == 8 ? launch_stft_multi<4>(pl, kp, d_audio, d_out, Xs, s)

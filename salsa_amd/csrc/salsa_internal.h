@@ -4,6 +4,7 @@
 //   multichannel.hip    the N-microphone contrib path (cov_eig_n_kernel) and the spectra relayout
 //   feature_utils.hip   the plan-free entry points (scaler, normalise, resample, PCM, augmentation, ...)
 //   salsa_plan.hip      host code only: the plan, the schedules of salsa_extract_batch, the one error message
+//   salsa_workspace.h   (plain C++, no HIP) the layout of the caller's workspace: regions, sizes, per-clip strides, the mask geometry
 // A unit's kernels stay in its own anonymous namespace; another unit reaches them through the launchers declared at the end of this
 // file.  The library is built without -fvisibility=hidden, so everything that crosses a unit boundary is marked SALSA_LOCAL: the
 // shared object exports the C ABI of include/*.h and nothing more.  baseline_kernels.hip, bank_batch.hip and tta.hip include this header
@@ -14,6 +15,7 @@
 
 #include "../../include/salsa_hip.h"
 #include "salsa_math.h"
+#include "salsa_workspace.h" // TR_CH, TR_BINS, align256, WorkspaceLayout
 
 #define SALSA_LOCAL __attribute__((visibility("hidden")))
 
@@ -81,8 +83,7 @@ struct KParams {
 constexpr int FEATURE_LOGSPEC_ONLY = 3;
 
 // ---- constants both sides of a launch need (the kernels that use them: salsa_kernels.hip; defaults as measured there)
-constexpr int TR_CH = 64;       // K2: frames per chunk
-constexpr int TR_BINS = 32;     // K2: bins per mask word: valid32[b][32-bin group][t]
+// (TR_CH, TR_BINS -- K2's frames per chunk and bins per mask word -- are part of the workspace's layout: salsa_workspace.h)
 #ifndef K3_FT_N
 #define K3_FT_N 8 // measured 2/4/8/16/32/64: 8 is fastest (tiles in bursts do ~10x the work of quiet ones: small tiles balance)
 #endif
@@ -170,19 +171,52 @@ struct salsa_plan {
     hipEvent_t ev_fork, ev_stft[SALSA_MAX_GROUPS], ev_stft2[SALSA_MAX_GROUPS], ev_join[SALSA_MAX_GROUPS + 1];
     hipStream_t cap_stream;
     hipGraphExec_t gexec;
-    struct {
+    struct GraphKey { // what a captured graph is good for: compared and assigned as a whole
         const float *audio;
         float *out;
         void *ws;
         const float *sc_mean, *sc_std;
         int batch, n_groups, flags;
         int64_t n_samples;
+        bool operator==(const GraphKey &o) const
+        {
+            return audio == o.audio && out == o.out && ws == o.ws && sc_mean == o.sc_mean && sc_std == o.sc_std && batch == o.batch &&
+                   n_groups == o.n_groups && flags == o.flags && n_samples == o.n_samples;
+        }
     } gkey;
 };
 
 namespace salsa_impl {
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// the workspace regions of the clip group that starts at clip g0 (salsa_workspace.h; g0 = 0: the whole batch).  The doubt mask and its
+// flag are bound only where the caller's plan gates (with_doubt): kp.doubt32 == NULL is how the kernels know an ungated plan.
+static inline void bind_workspace(const WorkspaceLayout &L, void *base, int g0, bool with_doubt, float4 *&Xs, unsigned *&valid, KParams &kp)
+{
+    unsigned char *w = (unsigned char *)base;
+    Xs = (float4 *)(w + L.spill_at(g0));
+    valid = (unsigned *)(w + L.gate_at(g0));
+    kp.doubt32 = with_doubt ? (unsigned *)(w + L.doubt_at(g0)) : nullptr;
+    kp.doubt_flag = with_doubt ? (unsigned *)(w + L.flag_at(g0)) : nullptr; // one per launch group: its first clip's
+}
+
+// refusals the entry points that run K1 share, word for word
+static inline int refuse_short_clip(const salsa_plan *pl, int64_t n_samples)
+{
+    if (n_samples <= pl->p.n_fft / 2) return fail(SALSA_EINVAL, "clip shorter than n_fft/2 samples cannot be reflect-padded%s");
+    return SALSA_OK;
+}
+static inline int refuse_other_device(const salsa_plan *pl)
+{
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != pl->device)
+        return fail(SALSA_EINVAL, "the plan's tables live on the device that was current at salsa_plan_create; make it current%s");
+    return SALSA_OK;
+}
+static inline int refuse_workspace(const void *d_workspace, size_t workspace_bytes, size_t need)
+{
+    if (!d_workspace || workspace_bytes < need) return fail(SALSA_EWORKSPACE, "workspace too small%s (need %ld bytes)", "", (long)need);
+    return SALSA_OK;
+}
 
 // salsa_plan.hip
 SALSA_LOCAL KParams make_kparams(const salsa_plan *pl, int batch, int64_t n_samples);

@@ -1,12 +1,15 @@
 // salsa_plan.hip -- the host side of the feature extractor's C ABI (include/salsa_hip.h): struct salsa_plan (salsa_internal.h)
-// created, configured and destroyed; workspace sizing; timing marks; and the schedules of salsa_extract_batch -- plain in-order issue,
-// clip groups on the plan's streams, split channel pairs, the captured hipGraph -- with salsa_logspec_batch and the two
-// salsa_eigvec entry points.  Host code only: no kernel lives here, every launch goes through a launcher of salsa_internal.h
+// created, configured and destroyed; the workspace queries (the layout itself: salsa_workspace.h); timing marks; and the schedules of
+// salsa_extract_batch as named steps -- issue_group (one group's launches, plain in-order issue when it is the whole batch),
+// issue_forked (clip groups and split channel pairs on the plan's streams), replay_graph (the captured hipGraph) -- with
+// salsa_logspec_batch and the two salsa_eigvec entry points.  Host code only: no kernel lives here, every launch goes through a launcher of salsa_internal.h
 // (K1 / K2 / K3: salsa_kernels.hip; the fused kernel: fused_kernel.hip; relayout: multichannel.hip).
 // The library's one error message is defined here: salsa_last_error / salsa_set_last_error_.
 #include "build_guard.h" // probe switches need -DSALSA_PROBE_BUILD; SALSA_BUILD_FLAGS (generated: tools/gen_build_guard.py)
 #include "salsa_internal.h"
 #include <string.h>
+#include <memory>
+#include <vector>
 
 using salsa::cplx;
 using namespace salsa_impl;
@@ -14,6 +17,7 @@ using namespace salsa_impl;
 namespace {
 
 thread_local char g_err[512] = "";
+constexpr double PI = 3.14159265358979323846;
 
 } // namespace
 
@@ -57,6 +61,191 @@ KParams make_kparams(const salsa_plan *pl, int batch, int64_t n_samples)
 }
 
 } // namespace salsa_impl
+
+namespace {
+
+// timing mode: bracket one launch with events on ITS stream
+static int mark_begin(salsa_plan *pl, hipStream_t s, const char *name)
+{
+    if (!pl->timing || pl->n_kernels >= SALSA_MAX_KERNELS) return -1;
+    const int i = pl->n_kernels++;
+    pl->names[i] = name;
+    if (!pl->ev0[i]) (void)hipEventCreate(&pl->ev0[i]);
+    if (!pl->ev1[i]) (void)hipEventCreate(&pl->ev1[i]);
+    (void)hipEventRecord(pl->ev0[i], s);
+    return i;
+}
+static void mark_end(salsa_plan *pl, hipStream_t s, int i)
+{
+    if (i >= 0) (void)hipEventRecord(pl->ev1[i], s);
+}
+
+// One kernel of a schedule = ONE event pair in timing mode, whatever is launched between the pair.  With a repeat count
+// (salsa_plan_set_timing(plan, K > 1)) a kernel that is idempotent on (audio, spill, masks) -- REPEATABLE -- is launched K times back
+// to back between that pair, so the per-launch figure is elapsed / K with no event between the launches (an event pair around a
+// single launch adds ~12 % to it); anything else is launched ONCE.  `launch` returns a SALSA code; the first failure ends the repeats.
+enum Repeat { ONCE, REPEATABLE };
+template <typename Launch>
+static int timed(salsa_plan *pl, hipStream_t s, const char *name, Repeat repeat, Launch launch)
+{
+    const int reps = repeat == REPEATABLE && pl->timing > 1 ? pl->timing : 1;
+    const int m = mark_begin(pl, s, name);
+    int rc = SALSA_OK;
+    for (int r = 0; r < reps && !rc; r++) rc = launch();
+    mark_end(pl, s, m);
+    return rc;
+}
+
+// one salsa_extract_batch call, as every step of its schedules sees it
+struct ExtractCall {
+    salsa_plan *pl;
+    KParams kp;          // the whole batch (no workspace pointer bound: a group binds its own)
+    const float *audio;
+    float *out;
+    bool full;           // full SALSA: the path goes on past K1, through the workspace
+    void *ws;
+    WorkspaceLayout lay;
+    bool doubt;          // the plan gates: the doubt mask is bound
+};
+
+// The launches of group g = clips [g0, g1): every buffer is clip-major, so a group is just a pointer offset.  s1 runs the STFT
+// launch(es); s2 the tracker and the covariance/eigen kernel (s1 == s2: plain in-order issue on one stream).
+static int issue_group(const ExtractCall &c, int g0, int g1, hipStream_t s1, hipStream_t s2, hipEvent_t after_first,
+                       hipEvent_t after_second, bool split)
+{
+    salsa_plan *pl = c.pl;
+    KParams gp = c.kp;
+    gp.B = g1 - g0;
+    const long T = gp.T;
+    const float *a = c.audio + (size_t)g0 * 4 * gp.N;
+    float *o = c.out + (size_t)g0 * 7 * T * gp.F;
+    float4 *xs = nullptr;
+    unsigned *vm = nullptr;
+    if (c.full) bind_workspace(c.lay, c.ws, g0, c.doubt, xs, vm, gp);
+    const bool two = split && c.full && gp.nd > 0;
+    gp.pair_sel = two ? 0 : -1;
+    int rc = timed(pl, s1, "stft_logspec", REPEATABLE, [&] { return launch_k1(pl, gp, a, o, xs, s1); });
+    if (rc || !c.full) return rc;
+    if (pl->stop_after == 1) return SALSA_PARTIAL; // (measurement mode: the caller is told the outputs are NOT complete)
+    if (s1 != s2) {
+        HIP_TRY(hipEventRecord(after_first, s1));
+        HIP_TRY(hipStreamWaitEvent(s2, after_first, 0));
+    }
+    if (gp.nd == 0) { // empty DOA band: channels 4-6 are all zero (:373-374)
+        HIP_TRY(hipMemset2DAsync(o + 4 * T * gp.F, sizeof(float) * 7 * T * gp.F, 0, sizeof(float) * 3 * T * gp.F, (size_t)gp.B, s2));
+        return SALSA_OK;
+    }
+    if (two) { // channels 2/3 (the tracker below only needs channel 0 and may run beside this launch)
+        gp.pair_sel = 1;
+        rc = timed(pl, s1, "stft_logspec", ONCE, [&] { return launch_stft(pl, gp, pl->d_window, a, o, xs, s1); });
+        if (rc) return rc;
+        gp.pair_sel = -1;
+        if (s1 != s2) HIP_TRY(hipEventRecord(after_second, s1));
+    }
+    if (gp.tracking) {
+        timed(pl, s2, "noise_floor_tracker", REPEATABLE, [&] { return launch_tracker(gp, s2, xs, vm), (int)SALSA_OK; });
+        HIP_TRY(hipGetLastError());
+    }
+    if (pl->stop_after == 2) return SALSA_PARTIAL;
+    if (two && s1 != s2) HIP_TRY(hipStreamWaitEvent(s2, after_second, 0));
+    // stage (a): the fused kernel on the masks of the launches above; its float64 records go where the group's spill was (dead
+    // once the tracker has read it: same stream)
+    if (pl->fused >= 1 && !two && fused_eligible(pl, gp) && fused_cold_bytes(gp) <= c.lay.spill_group_bytes(gp.B))
+        return timed(pl, s2, "fused_stft_cov_eig", REPEATABLE, [&] { return launch_fused(pl, gp, a, o, vm, (void *)xs, s2); });
+    const unsigned ntile = (unsigned)((gp.T + K3_FT - 1) / K3_FT);
+    dim3 grid(ntile, (unsigned)gp.B, (unsigned)((gp.nd + K3_NT - 1) / K3_NT));
+    timed(pl, s2, "cov_eig", REPEATABLE,
+          [&] { return launch_cov_eig<true>(gp, grid, s2, xs, vm, o, (double *)nullptr, (unsigned char *)nullptr), (int)SALSA_OK; });
+    HIP_TRY(hipGetLastError());
+    if (gp.flex && !gp.tracking && gp.nd > 0) { // (it consumes the marks cov_eig left: not repeatable)
+        timed(pl, s2, "flex_allpass", ONCE, [&] { return launch_flex_allpass(gp, s2, o), (int)SALSA_OK; });
+        HIP_TRY(hipGetLastError());
+    }
+    return SALSA_OK;
+}
+
+// the pipelined schedule: fork from `origin`, run the batch as G clip groups on the plan's streams, join back into `origin`
+static int issue_forked(const ExtractCall &c, int G, hipStream_t origin)
+{
+    salsa_plan *pl = c.pl;
+    const int batch = c.kp.B;
+    const bool split = (pl->pipe_flags & SALSA_PIPE_SPLIT_PAIRS) != 0;
+    HIP_TRY(hipEventRecord(pl->ev_fork, origin));
+    HIP_TRY(hipStreamWaitEvent(pl->streams[0], pl->ev_fork, 0));
+    for (int g = 0; g < G; g++) {
+        HIP_TRY(hipStreamWaitEvent(pl->streams[1 + g], pl->ev_fork, 0)); // orders this call after the caller's earlier work
+        const int g0 = (int)((long)batch * g / G), g1 = (int)((long)batch * (g + 1) / G);
+        const int rc = issue_group(c, g0, g1, pl->streams[0], pl->streams[1 + g], pl->ev_stft[g], pl->ev_stft2[g], split);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(pl->ev_join[1 + g], pl->streams[1 + g]));
+        HIP_TRY(hipStreamWaitEvent(origin, pl->ev_join[1 + g], 0));
+    }
+    HIP_TRY(hipEventRecord(pl->ev_join[0], pl->streams[0]));
+    HIP_TRY(hipStreamWaitEvent(origin, pl->ev_join[0], 0));
+    return SALSA_OK;
+}
+
+// one hipGraphLaunch per call: the fork/join above, captured once for these buffers and sizes (the plan's graph key)
+static int replay_graph(const ExtractCall &c, int G, hipStream_t s)
+{
+    salsa_plan *pl = c.pl;
+    const salsa_plan::GraphKey key = {c.audio, c.out, c.ws, pl->sc_mean, pl->sc_std, c.kp.B, G, pl->pipe_flags, (int64_t)c.kp.N};
+    if (!(pl->gexec && pl->gkey == key)) {
+        if (pl->gexec) {
+            (void)hipGraphExecDestroy(pl->gexec);
+            pl->gexec = nullptr;
+        }
+        hipGraph_t graph = nullptr;
+        HIP_TRY(hipStreamBeginCapture(pl->cap_stream, hipStreamCaptureModeThreadLocal));
+        const int rc = issue_forked(c, G, pl->cap_stream);
+        const hipError_t e = hipStreamEndCapture(pl->cap_stream, &graph);
+        if (rc) {
+            if (graph) (void)hipGraphDestroy(graph);
+            return rc;
+        }
+        HIP_TRY(e);
+        const hipError_t ei = hipGraphInstantiate(&pl->gexec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        HIP_TRY(ei);
+        pl->gkey = key;
+    }
+    HIP_TRY(hipGraphLaunch(pl->gexec, s));
+    return SALSA_OK;
+}
+
+// what the two salsa_eigvec entry points share once each has made its own checks: caller-supplied spectra relaid into the spill, the
+// tracker, then the covariance / eigen kernel writing features (FEAT) or eigenvectors and gates
+template <bool FEAT>
+static int eigvec_run(salsa_plan *pl, const float *d_X, int batch, int n_bins, int64_t n_frames, int lower_bin, float *d_feat,
+                      double *d_eig, unsigned char *d_gate, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    const WorkspaceLayout lay = workspace_layout(batch, (size_t)n_frames, n_bins, 4, MASK_CHUNKED);
+    if (const int rc = refuse_workspace(d_workspace, workspace_bytes, lay.total)) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    KParams kp = make_kparams(pl, batch, 0);
+    kp.T = (int)n_frames;
+    kp.nd = n_bins;
+    kp.lower = lower_bin;
+    kp.upper = lower_bin + n_bins;
+    kp.F = n_bins;
+    kp.feature = SALSA_FEATURE_SALSA;
+    float4 *Xs;
+    unsigned *valid;
+    bind_workspace(lay, d_workspace, 0, (kp.tracking || kp.flex) && kp.cond > 1.0, Xs, valid, kp);
+    launch_relayout((const float4 *)d_X, Xs, batch, n_bins, (int)n_frames, s);
+    HIP_TRY(hipGetLastError());
+    if (kp.tracking) {
+        launch_tracker(kp, s, Xs, valid);
+        HIP_TRY(hipGetLastError());
+    }
+    const unsigned ntile = (unsigned)((kp.T + K3_FT - 1) / K3_FT);
+    dim3 grid(ntile, (unsigned)kp.B, (unsigned)((n_bins + K3_NT - 1) / K3_NT));
+    launch_cov_eig<FEAT>(kp, grid, s, Xs, valid, d_feat, d_eig, d_gate);
+    HIP_TRY(hipGetLastError());
+    return SALSA_OK;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -104,6 +293,85 @@ int salsa_compress_matrix(int n_fft, int compress, float *W)
     return SALSA_OK;
 }
 
+// the plan's bands from its parameters: the DOA band [lower, upper) of nd bins, the spectrogram band, the F feature bins per frame
+static int plan_bands(salsa_plan *pl)
+{
+    const salsa_params &p = pl->p;
+    salsa_bin_limits(p.fs, p.n_fft, p.fmin_doa, p.fmax_doa, &pl->lower, &pl->upper, &pl->cutoff);
+    const int nbins = p.n_fft / 2 + 1;
+    if (pl->flex) {
+        // contrib/salsa_flexible.py SpatialFeaturesAbstract.__init__ (:177-184) + __call__ (:252-263): no fs/2 clamp on
+        // fmax_doa, the spectrogram cutoff comes from fmax_spec, spectrogram and spatial features share ONE band
+        // [lo, hi) (the cropped axis, or all n_fft/2+1 bins), spatial rows >= upper_bin OF THAT AXIS optionally zeroed.
+        if (p.audio_format != SALSA_FORMAT_MIC || p.feature_type == SALSA_FEATURE_IPD)
+            return fail(SALSA_EFORMAT, "the contrib (flex) surface has the MIC-style SALSA and SALSA-Lite features only%s");
+        pl->upper = (int)floor((double)((int64_t)p.fmax_doa * p.n_fft) / (double)p.fs);
+        pl->cutoff = (int)floor((double)((int64_t)(p.fmax_spec > 0 ? p.fmax_spec : 9000) * p.n_fft) / (double)p.fs);
+        if (pl->upper > pl->cutoff)
+            return fail(SALSA_EBINS, "Upper bin for spatial feature is higher than cutoff bin for spectrogram!%s");
+        const bool crop = !(p.flags & SALSA_FLAG_NO_CLIP_FREQS);
+        const int lo = crop ? pl->lower : 0, hi = crop ? (pl->cutoff < nbins ? pl->cutoff : nbins) : nbins;
+        const int zero_from = (p.flags & SALSA_FLAG_CLIP_SPATIAL_ALIAS) ? pl->upper : hi - lo; // index into the band
+        pl->lower = lo;
+        pl->cutoff = hi;
+        pl->F = hi - lo;
+        if (pl->F <= 0) return fail(SALSA_EBINS, "empty spectrogram band%s");
+        pl->ident = p.n_fft / 2;
+        pl->spec_lo = lo;
+        pl->spec_hi = hi;
+        if (p.feature_type == SALSA_FEATURE_SALSA) {
+            pl->nd = zero_from < pl->F ? zero_from : pl->F; // bins above it are never evaluated: cov_eig zero-fills them
+            pl->upper = lo + pl->nd;
+        } else {
+            pl->nd = 0;
+            pl->upper = zero_from;                           // the lite kernel zeroes band rows >= kp.upper
+        }
+    } else if (p.feature_type == SALSA_FEATURE_SALSA) {
+        pl->F = freq_dim(p.n_fft, p.is_compress_high_freq);
+        pl->ident = p.is_compress_high_freq ? (p.n_fft == 512 ? 192 : 96) : p.n_fft / 2;
+        pl->spec_lo = 1;
+        pl->spec_hi = pl->ident + 1;
+        pl->nd = pl->upper - pl->lower;
+        if (pl->nd < 0 || pl->nd > pl->F || pl->upper > nbins)
+            return fail(SALSA_EBINS, "DOA band [lower_bin, upper_bin) does not fit the feature axis%s");
+    } else {
+        if (pl->upper > pl->cutoff)
+            return fail(SALSA_EBINS, "Upper bin for spatial feature is higher than cutoff bin for spectrogram!%s");
+        if (pl->cutoff > nbins) pl->cutoff = nbins; // numpy slicing clips [lower:cutoff] at n_bins
+        pl->F = pl->cutoff - pl->lower;
+        pl->ident = 0;
+        pl->nd = 0;
+        if (pl->F <= 0) return fail(SALSA_EBINS, "empty spectrogram band%s");
+    }
+    return SALSA_OK;
+}
+
+// windows: scipy.signal.get_window('hann', win, fftbins=True), centre-padded to n_fft (librosa pad_center: (n_fft - win) // 2
+// zeros on the left) ; twiddles W_N^m.  Only the SALSA log-spectrogram honours win_len (salsa_feature_extraction.py:186-192); its
+// DOA STFT (:360-361) and both SALSA-Lite STFTs (salsa_lite_feature_extraction.py:97-98, win_len read at :44 and unused) pass no
+// win_length, i.e. the n_fft window.  Equal lengths: one table.
+static int plan_upload_tables(salsa_plan *pl)
+{
+    const int n_fft = pl->p.n_fft;
+    const int spec_win = (pl->p.feature_type == SALSA_FEATURE_SALSA && !pl->flex) ? pl->p.win_len : n_fft;
+    const int nwin = spec_win == n_fft ? 1 : 2;
+    std::vector<double> hw(2 * n_fft, 0.0);
+    std::vector<cplx<double>> htw(n_fft);
+    for (int n = 0; n < spec_win; n++) hw[(n_fft - spec_win) / 2 + n] = 0.5 - 0.5 * cos(2.0 * PI * n / spec_win);
+    for (int n = 0; n < n_fft; n++) hw[n_fft + n] = 0.5 - 0.5 * cos(2.0 * PI * n / n_fft);
+    for (int m = 0; m < n_fft; m++) htw[m] = {cos(-2.0 * PI * m / n_fft), sin(-2.0 * PI * m / n_fft)};
+    hipError_t e1 = hipMalloc((void **)&pl->d_window, sizeof(double) * n_fft * nwin);
+    hipError_t e2 = hipMalloc((void **)&pl->d_tw, sizeof(cplx<double>) * n_fft);
+    if (e1 == hipSuccess && e2 == hipSuccess) {
+        e1 = hipMemcpy(pl->d_window, hw.data(), sizeof(double) * n_fft * nwin, hipMemcpyHostToDevice);
+        e2 = hipMemcpy(pl->d_tw, htw.data(), sizeof(cplx<double>) * n_fft, hipMemcpyHostToDevice);
+    }
+    if (e1 != hipSuccess || e2 != hipSuccess)
+        return fail(SALSA_EHIP, "plan table upload failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+    pl->d_window_doa = nwin == 2 ? pl->d_window + n_fft : pl->d_window;
+    return SALSA_OK;
+}
+
 int salsa_plan_create(const salsa_params *params, salsa_plan **out_plan)
 {
     if (!params || !out_plan) return fail(SALSA_EINVAL, "salsa_plan_create: NULL argument%s");
@@ -125,104 +393,18 @@ int salsa_plan_create(const salsa_params *params, salsa_plan **out_plan)
     if (p.feature_type != SALSA_FEATURE_SALSA && p.audio_format != SALSA_FORMAT_MIC)
         return fail(SALSA_EFORMAT, "SALSA-Lite and SALSA-IPD are only for MIC format!%s");
     if (p.n_hopframes < 0 || p.n_hopframes > 16) return fail(SALSA_EINVAL, "n_hopframes out of range%s");
-    salsa_plan *pl = new salsa_plan();
-    memset(pl, 0, sizeof(*pl));
+    // the plan, and whatever device memory it comes to hold, is released by every refusal below: one `return` each
+    std::unique_ptr<salsa_plan, int (*)(salsa_plan *)> pl(new salsa_plan(), salsa_plan_destroy);
+    memset(pl.get(), 0, sizeof(salsa_plan));
     pl->p = p;
-    salsa_bin_limits(p.fs, p.n_fft, p.fmin_doa, p.fmax_doa, &pl->lower, &pl->upper, &pl->cutoff);
-    const int nbins = p.n_fft / 2 + 1;
     pl->flex = (p.flags & SALSA_FLAG_FLEX) != 0;
     pl->snr_ratio = p.floor_mask_ratio > 0 ? p.floor_mask_ratio : 1.5;
-    if (pl->flex) {
-        // contrib/salsa_flexible.py SpatialFeaturesAbstract.__init__ (:177-184) + __call__ (:252-263): no fs/2 clamp on
-        // fmax_doa, the spectrogram cutoff comes from fmax_spec, spectrogram and spatial features share ONE band
-        // [lo, hi) (the cropped axis, or all n_fft/2+1 bins), spatial rows >= upper_bin OF THAT AXIS optionally zeroed.
-        if (p.audio_format != SALSA_FORMAT_MIC || p.feature_type == SALSA_FEATURE_IPD) {
-            delete pl;
-            return fail(SALSA_EFORMAT, "the contrib (flex) surface has the MIC-style SALSA and SALSA-Lite features only%s");
-        }
-        pl->upper = (int)floor((double)((int64_t)p.fmax_doa * p.n_fft) / (double)p.fs);
-        pl->cutoff = (int)floor((double)((int64_t)(p.fmax_spec > 0 ? p.fmax_spec : 9000) * p.n_fft) / (double)p.fs);
-        if (pl->upper > pl->cutoff) {
-            delete pl;
-            return fail(SALSA_EBINS, "Upper bin for spatial feature is higher than cutoff bin for spectrogram!%s");
-        }
-        const bool crop = !(p.flags & SALSA_FLAG_NO_CLIP_FREQS);
-        const int lo = crop ? pl->lower : 0, hi = crop ? (pl->cutoff < nbins ? pl->cutoff : nbins) : nbins;
-        const int zero_from = (p.flags & SALSA_FLAG_CLIP_SPATIAL_ALIAS) ? pl->upper : hi - lo; // index into the band
-        pl->lower = lo;
-        pl->cutoff = hi;
-        pl->F = hi - lo;
-        if (pl->F <= 0) {
-            delete pl;
-            return fail(SALSA_EBINS, "empty spectrogram band%s");
-        }
-        pl->ident = p.n_fft / 2;
-        pl->spec_lo = lo;
-        pl->spec_hi = hi;
-        if (p.feature_type == SALSA_FEATURE_SALSA) {
-            pl->nd = zero_from < pl->F ? zero_from : pl->F; // bins above it are never evaluated: cov_eig zero-fills them
-            pl->upper = lo + pl->nd;
-        } else {
-            pl->nd = 0;
-            pl->upper = zero_from;                           // the lite kernel zeroes band rows >= kp.upper
-        }
-    } else if (p.feature_type == SALSA_FEATURE_SALSA) {
-        pl->F = freq_dim(p.n_fft, p.is_compress_high_freq);
-        pl->ident = p.is_compress_high_freq ? (p.n_fft == 512 ? 192 : 96) : p.n_fft / 2;
-        pl->spec_lo = 1;
-        pl->spec_hi = pl->ident + 1;
-        pl->nd = pl->upper - pl->lower;
-        if (pl->nd < 0 || pl->nd > pl->F || pl->upper > nbins) {
-            delete pl;
-            return fail(SALSA_EBINS, "DOA band [lower_bin, upper_bin) does not fit the feature axis%s");
-        }
-    } else {
-        if (pl->upper > pl->cutoff) {
-            delete pl;
-            return fail(SALSA_EBINS, "Upper bin for spatial feature is higher than cutoff bin for spectrogram!%s");
-        }
-        if (pl->cutoff > nbins) pl->cutoff = nbins; // numpy slicing clips [lower:cutoff] at n_bins
-        pl->F = pl->cutoff - pl->lower;
-        pl->ident = 0;
-        pl->nd = 0;
-        if (pl->F <= 0) {
-            delete pl;
-            return fail(SALSA_EBINS, "empty spectrogram band%s");
-        }
-    }
-    pl->delta = 2.0 * 3.14159265358979323846 * p.fs / (p.n_fft * 343.0);
-    if (hipGetDevice(&pl->device) != hipSuccess) {
-        delete pl;
-        return fail(SALSA_EHIP, "hipGetDevice failed (no HIP device?)%s");
-    }
-    // windows: scipy.signal.get_window('hann', win, fftbins=True), centre-padded to n_fft (librosa pad_center: (n_fft - win) // 2
-    // zeros on the left) ; twiddles W_N^m.  Only the SALSA log-spectrogram honours win_len (salsa_feature_extraction.py:186-192); its
-    // DOA STFT (:360-361) and both SALSA-Lite STFTs (salsa_lite_feature_extraction.py:97-98, win_len read at :44 and unused) pass no
-    // win_length, i.e. the n_fft window.  Equal lengths: one table.
-    const int spec_win = (p.feature_type == SALSA_FEATURE_SALSA && !pl->flex) ? p.win_len : p.n_fft;
-    const int nwin = spec_win == p.n_fft ? 1 : 2;
-    double *hw = new double[2 * p.n_fft];
-    cplx<double> *htw = new cplx<double>[p.n_fft];
-    for (int i = 0; i < 2 * p.n_fft; i++) hw[i] = 0.0;
-    for (int n = 0; n < spec_win; n++) hw[(p.n_fft - spec_win) / 2 + n] = 0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * n / spec_win);
-    for (int n = 0; n < p.n_fft; n++) hw[p.n_fft + n] = 0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * n / p.n_fft);
-    for (int m = 0; m < p.n_fft; m++)
-        htw[m] = {cos(-2.0 * 3.14159265358979323846 * m / p.n_fft), sin(-2.0 * 3.14159265358979323846 * m / p.n_fft)};
-    hipError_t e1 = hipMalloc((void **)&pl->d_window, sizeof(double) * p.n_fft * nwin);
-    hipError_t e2 = hipMalloc((void **)&pl->d_tw, sizeof(cplx<double>) * p.n_fft);
-    if (e1 == hipSuccess && e2 == hipSuccess) {
-        e1 = hipMemcpy(pl->d_window, hw, sizeof(double) * p.n_fft * nwin, hipMemcpyHostToDevice);
-        e2 = hipMemcpy(pl->d_tw, htw, sizeof(cplx<double>) * p.n_fft, hipMemcpyHostToDevice);
-    }
-    if (e1 == hipSuccess) pl->d_window_doa = nwin == 2 ? pl->d_window + p.n_fft : pl->d_window;
-    delete[] hw;
-    delete[] htw;
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        salsa_plan_destroy(pl);
-        return fail(SALSA_EHIP, "plan table upload failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-    }
+    if (const int rc = plan_bands(pl.get())) return rc;
+    pl->delta = 2.0 * PI * p.fs / (p.n_fft * 343.0);
+    if (hipGetDevice(&pl->device) != hipSuccess) return fail(SALSA_EHIP, "hipGetDevice failed (no HIP device?)%s");
+    if (const int rc = plan_upload_tables(pl.get())) return rc;
     pl->n_groups = 1; // measured on ROCm 7.2: multi-stream issue costs more host time than the overlap returns
-    *out_plan = pl;
+    *out_plan = pl.release();
     return SALSA_OK;
 }
 
@@ -257,37 +439,17 @@ int salsa_output_shape(const salsa_plan *pl, int64_t n_samples, int *C, int64_t 
     return SALSA_OK;
 }
 
-// one [B][32-bin group][T] uint32 bit mask (the tracker's gate masks; the doubt mask of the coherence test), rounded up to whole
-// 64-frame chunks and 64-bin groups
-static size_t mask_bytes(int batch, size_t T, int nd) { return align256((size_t)batch * ((T + 63) / 64) * ((nd + 63) / 64) * 64 * 8); }
-
+// (what the workspace holds and how large it is: salsa_workspace.h)
 size_t salsa_workspace_bytes(const salsa_plan *pl, int batch, int64_t n_samples)
 {
     if (!pl || batch <= 0 || n_samples <= 0 || pl->p.feature_type != SALSA_FEATURE_SALSA) return 0;
-    const size_t T = 1 + n_samples / pl->p.hop_len;
-    return align256((size_t)batch * T * 4 * pl->nd * sizeof(float2)) + 2 * mask_bytes(batch, T, pl->nd) + align256(sizeof(unsigned) * (size_t)batch) + 256; // spill, gate masks, doubt mask, doubt flags
+    return workspace_layout(batch, (size_t)(1 + n_samples / pl->p.hop_len), pl->nd, 4, MASK_CHUNKED).total;
 }
 
 size_t salsa_eigvec_workspace_bytes(const salsa_plan *pl, int batch, int n_bins, int64_t n_frames)
 {
     if (!pl || batch <= 0 || n_bins <= 0 || n_frames <= 0) return 0;
-    return align256((size_t)batch * n_frames * 4 * n_bins * sizeof(float2)) + 2 * mask_bytes(batch, (size_t)n_frames, n_bins) + align256(sizeof(unsigned) * (size_t)batch) + 256;
-}
-
-// timing mode: bracket one launch with events on ITS stream
-static int mark_begin(salsa_plan *pl, hipStream_t s, const char *name)
-{
-    if (!pl->timing || pl->n_kernels >= SALSA_MAX_KERNELS) return -1;
-    const int i = pl->n_kernels++;
-    pl->names[i] = name;
-    if (!pl->ev0[i]) (void)hipEventCreate(&pl->ev0[i]);
-    if (!pl->ev1[i]) (void)hipEventCreate(&pl->ev1[i]);
-    (void)hipEventRecord(pl->ev0[i], s);
-    return i;
-}
-static void mark_end(salsa_plan *pl, hipStream_t s, int i)
-{
-    if (i >= 0) (void)hipEventRecord(pl->ev1[i], s);
+    return workspace_layout(batch, (size_t)n_frames, n_bins, 4, MASK_CHUNKED).total;
 }
 
 int salsa_extract_batch(salsa_plan *pl, const float *d_audio, int batch, int64_t n_samples, float *d_out,
@@ -295,13 +457,8 @@ int salsa_extract_batch(salsa_plan *pl, const float *d_audio, int batch, int64_t
 {
     if (!pl || !d_audio || !d_out || batch <= 0 || n_samples <= 0)
         return fail(SALSA_EINVAL, "salsa_extract_batch: bad argument%s");
-    if (n_samples <= pl->p.n_fft / 2)
-        return fail(SALSA_EINVAL, "clip shorter than n_fft/2 samples cannot be reflect-padded%s");
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != pl->device)
-            return fail(SALSA_EINVAL, "the plan's tables live on the device that was current at salsa_plan_create; make it current%s");
-    }
+    if (const int rc = refuse_short_clip(pl, n_samples)) return rc;
+    if (const int rc = refuse_other_device(pl)) return rc;
     {   // kernels index inside one clip with 32-bit offsets
         const int64_t T64 = 1 + n_samples / pl->p.hop_len;
         if (n_samples * 16 >= INT32_MAX || T64 * 7 * pl->F >= INT32_MAX / 2 || T64 * 2 * (pl->nd > 0 ? pl->nd : 1) >= INT32_MAX / 8)
@@ -309,152 +466,23 @@ int salsa_extract_batch(salsa_plan *pl, const float *d_audio, int batch, int64_t
         if ((T64 + K3_FT - 1) / K3_FT > 65535) return fail(SALSA_EINVAL, "clip too long for one launch (split it)%s");
     }
     hipStream_t s = (hipStream_t)hip_stream;
-    KParams kp = make_kparams(pl, batch, n_samples);
-    const bool full = pl->p.feature_type == SALSA_FEATURE_SALSA;
-    float4 *Xs = nullptr;
-    unsigned *valid = nullptr;
-    if (full) {
-        const size_t need = salsa_workspace_bytes(pl, batch, n_samples);
-        if (!d_workspace || workspace_bytes < need) return fail(SALSA_EWORKSPACE, "workspace too small%s (need %ld bytes)", "", (long)need);
-        Xs = (float4 *)d_workspace;
-        valid = (unsigned *)((unsigned char *)d_workspace + align256((size_t)batch * kp.T * 4 * kp.nd * sizeof(float2)));
-        if ((kp.tracking || kp.flex) && kp.cond > 1.0 && kp.nd > 0) {
-            kp.doubt32 = (unsigned *)((unsigned char *)valid + mask_bytes(batch, (size_t)kp.T, kp.nd));
-            kp.doubt_flag = (unsigned *)((unsigned char *)kp.doubt32 + mask_bytes(batch, (size_t)kp.T, kp.nd)); // [batch]: one per launch group
-        }
+    ExtractCall c = {pl, make_kparams(pl, batch, n_samples), d_audio, d_out, pl->p.feature_type == SALSA_FEATURE_SALSA, d_workspace};
+    if (c.full) {
+        c.lay = workspace_layout(batch, (size_t)c.kp.T, c.kp.nd, 4, MASK_CHUNKED);
+        if (const int rc = refuse_workspace(d_workspace, workspace_bytes, c.lay.total)) return rc;
+        c.doubt = (c.kp.tracking || c.kp.flex) && c.kp.cond > 1.0 && c.kp.nd > 0;
     }
     pl->n_kernels = 0;
-    const long T = kp.T;
-    const size_t nchunks = (size_t)((T + TR_CH - 1) / TR_CH);
-    // group g = clips [g0, g1): every buffer is clip-major, so a group is just a pointer offset.  s1 runs the STFT launch(es);
-    // s2 the tracker and the covariance/eigen kernel (s1 == s2: plain in-order issue on one stream).
-    auto run_group = [&](int g0, int g1, hipStream_t s1, hipStream_t s2, hipEvent_t after_first, hipEvent_t after_second,
-                         bool split) -> int {
-        KParams gp = kp;
-        gp.B = g1 - g0;
-        const float *a = d_audio + (size_t)g0 * 4 * kp.N;
-        float *o = d_out + (size_t)g0 * 7 * T * kp.F;
-        float4 *xs = Xs ? Xs + (size_t)g0 * T * 2 * kp.nd : nullptr;
-        unsigned *vm = valid ? valid + (size_t)g0 * ((kp.nd + TR_BINS - 1) / TR_BINS) * T : nullptr; // [b][32-bin group][t]
-        if (kp.doubt32) gp.doubt32 = kp.doubt32 + (size_t)g0 * ((kp.nd + TR_BINS - 1) / TR_BINS) * T, gp.doubt_flag = kp.doubt_flag + g0;
-        const bool two = split && full && gp.nd > 0;
-        gp.pair_sel = two ? 0 : -1;
-        // timing mode with a repeat count (salsa_plan_set_timing(plan, K > 1)): every kernel is launched K times back to
-        // back between ONE event pair -- all of them are idempotent on (audio, spill, masks) -- so the per-launch figure is
-        // elapsed / K with no event between the launches (an event pair around a single launch adds ~12 % to it)
-        const int reps = pl->timing > 1 ? pl->timing : 1;
-        int m = mark_begin(pl, s1, "stft_logspec");
-        int rc = SALSA_OK;
-        for (int r = 0; r < reps && !rc; r++) rc = launch_k1(pl, gp, a, o, xs, s1);
-        mark_end(pl, s1, m);
-        if (rc || !full) return rc;
-        if (pl->stop_after == 1) return SALSA_PARTIAL; // (measurement mode: the caller is told the outputs are NOT complete)
-        if (s1 != s2) {
-            HIP_TRY(hipEventRecord(after_first, s1));
-            HIP_TRY(hipStreamWaitEvent(s2, after_first, 0));
-        }
-        if (gp.nd == 0) { // empty DOA band: channels 4-6 are all zero (:373-374)
-            HIP_TRY(hipMemset2DAsync(o + 4 * T * kp.F, sizeof(float) * 7 * T * kp.F, 0, sizeof(float) * 3 * T * kp.F, (size_t)gp.B, s2));
-            return SALSA_OK;
-        }
-        if (two) { // channels 2/3 (the tracker below only needs channel 0 and may run beside this launch)
-            gp.pair_sel = 1;
-            m = mark_begin(pl, s1, "stft_logspec");
-            rc = launch_stft(pl, gp, pl->d_window, a, o, xs, s1);
-            mark_end(pl, s1, m);
-            if (rc) return rc;
-            gp.pair_sel = -1;
-            if (s1 != s2) HIP_TRY(hipEventRecord(after_second, s1));
-        }
-        if (gp.tracking) {
-            m = mark_begin(pl, s2, "noise_floor_tracker");
-            for (int r = 0; r < reps; r++) launch_tracker(gp, s2, xs, vm);
-            mark_end(pl, s2, m);
-            HIP_TRY(hipGetLastError());
-        }
-        if (pl->stop_after == 2) return SALSA_PARTIAL;
-        if (two && s1 != s2) HIP_TRY(hipStreamWaitEvent(s2, after_second, 0));
-        // stage (a): the fused kernel on the masks of the launches above; its float64 records go where the spill was (dead
-        // once the tracker has read it: same stream)
-        if (pl->fused >= 1 && !two && fused_eligible(pl, gp) && fused_cold_bytes(gp) <= (size_t)gp.B * T * 4 * gp.nd * sizeof(float2)) {
-            m = mark_begin(pl, s2, "fused_stft_cov_eig");
-            for (int r = 0; r < reps && !rc; r++) rc = launch_fused(pl, gp, a, o, vm, (void *)xs, s2);
-            mark_end(pl, s2, m);
-            return rc;
-        }
-        m = mark_begin(pl, s2, "cov_eig");
-        const unsigned ntile = (unsigned)((gp.T + K3_FT - 1) / K3_FT);
-        dim3 grid(ntile, (unsigned)gp.B, (unsigned)((gp.nd + K3_NT - 1) / K3_NT));
-        for (int r = 0; r < reps; r++) launch_cov_eig<true>(gp, grid, s2, xs, vm, o, (double *)nullptr, (unsigned char *)nullptr);
-        mark_end(pl, s2, m);
-        HIP_TRY(hipGetLastError());
-        if (gp.flex && !gp.tracking && gp.nd > 0) {
-            m = mark_begin(pl, s2, "flex_allpass");
-            launch_flex_allpass(gp, s2, o);
-            mark_end(pl, s2, m);
-            HIP_TRY(hipGetLastError());
-        }
-        return SALSA_OK;
-    };
     // (a plan with two windows keeps the plain in-order schedule: the pipelined one launches K1 per channel pair with one window)
-    const bool piped = full && !pl->timing && !pl->stop_after && kp.nd > 0 && pl->d_window == pl->d_window_doa &&
+    const bool piped = c.full && !pl->timing && !pl->stop_after && c.kp.nd > 0 && pl->d_window == pl->d_window_doa &&
                        (pl->n_groups > 1 || (pl->pipe_flags & SALSA_PIPE_SPLIT_PAIRS));
-    if (!piped) return run_group(0, batch, s, s, nullptr, nullptr, false);
+    if (!piped) return issue_group(c, 0, batch, s, s, nullptr, nullptr, false);
     const int G = batch < pl->n_groups ? batch : pl->n_groups;
-    const bool split = (pl->pipe_flags & SALSA_PIPE_SPLIT_PAIRS) != 0;
-    // fork from `origin`, run the groups on the plan's streams, join back into `origin`
-    auto issue = [&](hipStream_t origin) -> int {
-        HIP_TRY(hipEventRecord(pl->ev_fork, origin));
-        HIP_TRY(hipStreamWaitEvent(pl->streams[0], pl->ev_fork, 0));
-        for (int g = 0; g < G; g++) {
-            HIP_TRY(hipStreamWaitEvent(pl->streams[1 + g], pl->ev_fork, 0)); // orders this call after the caller's earlier work
-            const int g0 = (int)((long)batch * g / G), g1 = (int)((long)batch * (g + 1) / G);
-            const int rc = run_group(g0, g1, pl->streams[0], pl->streams[1 + g], pl->ev_stft[g], pl->ev_stft2[g], split);
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(pl->ev_join[1 + g], pl->streams[1 + g]));
-            HIP_TRY(hipStreamWaitEvent(origin, pl->ev_join[1 + g], 0));
-        }
-        HIP_TRY(hipEventRecord(pl->ev_join[0], pl->streams[0]));
-        HIP_TRY(hipStreamWaitEvent(origin, pl->ev_join[0], 0));
-        return SALSA_OK;
-    };
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (s) (void)hipStreamIsCapturing(s, &cap);
     if (!(pl->pipe_flags & SALSA_PIPE_GRAPH) || cap != hipStreamCaptureStatusNone)
-        return issue(s); // eager fork/join (inside a caller's capture it becomes part of the caller's graph)
-    // one hipGraphLaunch per call: the fork/join above captured once for these buffers and sizes
-    const bool hit = pl->gexec && pl->gkey.audio == d_audio && pl->gkey.out == d_out && pl->gkey.ws == d_workspace &&
-                     pl->gkey.sc_mean == pl->sc_mean && pl->gkey.sc_std == pl->sc_std && pl->gkey.batch == batch &&
-                     pl->gkey.n_samples == n_samples && pl->gkey.n_groups == G && pl->gkey.flags == pl->pipe_flags;
-    if (!hit) {
-        if (pl->gexec) {
-            (void)hipGraphExecDestroy(pl->gexec);
-            pl->gexec = nullptr;
-        }
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(pl->cap_stream, hipStreamCaptureModeThreadLocal));
-        const int rc = issue(pl->cap_stream);
-        const hipError_t e = hipStreamEndCapture(pl->cap_stream, &graph);
-        if (rc) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc;
-        }
-        HIP_TRY(e);
-        const hipError_t ei = hipGraphInstantiate(&pl->gexec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        HIP_TRY(ei);
-        pl->gkey.audio = d_audio;
-        pl->gkey.out = d_out;
-        pl->gkey.ws = d_workspace;
-        pl->gkey.sc_mean = pl->sc_mean;
-        pl->gkey.sc_std = pl->sc_std;
-        pl->gkey.batch = batch;
-        pl->gkey.n_samples = n_samples;
-        pl->gkey.n_groups = G;
-        pl->gkey.flags = pl->pipe_flags;
-    }
-    HIP_TRY(hipGraphLaunch(pl->gexec, s));
-    return SALSA_OK;
+        return issue_forked(c, G, s); // eager fork/join (inside a caller's capture it becomes part of the caller's graph)
+    return replay_graph(c, G, s);
 }
 
 int salsa_logspec_batch(salsa_plan *pl, const float *d_audio, int batch, int n_channels, int64_t n_samples,
@@ -463,7 +491,7 @@ int salsa_logspec_batch(salsa_plan *pl, const float *d_audio, int batch, int n_c
     if (!pl || !d_audio || !d_out || batch <= 0 || n_samples <= 0) return fail(SALSA_EINVAL, "salsa_logspec_batch: bad argument%s");
     if (n_channels != 4) return fail(SALSA_EINVAL, "salsa_logspec_batch: n_channels must be 4 (pad with silent channels)%s");
     if (freq_dim(pl->p.n_fft, pl->p.is_compress_high_freq) < 0) return fail(SALSA_ENFFT, "nfft is not 512 or 256%s"); // (MagStftExtractor, :152)
-    if (n_samples <= pl->p.n_fft / 2) return fail(SALSA_EINVAL, "clip shorter than n_fft/2 samples cannot be reflect-padded%s");
+    if (const int rc = refuse_short_clip(pl, n_samples)) return rc;
     if (n_samples * 16 >= INT32_MAX || (1 + n_samples / pl->p.hop_len) * 7 * 256 >= INT32_MAX / 2)
         return fail(SALSA_EINVAL, "clip too long for 32-bit per-clip indexing (split it)%s");
     KParams kp = make_kparams(pl, batch, n_samples);
@@ -486,33 +514,7 @@ int salsa_eigvec_batch(salsa_plan *pl, const float *d_X, int batch, int n_bins, 
     if (!pl || !d_X || !d_out || batch <= 0 || n_bins <= 0 || n_frames <= 0)
         return fail(SALSA_EINVAL, "salsa_eigvec_batch: bad argument%s");
     if ((int64_t)n_frames * 2 * n_bins >= INT32_MAX) return fail(SALSA_EINVAL, "block too large for 32-bit per-clip indexing%s");
-    const size_t need = salsa_eigvec_workspace_bytes(pl, batch, n_bins, n_frames);
-    if (!d_workspace || workspace_bytes < need) return fail(SALSA_EWORKSPACE, "workspace too small%s (need %ld bytes)", "", (long)need);
-    hipStream_t s = (hipStream_t)hip_stream;
-    KParams kp = make_kparams(pl, batch, 0);
-    kp.T = (int)n_frames;
-    kp.nd = n_bins;
-    kp.lower = lower_bin;
-    kp.upper = lower_bin + n_bins;
-    kp.F = n_bins;
-    kp.feature = SALSA_FEATURE_SALSA;
-    float4 *Xs = (float4 *)d_workspace;
-    unsigned *valid = (unsigned *)((unsigned char *)d_workspace + align256((size_t)batch * n_frames * 4 * n_bins * sizeof(float2)));
-    if ((kp.tracking || kp.flex) && kp.cond > 1.0) {
-        kp.doubt32 = (unsigned *)((unsigned char *)valid + mask_bytes(batch, (size_t)n_frames, n_bins));
-        kp.doubt_flag = (unsigned *)((unsigned char *)kp.doubt32 + mask_bytes(batch, (size_t)n_frames, n_bins));
-    }
-    launch_relayout((const float4 *)d_X, Xs, batch, n_bins, (int)n_frames, s);
-    HIP_TRY(hipGetLastError());
-    if (kp.tracking) {
-        launch_tracker(kp, s, Xs, valid);
-        HIP_TRY(hipGetLastError());
-    }
-    const unsigned ntile = (unsigned)((kp.T + K3_FT - 1) / K3_FT);
-    dim3 grid(ntile, (unsigned)kp.B, (unsigned)((n_bins + K3_NT - 1) / K3_NT));
-    launch_cov_eig<false>(kp, grid, s, Xs, valid, (float *)nullptr, d_out, d_gate);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
+    return eigvec_run<false>(pl, d_X, batch, n_bins, n_frames, lower_bin, nullptr, d_out, d_gate, d_workspace, workspace_bytes, hip_stream);
 }
 
 int salsa_eigvec_feature_batch(salsa_plan *pl, const float *d_X, int batch, int n_bins, int64_t n_frames, int lower_bin,
@@ -523,34 +525,7 @@ int salsa_eigvec_feature_batch(salsa_plan *pl, const float *d_X, int batch, int 
     if ((int64_t)n_frames * 2 * n_bins >= INT32_MAX / 8 || (int64_t)n_frames * 7 * n_bins >= INT32_MAX / 2)
         return fail(SALSA_EINVAL, "block too large for 32-bit per-clip indexing%s");
     if ((n_frames + K3_FT - 1) / K3_FT > 65535) return fail(SALSA_EINVAL, "block too long for one launch%s");
-    const size_t need = salsa_eigvec_workspace_bytes(pl, batch, n_bins, n_frames);
-    if (!d_workspace || workspace_bytes < need) return fail(SALSA_EWORKSPACE, "workspace too small%s (need %ld bytes)", "", (long)need);
-    hipStream_t s = (hipStream_t)hip_stream;
-    KParams kp = make_kparams(pl, batch, 0);
-    kp.T = (int)n_frames;
-    kp.nd = n_bins;
-    kp.lower = lower_bin;
-    kp.upper = lower_bin + n_bins;
-    kp.F = n_bins;
-    kp.OC = 7;
-    kp.feature = SALSA_FEATURE_SALSA;
-    float4 *Xs = (float4 *)d_workspace;
-    unsigned *valid = (unsigned *)((unsigned char *)d_workspace + align256((size_t)batch * n_frames * 4 * n_bins * sizeof(float2)));
-    if ((kp.tracking || kp.flex) && kp.cond > 1.0) {
-        kp.doubt32 = (unsigned *)((unsigned char *)valid + mask_bytes(batch, (size_t)n_frames, n_bins));
-        kp.doubt_flag = (unsigned *)((unsigned char *)kp.doubt32 + mask_bytes(batch, (size_t)n_frames, n_bins));
-    }
-    launch_relayout((const float4 *)d_X, Xs, batch, n_bins, (int)n_frames, s);
-    HIP_TRY(hipGetLastError());
-    if (kp.tracking) {
-        launch_tracker(kp, s, Xs, valid);
-        HIP_TRY(hipGetLastError());
-    }
-    const unsigned ntile = (unsigned)((kp.T + K3_FT - 1) / K3_FT);
-    dim3 grid(ntile, (unsigned)kp.B, (unsigned)((n_bins + K3_NT - 1) / K3_NT));
-    launch_cov_eig<true>(kp, grid, s, Xs, valid, d_feat, (double *)nullptr, (unsigned char *)nullptr);
-    HIP_TRY(hipGetLastError());
-    return SALSA_OK;
+    return eigvec_run<true>(pl, d_X, batch, n_bins, n_frames, lower_bin, d_feat, nullptr, nullptr, d_workspace, workspace_bytes, hip_stream);
 }
 
 int salsa_plan_set_fused(salsa_plan *pl, int mode)

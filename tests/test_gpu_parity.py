@@ -398,6 +398,98 @@ def test_clip_group_pipeline_is_bit_identical(dev):
     assert torch.equal(o2, ref)
 
 
+def _align256(x):
+    return (x + 255) & ~255
+
+
+def _mask_chunked(b, T, nd):
+    """one [B][32-bin group][T] uint32 mask rounded up to whole 64-frame chunks and 64-bin groups (the 4-channel entry points)"""
+    return _align256(b * ((T + 63) // 64) * ((nd + 63) // 64) * 64 * 8)
+
+
+def _ws_four(b, T, nd):
+    """spill, gate masks, doubt mask, doubt flags, 256 spare: salsa_workspace_bytes / salsa_eigvec_workspace_bytes"""
+    return _align256(b * T * 4 * nd * 8) + 2 * _mask_chunked(b, T, nd) + _align256(4 * b) + 256
+
+
+def _ws_multi(b, T, nd, nch):
+    """spill, ONE tightly sized gate mask, 256 spare: salsa_multichannel_workspace_bytes"""
+    return _align256(b * T * nch * nd * 8) + _align256(b * ((nd + 31) // 32) * T * 4) + 256
+
+
+def _workspace_queries_are_pinned():
+    """the three *_workspace_bytes queries on live plans, against the formulas restated above"""
+    from salsa_amd import _lib
+    from salsa_amd.extractor import bin_limits
+    Ts, batches = (1, 63, 64, 65, 161), (1, 5)
+    n_of = lambda T: (T - 1) * 300 + 1                                     # T = 1 + n // hop
+    for nd in (1, 33, 64, 65, 191):
+        fmax = -(-(nd + 1) * 24000 // 512)                                 # upper_bin = nd + 1, lower_bin = 1
+        assert bin_limits(24000, 512, 50, fmax)[:2] == (1, nd + 1)
+        ex = _extractor(fmax_doa=fmax)
+        # the contrib surface counts the band from bin 0 of the cropped axis: nd = upper_bin (include/salsa_hip.h, SALSA_FLAG_FLEX)
+        fmax_flex = -(-nd * 24000 // 512)
+        assert bin_limits(24000, 512, 50, fmax_flex)[1] == nd
+        fx = _extractor(fmax_doa=fmax_flex, fmax_spec=9000, audio_format='mic', is_compress_high_freq=False,
+                        flags=_lib.FLAG_FLEX | _lib.FLAG_CLIP_SPATIAL_ALIAS)
+        for T in Ts:
+            for b in batches:
+                assert ex.workspace_bytes(b, n_of(T)) == _ws_four(b, T, nd), (nd, T, b)
+                assert ex.L.salsa_eigvec_workspace_bytes(ex._plan, b, nd, T) == _ws_four(b, T, nd), (nd, T, b)
+                for nch in (6, 16):
+                    got = fx.L.salsa_multichannel_workspace_bytes(fx._plan, nch, b, n_of(T))
+                    assert got == _ws_multi(b, T, nd, nch), (nd, T, b, nch)
+    assert ex.workspace_bytes(0, 300) == 0 and ex.workspace_bytes(1, 0) == 0
+    assert ex.L.salsa_eigvec_workspace_bytes(ex._plan, 1, 0, 8) == 0 and ex.L.salsa_eigvec_workspace_bytes(ex._plan, 1, 8, 0) == 0
+    for nch in (2, 7, 18):
+        assert fx.L.salsa_multichannel_workspace_bytes(fx._plan, nch, 1, 300) == 0
+    lite = _extractor(audio_format='mic', feature_type='salsa_lite', fmax_doa=2000)
+    assert lite.workspace_bytes(5, n_of(161)) == 0                          # no spill: the early-outs stay
+    assert lite.L.salsa_multichannel_workspace_bytes(lite._plan, 6, 5, n_of(161)) == 256
+
+
+def test_every_schedule_on_a_one_window_plan_is_bit_identical(dev):
+    """Plans with win_len == n_fft are the only ones the pipelined schedules run on (a two-window plan keeps plain issue), so this is
+    where split channel pairs, clip groups, graph replay and the fused stage are held to the plain call bit for bit: 5 distinct clips
+    of T = 161 frames (no multiple of the 8-frame tile, three 64-frame tracker chunks; 5 divides by neither 2 nor 3), each schedule
+    called three times into a poisoned buffer (a graph row: captured once, replayed twice), then every way of missing the graph key.
+    The workspace sizes every one of those calls relies on are pinned at the end."""
+    a = torch.from_numpy(np.stack([synth_clip(1700 + i, 2 * 24000) for i in range(5)])).to(dev)
+    a2 = torch.from_numpy(np.stack([synth_clip(1750 + i, 2 * 24000) for i in range(5)])).to(dev)
+    for kw in ({}, dict(audio_format='mic', fmax_doa=4000)):
+        ex = _extractor(**kw)
+        ref, ref2, ref_b2 = ex.extract(a).clone(), ex.extract(a2).clone(), ex.extract(a[:2].contiguous()).clone()
+        assert ref.shape[2] == 161 and bool((ref[:, 4:] != 0).any()) and not torch.equal(ref, ref2)
+        out = torch.empty_like(ref)
+        for groups, split, graph in ((1, True, False), (2, False, False), (2, True, False), (3, True, True), (8, False, True)):
+            ex.set_pipeline(groups, split_pairs=split, graph=graph)
+            for rep in range(3):
+                out.fill_(7.0)
+                ex.extract(a, out=out)
+                assert torch.equal(out, ref), (kw, groups, split, graph, rep, int((out != ref).sum()))
+        # still under the last graph row: another input, another output buffer, another batch size -- each misses the key
+        for row in ((3, True, True), (8, False, True)):
+            ex.set_pipeline(row[0], split_pairs=row[1], graph=row[2])
+            out.fill_(7.0)
+            assert torch.equal(ex.extract(a, out=out), ref), (kw, row)
+            out.fill_(7.0)
+            assert torch.equal(ex.extract(a2, out=out), ref2), (kw, row, 'second input')
+            other = torch.full_like(ref, 7.0)
+            assert torch.equal(ex.extract(a2, out=other), ref2) and other.data_ptr() != out.data_ptr(), (kw, row, 'second output')
+            assert torch.equal(ex.extract(a[:2].contiguous()), ref_b2), (kw, row, 'batch of 2')
+            out.fill_(7.0)
+            assert torch.equal(ex.extract(a, out=out), ref), (kw, row, 'back to the first key')
+        ex.set_pipeline(2)
+        ex.set_fused(1)
+        for rep in range(3):
+            out.fill_(7.0)
+            assert torch.equal(ex.extract(a, out=out), ref), (kw, 'fused, 2 groups', rep)
+        ex.set_fused(0)
+        ex.set_pipeline(1)
+        assert torch.equal(ex.extract(a), ref)
+    _workspace_queries_are_pinned()
+
+
 # ----------------------------------------------------------------------------------------------- reference surface
 def _make_tree(tmp, fmt, clips, fmax, n_fft=512, hop=300, win=None):
     import yaml
