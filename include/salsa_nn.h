@@ -439,6 +439,69 @@ int salsa_nn_add_layernorm_bwd(const float *dy, const float *x, const float *res
                                const float *rstd, float *dx, float *dgamma, float *dbeta, void *ws, size_t ws_bytes,
                                int64_t M, int C, void *hip_stream);
 
+/* The decoder's optional Conformer blocks (salsa_amd/csrc/conformer.hip): everything of a block but its GEMMs and
+ * the attention core above.  All float32; no atomics, every sum in a fixed order: bit-reproducible for a given shape, and a sample's
+ * result does not depend on the rest of the batch, with one exception: a dropout mask depends on the element's flat index.
+ * Dropout (drop_p, drop_seed) is the element-wise BatchNorm dropout's (salsa_nn_bn_train_fwd): p quantised to thresh = round(65536 p)
+ * (at most 65535), one 32-bit hash of (flat index / 2, seed) serves two neighbouring elements -- the even one takes the low 16 bits --
+ * an element is dropped when its 16 bits < thresh and kept ones are scaled by 65536 / (65536 - thresh); the flat index is the element's
+ * in the tensor the mask applies to, which must have fewer than 2^32 elements.  No mask is stored: a backward regenerates it from the
+ * same (drop_p, drop_seed).  0 <= drop_p < 1.  Every launcher returns 0, -1 for an unsupported shape, a bad argument or a missing
+ * pointer (before any device call), -5 when ws_bytes is too small, -6 when a launch fails; every _ws_bytes is 0 for an unsupported
+ * shape.
+ *
+ * Pre-norm residual step on [M][C] rows, C = 256 or 512, M >= 1, M C < 2^32 (salsa_nn_res_layernorm_supported):
+ *     z = x + scale * drop(branch),   y = LayerNorm(z) * gamma + beta   (biased variance, eps inside the square root)
+ *   branch NULL: z = x (drop_p and scale unused).  z_out NULL: z is not written.  y_out NULL: no LayerNorm (gamma, beta, mean, rstd
+ *   unused and may be NULL); with y_out all four are required, and mean / rstd [M] are kept for the backward.  One of z_out / y_out
+ *   is required.  Where the mask drops, z is x bit for bit.  With scale 1, drop_p 0 and a branch, y, mean and rstd are
+ *   salsa_nn_add_layernorm_fwd's bits on the same operands (the same two-pass statistics).
+ * _bwd: dy is the gradient of y (NULL when there was no y_out), dz_in the gradient that reaches z directly (NULL: none); one of them is
+ *   required.  x, branch, scale, drop_p, drop_seed as in the forward (z is recomputed).
+ *     dx = dz_in + LayerNorm_backward(dy),   dbranch = scale * mask * dropscale * dx   (dbranch NULL: not written),
+ *   dgamma / dbeta [C] through per-workgroup slabs in ws and one ordered pass (with dy: gamma, mean, rstd, dgamma, dbeta and ws of
+ *   salsa_nn_res_layernorm_ws_bytes(M, C) are required; without dy they are unused). */
+int salsa_nn_res_layernorm_supported(int64_t M, int C);
+size_t salsa_nn_res_layernorm_ws_bytes(int64_t M, int C);
+int salsa_nn_res_layernorm_fwd(const float *x, const float *branch, float scale, float drop_p, uint32_t drop_seed,
+                               const float *gamma, const float *beta, float *z_out, float *y_out, float *mean, float *rstd,
+                               int64_t M, int C, float eps, void *hip_stream);
+int salsa_nn_res_layernorm_bwd(const float *dy, const float *dz_in, const float *x, const float *branch, float scale, float drop_p,
+                               uint32_t drop_seed, const float *gamma, const float *mean, const float *rstd, float *dx,
+                               float *dbranch, float *dgamma, float *dbeta, void *ws, size_t ws_bytes, int64_t M, int C,
+                               void *hip_stream);
+
+/* The feed-forward epilogue on [M][C], C a multiple of 4 and <= 4096, M C < 2^32:  h = drop(swish(a + bias)),  swish(v) = v sigmoid(v).
+ * THE BIAS ENTERS HERE: the caller's GEMM runs without one (F.linear(n, W1, None)) and this kernel adds W1's bias, so that the bias
+ * gradient is this file's fixed-order column sum and no separate reduction over the rows is launched.  bias NULL: a already holds it.
+ * _bwd: da = dh * mask * dropscale * swish'(a + bias), swish'(v) = s (1 + v (1 - s)), s = sigmoid(v) (recomputed from a);
+ * dbias [C] = the column sum of da, through slabs in ws (salsa_nn_bias_swish_dropout_ws_bytes(M, C)) and one ordered pass; dbias NULL:
+ * not produced and ws unused. */
+int salsa_nn_bias_swish_dropout_supported(int64_t M, int C);
+size_t salsa_nn_bias_swish_dropout_ws_bytes(int64_t M, int C);
+int salsa_nn_bias_swish_dropout_fwd(const float *a, const float *bias, float *h, int64_t M, int C, float drop_p, uint32_t drop_seed,
+                                    void *hip_stream);
+int salsa_nn_bias_swish_dropout_bwd(const float *dh, const float *a, const float *bias, float *da, float *dbias, void *ws,
+                                    size_t ws_bytes, int64_t M, int C, float drop_p, uint32_t drop_seed, void *hip_stream);
+
+/* The convolution module between its two pointwise GEMMs:  u = swish(LayerNorm(DW(glu(a))) * gamma + beta)
+ *   a (B, T, 2 d): glu(a) = first half * sigmoid(second half);  DW: depthwise convolution along T per sample, `kernel` taps, zero
+ *   padding kernel / 2 at both ends, out[t][c] = dw_bias[c] + sum_k dw_weight[c][k] glu[t - kernel / 2 + k][c], dw_weight [d][kernel]
+ *   (nn.Conv1d(d, d, kernel, groups=d)'s weight);  LayerNorm over the d channels;  u (B, T, d).
+ * Supported: d = 256 or 512, 1 <= T <= 512, kernel odd in 3 .. 31, 1 <= B <= 65535 (salsa_nn_conv_module_supported).  One workgroup
+ * owns SALSA_NN_CONV_MODULE_TILE time steps of one sample in the forward and in the data gradient.
+ * _bwd recomputes the activations from a (nothing but a is kept): da (B, T, 2 d), d_dw_weight [d][kernel], d_dw_bias, dgamma, dbeta
+ * [d]; the four parameter gradients through per-workgroup slabs and one ordered pass.  ws: salsa_nn_conv_module_ws_bytes(B, T, d,
+ * kernel) bytes (the gradient at the depthwise output, (B, T, d), and the slabs).  Three launches. */
+#define SALSA_NN_CONV_MODULE_TILE 16
+int salsa_nn_conv_module_supported(int T, int d, int kernel);
+size_t salsa_nn_conv_module_ws_bytes(int B, int T, int d, int kernel);
+int salsa_nn_conv_module_fwd(const float *a, const float *dw_weight, const float *dw_bias, const float *gamma, const float *beta,
+                             float *u, int B, int T, int d, int kernel, float eps, void *hip_stream);
+int salsa_nn_conv_module_bwd(const float *du, const float *a, const float *dw_weight, const float *dw_bias, const float *gamma,
+                             const float *beta, float *da, float *d_dw_weight, float *d_dw_bias, float *dgamma, float *dbeta,
+                             void *ws, size_t ws_bytes, int B, int T, int d, int kernel, float eps, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

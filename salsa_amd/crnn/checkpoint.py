@@ -29,7 +29,7 @@ def to_reference_key(k: str) -> str:
     m = re.match(r'decoder\.(event|x|y|z)\.fc(\d)\.(.*)', k)
     if m:
         return 'decoder.%s_fc_%s.%s' % m.groups()
-    return k                                                       # decoder.gru.* / decoder.lstm.*, decoder.attn.{i}.{mha,norm}.* (ours only)
+    return k                                                       # decoder.gru.* / decoder.lstm.*, decoder.attn.{i}.*, decoder.conformer.{i}.* (ours only)
 
 
 def reference_state_dict(model) -> 'OrderedDict[str, torch.Tensor]':

@@ -90,7 +90,7 @@ def _save(path, trainer, loader, epoch, global_step, history, best, val=None):
     ckpt = dict(state_dict=reference_state_dict(trainer.raw_model), optimizer=trainer.opt.state_dict(), epoch=epoch,
                 global_step=global_step, history=history, best=best, val=val, loader_seed=loader.seed,
                 output_format=trainer.output_format, n_classes=trainer.n_classes,
-                n_attn_layers=trainer.n_attn_layers, n_attn_heads=trainer.n_attn_heads,
+                n_attn_layers=trainer.n_attn_layers, n_attn_heads=trainer.n_attn_heads, **trainer.conformer,
                 rng_cpu=torch.get_rng_state(), rng_device=torch.cuda.get_rng_state(dev) if dev.type == 'cuda' else None)
     tmp = path + '.tmp'
     torch.save(ckpt, tmp)
@@ -109,6 +109,14 @@ def _load(path, trainer, loader):
     if stored[0] != trainer.n_attn_layers or (stored[0] > 0 and stored[1] != trainer.n_attn_heads):
         raise ValueError('resume: the checkpoint was trained with n_attn_layers %d, n_attn_heads %d, this trainer has %d, %d'
                          % (stored + (trainer.n_attn_layers, trainer.n_attn_heads)))
+    # (likewise a checkpoint from before the Conformer blocks; with blocks, every setting of theirs must agree)
+    if ckpt.get('n_conformer_layers', 0) != trainer.conformer['n_conformer_layers']:
+        raise ValueError('resume: the checkpoint was trained with n_conformer_layers %d, this trainer has %d'
+                         % (ckpt.get('n_conformer_layers', 0), trainer.conformer['n_conformer_layers']))
+    if trainer.conformer['n_conformer_layers'] > 0:
+        for key in ('conformer_heads', 'conformer_ff', 'conformer_kernel', 'conformer_dropout'):
+            if ckpt.get(key, trainer.conformer[key]) != trainer.conformer[key]:
+                raise ValueError('resume: the checkpoint was trained with %s %r, this trainer has %r' % (key, ckpt[key], trainer.conformer[key]))
     load_reference_state_dict(trainer.raw_model, ckpt['state_dict'])
     trainer.opt.load_state_dict(ckpt['optimizer'])
     torch.set_rng_state(ckpt['rng_cpu'])
@@ -128,8 +136,8 @@ def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, 
     checkpoint by valSeld is kept, 'eval': the latest only).  ``epochs`` caps how many epochs THIS call runs (time-sliced jobs);
     ``resume`` continues from the lexicographically last file of <out_dir>/checkpoint (train.py:37-45; none there: from scratch).
     val_bank / val_gt: the validation clips and their ground-truth rows; chunk_len .. sed_threshold, tta and unify_deg go to the
-    validation pass (validate).  The trainer's output_format, n_attn_layers and n_attn_heads are stored in every checkpoint and
-    checked on resume; a 'multi_accdoa' trainer takes a bank of trackwise labels (GpuFeatureBank(n_classes=3 C,
+    validation pass (validate).  The trainer's output_format, n_attn_layers, n_attn_heads and the five Conformer settings are stored in
+    every checkpoint and checked on resume; a 'multi_accdoa' trainer takes a bank of trackwise labels (GpuFeatureBank(n_classes=3 C,
     label_format='trackwise')).
     -> the history: dict(steps=[epoch, step, lr, mom, loss, sed_loss, doa_loss per step], val=[dict per validated epoch],
     best=dict | None, epoch=epochs finished, global_step)."""

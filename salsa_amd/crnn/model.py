@@ -181,6 +181,57 @@ class AttnBlock(nn.Module):
         return self.norm(x + self.drop(self.mha(x, x, x)[0]))
 
 
+class ConformerBlock(nn.Module):
+    """one Conformer block after the recurrent stack, x (B, T, d) float32:
+        x1 = x  + 1/2 drop(FF1(norm_ff1(x)))        FF(n) = w2(drop(swish(w1(n))))
+        x2 = x1 +     drop(MHSA(norm_att(x1)))      no mask, no positional term, no dropout on the probabilities
+        x3 = x2 +     drop(CONV(norm_conv(x2)))     CONV(n) = conv_p2(swish(conv_norm(conv_dw(glu(conv_p1(n))))))
+        x4 = x3 + 1/2 drop(FF2(norm_ff2(x3)))
+        y  = norm_out(x4)
+    conv_dw is a depthwise convolution along time with zero padding, conv_norm a LayerNorm over the channels (a sample stays
+    independent of its batch).  Plain torch modules hold the parameters; on the GPU the forward runs through
+    conformer.block_forward (the HIP residual / LayerNorm, feed-forward epilogue and convolution-module kernels)."""
+
+    def __init__(self, d, n_heads=8, ff=1024, kernel=7, dropout=0.1):
+        super().__init__()
+        if n_heads < 1 or d % n_heads != 0:
+            raise ValueError('conformer_heads: the width %d is not divisible into %r heads' % (d, n_heads))
+        if kernel % 2 != 1 or not 3 <= kernel <= 31:
+            raise ValueError('conformer_kernel must be odd and in 3 .. 31, got %r' % (kernel,))
+        if ff < 1:
+            raise ValueError('conformer_ff must be >= 1, got %r' % (ff,))
+        self.norm_ff1, self.ff1_w1, self.ff1_w2 = nn.LayerNorm(d), nn.Linear(d, ff), nn.Linear(ff, d)
+        self.norm_att = nn.LayerNorm(d)
+        self.mha = nn.MultiheadAttention(d, n_heads, dropout=0.0, batch_first=True)
+        self.norm_conv, self.conv_p1 = nn.LayerNorm(d), nn.Linear(d, 2 * d)
+        self.conv_dw = nn.Conv1d(d, d, kernel, padding=kernel // 2, groups=d, bias=True)
+        self.conv_norm, self.conv_p2 = nn.LayerNorm(d), nn.Linear(d, d)
+        self.norm_ff2, self.ff2_w1, self.ff2_w2 = nn.LayerNorm(d), nn.Linear(d, ff), nn.Linear(ff, d)
+        self.norm_out = nn.LayerNorm(d)
+        self.drop = nn.Dropout(dropout)
+
+    def _ff(self, n, w1, w2):
+        return w2(self.drop(F.silu(w1(n))))
+
+    def _conv(self, n):
+        v = self.conv_dw(F.glu(self.conv_p1(n), dim=-1).transpose(1, 2)).transpose(1, 2)
+        return self.conv_p2(F.silu(self.conv_norm(v)))
+
+    def forward_torch(self, x):
+        x = x + 0.5 * self.drop(self._ff(self.norm_ff1(x), self.ff1_w1, self.ff1_w2))
+        n = self.norm_att(x)
+        x = x + self.drop(self.mha(n, n, n, need_weights=False)[0])
+        x = x + self.drop(self._conv(self.norm_conv(x)))
+        x = x + 0.5 * self.drop(self._ff(self.norm_ff2(x), self.ff2_w1, self.ff2_w2))
+        return self.norm_out(x)
+
+    def forward(self, x):
+        if x.is_cuda:
+            from .conformer import block_forward
+            return block_forward(self, x, self.training)
+        return self.forward_torch(x)
+
+
 DECODER_TYPES = ('gru', 'bigru', 'lstm', 'bilstm')
 FREQ_POOLS = ('avg', 'max', 'avg_max')
 
@@ -189,10 +240,12 @@ class Decoder(nn.Module):
     """frequency pool -> 2-layer recurrent decoder (size 256) with dropout 0.3 -> SED head + x/y/z heads (decoders.py:13-154).
     decoder_type 'bigru' (the default), 'gru', 'lstm' or 'bilstm'; freq_pool 'avg' (the default), 'max' or 'avg_max'.  The module
     attribute is ``gru`` or ``lstm``, as in the reference's state dict.  n_attn_layers > 0 (beyond the reference) appends that many
-    AttnBlocks of n_attn_heads heads between the recurrent stack and the heads; 0 adds no module and no state-dict key."""
+    AttnBlocks of n_attn_heads heads between the recurrent stack and the heads; 0 adds no module and no state-dict key.
+    n_conformer_layers > 0 appends that many ConformerBlocks (conformer_heads, conformer_ff, conformer_kernel, conformer_dropout) in
+    the same place instead: the two stages exclude each other."""
 
     def __init__(self, n_in=512, n_classes=12, size=256, decoder_type='bigru', freq_pool='avg', n_attn_layers=0, n_attn_heads=8,
-                 attn_dropout=0.05):
+                 attn_dropout=0.05, n_conformer_layers=0, conformer_heads=8, conformer_ff=1024, conformer_kernel=7, conformer_dropout=0.1):
         super().__init__()
         if decoder_type == 'transformer':
             raise NotImplementedError("decoder_type 'transformer' is not implemented (supported: %s)" % ', '.join(DECODER_TYPES))
@@ -202,6 +255,10 @@ class Decoder(nn.Module):
             raise NotImplementedError('freq pooling %r is not implemented (supported: %s)' % (freq_pool, ', '.join(FREQ_POOLS)))
         if n_attn_layers < 0:
             raise ValueError('n_attn_layers must be >= 0, got %r' % (n_attn_layers,))
+        if n_conformer_layers < 0:
+            raise ValueError('n_conformer_layers must be >= 0, got %r' % (n_conformer_layers,))
+        if n_attn_layers > 0 and n_conformer_layers > 0:
+            raise ValueError('n_attn_layers and n_conformer_layers exclude each other, got %r and %r' % (n_attn_layers, n_conformer_layers))
         self.n_classes, self.decoder_type, self.freq_pool = n_classes, decoder_type, freq_pool
         bidirectional = decoder_type.startswith('bi')
         if decoder_type == 'bigru':
@@ -215,6 +272,8 @@ class Decoder(nn.Module):
             _init_rnn_reference(self.lstm)
         d = (2 if bidirectional else 1) * size
         self.attn = nn.ModuleList(AttnBlock(d, n_attn_heads, attn_dropout) for _ in range(n_attn_layers))
+        self.conformer = nn.ModuleList(ConformerBlock(d, conformer_heads, conformer_ff, conformer_kernel, conformer_dropout)
+                                       for _ in range(n_conformer_layers))
         self.event = Head(d, n_classes)
         self.x, self.y, self.z = Head(d, n_classes), Head(d, n_classes), Head(d, n_classes)
 
@@ -246,6 +305,8 @@ class Decoder(nn.Module):
                         seq, _ = self.rnn(seq.float())
                 for block in self.attn:                         # (float32, like the scans: softmax and LayerNorm statistics)
                     seq = block(seq)
+                for block in self.conformer:
+                    seq = block(seq)
             # the heads too (0.02 % of the FLOPs): under autocast their eight small linears cost 32 cast kernels per step
             # (weights and biases to bf16, their gradients back) around GEMMs of a few microseconds
             with torch.autocast(device_type='cuda', enabled=False):
@@ -253,6 +314,8 @@ class Decoder(nn.Module):
         else:
             seq, _ = self.rnn(seq)
             for block in self.attn:
+                seq = block(seq)
+            for block in self.conformer:
                 seq = block(seq)
         return self._heads(seq)
 
@@ -305,14 +368,19 @@ class SeldCRNN(nn.Module):
     """forward(x (B,7,T,200)) -> dict at the LABEL rate (seld_models.py:39-66: encoder, decoder, then
     interpolate by time_downsample_ratio * label_rate / feature_rate = 16 * 10 / 80 = 2).  decoder_type, freq_pool and
     decoder_size are the reference's YAML keys of the same names (see Decoder); n_attn_layers, n_attn_heads and attn_dropout add
-    self-attention blocks after the recurrent decoder (AttnBlock; 0 layers by default: the reference's network)."""
+    self-attention blocks after the recurrent decoder (AttnBlock; 0 layers by default: the reference's network); n_conformer_layers,
+    conformer_heads, conformer_ff, conformer_kernel and conformer_dropout add Conformer blocks there instead (ConformerBlock; 0 by
+    default)."""
 
     def __init__(self, n_input_channels=7, n_classes=12, label_rate=10, feature_rate=80, decoder_type='bigru', freq_pool='avg',
-                 decoder_size=256, n_attn_layers=0, n_attn_heads=8, attn_dropout=0.05):
+                 decoder_size=256, n_attn_layers=0, n_attn_heads=8, attn_dropout=0.05, n_conformer_layers=0, conformer_heads=8,
+                 conformer_ff=1024, conformer_kernel=7, conformer_dropout=0.1):
         super().__init__()
         self.encoder = Encoder(n_input_channels)
         self.decoder = Decoder(self.encoder.n_output_channels, n_classes, decoder_size, decoder_type, freq_pool,
-                               n_attn_layers=n_attn_layers, n_attn_heads=n_attn_heads, attn_dropout=attn_dropout)
+                               n_attn_layers=n_attn_layers, n_attn_heads=n_attn_heads, attn_dropout=attn_dropout,
+                               n_conformer_layers=n_conformer_layers, conformer_heads=conformer_heads, conformer_ff=conformer_ff,
+                               conformer_kernel=conformer_kernel, conformer_dropout=conformer_dropout)
         self.ratio = self.encoder.time_downsample_ratio * label_rate / feature_rate
 
     def forward(self, x):

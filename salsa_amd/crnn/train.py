@@ -46,7 +46,8 @@ class Trainer:
     def __init__(self, device, amp_dtype=torch.bfloat16, ddp: bool = None, total_steps: int = 1313 * 50,
                  bf16_grad_allreduce: bool = True, seed: int = 2021, n_input_channels: int = 7, decoder_type: str = 'bigru',
                  freq_pool: str = 'avg', decoder_size: int = 256, output_format: str = 'reg_xyz', n_classes: int = 12,
-                 n_attn_layers: int = 0, n_attn_heads: int = 8, attn_dropout: float = 0.05):
+                 n_attn_layers: int = 0, n_attn_heads: int = 8, attn_dropout: float = 0.05, n_conformer_layers: int = 0,
+                 conformer_heads: int = 8, conformer_ff: int = 1024, conformer_kernel: int = 7, conformer_dropout: float = 0.1):
         """n_input_channels: 7 (SALSA, melspeciv, linspeciv) or 10 (melspecgcc, linspecgcc), experiments/configs/seld.yml;
         decoder_type ('bigru' | 'gru' | 'lstm' | 'bilstm'), freq_pool ('avg' | 'max' | 'avg_max') and decoder_size: the YAML's
         model.decoder keys of the same names (SeldCRNN); output_format: the YAML's data.output_format, 'reg_xyz' (SED from the
@@ -54,11 +55,14 @@ class Trainer:
         tracks per class, DESIGN.md section 9i: the model is SeldCRNN(n_classes=3 * n_classes), trained with loss.adpit_loss on
         trackwise labels, while self.n_classes stays the number of real classes); n_classes: the YAML's data.n_classes (12 for
         TNSSE2021, 14 for TNSSE2020); n_attn_layers, n_attn_heads, attn_dropout: self-attention blocks after the recurrent decoder
-        (SeldCRNN), none by default."""
+        (SeldCRNN), none by default; n_conformer_layers, conformer_heads, conformer_ff, conformer_kernel,
+        conformer_dropout: Conformer blocks there instead, none by default."""
         if output_format not in OUTPUT_FORMATS:
             raise ValueError('invalid output_format %r (supported: %s)' % (output_format, ', '.join(OUTPUT_FORMATS)))
         self.output_format = output_format
         self.n_attn_layers, self.n_attn_heads = n_attn_layers, n_attn_heads
+        self.conformer = dict(n_conformer_layers=n_conformer_layers, conformer_heads=conformer_heads, conformer_ff=conformer_ff,
+                              conformer_kernel=conformer_kernel, conformer_dropout=conformer_dropout)
         torch.manual_seed(seed)
         self.device = torch.device(device)
         if self.device.type == 'cuda' and os.environ.get('SALSA_MIOPEN_FIND', '0') == '1':
@@ -70,7 +74,7 @@ class Trainer:
         self.n_model_classes = 3 * n_classes if output_format == 'multi_accdoa' else n_classes    # pseudo-classes: track n, class c -> n C + c
         model = SeldCRNN(n_input_channels=n_input_channels, n_classes=self.n_model_classes, decoder_type=decoder_type, freq_pool=freq_pool,
                          decoder_size=decoder_size, n_attn_layers=n_attn_layers, n_attn_heads=n_attn_heads,
-                         attn_dropout=attn_dropout).to(self.device)
+                         attn_dropout=attn_dropout, **self.conformer).to(self.device)
         self.channels_last = self.device.type == 'cuda' and os.environ.get('SALSA_CHANNELS_LAST', '1') == '1'
         if self.channels_last:
             model = model.to(memory_format=torch.channels_last)

@@ -4,7 +4,7 @@ drawn from different seeds over ONE event pool and ONE response bank (salsa_amd/
 GpuFeatureBanks, and Trainer.fit runs a few epochs.  The SELD 2021 scores on the held-out scenes are recorded before training and
 after every epoch.  No score is promised; the JSON lines say what was seen.
 
-    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--moving 0.5] [--room] [--format mic --baffle rigid] [--ambient diffuse --snr-db 20] [--out profiles/scene_training.jsonl]
+    python tools/train_on_scenes.py [--train-clips 48] [--val-clips 8] [--epochs 8] [--moving 0.5] [--room] [--format mic --baffle rigid] [--ambient diffuse --snr-db 20] [--conformer 2] [--out profiles/scene_training.jsonl]
 
 --moving FRACTION makes that share of the items move in azimuth in the training and the held-out scenes alike, so
 the ground truth's directions change inside events; 0 (the default) leaves the run as it was.
@@ -46,6 +46,7 @@ def parse_args(argv=None):
     ap.add_argument('--ambient', choices=['white', 'diffuse'], default='white',
                     help='white: independent noise of rms 1e-3 per channel; diffuse: the diffuse field of DESIGN.md section 9q at --snr-db')
     ap.add_argument('--snr-db', type=float, default=20.0, help='--ambient diffuse: each clip\'s mean square over the noise\'s expected one, dB')
+    ap.add_argument('--conformer', type=int, default=0, help='Conformer blocks after the recurrent decoder (DESIGN.md section 9r); 0: the run as it was')
     ap.add_argument('--out', default=None, help='append the JSON lines to this file too')
     args = ap.parse_args(argv)
     if args.baffle == 'rigid' and args.format != 'mic':
@@ -129,8 +130,9 @@ def main():
                       val_moving_items=int((np.diff(drawn['val'].traj_start) > 0).sum()),
                       val_rows_whose_direction_differs_from_the_items_first=int(sum(
                           (sc.scene_rows(drawn['val'][b])[:, 3] != sc.scene_rows(static_view(drawn['val'][b]))[:, 3]).sum()
-                          for b in range(args.val_clips)))) if args.moving else {})))
-    tr = Trainer('cuda', seed=args.seed)
+                          for b in range(args.val_clips)))) if args.moving else {}),
+              **(dict(n_conformer_layers=args.conformer) if args.conformer else {})))
+    tr = Trainer('cuda', seed=args.seed, n_conformer_layers=args.conformer)
     keys = ('valER', 'valF1', 'valLE', 'valLR', 'valSeld')
     before = validate(tr, banks['val'], val_gt)
     emit(dict(record='scene_training', what='held-out scores before training', **{k: round(before[k], 4) for k in keys}))
