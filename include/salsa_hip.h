@@ -504,6 +504,42 @@ int salsa_band_merge(const float *d_bands, const float *d_filters, int n, int n_
                      void *hip_stream);
 int salsa_band_split(const float *d_x, const float *d_filters, int n, int n_bands, int length, int half, float *d_out, void *hip_stream);
 
+/* Sources localised from the features' directional channels by a DOA histogram (salsa_amd/localize.py; the
+ * reference has no counterpart: the definition is this project's).  d_feat float32 [batch][n_channels >= 7][n_frames][n_freq], time-major
+ * as salsa_extract_batch writes it; only the columns [col0, col1) of the channels 4 - 6 are read.  frames_per_label = P feature frames
+ * make one label frame, Fl = n_frames / P of them (trailing frames are ignored).  The votes of label frame f are the cells (t, col),
+ * P f <= t < P (f + 1), t ascending, then col ascending:
+ *     v = (ch4, ch5, ch6)[t][col]; no vote when all three are zero (either sign) or one is not finite
+ *     FOA: u = (v[2], v[0], v[1]) (the channels are Y, Z, X);  MIC: u_i = fmaf(M[i][2], v[2], fmaf(M[i][1], v[1], M[i][0] v[0])),
+ *         M = mic_matrix, HOST float32 [3][3], the inverse of the rows p_m - p_0 of the capsule positions (NULL for FOA)
+ *     n = sqrtf(fmaf(u_z, u_z, fmaf(u_y, u_y, u_x u_x))); no vote unless norm_lo <= n <= norm_hi; u = u / n
+ * The grid is equal-angle with a step of grid_step degrees (it divides 90, 3 .. 30): elevation -90 .. 90, each pole ONE cell, elsewhere
+ * the azimuths -180 .. 180 - step, numbered elevation-major: salsa_doa_hist_cells(step) = (360 / step)(180 / step - 1) + 2 cells (0 for a
+ * step not taken).  d_grid float32 [cells][3] holds their unit vectors (x, y, z), the caller's table.
+ *     score[g] = sum over the votes, in vote order, of max(0, (dot(u, U[g]) - cos_kernel) inv_kernel),
+ *     dot(u, U) = fmaf(u_z, U_z, fmaf(u_y, U_y, u_x U_x)),
+ * float32 throughout, no transcendental.  Peaks, for k = 0 .. max_sources - 1: g* is the unsuppressed cell of greatest score, the lowest
+ * index on a tie; stop when score[g*] < min_score; the refined direction is m / |m|, m the float32 sum in vote order of the votes with
+ * dot(u, U[g*]) >= cos_kernel; then every cell with dot(U[g], U[g*]) >= cos_suppress is suppressed.
+ * Outputs per (clip, label frame): d_count int32 [batch][Fl] the peaks found, d_votes int32 [batch][Fl] the votes cast, d_cell int32
+ * [batch][Fl][K], d_score float32 [batch][Fl][K], d_direction float32 [batch][Fl][K][3] (x, y, z); unused slots hold -1, +0.0, +0.0.
+ * d_spectrum float32 [batch][Fl][cells] or NULL: every cell's score, none suppressed; the other outputs' bits are the same either way.
+ * One launch on hip_stream, one workgroup per label frame, no atomics, no scratch, nothing allocated or synchronised: two calls give
+ * equal bits and a clip's result does not depend on its batch.
+ * salsa_doa_hist_supported (host only, 1 or 0): n_channels >= 7, 0 <= col0 < col1 <= n_freq, P >= 1, P (col1 - col0) <= 4096, a step
+ * taken, 1 <= max_sources <= 8.  salsa_doa_hist_limits writes the largest number of cells per label frame (4096), of sources (8) and
+ * of grid cells (each pointer may be NULL) and returns the workgroup's size.  Further batch >= 1, Fl >= 1, batch Fl < 2^31, -1 <
+ * cos_kernel < 1, inv_kernel > 0, -1 <= cos_suppress <= 0.9999 (a peak must suppress its own cell), min_score > 0, 0 < norm_lo <=
+ * norm_hi finite.  Returns -1 for a null pointer or an argument outside these limits, before any device call; -6 when the launch fails. */
+int salsa_doa_hist_limits(int *max_votes, int *max_sources, int *max_cells);
+int salsa_doa_hist_cells(int grid_step);
+int salsa_doa_hist_supported(int n_channels, int n_freq, int col0, int col1, int frames_per_label, int grid_step, int max_sources);
+int salsa_doa_hist(const float *d_feat, int batch, int n_channels, int64_t n_frames, int n_freq, int col0, int col1,
+                   int frames_per_label, int audio_format, const float *mic_matrix, const float *d_grid, int grid_step,
+                   float cos_kernel, float inv_kernel, float cos_suppress, float min_score, float norm_lo, float norm_hi,
+                   int max_sources, int *d_count, int *d_votes, int *d_cell, float *d_score, float *d_direction,
+                   float *d_spectrum, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

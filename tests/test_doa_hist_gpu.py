@@ -1,0 +1,135 @@
+"""The DOA histogram on the GPU: salsa_doa_hist through the C ABI on the built vote sets of
+tests/doa_hist_reference.py (B = 3, T = 25: three label frames and one ignored frame per clip, F = 200; FOA columns [0, 191) with 7
+channels, MIC columns [0, 33) with 7 and 10, the channels beyond 6 NaN), every output between NaN guard bands, against the float64
+reference (decisions exact under the reference's margin condition, scores and directions within its bounds) and against the composed
+torch path on the device; the structural promises; and one rendered scene per format end to end."""
+import numpy as np
+import pytest
+import torch
+
+import doa_hist_reference as ref
+from salsa_amd import localize as lz
+from salsa_amd import scenes as sc
+from salsa_amd.extractor import SalsaExtractor
+from test_attn_gpu import DEV, GUARD
+from test_doa_hist_cpu import CASES, as_dict, built
+
+pytestmark = pytest.mark.gpu
+MEASURED = """largest ratio (error) / (bound of tests/doa_hist_reference.py) over every case and built frame, on one MI355X; decisions
+(count, cell, n_votes) were equal to the reference's in every frame:
+                          score   direction   spectrum
+  salsa_doa_hist, FOA     0.18    0.07        0.30
+  salsa_doa_hist, MIC     0.10    0.04        0.14
+  torch on device, FOA    0.10    0.09        0.30
+  torch on device, MIC    0.05    0.05        0.13
+  torch against the kernel, the kernel's outputs in the reference's place:
+                    FOA   0.29    0.16        0.32
+                    MIC   0.15    0.05        0.17
+End to end (30, 10): FOA 0.10, MIC open 0.10, MIC rigid 2.67 degrees worst over the ten active label frames; 1528 (FOA) and 264 (MIC)
+votes in each of them, none in the silent frames."""
+NAN_BITS = 0x7FC00000
+
+
+def _guarded(shape, dtype):
+    """a NaN-filled float32 buffer with the tensor (float32, or int32 over the same words) in its middle -> (buffer, view)"""
+    n = int(np.prod(shape))
+    buf = torch.full((n + 2 * GUARD,), float('nan'), dtype=torch.float32, device=DEV)
+    return buf, buf[GUARD:GUARD + n].view(dtype).view(*shape)
+
+
+def _run_guarded(loc, x, spectrum=True):
+    B, Fl, K, G = x.shape[0], x.shape[2] // loc.frames_per_label, loc.max_sources, loc.n_cells
+    shapes = dict(count=((B, Fl), torch.int32), n_votes=((B, Fl), torch.int32), cell=((B, Fl, K), torch.int32),
+                  score=((B, Fl, K), torch.float32), direction=((B, Fl, K, 3), torch.float32))
+    if spectrum:
+        shapes['spectrum'] = ((B, Fl, G), torch.float32)
+    bufs = {k: _guarded(*v) for k, v in shapes.items()}
+    res = lz.DoaResult(**{k: v[1] for k, v in bufs.items()})
+    loc.launch(x, res)
+    torch.cuda.synchronize()
+    for name, (buf, view) in bufs.items():
+        assert bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[GUARD + view.numel():]).all()), '%s: a guard band was written' % name
+        words = buf[GUARD:GUARD + view.numel()].view(torch.int32)
+        assert not bool((words == NAN_BITS).any()), '%s: an element was not written' % name
+    return res
+
+
+def _bits_equal(a, b):
+    return all(torch.equal(getattr(a, f).view(torch.int32), getattr(b, f).view(torch.int32))
+               for f in ('count', 'n_votes', 'cell', 'score', 'direction', 'spectrum') if getattr(a, f) is not None)
+
+
+@pytest.mark.parametrize('fmt,n_channels,K,step', CASES)
+def test_kernel_against_reference_and_torch_path(fmt, n_channels, K, step, monkeypatch):
+    loc, xs, refs = built(fmt, n_channels, K, step)
+    case = (fmt, n_channels, K, step)
+    for x_host, r in zip(xs, refs):
+        ref.check_margins(r)
+        x = torch.from_numpy(x_host.copy()).to(DEV)
+        res = _run_guarded(loc, x)
+        got = as_dict(res)
+        print('HIP %s %s' % (case, ref.check_against(got, r, what='hip %s' % (case,))))
+        # the spectrum at each peak is the returned score, and its row maximum is the first peak
+        cell, score, spec = got['cell'], got['score'], got['spectrum']
+        used = cell >= 0
+        at = np.take_along_axis(spec, np.maximum(cell, 0).astype(np.int64), axis=2)
+        assert np.array_equal(at[used].view(np.uint32), score[used].view(np.uint32))
+        first = used[..., 0]
+        assert np.array_equal(spec.argmax(axis=2)[first], cell[..., 0][first]) and np.array_equal(spec.max(axis=2)[first], score[..., 0][first])
+        assert np.all(cell[~used] == -1)
+        # two runs, with and without the spectrum, and each clip alone: equal bits
+        again = _run_guarded(loc, x, spectrum=False)
+        assert _bits_equal(again, res)
+        for b in range(x.shape[0]):
+            alone = _run_guarded(loc, x[b:b + 1].contiguous())
+            part = lz.DoaResult(*(getattr(res, f)[b:b + 1] for f in ('count', 'n_votes', 'cell', 'score', 'direction', 'spectrum')))
+            assert _bits_equal(alone, part), 'clip %d alone differs from the clip in its batch' % b
+        # the public call, and the composed torch path on the device to the same bounds
+        assert _bits_equal(loc.localize(x, spectrum=True), res)
+        monkeypatch.setattr(lz, 'HIP_DOA', False)
+        torch_res = loc.localize(x, spectrum=True)
+        monkeypatch.setattr(lz, 'HIP_DOA', True)
+        assert torch_res.count.is_cuda
+        print('TORCH-ON-DEVICE %s %s' % (case, ref.check_against(as_dict(torch_res), r, what='torch on device %s' % (case,))))
+        hip_as_ref = dict(r, **{k: np.asarray(v, np.int64 if v.dtype == np.int32 else np.float64) for k, v in got.items()})
+        print('HIP-VS-TORCH %s %s' % (case, ref.check_against(as_dict(torch_res), hip_as_ref, what='torch against hip %s' % (case,))))
+
+
+def _scene(fmt, baffle):
+    """a 2-s clip: one second of AR(1) noise from (30, 10), starting at 0.5 s, in white noise of 0.001"""
+    rng = np.random.default_rng(5)
+    w = rng.standard_normal(24000)
+    s = np.zeros(24000)
+    acc = 0.0
+    for n in range(24000):
+        acc = 0.9 * acc + w[n]
+        s[n] = acc
+    pool = sc.EventPool([0.1 * s / s.std()], [0])
+    bank = sc.make_rir_bank(fmt, [(30, 10)], 96, baffle=baffle)
+    scenes = sc.Scenes.from_items(48000, [[(0, 0, 12000, 1.0, 0)]], pool, bank)
+    ambient = (0.001 * torch.from_numpy(rng.standard_normal((1, 4, 48000)).astype(np.float32))).to(DEV)
+    return scenes, sc.render_scenes(scenes, pool, bank, ambient=ambient)
+
+
+@pytest.mark.parametrize('fmt,baffle,bound', [('foa', 'open', ref.SINGLE_BOUND_DEG['foa']), ('mic', 'open', ref.SINGLE_BOUND_DEG['mic_open']),
+                                              ('mic', 'rigid', ref.SINGLE_RIGID_BOUND_DEG)])
+def test_rendered_scene_end_to_end(fmt, baffle, bound):
+    """render -> extract -> localize.  Active label frames: those the event covers whole (its samples 12000 .. 35999, label frames of 2400
+    samples: 5 .. 14).  Silent ones: those no analysis window that sees the event reaches -- the response's 96 taps, half a window of 256
+    and one frame of covariance averaging, 300, on either side: label frames 0 .. 3 and 16 .. 19.  The two frames in between are the
+    onset's and the decay's and are not asked about."""
+    scenes, audio = _scene(fmt, baffle)
+    fmax = 9000 if fmt == 'foa' else 4000
+    feat = SalsaExtractor(audio_format=fmt, fmax_doa=fmax, device=DEV).extract(audio)
+    loc = lz.DoaHistogram(audio_format=fmt, fmax_doa=fmax)
+    res = loc.localize(feat)
+    r = res.numpy()
+    active, silent = np.arange(5, 15), np.array([0, 1, 2, 3, 16, 17, 18, 19])
+    err = ref.angle_deg(r.direction[0, active, 0], ref.unit(30, 10))
+    print('E2E %s %s count %s votes %s worst %.3f deg, silent scores %s' % (fmt, baffle, r.count[0], r.n_votes[0], err.max(), r.score[0, silent, 0]))
+    assert r.count.shape == (1, 20)
+    assert np.all(r.count[0, active] == 1), r.count
+    assert np.all(r.count[0, silent] == 0), r.count
+    assert err.max() <= bound, err
+    e = lz.angular_errors(res, scenes)
+    assert e.n_frames == 20 and e.missed == 0 and len(e.errors) == 10 and e.errors.max() <= bound
