@@ -1,6 +1,7 @@
 """The float64 reference of the DOA histogram (salsa_amd/localize.py, include/salsa_hip.h: salsa_doa_hist), its error bounds with their
-rounding counts, the conditions under which decisions are compared exactly, and the built vote sets of tests/test_doa_hist_cpu.py and
-tests/test_doa_hist_gpu.py.  numpy only; the constants (grid table, c0, inv, cos_suppress, matrix, norm range) are the float32 values of
+rounding counts, the conditions under which decisions are compared exactly, the built vote sets of tests/test_doa_hist_cpu.py,
+tests/test_doa_hist_gpu.py and the two tests/test_doa_hist_edges_*.py, and a float32 evaluation in the stated operation order for the
+frames built to tie (kernel_order_float32).  numpy only; the constants (grid table, c0, inv, cos_suppress, matrix, norm range) are the float32 values of
 the DoaHistogram under test, read as float64, so reference and code disagree by rounding alone.
 
 Bounds (u = 2^-24, float32 unit roundoff; every product below carries a factor 1.01 for the second-order terms):
@@ -186,6 +187,55 @@ def check_against(got, ref, direction_tol=None, what=''):
     return worst
 
 
+# ---------------------------------------------------------------------------------------------------------------- float32, as stated
+def _fma(a, b, c):
+    """fmaf: the product of two float32 is exact in float64; the sum is rounded to float64 and then to float32, which is fmaf's single
+    rounding unless the float64 sum is inexact AND lands on a float32 tie -- not so for the tie frames, whose sums are exact"""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
+
+
+def _dot3(u, g):
+    """include/salsa_hip.h: dot = fmaf(u_z, U_z, fmaf(u_y, U_y, u_x U_x))"""
+    return _fma(u[..., 2], g[..., 2], _fma(u[..., 1], g[..., 1], u[..., 0] * g[..., 0]))
+
+
+def kernel_order_float32(v, loc):
+    """One FOA label frame in float32, in the operation order include/salsa_hip.h states (salsa_doa_hist): the votes normalised, every
+    cell's score summed in vote order, the greedy peaks with the lowest index on a tie (np.argmax takes the first of the largest), the
+    refinement summed in vote order.  v float32 (n_cells, 3): channels 4, 5, 6.  -> dict(count, n_votes, cell, score, direction,
+    spectrum), float32.  For the frames built to tie: it shows that the tied scores have equal bits, which is not assumed."""
+    assert loc.matrix is None
+    f, K, G = np.float32, loc.max_sources, loc.n_cells
+    v = np.asarray(v, f).reshape(-1, 3)
+    Ug, c0, inv = loc.grid, f(loc.c0), f(loc.inv)
+    with np.errstate(all='ignore'):
+        u = v[:, [2, 0, 1]]
+        length = np.sqrt(_fma(u[:, 2], u[:, 2], _fma(u[:, 1], u[:, 1], u[:, 0] * u[:, 0])))
+        ok = np.isfinite(v).all(axis=1) & (v != 0).any(axis=1) & (length >= f(loc.norm_lo)) & (length <= f(loc.norm_hi))
+        u = (u[ok] / length[ok][:, None]).astype(f)
+    sc = np.zeros(G, f)
+    for w in u:
+        sc = sc + np.maximum(f(0), (_dot3(w, Ug) - c0) * inv)
+    assert sc.dtype == f
+    out = dict(count=0, n_votes=len(u), cell=np.full(K, -1, np.int32), score=np.zeros(K, f), direction=np.zeros((K, 3), f), spectrum=sc)
+    free = np.ones(G, bool)
+    for k in range(K):
+        if not free.any():
+            break
+        s = np.where(free, sc, f(-1))
+        g = int(np.argmax(s))
+        if not s[g] >= f(loc.min_score):
+            break
+        m = np.zeros(3, f)
+        for w in u[_dot3(u, Ug[g]) >= c0]:
+            m = m + w
+        out['cell'][k], out['score'][k] = g, s[g]
+        out['direction'][k] = m / np.sqrt(_fma(m[2], m[2], _fma(m[1], m[1], m[0] * m[0])))
+        out['count'] += 1
+        free &= ~(_dot3(Ug, Ug[g]) >= f(loc.cos_suppress))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- built vote sets
 def _votes_around(rng, centre_deg, n, spread_deg, length=(0.8, 1.25)):
     """n unit vectors scattered about a direction, each scaled by a length inside the norm range -> float64 (n, 3) (x, y, z)"""
@@ -247,35 +297,64 @@ def frame_recipes(loc):
         v = np.concatenate([good, bad])
         return v[rng.permutation(len(v))]
 
+    def dense(rng, ncells):                                                    # every cell votes, no background: 2500 / 4096 of them in one cap
+        a = (2500 * ncells) // 4096
+        v = np.concatenate([_votes_around(rng, near(-60, 30), a, 3.0), _votes_around(rng, near(105, -15), ncells - a, 3.0)])
+        return v[rng.permutation(ncells)]
+
+    def clusters(n):                                                           # n clusters of 20 + 2 i votes: K = 8 meets eight and nine peaks
+        def build(rng, ncells):
+            v = np.concatenate([_votes_around(rng, near(*CLUSTER_CENTRES[i]), 20 + 2 * i, 2.0) for i in range(n)])
+            return v[rng.permutation(len(v))]
+        return build
+
+    def extreme(rng, ncells):                                                  # good votes among lengths that float32 cannot square, or hold
+        good = _votes_around(rng, near(150, -30), 40, 2.0)
+        bad = _votes_around(rng, near(150, -30), 3 * len(EXTREME_SCALES), 2.0)
+        bad *= np.repeat(EXTREME_SCALES, 3)[:, None] / np.sqrt((bad ** 2).sum(axis=1, keepdims=True))
+        v = np.concatenate([good, bad])
+        return v[rng.permutation(len(v))]
+
     return {'n0': counted(0), 'n1': counted(1), 'n255': counted(255), 'n256': counted(256), 'n257': counted(257), 'full': full,
             'north': lambda rng, n: _votes_around(rng, (40, 89.2), 50, 1.5), 'south': lambda rng, n: _votes_around(rng, (-70, -89.4), 50, 1.5),
             'seam': lambda rng, n: _votes_around(rng, (179.6, 10 + 0.2 * s), 60, 2.0),
             'apart29': two(29.0), 'apart31': two(31.0), 'above': threshold(True), 'below': threshold(False), 'dirty': dirty,
-            'two': lambda rng, n: np.concatenate([_votes_around(rng, near(40, 0), 50, 2.0), _votes_around(rng, near(-100, 20), 30, 2.0)])}
+            'two': lambda rng, n: np.concatenate([_votes_around(rng, near(40, 0), 50, 2.0), _votes_around(rng, near(-100, 20), 30, 2.0)]),
+            'n63': counted(63), 'n64': counted(64), 'n65': counted(65), 'full4096': full, 'dense4096': dense,
+            'eight': clusters(8), 'nine': clusters(9), 'extreme': extreme}
 
 
 FRAME_NAMES = ('n0', 'n1', 'n255', 'n256', 'n257', 'full', 'north', 'south', 'seam', 'apart29', 'apart31', 'above', 'below', 'dirty',
                'two', 'n256', 'seam', 'full')                                                   # 18 = two tensors of 3 clips x 3 label frames
+CLUSTER_CENTRES = ((45, 35), (-45, 35), (45, -35), (-45, -35), (135, 35), (-135, 35), (135, -35), (-135, -35), (0, 0))
+# lengths of the 'extreme' frame's bad votes: float32 flushes the first to zero (a gate) or to a subnormal, the second is subnormal, the
+# squares of the next two underflow (to zero, to a subnormal), 1e-10 and 1e10 are plainly out of range, 1e19 squares to 1e38 (the sum
+# of three squares may still be finite), the squares of the last three overflow
+EXTREME_SCALES = (1e-45, 1e-40, 1e-30, 1e-20, 1e-10, 1e10, 1e19, 1e20, 1e30, 3e38)
 
 
-def build_features(loc, n_channels=7, n_freq=200, seed=0):
-    """Two tensors float32 (3, n_channels, 25, n_freq), 3 label frames of 8 and one ignored frame each, holding FRAME_NAMES in order.  A
-    frame's votes sit at randomly chosen cells of its (8, col1 - col0) window, in order; every other cell of the window is a gate, +0.0
-    or -0.0 at random.  Outside the window -- other columns, the 25th frame -- channels 4-6 hold loud votes toward (0, 0) that must not
-    count, channels 0-3 noise, channels beyond 6 NaN."""
+def build_features(loc, n_channels=7, n_freq=200, seed=0, names=FRAME_NAMES, clips=3, label_frames=3):
+    """len(names) / (clips label_frames) tensors float32 (clips, n_channels, T, n_freq) holding the frames `names` in order, clip-major:
+    label_frames label frames of P = loc.frames_per_label feature frames each, and for P > 1 one more, ignored, feature frame (P = 1
+    leaves no remainder).  A frame's votes sit at randomly chosen cells of its (P, col1 - col0) window, in order (a recipe that gives
+    more votes than the window has cells is cut short); every other cell of the window is a gate, +0.0 or -0.0 at random.  Outside
+    the window -- the columns below col0 and from col1 on, the ignored frame -- channels 4-6 hold loud votes toward (0, 0) that must
+    not count, channels 0-3 noise, channels beyond 6 NaN.  With the defaults: two tensors (3, n_channels, 25, n_freq) for P = 8."""
     P, ncol = loc.frames_per_label, loc.col1 - loc.col0
-    assert P == 8
+    per = clips * label_frames
+    assert len(names) % per == 0 and loc.col1 <= n_freq
+    T = label_frames * P + (1 if P > 1 else 0)
     D = np.linalg.inv(loc.matrix.astype(np.float64)) if loc.matrix is not None else None
     tensors = []
-    for t in range(2):
+    for t in range(len(names) // per):
         rng = np.random.default_rng([seed, t, loc.grid_step, ncol])
-        x = np.full((3, n_channels, 25, n_freq), np.nan, np.float32)
-        x[:, :4] = rng.standard_normal((3, 4, 25, n_freq)).astype(np.float32)
-        x[:, 4:7] = _encode(np.tile(unit(0.0, 0.0), (3 * 25 * n_freq, 1)), D).reshape(3, 25, n_freq, 3).transpose(0, 3, 1, 2)
-        for i in range(9):
-            b, f = divmod(i, 3)
-            name = FRAME_NAMES[9 * t + i]
-            votes = frame_recipes(loc)[name](np.random.default_rng([seed, t, i, loc.grid_step, ncol]), P * ncol)
+        x = np.full((clips, n_channels, T, n_freq), np.nan, np.float32)
+        x[:, :4] = rng.standard_normal((clips, 4, T, n_freq)).astype(np.float32)
+        x[:, 4:7] = _encode(np.tile(unit(0.0, 0.0), (clips * T * n_freq, 1)), D).reshape(clips, T, n_freq, 3).transpose(0, 3, 1, 2)
+        for i in range(per):
+            b, f = divmod(i, label_frames)
+            name = names[per * t + i]
+            votes = frame_recipes(loc)[name](np.random.default_rng([seed, t, i, loc.grid_step, ncol]), P * ncol)[:P * ncol]
             win = np.zeros((P * ncol, 3), np.float32)
             win[rng.random((P * ncol, 3)) < 0.5] = -0.0
             at = np.sort(rng.choice(P * ncol, len(votes), replace=False))
@@ -288,7 +367,7 @@ def build_features(loc, n_channels=7, n_freq=200, seed=0):
 def _encode(d, D):
     """direction votes (x, y, z) -> channels (4, 5, 6), float32: FOA (y, z, x); MIC D d, the path differences in metres"""
     d = np.asarray(d, np.float64)
-    with np.errstate(invalid='ignore'):
+    with np.errstate(invalid='ignore', over='ignore', under='ignore'):
         return (d @ D.T if D is not None else d[:, [1, 2, 0]]).astype(np.float32)
 
 

@@ -59,16 +59,21 @@ def _bits_equal(a, b):
                for f in ('count', 'n_votes', 'cell', 'score', 'direction', 'spectrum') if getattr(a, f) is not None)
 
 
-@pytest.mark.parametrize('fmt,n_channels,K,step', CASES)
-def test_kernel_against_reference_and_torch_path(fmt, n_channels, K, step, monkeypatch):
-    loc, xs, refs = built(fmt, n_channels, K, step)
-    case = (fmt, n_channels, K, step)
+def check_kernel_case(loc, xs, refs, case, monkeypatch):
+    """One built case on the kernel: everything test_kernel_against_reference_and_torch_path promises (tests/test_doa_hist_edges_gpu.py
+    runs its cases through it too).  -> {'hip' | 'torch' | 'torch-vs-hip': the worst (error) / (bound) ratios over the case's tensors}"""
+    worst = {}
+
+    def keep(leg, ratios):
+        worst[leg] = {k: max(v, worst.get(leg, {}).get(k, 0.0)) for k, v in ratios.items()}
+        return ratios
+
     for x_host, r in zip(xs, refs):
         ref.check_margins(r)
         x = torch.from_numpy(x_host.copy()).to(DEV)
         res = _run_guarded(loc, x)
         got = as_dict(res)
-        print('HIP %s %s' % (case, ref.check_against(got, r, what='hip %s' % (case,))))
+        print('HIP %s %s' % (case, keep('hip', ref.check_against(got, r, what='hip %s' % (case,)))))
         # the spectrum at each peak is the returned score, and its row maximum is the first peak
         cell, score, spec = got['cell'], got['score'], got['spectrum']
         used = cell >= 0
@@ -90,9 +95,16 @@ def test_kernel_against_reference_and_torch_path(fmt, n_channels, K, step, monke
         torch_res = loc.localize(x, spectrum=True)
         monkeypatch.setattr(lz, 'HIP_DOA', True)
         assert torch_res.count.is_cuda
-        print('TORCH-ON-DEVICE %s %s' % (case, ref.check_against(as_dict(torch_res), r, what='torch on device %s' % (case,))))
+        print('TORCH-ON-DEVICE %s %s' % (case, keep('torch', ref.check_against(as_dict(torch_res), r, what='torch on device %s' % (case,)))))
         hip_as_ref = dict(r, **{k: np.asarray(v, np.int64 if v.dtype == np.int32 else np.float64) for k, v in got.items()})
-        print('HIP-VS-TORCH %s %s' % (case, ref.check_against(as_dict(torch_res), hip_as_ref, what='torch against hip %s' % (case,))))
+        print('HIP-VS-TORCH %s %s' % (case, keep('torch-vs-hip', ref.check_against(as_dict(torch_res), hip_as_ref, what='torch against hip %s' % (case,)))))
+    return worst
+
+
+@pytest.mark.parametrize('fmt,n_channels,K,step', CASES)
+def test_kernel_against_reference_and_torch_path(fmt, n_channels, K, step, monkeypatch):
+    loc, xs, refs = built(fmt, n_channels, K, step)
+    check_kernel_case(loc, xs, refs, (fmt, n_channels, K, step), monkeypatch)
 
 
 def _scene(fmt, baffle):
