@@ -327,6 +327,20 @@ int salsa_nn_seld_score2020(const int16_t *pred_rows, const int *pred_counts, in
                             const int *gt_counts, int gt_capacity, int n_files, int n_frames, int label_rate, int n_classes,
                             double doa_threshold, double margin, int *counters, double *total_de, int *status, int64_t *sum_counters,
                             double *sum_de, void *hip_stream);
+/* The same rows by the class-wise SELD 2022 metric: the counters of crnn/metrics.py::SeldMetrics2022.update (the project's restatement
+ * of the public DCASE 2022 metric) per (file, segment) AND per class.  The inputs, the record order, the
+ * pairing, the doubt and refusal rules and the return codes are salsa_nn_seld_score's; the same kernel code bins the rows and books
+ * the classes.  Outputs, every element written: class_counters [records][n_classes][5] int32 (TP Nref DE_TP DE_FP DE_FN; per class
+ * FP == DE_FP, FN == DE_FN and FP_spatial == DE_TP - TP, so these five are all), class_de [records][n_classes] float64 (the class's
+ * slot averages added from 0.0 in the order SeldMetrics2022 adds them; 8-byte aligned), sdi [records][3] int32 (S D I, formed per
+ * segment over all classes), status [records] int32 as above.  Records of status 1 and 2 carry zeros.  file_counters
+ * [n_files][n_classes][5] int64, file_de [n_files][n_classes] float64 and file_sdi [n_files][3] int64 (all three or none NULL;
+ * 8-byte aligned) receive, per file, the file's status-0 records added up by a second kernel: every sum is one running sum in
+ * segment order, and a file's sums depend on that file's records alone.  Bit-reproducible (no atomics). */
+int salsa_nn_seld_score2022(const int16_t *pred_rows, const int *pred_counts, int pred_capacity, const int16_t *gt_rows,
+                            const int *gt_counts, int gt_capacity, int n_files, int n_frames, int label_rate, int n_classes,
+                            double doa_threshold, double margin, int *class_counters, double *class_de, int *sdi, int *status,
+                            int64_t *file_counters, double *file_de, int64_t *file_sdi, void *hip_stream);
 /* salsa_nn_seld_score's distance statement alone: quads [n][4] int16 (azimuth1, elevation1, azimuth2, elevation2) -> out [n]
  * float64 degrees (tools/probe_score_distance.py measures its deviation from the host's, which sizes `margin`). */
 int salsa_nn_seld_distance(const int16_t *quads, int64_t n, double *out, void *hip_stream);

@@ -132,14 +132,14 @@ def decode_multi_rows(act, xyz, n_frames: int = 600, sed_threshold: float = 0.5,
 
 def rows_to_list(rows, counts, eval_version: str = '2021', as_array: bool = False) -> list:
     """decode_dcase_rows' rows (n_files, capacity, 4) and counts (n_files,) ON THE HOST (numpy arrays or CPU tensors) -> per file
-    exactly what to_dcase_rows returns: [frame, class, 0, azimuth, elevation] rows for eval_version '2021' (the zero track column
+    exactly what to_dcase_rows returns: [frame, class, 0, azimuth, elevation] rows for eval_version '2021' and '2022' (the zero track column
     is added here), [frame, class, azimuth, elevation] otherwise; int64, a list of lists or with as_array one (n, 5 | 4) array."""
     rows = rows.numpy() if hasattr(rows, 'numpy') else np.asarray(rows)
     counts = counts.numpy() if hasattr(counts, 'numpy') else np.asarray(counts)
     out = []
     for f in range(rows.shape[0]):
         r = rows[f, :int(counts[f])].astype(np.int64)
-        if eval_version == '2021':
+        if eval_version in ('2021', '2022'):
             r = np.concatenate([r[:, :2], np.zeros((r.shape[0], 1), dtype=np.int64), r[:, 2:]], axis=1)
         out.append(r if as_array else r.tolist())
     return out

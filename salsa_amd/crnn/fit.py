@@ -46,17 +46,19 @@ def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, comb
              doa_threshold=20, eval_version='2021', sub_batch=8, return_rows=False, tta=None, unify_deg=15.0):
     """One validation pass (models/seld_models.py:96-108 + interfaces.py:163-180): every clip of ``val_bank`` through
     infer_pipelined(Trainer.infer) in test chunks, rows against ``val_gt`` (per clip a list of rows, metrics.load_dcase_csv).  On the
-    GPU the rows are decoded and scored on the device (DeviceSeldScore / DeviceSeldScore2020 by eval_version), on the CPU by the host
-    classes.  tta = (audio_format, feature_type) or a tta.TtaForward: the forward is Trainer.infer under test-time augmentation (all
+    GPU the rows are decoded and scored on the device (DeviceSeldScore / DeviceSeldScore2020 / DeviceSeldScore2022 by eval_version), on
+    the CPU by the host classes.  eval_version '2022': valF1, valLE, valLR and valSeld are the class-wise (macro) figures of SeldMetrics2022.  tta = (audio_format, feature_type) or a tta.TtaForward: the forward is Trainer.infer under test-time augmentation (all
     channel-swap variants, the trainer's n_classes and output_format); None: Trainer.infer itself.  A 'multi_accdoa' trainer is
     decoded with track unification (infer_pipelined's output_format / unify_deg): whole clips or non-overlapping chunks, no tta.
     -> dict valER valF1 valLE valLR valSeld (+ the scorer under 'scorer', and 'rows' when asked)."""
     from .infer import infer_pipelined
     from .tta import wrap_forward
-    from .metrics import SeldMetrics, SeldMetrics2020
-    from .score import DeviceSeldScore, DeviceSeldScore2020, gt_rows_to_device
-    if eval_version not in ('2020', '2021'):
+    from .metrics import SeldMetrics, SeldMetrics2020, SeldMetrics2022
+    from .score import DeviceSeldScore, DeviceSeldScore2020, DeviceSeldScore2022, gt_rows_to_device
+    if eval_version not in ('2020', '2021', '2022'):
         raise ValueError('Unknown eval_version {}'.format(eval_version))
+    device_cls, host_cls = {'2020': (DeviceSeldScore2020, SeldMetrics2020), '2021': (DeviceSeldScore, SeldMetrics),
+                            '2022': (DeviceSeldScore2022, SeldMetrics2022)}[eval_version]
     n = len(val_bank.clip_len)
     if n == 0 or len(val_gt) != n:
         raise ValueError('validation: ground truth of %d clips for a bank of %d' % (len(val_gt), n))
@@ -70,11 +72,11 @@ def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, comb
               combine_method=combine_method, n_classes=nc, output_format=trainer.output_format, unify_deg=unify_deg,
               eval_version='2020')       # (the ROW shape only: (frame, class, azimuth, elevation), what SeldMetrics.update reads)
     if on_gpu:
-        scorer = (DeviceSeldScore2020 if eval_version == '2020' else DeviceSeldScore)(nc, doa_threshold, rate)
+        scorer = device_cls(nc, doa_threshold, rate)
         gt_rows, gt_counts = gt_rows_to_device(val_gt, trainer.device)
         rows = infer_pipelined(n, val_bank.clip_batch, forward, decode='device', score=(gt_rows, gt_counts, scorer), **kw)
     else:
-        scorer = (SeldMetrics2020 if eval_version == '2020' else SeldMetrics)(nc, doa_threshold)
+        scorer = host_cls(nc, doa_threshold)
         rows = infer_pipelined(n, val_bank.clip_batch, forward, decode='host', **kw)
         for pred, gt in zip(rows, val_gt):
             scorer.update(pred, gt, max_frames=n_label, label_rate=rate)
@@ -132,7 +134,8 @@ def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, 
         sed_threshold=0.3, doa_threshold=20, val_sub_batch=8, loader=None, tta=None, unify_deg=15.0):
     """Train ``trainer`` for ``max_epochs`` epochs of ``bank`` (a finalized GpuFeatureBank).  The keywords are the YAML's keys
     (INTEGRATION.md has the table): batch_size = training.train_batch_size; milestones / lrs / moms = training.lr_scheduler.*;
-    max_epochs, val_interval = training.*; train_fraction, n_classes (Trainer's) = data.*; eval_version; mode ('crossval': the best
+    max_epochs, val_interval = training.*; train_fraction, n_classes (Trainer's) = data.*; eval_version ('2022': valSeld, and with it
+    the best checkpoint and its name, is the class-wise macro seld_error of SeldMetrics2022); mode ('crossval': the best
     checkpoint by valSeld is kept, 'eval': the latest only).  ``epochs`` caps how many epochs THIS call runs (time-sliced jobs);
     ``resume`` continues from the lexicographically last file of <out_dir>/checkpoint (train.py:37-45; none there: from scratch).
     val_bank / val_gt: the validation clips and their ground-truth rows; chunk_len .. sed_threshold, tta and unify_deg go to the
@@ -146,6 +149,8 @@ def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, 
         raise ValueError('Invalid mode {}'.format(mode))
     if (val_bank is None) != (val_gt is None):
         raise ValueError('val_bank and val_gt come together')
+    if val_bank is not None and eval_version not in ('2020', '2021', '2022'):     # (what validate refuses, before an epoch is spent)
+        raise ValueError('Unknown eval_version {}'.format(eval_version))
     if val_bank is not None and len(set(val_bank.clip_len)) != 1:
         raise ValueError('validation: clips of unequal length in the bank: %s frames' % sorted(set(val_bank.clip_len)))
     if loader is None:

@@ -64,7 +64,8 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
     (score.gt_rows_to_device) and a score.DeviceSeldScore.  Each sub-batch's rows are scored against their slice of the ground truth
     on the same stream right behind the decode launch (score.score_dcase_rows_async, with the accumulator's n_classes, threshold,
     label_rate and margin) and merged into the accumulator when the sub-batch is finished.  The rows returned are unchanged.  The
-    TYPE of the accumulator selects the metric (score.DeviceSeldScore2020: the SELD 2020 one); eval_version only shapes the rows.
+    TYPE of the accumulator selects the metric (score.DeviceSeldScore2020: the SELD 2020 one, score.DeviceSeldScore2022: the
+    class-wise 2022 one, with one file record per item); eval_version only shapes the rows ('2022' rows are '2021' rows).
 
     tta = (audio_format, feature_type), or a ready tta.TtaForward (which carries its own forwards): test-time augmentation.  forward is
     wrapped in a TtaForward over all channel-swap variants of that recipe (n_classes as given, output_format 'reg_xyz'), so each
@@ -180,12 +181,13 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
         if s['event'] is not None:
             s['event'].record()
         if score is not None:
-            from .metrics import SeldMetrics2020
+            from .metrics import SeldMetrics2020, SeldMetrics2022
             from .score import score_dcase_rows_async
+            version = '2022' if isinstance(accumulator, SeldMetrics2022) else ('2020' if isinstance(accumulator, SeldMetrics2020) else '2021')
             s['score'] = score_dcase_rows_async(rows, counts, gt_rows[lo:hi], gt_counts[lo:hi], n_frames=n_label_frames,
                                                 label_rate=accumulator.label_rate, n_classes=accumulator.n_classes,
                                                 doa_threshold=accumulator.doa_threshold, margin=accumulator.margin,
-                                                eval_version='2020' if isinstance(accumulator, SeldMetrics2020) else '2021')
+                                                eval_version=version, average=getattr(accumulator, 'average', 'macro'))
         pending.append((k, lo, hi, t_issue, lab_len, lab_hop))
         while len(pending) >= depth:                     # slot (k + 1) % depth is free again before sub-batch k + 1 is issued
             finish(*pending.popleft())

@@ -55,7 +55,7 @@ def to_dcase_rows(event_prob: np.ndarray, doa_xyz: np.ndarray, sed_threshold: fl
     azi = np.around(np.arctan2(y, x) * 180.0 / np.pi).astype(np.int64)
     ele = np.around(np.arctan2(z, np.sqrt(x ** 2 + y ** 2)) * 180.0 / np.pi).astype(np.int64)
     azi[azi == 180] = -180
-    cols = [t, c, np.zeros_like(t), azi, ele] if eval_version == '2021' else [t, c, azi, ele]
+    cols = [t, c, np.zeros_like(t), azi, ele] if eval_version in ('2021', '2022') else [t, c, azi, ele]
     rows = np.stack(cols, axis=1).astype(np.int64)
     return rows if as_array else rows.tolist()
 
@@ -136,7 +136,7 @@ def multi_accdoa_rows(act: np.ndarray, xyz: np.ndarray, sed_threshold: float = 0
     azi = np.where(np.isnan(azi), 0.0, azi).astype(np.int64)
     ele = np.where(np.isnan(ele), 0.0, ele).astype(np.int64)
     azi[azi == 180] = -180
-    cols = [t, c, np.zeros_like(t), azi, ele] if eval_version == '2021' else [t, c, azi, ele]
+    cols = [t, c, np.zeros_like(t), azi, ele] if eval_version in ('2021', '2022') else [t, c, azi, ele]
     rows = np.stack(cols, axis=1).astype(np.int64)
     return rows if as_array else rows.tolist()
 

@@ -1,6 +1,7 @@
 // seld_score.h -- per-element statements of salsa_nn_seld_score (seld_score.hip): the great-circle distance of two integer-degree
 // directions, the pairing of one (class, frame) cell, the bookkeeping of one class of a segment and the record of the segment;
-// behind them the same three for the SELD 2020 metric (salsa_nn_seld_score2020; tests/hostemu/score2020_emu.cpp, SeldMetrics2020).
+// behind them the per-class record of the SELD 2022 metric (salsa_nn_seld_score2022; tests/hostemu/score2022_emu.cpp, SeldMetrics2022)
+// and the same three for the SELD 2020 metric (salsa_nn_seld_score2020; tests/hostemu/score2020_emu.cpp, SeldMetrics2020).
 // Host + device inline functions over plain arrays (LDS on the device); the same header compiles with g++
 // (tests/hostemu/score_emu.cpp), so the CPU suite holds every statement to crnn/metrics.py::SeldMetrics.  That host build is a test
 // harness, never a fallback of the product.
@@ -224,6 +225,58 @@ SCORE_HD void segment_record(const ClassResult *res, int n_classes, int *counter
     for (int k = 0; k < N_COUNTERS; k++) counters[k] = st == SCORED ? cnt[k] : 0;
     *total_de = st == SCORED ? total : 0.0;
     *status = st;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The class-wise SELD 2022 metric (salsa_nn_seld_score2022; crnn/metrics.py::SeldMetrics2022, the project's own restatement of the
+// public DCASE 2022 metric: DESIGN.md section 9t).  The pairing and the bookkeeping are the 2021 ones, score_class above; only where
+// the bookkeeping lands changes: the class axis is kept, and a slot average above the threshold is a false positive of its own kind
+// (FP_spatial), no longer part of FP.  So per class FP == DE_FP, FN == DE_FN and FP_spatial == DE_TP - TP, and five counters are
+// all a class of a segment has to carry.
+constexpr int N_CLASS_COUNTERS = 5;
+enum { K_TP, K_NREF, K_DE_TP, K_DE_FP, K_DE_FN };
+
+// The segment's own part, from its classes in class order: S, D, I from seg_fp / seg_fn over all classes (a slot average above the
+// threshold still counts in seg_fp), and the status by segment_record's rules.  A segment in doubt or refused carries zeros.
+SCORE_HD void segment_sdi2022(const ClassResult *res, int n_classes, int *sdi, int *status)
+{
+    int seg_fp = 0, seg_fn = 0, flags = 0;
+    for (int c = 0; c < n_classes; c++) {
+        seg_fp += res[c].seg_fp;
+        seg_fn += res[c].seg_fn;
+        flags |= res[c].flags;
+    }
+    const int st = flags & 2 ? REFUSED : (flags & 1 ? DOUBT : SCORED);
+    sdi[0] = st == SCORED ? (seg_fp < seg_fn ? seg_fp : seg_fn) : 0;
+    sdi[1] = st == SCORED && seg_fn > seg_fp ? seg_fn - seg_fp : 0;
+    sdi[2] = st == SCORED && seg_fp > seg_fn ? seg_fp - seg_fn : 0;
+    *status = st;
+}
+
+// One class of a segment of status `st`: the five independent counters and the class's share of total_DE, its slot averages added
+// from 0.0 in the order score_class left them in avg[] -- what SeldMetrics2022 adds to total_DE[c] for the segment alone.
+SCORE_HD void class_record2022(const ClassResult *res, int st, int *counters, double *class_de)
+{
+#if defined(__HIPCC__)
+#pragma clang fp contract(off)
+#endif
+    double total = 0.0;
+    for (int k = 0; k < res->n_avg; k++) total += res->avg[k];
+    const bool scored = st == SCORED;
+    counters[K_TP] = scored ? res->counters[C_TP] : 0;
+    counters[K_NREF] = scored ? res->counters[C_NREF] : 0;
+    counters[K_DE_TP] = scored ? res->counters[C_DE_TP] : 0;
+    counters[K_DE_FP] = scored ? res->counters[C_DE_FP] : 0;
+    counters[K_DE_FN] = scored ? res->counters[C_DE_FN] : 0;
+    *class_de = scored ? total : 0.0;
+}
+
+// The per-class record of one segment: class_counters [n_classes][5], class_de [n_classes], sdi [3] and the status (the kernel
+// gives class_record2022 a thread per class; this is the same two statements in a row)
+SCORE_HD void segment_record2022(const ClassResult *res, int n_classes, int *class_counters, double *class_de, int *sdi, int *status)
+{
+    segment_sdi2022(res, n_classes, sdi, status);
+    for (int c = 0; c < n_classes; c++) class_record2022(res + c, *status, class_counters + c * N_CLASS_COUNTERS, class_de + c);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
