@@ -369,6 +369,34 @@ int salsa_nn_tta_variant(const float *d_in, int64_t in_batch_stride, int64_t in_
 int salsa_nn_tta_merge(const float *d_prob_slab, const float *d_xyz_slab, int n_models, const int *variant_ids, int n_variants, int kind,
                        int batch, int label_frames, int n_classes, float *d_prob_out, float *d_xyz_out, void *hip_stream);
 
+/* Merging Multi-ACCDOA forwards of one clip after their tracks are aligned (track_merge 'align'; DESIGN.md section 9u;
+ * salsa_amd/csrc/track_align.hip, statements in track_align.h).  C = n_real_classes, rows of 9 C vector columns (component (axis a,
+ * track n, class c) at column (3 a + n) C + c) and 3 C activity columns (n C + c), float32 contiguous.  The tracks of a (row, class)
+ * cell are an unordered set: an incoming cell V is permuted onto an anchor cell R by the candidate pi (012 021 102 120 201 210, the
+ * k = 3 table of salsa_nn_adpit_loss) of least cost sum_n sum_a (R[n][a] - V[pi(n)][a])^2 -- one running float64 sum, tracks outer,
+ * axes inner, no fma; a later candidate wins only when strictly smaller, so ties keep the lower index and a NaN cost keeps candidate 0.
+ *
+ * salsa_nn_tta_merge_multi: the N = n_models * n_variants slabs d_xyz_slab [N][batch][label_frames][9 C], ordered and un-swapped as
+ * salsa_nn_tta_merge's (per column, so per track).  Slab 0 is the anchor; every later slab is aligned to slab 0 alone; the permuted
+ * vectors are added in float32 in slab order starting from slab 0 and divided once by float(N), correctly rounded.  d_xyz_out
+ * [batch][label_frames][9 C]; d_act_out [..][3 C] = the lengths of the merged vectors as salsa_nn_accdoa_sed forms them; d_perm_out,
+ * when not NULL, [N][batch][label_frames][C] int32 receives the chosen candidates (0 for slab 0).  variant_ids is a HOST array.
+ *
+ * salsa_nn_chunk_merge_multi: chunk outputs d_act [n_files][n_chunks][chunk_len][3 C] and d_xyz [..][9 C] -> file outputs d_file_act
+ * [n_files][n_frames][3 C] and d_file_xyz [..][9 C], what salsa_nn_seld_decode_multi takes.  The walk is salsa_nn_seld_decode's (same
+ * starts, leftover chunk and trimming), per cell: chunk 0 and the frames of a chunk behind its first chunk_len - chunk_hop overwrite;
+ * otherwise the fresh cell is aligned to the running one and v = (v + fresh[pi]) / 2.0f per component, the three activities with the
+ * same pi.  With chunk_hop == chunk_len or one chunk no arithmetic is done: plain placement.
+ *
+ * One launch each, no atomics, no scratch: bit-reproducible, and a clip's result does not depend on its batch.  Both return 0; -1,
+ * before any device call and with the reason in salsa_last_error, for a NULL required pointer, an unknown kind, a variant id outside
+ * [0, V), N < 1 or more than 16 variant ids, a count below 1, a slab, chunk or output array beyond int32 indexing, n_chunks different
+ * from the number of starts, or chunk_hop > chunk_len or chunk_len > n_frames with more than one chunk; -6 when the launch fails. */
+int salsa_nn_tta_merge_multi(const float *d_xyz_slab, int n_models, const int *variant_ids, int n_variants, int kind, int batch,
+                             int label_frames, int n_real_classes, float *d_xyz_out, float *d_act_out, int *d_perm_out, void *hip_stream);
+int salsa_nn_chunk_merge_multi(const float *d_act, const float *d_xyz, int n_files, int n_chunks, int chunk_len, int chunk_hop,
+                               int n_frames, int n_real_classes, float *d_file_act, float *d_file_xyz, void *hip_stream);
+
 /* The decoder's frequency mean (reference models/decoders.py: x.mean(dim=3) then (B, C, T) -> (B, T, C)) in one pass:
  * x bf16 channels-last [N][H][W][C] -> float32 y [H][N][C] (time_major != 0: the GRU scans' order) or [N][H][C]; C % 8 == 0.
  * _bwd: dx[n][h][w][c] = g[row(n, h)][c] / W, bf16 channels-last. */

@@ -130,6 +130,38 @@ def decode_multi_rows(act, xyz, n_frames: int = 600, sed_threshold: float = 0.5,
     return rows, counts
 
 
+def chunk_merge_multi(act, xyz, chunk_len: int, chunk_hop: int, n_frames: int = 600, n_classes: int = 12):
+    """The chunk combine of track_merge='align' on the device: Multi-ACCDOA chunk outputs act (n_files, n_chunks,
+    chunk_len, 3 C) and xyz (.., 9 C), CUDA float32 at the label rate, chunk_len / chunk_hop in label frames -> file outputs
+    (n_files, n_frames, 3 C) and (.., 9 C), decode_multi_rows' input: overlapping frames are averaged pairwise in chunk order after
+    the fresh chunk's tracks are aligned, cell by cell, to the running value.  One salsa_nn_chunk_merge_multi launch on the current
+    stream, no synchronisation; CPU tensors are refused (the host function is postprocess.combine_chunks_multi, whose result this
+    equals bit for bit)."""
+    import torch
+    if act.dim() != 4 or xyz.dim() != 4 or act.shape[:3] != xyz.shape[:3] or act.shape[3] != 3 * n_classes or xyz.shape[3] != 9 * n_classes:
+        raise ValueError('chunk_merge_multi: act %s / xyz %s are not (files, chunks, frames, %d) / (.., %d)'
+                         % (tuple(act.shape), tuple(xyz.shape), 3 * n_classes, 9 * n_classes))
+    if not (act.is_cuda and xyz.is_cuda and act.device == xyz.device and act.dtype == torch.float32 and xyz.dtype == torch.float32):
+        raise ValueError('chunk_merge_multi takes float32 tensors on one CUDA device (the host path is postprocess.combine_chunks_multi)')
+    n_files, n_chunks, L = act.shape[:3]
+    if L != chunk_len:
+        raise ValueError('chunk_merge_multi: chunks of %d frames, chunk_len = %d' % (L, chunk_len))
+    if n_files == 0:
+        raise ValueError('chunk_merge_multi: no files')
+    act, xyz = act.contiguous(), xyz.contiguous()
+    dev = act.device
+    fa = torch.empty((n_files, n_frames, 3 * n_classes), dtype=torch.float32, device=dev)
+    fx = torch.empty((n_files, n_frames, 9 * n_classes), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().salsa_nn_chunk_merge_multi(_ptr(act), _ptr(xyz), n_files, n_chunks, chunk_len, chunk_hop, n_frames, n_classes,
+                                                    _ptr(fa), _ptr(fx), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == _lib.E_INVAL:
+        raise ValueError('salsa_nn_chunk_merge_multi refused: ' + _lib.last_error())
+    if rc:
+        raise RuntimeError('salsa_nn_chunk_merge_multi failed (%d)' % rc)
+    return fa, fx
+
+
 def rows_to_list(rows, counts, eval_version: str = '2021', as_array: bool = False) -> list:
     """decode_dcase_rows' rows (n_files, capacity, 4) and counts (n_files,) ON THE HOST (numpy arrays or CPU tensors) -> per file
     exactly what to_dcase_rows returns: [frame, class, 0, azimuth, elevation] rows for eval_version '2021' and '2022' (the zero track column

@@ -43,13 +43,15 @@ def _ckpt_files(d):
 
 
 def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, combine_method='mean', sed_threshold=0.3,
-             doa_threshold=20, eval_version='2021', sub_batch=8, return_rows=False, tta=None, unify_deg=15.0):
+             doa_threshold=20, eval_version='2021', sub_batch=8, return_rows=False, tta=None, unify_deg=15.0, track_merge=None):
     """One validation pass (models/seld_models.py:96-108 + interfaces.py:163-180): every clip of ``val_bank`` through
     infer_pipelined(Trainer.infer) in test chunks, rows against ``val_gt`` (per clip a list of rows, metrics.load_dcase_csv).  On the
     GPU the rows are decoded and scored on the device (DeviceSeldScore / DeviceSeldScore2020 / DeviceSeldScore2022 by eval_version), on
     the CPU by the host classes.  eval_version '2022': valF1, valLE, valLR and valSeld are the class-wise (macro) figures of SeldMetrics2022.  tta = (audio_format, feature_type) or a tta.TtaForward: the forward is Trainer.infer under test-time augmentation (all
     channel-swap variants, the trainer's n_classes and output_format); None: Trainer.infer itself.  A 'multi_accdoa' trainer is
-    decoded with track unification (infer_pipelined's output_format / unify_deg): whole clips or non-overlapping chunks, no tta.
+    decoded with track unification (infer_pipelined's output_format / unify_deg): whole clips or non-overlapping chunks, no tta --
+    unless track_merge='align' (DESIGN.md section 9u), under which overlapping chunks and tta=, alone or together, are merged after
+    their tracks are aligned cell by cell.
     -> dict valER valF1 valLE valLR valSeld (+ the scorer under 'scorer', and 'rows' when asked)."""
     from .infer import infer_pipelined
     from .tta import wrap_forward
@@ -67,10 +69,10 @@ def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, comb
     n_label = val_bank.clip_len[0] // val_bank.upsample
     nc, rate = trainer.n_classes, val_bank.label_rate
     on_gpu = trainer.device.type == 'cuda'
-    forward = wrap_forward(trainer.infer, tta, nc, trainer.output_format)
+    forward = wrap_forward(trainer.infer, tta, nc, trainer.output_format, track_merge)
     kw = dict(sub_batch=sub_batch, sed_threshold=sed_threshold, n_label_frames=n_label, chunk_len=chunk_len, chunk_hop_len=chunk_hop_len,
               combine_method=combine_method, n_classes=nc, output_format=trainer.output_format, unify_deg=unify_deg,
-              eval_version='2020')       # (the ROW shape only: (frame, class, azimuth, elevation), what SeldMetrics.update reads)
+              track_merge=track_merge, eval_version='2020')       # (the ROW shape only: (frame, class, azimuth, elevation), what SeldMetrics.update reads)
     if on_gpu:
         scorer = device_cls(nc, doa_threshold, rate)
         gt_rows, gt_counts = gt_rows_to_device(val_gt, trainer.device)
@@ -131,15 +133,15 @@ def _load(path, trainer, loader):
 def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, max_epochs=50, epochs=None, milestones=MILESTONES,
         lrs=LRS, moms=MOMS, val_interval=1, train_fraction=1.0, audio_format='foa', feature_type='salsa', augment=True, seed=2021,
         mode='crossval', eval_version='2021', resume=False, chunk_len=None, chunk_hop_len=None, combine_method='mean',
-        sed_threshold=0.3, doa_threshold=20, val_sub_batch=8, loader=None, tta=None, unify_deg=15.0):
+        sed_threshold=0.3, doa_threshold=20, val_sub_batch=8, loader=None, tta=None, unify_deg=15.0, track_merge=None):
     """Train ``trainer`` for ``max_epochs`` epochs of ``bank`` (a finalized GpuFeatureBank).  The keywords are the YAML's keys
     (INTEGRATION.md has the table): batch_size = training.train_batch_size; milestones / lrs / moms = training.lr_scheduler.*;
     max_epochs, val_interval = training.*; train_fraction, n_classes (Trainer's) = data.*; eval_version ('2022': valSeld, and with it
     the best checkpoint and its name, is the class-wise macro seld_error of SeldMetrics2022); mode ('crossval': the best
     checkpoint by valSeld is kept, 'eval': the latest only).  ``epochs`` caps how many epochs THIS call runs (time-sliced jobs);
     ``resume`` continues from the lexicographically last file of <out_dir>/checkpoint (train.py:37-45; none there: from scratch).
-    val_bank / val_gt: the validation clips and their ground-truth rows; chunk_len .. sed_threshold, tta and unify_deg go to the
-    validation pass (validate).  The trainer's output_format, n_attn_layers, n_attn_heads and the five Conformer settings are stored in
+    val_bank / val_gt: the validation clips and their ground-truth rows; chunk_len .. sed_threshold, tta, unify_deg and track_merge go to the
+    validation pass (validate) and to nothing else: no checkpoint stores them.  The trainer's output_format, n_attn_layers, n_attn_heads and the five Conformer settings are stored in
     every checkpoint and checked on resume; a 'multi_accdoa' trainer takes a bank of trackwise labels (GpuFeatureBank(n_classes=3 C,
     label_format='trackwise')).
     -> the history: dict(steps=[epoch, step, lr, mom, loss, sed_loss, doa_loss per step], val=[dict per validated epoch],
@@ -151,6 +153,9 @@ def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, 
         raise ValueError('val_bank and val_gt come together')
     if val_bank is not None and eval_version not in ('2020', '2021', '2022'):     # (what validate refuses, before an epoch is spent)
         raise ValueError('Unknown eval_version {}'.format(eval_version))
+    if val_bank is not None:
+        from .tta import _check_track_merge
+        _check_track_merge(track_merge, trainer.output_format)
     if val_bank is not None and len(set(val_bank.clip_len)) != 1:
         raise ValueError('validation: clips of unequal length in the bank: %s frames' % sorted(set(val_bank.clip_len)))
     if loader is None:
@@ -183,7 +188,7 @@ def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, 
         val = None
         if val_bank is not None and (epoch + 1) % val_interval == 0:
             val = validate(trainer, val_bank, val_gt, chunk_len, chunk_hop_len, combine_method, sed_threshold, doa_threshold,
-                           eval_version, val_sub_batch, tta=tta, unify_deg=unify_deg)
+                           eval_version, val_sub_batch, tta=tta, unify_deg=unify_deg, track_merge=track_merge)
             val.pop('scorer')
             val['epoch'] = epoch
             history['val'].append(val)

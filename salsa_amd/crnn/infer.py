@@ -16,7 +16,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from ..distributed import shard_list
-from .postprocess import combine_chunks, multi_accdoa_rows, to_dcase_rows
+from .postprocess import combine_chunks, combine_chunks_multi, multi_accdoa_rows, to_dcase_rows
 
 
 def _forward_chunks(feat, forward, chunk_len, chunk_hop_len, chunk_batch, sub_batch, n_label_frames):
@@ -47,7 +47,8 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
                     as_array: bool = False, stamps: Optional[list] = None, chunk_len: Optional[int] = None,
                     chunk_hop_len: Optional[int] = None, decode: str = 'host', combine_method: str = 'mean',
                     eval_version: str = '2021', n_classes: int = 12, chunk_batch: Optional[int] = None,
-                    score: Optional[tuple] = None, tta=None, output_format: str = 'reg_xyz', unify_deg: float = 15.0) -> list:
+                    score: Optional[tuple] = None, tta=None, output_format: str = 'reg_xyz', unify_deg: float = 15.0,
+                    track_merge: Optional[str] = None) -> list:
     """featurize(lo, hi) -> feature tensor [hi - lo, 7, T, F] of items lo..hi-1 on the model's device; forward(features) ->
     (event probabilities [b, n_label_frames, 12], xyz [b, n_label_frames, 36]).  Returns the DCASE rows of every item, in
     item order.  The device is never idle waiting for the host: up to `depth` sub-batches are in flight.
@@ -77,19 +78,36 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
     (host) or decode.decode_multi_rows (device, one salsa_nn_seld_decode_multi launch) with tracks of a class closer than unify_deg
     degrees unified, so a class may hold several rows in a frame.  Whole clips, or test chunks with chunk_hop_len == chunk_len that
     tile n_label_frames exactly (reshaped to file level, no arithmetic).  The track order is not consistent between two forwards, so
-    averaging track n of one with track n of another is undefined: overlapping chunks and tta= raise ValueError.  score= works as
-    before (an accumulator of C classes).  Any other output_format: forward's outputs are taken as they are."""
+    averaging track n of one with track n of another is undefined: by default (track_merge None) overlapping chunks and tta= raise
+    ValueError.  score= works as before (an accumulator of C classes).  Any other output_format: forward's outputs are taken as they
+    are.
+
+    track_merge = 'align' ('multi_accdoa' only, anything else raises ValueError): two forwards are merged after
+    the tracks of one are permuted, (frame, class) cell by cell, onto the other's by the permutation of least squared distance.
+    tta= wraps forward in a TtaForward(output_format='multi_accdoa', track_merge='align'); several chunks per file, overlapping or
+    not, go through postprocess.combine_chunks_multi (host) or decode.chunk_merge_multi (device, one salsa_nn_chunk_merge_multi
+    launch) and then the decoders above; both together compose (the wrapped forward merges per chunk batch, then the chunks are
+    combined).  combine_method 'gmean' with overlapping chunks raises ValueError: a geometric mean of signed components is not
+    defined.  With chunk_hop_len == chunk_len, or one chunk, the rows are those of the reshape path."""
     import torch
     assert depth >= 1 and sub_batch >= 1
     if output_format not in ('reg_xyz', 'accdoa', 'multi_accdoa'):
         raise ValueError('invalid output_format %r' % (output_format,))
     multi = output_format == 'multi_accdoa'
-    if multi and tta is not None:
-        raise ValueError("output_format 'multi_accdoa' has no test-time augmentation: the track order differs between forwards, so "
-                         'the variants cannot be averaged track by track')
-    if multi and chunk_len is not None and chunk_hop_len is not None and chunk_hop_len < chunk_len:
+    from .tta import _check_track_merge
+    _check_track_merge(track_merge, output_format)
+    align = track_merge == 'align'
+    overlapping = chunk_len is not None and chunk_hop_len is not None and chunk_hop_len < chunk_len
+    if multi and tta is not None and not align:
+        raise ValueError("output_format 'multi_accdoa' has no test-time augmentation by default: the track order differs between "
+                         "forwards, so the variants cannot be averaged track by track (track_merge='align' aligns them first)")
+    if multi and overlapping and not align:
         raise ValueError("output_format 'multi_accdoa' takes whole clips or non-overlapping test chunks (chunk_hop_len %d < chunk_len %d): "
-                         'the track order differs between forwards, so overlaps cannot be averaged' % (chunk_hop_len, chunk_len))
+                         "the track order differs between forwards, so overlaps cannot be averaged (track_merge='align' aligns them "
+                         'first)' % (chunk_hop_len, chunk_len))
+    if align and overlapping and combine_method == 'gmean':
+        raise ValueError("combine_method 'gmean' with overlapping 'multi_accdoa' chunks: a geometric mean of signed vector components "
+                         'is not defined')
     if decode not in ('host', 'device'):
         raise ValueError("decode must be 'host' or 'device', not {!r}".format(decode))
     if combine_method not in ('mean', 'gmean'):
@@ -106,7 +124,7 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
             raise ValueError('score=: ground truth of %d files for %d items' % (gt_rows.shape[0], n_items))
     if tta is not None:
         from .tta import wrap_forward
-        forward = wrap_forward(forward, tta, n_classes)
+        forward = wrap_forward(forward, tta, n_classes, output_format, track_merge) if align else wrap_forward(forward, tta, n_classes)
     results = [None] * n_items
     slots: Dict[int, dict] = {}
     pending = collections.deque()
@@ -123,8 +141,11 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
         else:
             p, d = s['p'][:hi - lo].numpy(), s['d'][:hi - lo].numpy()
             for i in range(lo, hi):
-                if multi:                                # file-level outputs already (chunks were reshaped, not combined)
-                    results[i] = multi_accdoa_rows(p[i - lo], d[i - lo], sed_threshold=sed_threshold, unify_deg=unify_deg,
+                if multi:                                # file-level outputs already (chunks were reshaped, not combined) ...
+                    pi, di = p[i - lo], d[i - lo]
+                    if pi.ndim == 3:                     # ... or, under track_merge='align', a file's chunks: combined here
+                        pi, di = combine_chunks_multi(pi, di, lab_len, lab_hop, n_frames=n_label_frames, n_classes=n_classes)
+                    results[i] = multi_accdoa_rows(pi, di, sed_threshold=sed_threshold, unify_deg=unify_deg,
                                                    n_classes=n_classes, max_nframes_per_file=n_label_frames, eval_version=eval_version,
                                                    as_array=as_array)
                     continue
@@ -150,12 +171,19 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
             lab_len = lab_hop = n_label_frames
         on_gpu = prob.is_cuda
         if multi:
-            if prob.dim() == 4:                          # chunks that tile the file: (files, n_chunks, Lc, .) -> (files, n_chunks Lc, .)
+            if prob.dim() == 4 and align and prob.shape[1] > 1:      # several chunks: the aligned combine (device: here; host: in finish)
+                if prob.shape[2:] != (lab_len, 3 * n_classes) or xyz.shape[2:] != (lab_len, 9 * n_classes):
+                    raise ValueError("output_format 'multi_accdoa': forward gave %s / %s, expected (b, %d, %d) / (.., %d) per chunk"
+                                     % (tuple(prob.shape[2:]), tuple(xyz.shape[2:]), lab_len, 3 * n_classes, 9 * n_classes))
+                if decode == 'device':
+                    from .decode import chunk_merge_multi
+                    prob, xyz = chunk_merge_multi(prob, xyz, lab_len, lab_hop, n_frames=n_label_frames, n_classes=n_classes)
+            elif prob.dim() == 4:                        # chunks that tile the file: (files, n_chunks, Lc, .) -> (files, n_chunks Lc, .)
                 if prob.shape[1] > 1 and prob.shape[1] * lab_len != n_label_frames:
                     raise ValueError("output_format 'multi_accdoa': %d chunks of %d label frames do not tile %d label frames exactly"
                                      % (prob.shape[1], lab_len, n_label_frames))
                 prob, xyz = prob.reshape(prob.shape[0], -1, prob.shape[3]), xyz.reshape(xyz.shape[0], -1, xyz.shape[3])
-            if prob.shape[1] < n_label_frames or prob.shape[2] != 3 * n_classes or xyz.shape[2] != 9 * n_classes:
+            if prob.dim() == 3 and (prob.shape[1] < n_label_frames or prob.shape[2] != 3 * n_classes or xyz.shape[2] != 9 * n_classes):
                 raise ValueError("output_format 'multi_accdoa': forward gave %s / %s, expected (b, >= %d, %d) / (.., %d)"
                                  % (tuple(prob.shape), tuple(xyz.shape), n_label_frames, 3 * n_classes, 9 * n_classes))
         if multi and decode == 'device':
@@ -202,7 +230,7 @@ def infer_clips_sharded(names: Sequence[str], featurize: Callable[[List[str]], '
                         stamps: Optional[list] = None, chunk_len: Optional[int] = None, chunk_hop_len: Optional[int] = None,
                         decode: str = 'host', combine_method: str = 'mean', eval_version: str = '2021', n_classes: int = 12,
                         chunk_batch: Optional[int] = None, score: Optional[tuple] = None, tta=None, output_format: str = 'reg_xyz',
-                        unify_deg: float = 15.0) -> Dict[str, list]:
+                        unify_deg: float = 15.0, track_merge: Optional[str] = None) -> Dict[str, list]:
     """names: all clip names (any order; sharded over the SORTED list).  featurize(list of names) -> feature tensor
     [b, 7, T, F] on the model's device (e.g. SalsaExtractor.extract of the clips' audio with the scaler attached, cropped
     to 8 * n_label_frames frames); forward(features) -> (event probabilities [b, n_label_frames, 12], xyz [b, .., 36]), e.g.
@@ -210,13 +238,13 @@ def infer_clips_sharded(names: Sequence[str], featurize: Callable[[List[str]], '
     chunk_len, chunk_hop_len, decode, combine_method, eval_version, n_classes, chunk_batch: infer_pipelined's test-chunk and
     device-decoding options, handed through.  score = (gt_rows, gt_counts, accumulator): infer_pipelined's, for THIS rank's shard
     (the ground truth of shard_list(sorted(names), rank, world), in that order); every rank's accumulator holds its shard's score,
-    to be combined with DeviceSeldScore.merge.  tta, output_format, unify_deg: infer_pipelined's, handed through."""
+    to be combined with DeviceSeldScore.merge.  tta, output_format, unify_deg, track_merge: infer_pipelined's, handed through."""
     mine = shard_list(sorted(names), rank, world)
     rows = infer_pipelined(len(mine), lambda lo, hi: featurize(mine[lo:hi]), forward, sub_batch=sub_batch, depth=depth,
                            sed_threshold=sed_threshold, n_label_frames=n_label_frames, stamps=stamps, chunk_len=chunk_len,
                            chunk_hop_len=chunk_hop_len, decode=decode, combine_method=combine_method, eval_version=eval_version,
                            n_classes=n_classes, chunk_batch=chunk_batch, score=score, tta=tta, output_format=output_format,
-                           unify_deg=unify_deg)
+                           unify_deg=unify_deg, track_merge=track_merge)
     out = dict(zip(mine, rows))
     if gather and world > 1:
         import torch.distributed as dist

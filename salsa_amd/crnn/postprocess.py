@@ -116,6 +116,68 @@ def multi_accdoa_cells(act: np.ndarray, xyz: np.ndarray, sed_threshold: float, c
     return n_out, out, flags
 
 
+TRACK_PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))     # csrc/multi_accdoa.h, source_of(3, cand, n)
+
+
+def align_cells(anchor: np.ndarray, fresh: np.ndarray) -> np.ndarray:
+    """csrc/track_align.h's align_cell in numpy, statement for statement: anchor, fresh (..., track, axis)
+    float32 -> the candidate (..., ) int32 in 0 .. 5 whose permutation TRACK_PERMS[cand] of fresh's tracks is closest to anchor.  The
+    cost is one running float64 sum, tracks outer and axes inner; a later candidate wins only when strictly smaller (explicit walk,
+    not argmin: a NaN cost keeps candidate 0, a tie the lower index)."""
+    R, V = np.asarray(anchor, np.float32).astype(np.float64), np.asarray(fresh, np.float32).astype(np.float64)
+    chosen, best = np.zeros(R.shape[:-2], dtype=np.int32), None
+    with np.errstate(invalid='ignore', over='ignore'):
+        for cand, perm in enumerate(TRACK_PERMS):
+            e = np.zeros(R.shape[:-2], dtype=np.float64)
+            for n in range(3):
+                for a in range(3):
+                    d = R[..., n, a] - V[..., perm[n], a]
+                    e = e + d * d
+            if cand == 0:
+                best = e
+            else:
+                less = e < best
+                best, chosen = np.where(less, e, best), np.where(less, np.int32(cand), chosen)
+    return chosen
+
+
+def combine_chunks_multi(act: np.ndarray, xyz: np.ndarray, chunk_len: int, chunk_hop_len: int, n_frames: int = 600,
+                         n_classes: int = 12):
+    """combine_chunks for output_format 'multi_accdoa' under track_merge='align' (the host twin of
+    salsa_nn_chunk_merge_multi and what decode='host' runs): one file's chunk outputs act (n_chunks, chunk_len, 3 C) and xyz
+    (n_chunks, chunk_len, 9 C) at the label rate -> file outputs (n_frames, 3 C), (n_frames, 9 C) float32, multi_accdoa_rows' input.
+    combine_chunks' walk per (frame, class) cell: chunk 0 is copied; of chunk i >= 1 the first chunk_len - chunk_hop_len frames are
+    aligned to the running value (align_cells on the vectors) and become (old + new[pi]) / 2, activities with the same pi, and the
+    rest overwrite.  One chunk at least as long as the file is placed and trimmed."""
+    from .decode import chunk_starts
+    C = n_classes
+    act, xyz = np.asarray(act, np.float32), np.asarray(xyz, np.float32)
+    n = act.shape[0]
+    if act.shape != (n, chunk_len, 3 * C) or xyz.shape != (n, chunk_len, 9 * C):
+        raise ValueError('combine_chunks_multi: act %s / xyz %s are not (chunks, %d, %d) / (.., %d)' % (act.shape, xyz.shape, chunk_len, 3 * C, 9 * C))
+    starts = chunk_starts(n_frames, chunk_len, chunk_hop_len)
+    if len(starts) != n or (n > 1 and chunk_hop_len > chunk_len):
+        raise ValueError('combine_chunks_multi: %d chunks of %d frames at hop %d for %d frames (expected %d chunks)'
+                         % (n, chunk_len, chunk_hop_len, n_frames, len(starts)))
+    if n == 1:
+        return act[0, :n_frames].copy(), xyz[0, :n_frames].copy()
+    a = act.reshape(n, chunk_len, 3, C).transpose(0, 1, 3, 2)                          # (chunk, frame, class, track)
+    v = xyz.reshape(n, chunk_len, 3, 3, C).transpose(0, 1, 4, 3, 2)                    # (chunk, frame, class, track, axis)
+    out_a, out_v = np.zeros((n_frames, C, 3), np.float32), np.zeros((n_frames, C, 3, 3), np.float32)
+    overlap, perms = chunk_len - chunk_hop_len, np.asarray(TRACK_PERMS)
+    for i, s in enumerate(starts):
+        if i == 0:
+            out_a[s:s + chunk_len], out_v[s:s + chunk_len] = a[i], v[i]
+            continue
+        src = perms[align_cells(out_v[s:s + overlap], v[i, :overlap])]                 # (frame, class, track): the source of track n
+        with np.errstate(invalid='ignore', over='ignore'):
+            out_v[s:s + overlap] = (out_v[s:s + overlap] + np.take_along_axis(v[i, :overlap], src[..., None], axis=2)) / np.float32(2.0)
+            out_a[s:s + overlap] = (out_a[s:s + overlap] + np.take_along_axis(a[i, :overlap], src, axis=2)) / np.float32(2.0)
+        out_a[s + overlap:s + chunk_len], out_v[s + overlap:s + chunk_len] = a[i, overlap:], v[i, overlap:]
+    return (np.ascontiguousarray(out_a.transpose(0, 2, 1)).reshape(n_frames, 3 * C),
+            np.ascontiguousarray(out_v.transpose(0, 3, 2, 1)).reshape(n_frames, 9 * C))
+
+
 def multi_accdoa_rows(act: np.ndarray, xyz: np.ndarray, sed_threshold: float = 0.5, unify_deg: float = 15.0, n_classes: int = 12,
                       max_nframes_per_file: int = 600, eval_version: str = '2021', as_array: bool = False):
     """The host decoder of output_format 'multi_accdoa' (what decode='host' runs and the yardstick of

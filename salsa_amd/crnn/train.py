@@ -165,11 +165,16 @@ class Trainer:
     def infer_tta(self, x, audio_format=None, feature_type='salsa', variants='all'):
         """infer under test-time augmentation (tta.TtaForward over this trainer's infer, output_format and n_classes): the merged SED
         activities and xyz of the selected channel-swap variants of x.  audio_format None: 'foa'.  The wrapper, with its buffers, is
-        kept per (audio_format, feature_type, variants)."""
+        kept per (audio_format, feature_type, variants, track_merge).  A 'multi_accdoa' trainer is refused unless its ``track_merge``
+        attribute is 'align' (an attribute because this method's signature is pinned): then the variants are
+        merged after their tracks are aligned cell by cell, and the result is the merged track activities and xyz."""
         from .tta import TtaForward
-        key = (audio_format or 'foa', feature_type, variants if isinstance(variants, str) or variants is None else tuple(variants))
+        key = (audio_format or 'foa', feature_type, variants if isinstance(variants, str) or variants is None else tuple(variants),
+               self.track_merge)
         cache = self.__dict__.setdefault('_tta', {})
         if key not in cache:
             cache[key] = TtaForward(self.infer, key[0], feature_type, variants=variants, n_classes=self.n_classes,
-                                    output_format=self.output_format)
+                                    output_format=self.output_format, track_merge=self.track_merge)
         return cache[key](x)
+
+    track_merge = None      # None | 'align': how infer_tta merges the forwards of a 'multi_accdoa' trainer (set it on the instance)

@@ -11,8 +11,13 @@ numbers for both ("FOA SALSA w/ TTA", the DCASE 2021 ensemble) but ships code fo
              first, and divided once by float(N) (correctly rounded).  prob and xyz alike; with output_format 'accdoa' the merged
              activity is nn_ops.accdoa_sed(merged xyz), not the mean of the lengths.
 
-CUDA float32 tensors go through salsa_nn_tta_variant / salsa_nn_tta_merge (csrc/tta.hip); CPU tensors, and everything under
-SALSA_HIP_TTA=0, through the torch operators."""
+  multi      output_format 'multi_accdoa' holds three unordered tracks per class, so its forwards are merged only under
+             track_merge='align' (tta_merge_multi): every slab is un-swapped, every slab after the first is
+             permuted, (clip, frame, class) cell by cell, onto slab 0 by the candidate of least squared distance (ADPIT's six
+             permutations and cost walk), then the same fixed-order sum and one division; the activities are the merged lengths.
+
+CUDA float32 tensors go through salsa_nn_tta_variant / salsa_nn_tta_merge / salsa_nn_tta_merge_multi (csrc/tta.hip,
+csrc/track_align.hip); CPU tensors, and everything under SALSA_HIP_TTA=0, through the torch operators."""
 import ctypes as C
 import os
 
@@ -156,6 +161,88 @@ def tta_merge(prob_slab, xyz_slab, n_models, variant_ids, kind, n_classes: int =
     return prob, xyz
 
 
+def _check_track_merge(track_merge, output_format):
+    if track_merge not in (None, 'align'):
+        raise ValueError("track_merge must be None or 'align', not {!r}".format(track_merge))
+    if track_merge == 'align' and output_format != 'multi_accdoa':
+        raise ValueError("track_merge='align' aligns the tracks of output_format 'multi_accdoa'; %r has none" % (output_format,))
+
+
+def _align_torch(R, V):
+    """csrc/track_align.h's align_cell on (B, L, axis, track, C) float32 tensors -> candidates (B, L, C) int64: sequential float64
+    adds, tracks outer and axes inner, and an explicit strict-less walk over the six candidates (argmin's NaN rule differs)"""
+    from .postprocess import TRACK_PERMS
+    R, V = R.double(), V.double()
+    chosen = best = None
+    for cand, perm in enumerate(TRACK_PERMS):
+        e = torch.zeros(R.shape[:2] + R.shape[4:], dtype=torch.float64, device=R.device)
+        for n in range(3):
+            for a in range(3):
+                d = R[:, :, a, n] - V[:, :, a, perm[n]]
+                e = e + d * d
+        if cand == 0:
+            best, chosen = e, torch.zeros(e.shape, dtype=torch.long, device=R.device)
+        else:
+            less = e < best
+            best, chosen = torch.where(less, e, best), torch.where(less, torch.full_like(chosen, cand), chosen)
+    return chosen
+
+
+def _merge_multi_torch(xyz_slab, n_models, ids, kind, n_classes):
+    """tta_merge_multi's rules with torch operators: un-swap (per column, so per track), align every later slab to slab 0,
+    sequential float32 adds in slab order from slab 0, one true division by a tensor -> (xyz (B, L, 9 C), perm (N, B, L, C) int32)"""
+    from .postprocess import TRACK_PERMS
+    fmt = 'foa' if kind == 'foa' else 'mic'
+    N, B, L, _ = xyz_slab.shape
+    table = torch.tensor(TRACK_PERMS, dtype=torch.long, device=xyz_slab.device)
+    perm = torch.zeros((N, B, L, n_classes), dtype=torch.int32, device=xyz_slab.device)
+    R = acc = None
+    for k in range(N):
+        m = torch.tensor(variant_bits(kind, ids[k % len(ids)]), dtype=torch.long).expand(B, -1)
+        V = unswap_targets(xyz_slab[k], m, fmt, 3 * n_classes).reshape(B, L, 3, 3, n_classes)       # (B, L, axis, track, C)
+        if k == 0:
+            R = acc = V
+            continue
+        cand = _align_torch(R, V)
+        perm[k] = cand.to(torch.int32)
+        src = table[cand].permute(0, 1, 3, 2)[:, :, None].expand(B, L, 3, 3, n_classes)             # the source of (axis, track n, c)
+        acc = acc + torch.gather(V, 3, src)
+    div = torch.full((), float(N), dtype=torch.float32, device=xyz_slab.device)
+    return (acc / div).reshape(B, L, 9 * n_classes), perm
+
+
+def tta_merge_multi(xyz_slab, n_models, variant_ids, kind, n_classes: int = 12, return_perm: bool = False, _ids_c=None):
+    """The merge of output_format 'multi_accdoa' under track_merge='align' (DESIGN.md section 9u): xyz_slab (N, B, L, 9 C) float32,
+    N = n_models * len(variant_ids) ordered as tta_merge's, C = n_classes REAL classes -> (act (B, L, 3 C), xyz (B, L, 9 C)), and with
+    return_perm the chosen candidates (N, B, L, C) int32 (postprocess.TRACK_PERMS[cand][n] = the track of the slab that was added to
+    track n; 0 for slab 0).  Slab 0 is the anchor; every later slab is aligned to it alone.  act = nn_ops.accdoa_sed(xyz, 3 C).  CUDA:
+    one salsa_nn_tta_merge_multi launch on the current stream; CPU (and SALSA_HIP_TTA=0): the torch restatement, the same bits."""
+    ids = _ids(_kind(kind), variant_ids)
+    N = n_models * len(ids)
+    if n_models < 1 or xyz_slab.dim() != 4 or xyz_slab.shape[0] != N or xyz_slab.shape[3] != 9 * n_classes:
+        raise ValueError('slab %s for %d models x %d variants of %d classes with three tracks' % (tuple(xyz_slab.shape), n_models, len(ids), n_classes))
+    if not (USE_HIP_TTA and xyz_slab.is_cuda and xyz_slab.numel() > 0):
+        from .nn_ops import accdoa_sed
+        xyz, perm = _merge_multi_torch(xyz_slab.float(), n_models, ids, kind, n_classes)
+        act = accdoa_sed(xyz, 3 * n_classes)
+        return (act, xyz, perm) if return_perm else (act, xyz)
+    if xyz_slab.dtype != torch.float32 or not xyz_slab.is_contiguous():
+        raise ValueError('the slab is a dense float32 tensor')
+    _, B, L, _ = xyz_slab.shape
+    dev = xyz_slab.device
+    act = torch.empty((B, L, 3 * n_classes), dtype=torch.float32, device=dev)
+    xyz = torch.empty((B, L, 9 * n_classes), dtype=torch.float32, device=dev)
+    perm = torch.empty((N, B, L, n_classes), dtype=torch.int32, device=dev) if return_perm else None
+    ids_c = _ids_c if _ids_c is not None else (C.c_int * len(ids))(*ids)
+    with torch.cuda.device(dev):
+        rc = _lib.load().salsa_nn_tta_merge_multi(C.c_void_p(xyz_slab.data_ptr()), n_models, ids_c, len(ids), KIND[kind], B, L, n_classes,
+                                                  C.c_void_p(xyz.data_ptr()), C.c_void_p(act.data_ptr()),
+                                                  C.c_void_p(perm.data_ptr()) if return_perm else None, _stream(xyz_slab))
+    if rc:
+        raise RuntimeError('salsa_nn_tta_merge_multi failed: ' + _lib.last_error())
+    return (act, xyz, perm) if return_perm else (act, xyz)
+
+
 class TtaForward:
     """A forward that runs ``forwards`` on every selected variant of its input and returns the merged (prob, xyz), with the shapes
     and dtypes of one forward call -- so it goes wherever a forward goes (infer_pipelined, with chunks, either decode, scoring,
@@ -164,19 +251,25 @@ class TtaForward:
     A variant is formed once and fed to every model.  One variant buffer and one pair of slabs are kept and reused across calls
     (reallocated only to grow); every forward output is COPIED into its slab, so a forward may reuse its output storage.  All
     work is issued on the current stream; nothing waits for the device.  The variant list is fixed at construction and travels
-    to the merge kernel in its arguments."""
+    to the merge kernel in its arguments.
+
+    output_format 'multi_accdoa' is refused unless track_merge='align': then the forwards return the track activities (b, frames,
+    3 C) and xyz (b, frames, 9 C) of n_classes = C real classes, only an xyz slab is kept, the tracks are aligned cell by cell before
+    the sum (tta_merge_multi) and the result is (accdoa_sed(xyz, 3 C), xyz)."""
 
     def __init__(self, forwards, audio_format, feature_type='salsa', variants='all', n_classes: int = 12,
-                 output_format: str = 'reg_xyz'):
+                 output_format: str = 'reg_xyz', track_merge=None):
         self.kind = augment.recipe(audio_format, feature_type)[0]
         self.forwards = [forwards] if callable(forwards) else list(forwards)
         if not self.forwards or not all(callable(f) for f in self.forwards):
             raise ValueError('forwards: one callable or a non-empty sequence of callables')
-        if output_format == 'multi_accdoa':
-            raise ValueError("output_format 'multi_accdoa' has no test-time augmentation: the track order differs between forwards, so "
-                             'the variants cannot be averaged track by track (DESIGN.md section 9i)')
-        if output_format not in ('reg_xyz', 'accdoa'):
+        if output_format not in ('reg_xyz', 'accdoa', 'multi_accdoa'):
             raise ValueError('invalid output_format %r' % (output_format,))
+        _check_track_merge(track_merge, output_format)
+        if output_format == 'multi_accdoa' and track_merge is None:
+            raise ValueError("output_format 'multi_accdoa' has no test-time augmentation by default: the track order differs between "
+                             "forwards, so the variants cannot be averaged track by track; track_merge='align' aligns them first "
+                             '(DESIGN.md sections 9i, 9u)')
         if isinstance(variants, str):
             if variants != 'all':
                 raise ValueError("variants: 'all', None, () or a list of ids, not {!r}".format(variants))
@@ -185,7 +278,7 @@ class TtaForward:
             variants = (0,)
         self.variant_ids = _ids(self.kind, variants)
         self._ids_c = (C.c_int * len(self.variant_ids))(*self.variant_ids)
-        self.n_classes, self.output_format = n_classes, output_format
+        self.n_classes, self.output_format, self.track_merge = n_classes, output_format, track_merge
         self._buf = self._prob = self._xyz = None
 
     @staticmethod
@@ -204,21 +297,28 @@ class TtaForward:
         _check_features(features, self.kind)
         nv, nc = len(self.variant_ids), self.n_classes
         N = len(self.forwards) * nv
+        multi = self.output_format == 'multi_accdoa'
+        w = 3 if multi else 1                                                # columns per real class: the tracks
         prob_slab = xyz_slab = p = d = None
         for vi, v in enumerate(self.variant_ids):
             xv = self._variant(features, v)
             for mi, forward in enumerate(self.forwards):
                 p, d = forward(xv)
                 if prob_slab is None:
-                    if p.dim() != 3 or d.dim() != 3 or p.shape[2] != nc or d.shape[2] != 3 * nc or p.shape[:2] != d.shape[:2]:
+                    if p.dim() != 3 or d.dim() != 3 or p.shape[2] != w * nc or d.shape[2] != 3 * w * nc or p.shape[:2] != d.shape[:2]:
                         raise ValueError('forward gave %s / %s, expected (b, frames, %d) / (b, frames, %d)'
-                                         % (tuple(p.shape), tuple(d.shape), nc, 3 * nc))
-                    self._prob = self._grown(self._prob, N * p.numel(), p.device)
+                                         % (tuple(p.shape), tuple(d.shape), w * nc, 3 * w * nc))
+                    if not multi:
+                        self._prob = self._grown(self._prob, N * p.numel(), p.device)
+                        prob_slab = self._prob[:N * p.numel()].view((N,) + tuple(p.shape))
                     self._xyz = self._grown(self._xyz, N * d.numel(), d.device)
-                    prob_slab = self._prob[:N * p.numel()].view((N,) + tuple(p.shape))
                     xyz_slab = self._xyz[:N * d.numel()].view((N,) + tuple(d.shape))
-                prob_slab[mi * nv + vi].copy_(p.detach())
+                if not multi:
+                    prob_slab[mi * nv + vi].copy_(p.detach())
                 xyz_slab[mi * nv + vi].copy_(d.detach())
+        if multi:
+            act, xyz = tta_merge_multi(xyz_slab, len(self.forwards), self.variant_ids, self.kind, nc, _ids_c=self._ids_c)
+            return act.to(p.dtype), xyz.to(d.dtype)
         prob, xyz = tta_merge(prob_slab, xyz_slab, len(self.forwards), self.variant_ids, self.kind, nc, _ids_c=self._ids_c)
         if self.output_format == 'accdoa':
             from .nn_ops import accdoa_sed
@@ -226,12 +326,15 @@ class TtaForward:
         return prob.to(p.dtype), xyz.to(d.dtype)
 
 
-def wrap_forward(forward, tta, n_classes: int = 12, output_format: str = 'reg_xyz'):
+def wrap_forward(forward, tta, n_classes: int = 12, output_format: str = 'reg_xyz', track_merge=None):
     """the ``tta=`` keyword of infer_pipelined / validate / fit: None -> forward; a TtaForward -> itself (it carries its own
-    forwards); an (audio_format, feature_type) pair -> TtaForward(forward, *pair) over all variants"""
+    forwards; with track_merge='align' it must have been built with it); an (audio_format, feature_type) pair ->
+    TtaForward(forward, *pair) over all variants"""
     if tta is None:
         return forward
     if isinstance(tta, TtaForward):
+        if track_merge == 'align' and tta.track_merge != 'align':
+            raise ValueError("track_merge='align' with a ready TtaForward that was built without it")
         return tta
     audio_format, feature_type = tta
-    return TtaForward(forward, audio_format, feature_type, n_classes=n_classes, output_format=output_format)
+    return TtaForward(forward, audio_format, feature_type, n_classes=n_classes, output_format=output_format, track_merge=track_merge)
