@@ -276,6 +276,11 @@ int salsa_nn_adpit_loss(const float *doa, const float *sed_gt, const float *doa_
  * NaN or outside [-1, 1]; -6 when the launch fails. */
 int salsa_nn_seld_decode_multi(const float *act, const float *xyz, int n_files, int n_in_frames, int n_frames, int n_real_classes,
                                float sed_threshold, double cos_unify, int16_t *rows, int *counts, void *hip_stream);
+/* salsa_nn_seld_decode_multi_thr: salsa_nn_seld_decode_multi with one threshold per REAL class, d_thresholds [n_real_classes] float32
+ * on the device (4-byte aligned, not NULL), applied to the class's three tracks; a NaN threshold makes its class inactive.  The same
+ * kernel code and checks; equal entries give salsa_nn_seld_decode_multi's rows and counts bit for bit. */
+int salsa_nn_seld_decode_multi_thr(const float *act, const float *xyz, int n_files, int n_in_frames, int n_frames, int n_real_classes,
+                                   const float *d_thresholds, double cos_unify, int16_t *rows, int *counts, void *hip_stream);
 
 /* Test-time chunk combination and DCASE row decoding in one launch (reference models/interfaces.py:97-139 combine_chunks, then
  * :232-256 of write_classwise_output_to_file; salsa_amd/csrc/seld_decode.hip): sed [n_files][n_chunks][chunk_len][nc] ACTIVITIES (not
@@ -295,6 +300,12 @@ int salsa_nn_seld_decode_multi(const float *act, const float *xyz, int n_files, 
 int salsa_nn_seld_decode(const float *sed, const float *xyz, int n_files, int n_chunks, int chunk_len, int chunk_hop, int n_frames,
                          int nc, float sed_threshold, int combine, int16_t *rows, int *counts, float *file_sed, float *file_xyz,
                          void *hip_stream);
+/* salsa_nn_seld_decode_thr: salsa_nn_seld_decode with one threshold per class, d_thresholds [nc] float32 on the device (4-byte
+ * aligned, not NULL): pair (frame, c) is active when its combined activity >= d_thresholds[c] in float32 (NaN on either side:
+ * inactive).  The same kernel code and checks; equal entries give salsa_nn_seld_decode's rows, counts and file outputs bit for bit. */
+int salsa_nn_seld_decode_thr(const float *sed, const float *xyz, int n_files, int n_chunks, int chunk_len, int chunk_hop, int n_frames,
+                             int nc, const float *d_thresholds, int combine, int16_t *rows, int *counts, float *file_sed,
+                             float *file_xyz, void *hip_stream);
 
 /* DCASE rows against ground-truth rows: the SELD 2021 counters of crnn/metrics.py::SeldMetrics.update (reference metrics/
  * SELD2021_evaluation_metrics.py:81-195) per (file, segment), on the device (salsa_amd/csrc/seld_score.hip; statements in
@@ -344,6 +355,36 @@ int salsa_nn_seld_score2022(const int16_t *pred_rows, const int *pred_counts, in
 /* salsa_nn_seld_score's distance statement alone: quads [n][4] int16 (azimuth1, elevation1, azimuth2, elevation2) -> out [n]
  * float64 degrees (tools/probe_score_distance.py measures its deviation from the host's, which sizes `margin`). */
 int salsa_nn_seld_distance(const int16_t *quads, int64_t n, double *out, void *hip_stream);
+
+/* The per-class SED threshold sweep (salsa_amd/csrc/seld_sweep.hip; statements in seld_sweep.h): the class-wise
+ * SELD 2022 counters of K candidate thresholds per class, straight from the combined file outputs, in one launch.  act / xyz are
+ * file-level float32 arrays on the device with n_in_frames >= n_frames frames per file, of which the first n_frames are decoded:
+ * multi 0 -- act [n_files][n_in_frames][nc] activities and xyz [..][3 nc] (what salsa_nn_seld_decode writes to file_sed / file_xyz, or
+ * a whole-clip forward); multi 1 -- act [..][3 C] track activities and xyz [..][9 C] (salsa_nn_chunk_merge_multi's or
+ * salsa_nn_tta_merge_multi's outputs, or a forward), unified with cos_unify as salsa_nn_seld_decode_multi does.  thresholds [K][n_classes]
+ * float32 on the device; gt_rows / gt_counts / gt_capacity as salsa_nn_seld_score2022 takes them.  record = file * n_seg + segment,
+ * n_seg = ceil(n_frames / label_rate).
+ *
+ * For record r, candidate k and class c, class_counters [records][K][n_classes][5] int32 (TP Nref DE_TP DE_FP DE_FN) and class_de
+ * [records][K][n_classes] float64 are the class-c entries of salsa_nn_seld_score2022's record for the rows salsa_nn_seld_decode_thr /
+ * salsa_nn_seld_decode_multi_thr give at thresholds[k]: the same integer angles, distances, pairing and slot averages, class_de added
+ * from 0.0 in the host's order.  status [records][K][n_classes] int32 is decided per (record, k, class), a class's counters depending
+ * on its own rows alone: 1 doubt (in a common frame of the class another pairing costs within `margin` of the best, or a slot average
+ * of the class lies within `margin` of doa_threshold), 2 refused (a reference cell of the class with more than 4 DOAs, or a gt count
+ * that is negative or above gt_capacity, in which case no row of the file is read); such entries carry zeros and the host scores
+ * them.  A cell is decoded and paired once per distinct predicted set (one for multi 0, at most seven for multi 1), never per
+ * candidate.  file_counters [n_files][K][n_classes][5] int64 and file_de [n_files][K][n_classes] float64 (both or neither NULL)
+ * receive each file's status-0 entries added up by a second kernel in segment order.  Every output element is written; no atomics:
+ * bit-reproducible, and a file's entries do not depend on its batch.
+ *
+ * Returns 0; -1, before any device call and with the reason in salsa_last_error, for a NULL required pointer, a misaligned pointer (8
+ * bytes for gt_rows and the 8-byte outputs, 4 otherwise), n_files outside 1 .. 65535, n_frames or n_in_frames outside 1 .. 32767,
+ * n_in_frames < n_frames, gt_capacity < 1, n_classes or label_rate outside 1 .. 32, K outside 1 .. 64, multi not 0 / 1, with multi 1 a
+ * cos_unify that is NaN or outside [-1, 1], a NaN doa_threshold, or a margin that is negative, NaN or infinite; -6 when a launch fails. */
+int salsa_nn_seld_sweep(const float *act, const float *xyz, int n_files, int n_in_frames, int n_frames, int n_classes, int multi,
+                        double cos_unify, const float *thresholds, int K, const int16_t *gt_rows, const int *gt_counts, int gt_capacity,
+                        int label_rate, double doa_threshold, double margin, int *class_counters, double *class_de, int *status,
+                        int64_t *file_counters, double *file_de, void *hip_stream);
 
 /* Test-time augmentation and model ensembling around the forward (salsa_amd/csrc/tta.hip, statements in tta.h).
  * kind: 1 foa (V = 16 variants, 7 channels), 2 mic (V = 8, 7 channels), 3 gcc (V = 4, 10 channels) -- SALSA_BANK_FOA / _MIC / _GCC.

@@ -56,6 +56,22 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _device_thresholds(sed_threshold, n_classes, device):
+    """None for a scalar sed_threshold (the scalar entry point takes it); for a sequence the (n_classes,) float32 tensor on `device`
+    that the _thr entry points read -- a wrong length raises ValueError here, before any device call.  A float32 tensor already on
+    `device` is taken as it is: a caller that decodes many sub-batches uploads the vector once."""
+    import torch
+    if torch.is_tensor(sed_threshold):                  # uploaded already (infer_pipelined and validate do it once for all sub-batches)
+        if sed_threshold.shape != (n_classes,) or sed_threshold.dtype != torch.float32 or sed_threshold.device != torch.device(device):
+            raise ValueError('sed_threshold: a %s %s tensor on %s for %d classes on %s'
+                             % (tuple(sed_threshold.shape), sed_threshold.dtype, sed_threshold.device, n_classes, device))
+        return sed_threshold.contiguous()
+    if np.ndim(sed_threshold) == 0:
+        return None
+    from .postprocess import class_thresholds
+    return torch.from_numpy(class_thresholds(sed_threshold, n_classes)).to(device)
+
+
 def decode_dcase_rows(sed, xyz, chunk_len: int, chunk_hop: int, n_frames: int = 600, sed_threshold: float = 0.3,
                       combine_method: str = 'mean', return_file_outputs: bool = False):
     """sed (n_files, n_chunks, chunk_len, nc) ACTIVITIES (Trainer.infer's first output, for reg_xyz and accdoa alike) and xyz
@@ -64,7 +80,8 @@ def decode_dcase_rows(sed, xyz, chunk_len: int, chunk_hop: int, n_frames: int = 
     elevation), of which the first counts[f] of file f are written (the rest is uninitialised memory), counts (n_files,) int32, and
     with return_file_outputs the combined float32 file_sed (n_files, n_frames, nc) and file_xyz (.., 3 nc) -- what the reference's
     write_output_prediction stores.  One launch on the current stream of the tensors' device, no synchronisation; there is no
-    host fallback: CPU tensors are refused (crnn/postprocess.py holds the host functions)."""
+    host fallback: CPU tensors are refused (crnn/postprocess.py holds the host functions).  sed_threshold: a scalar
+    (salsa_nn_seld_decode), or one value per class (salsa_nn_seld_decode_thr; postprocess.class_thresholds)."""
     import torch
     if combine_method not in COMBINE:
         raise ValueError('combine method {} is unknown'.format(combine_method))
@@ -81,14 +98,16 @@ def decode_dcase_rows(sed, xyz, chunk_len: int, chunk_hop: int, n_frames: int = 
         raise ValueError('decode_dcase_rows: no files')
     sed, xyz = sed.contiguous(), xyz.contiguous()
     dev = sed.device
+    thr = _device_thresholds(sed_threshold, nc, dev)
     rows = torch.empty((n_files, n_frames * nc, 4), dtype=torch.int16, device=dev)
     counts = torch.empty((n_files,), dtype=torch.int32, device=dev)
     fs = torch.empty((n_files, n_frames, nc), dtype=torch.float32, device=dev) if return_file_outputs else None
     fx = torch.empty((n_files, n_frames, 3 * nc), dtype=torch.float32, device=dev) if return_file_outputs else None
     with torch.cuda.device(dev):
-        rc = _lib.load().salsa_nn_seld_decode(_ptr(sed), _ptr(xyz), n_files, n_chunks, chunk_len, chunk_hop, n_frames, nc,
-                                              float(sed_threshold), COMBINE[combine_method], _ptr(rows), _ptr(counts), _ptr(fs),
-                                              _ptr(fx), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        export = _lib.load().salsa_nn_seld_decode if thr is None else _lib.load().salsa_nn_seld_decode_thr
+        rc = export(_ptr(sed), _ptr(xyz), n_files, n_chunks, chunk_len, chunk_hop, n_frames, nc,
+                    float(sed_threshold) if thr is None else _ptr(thr), COMBINE[combine_method], _ptr(rows), _ptr(counts), _ptr(fs),
+                    _ptr(fx), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if rc == _lib.E_INVAL:
         raise ValueError('salsa_nn_seld_decode refused %d chunks of %d frames at hop %d for %d frames x %d classes (expected %d chunks)'
                          % (n_chunks, chunk_len, chunk_hop, n_frames, nc, len(chunk_starts(n_frames, chunk_len, max(1, chunk_hop)))))
@@ -103,7 +122,8 @@ def decode_multi_rows(act, xyz, n_frames: int = 600, sed_threshold: float = 0.5,
     (n_files, 3 * n_frames * C, 4) int16 = (frame, real class, azimuth, elevation) with near-identical tracks of a class unified, of
     which the first counts[f] of file f are written, and counts (n_files,) int32 -- rows_to_list's and the scorers' input.  One
     salsa_nn_seld_decode_multi launch on the current stream, no synchronisation; CPU tensors are refused (the host function is
-    postprocess.multi_accdoa_rows, whose result this equals)."""
+    postprocess.multi_accdoa_rows, whose result this equals).  sed_threshold: a scalar, or one value per REAL class, applied to
+    its three tracks (salsa_nn_seld_decode_multi_thr)."""
     import torch
     from .postprocess import cos_unify_of
     cos_unify = cos_unify_of(unify_deg)
@@ -117,12 +137,13 @@ def decode_multi_rows(act, xyz, n_frames: int = 600, sed_threshold: float = 0.5,
         raise ValueError('decode_multi_rows: no files')
     act, xyz = act.contiguous(), xyz.contiguous()
     dev = act.device
+    thr = _device_thresholds(sed_threshold, n_classes, dev)
     rows = torch.empty((n_files, 3 * n_frames * n_classes, 4), dtype=torch.int16, device=dev)
     counts = torch.empty((n_files,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.load().salsa_nn_seld_decode_multi(_ptr(act), _ptr(xyz), n_files, n_in, n_frames, n_classes, float(sed_threshold),
-                                                    cos_unify, _ptr(rows), _ptr(counts),
-                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        export = _lib.load().salsa_nn_seld_decode_multi if thr is None else _lib.load().salsa_nn_seld_decode_multi_thr
+        rc = export(_ptr(act), _ptr(xyz), n_files, n_in, n_frames, n_classes, float(sed_threshold) if thr is None else _ptr(thr),
+                    cos_unify, _ptr(rows), _ptr(counts), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if rc == _lib.E_INVAL:
         raise ValueError('salsa_nn_seld_decode_multi refused %d files of %d frames (%d decoded) x %d classes' % (n_files, n_in, n_frames, n_classes))
     if rc:

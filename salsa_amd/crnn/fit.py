@@ -42,8 +42,38 @@ def _ckpt_files(d):
     return sorted(f for f in os.listdir(d) if f.startswith('epoch') and f.endswith('ckpt')) if os.path.isdir(d) else []
 
 
-def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, combine_method='mean', sed_threshold=0.3,
-             doa_threshold=20, eval_version='2021', sub_batch=8, return_rows=False, tta=None, unify_deg=15.0, track_merge=None):
+def _rescore_kept(sweep, scorer, sed_threshold, val_gt, gt_rows, gt_counts, n_label, rate, trainer, unify_deg, on_gpu, return_rows):
+    """the second half of validate(calibrate=): the combined file outputs the sweep kept, decoded at `sed_threshold` and scored into
+    `scorer`, sub-batch by sub-batch in item order -- no forward.  -> the rows per clip (on the GPU only when return_rows asks for
+    them: the scorer reads the rows on the device)"""
+    from .calibrate import host_rows
+    from .decode import _device_thresholds, decode_dcase_rows, decode_multi_rows, rows_to_list
+    from .score import score_dcase_rows
+    nc, fmt, rows, lo = trainer.n_classes, trainer.output_format, [], 0
+    thr = _device_thresholds(sed_threshold, nc, trainer.device) if on_gpu else None      # uploaded once for all sub-batches
+    for act, xyz in sweep.outputs:
+        hi = lo + len(act)
+        if on_gpu:
+            if fmt == 'multi_accdoa':
+                r, c = decode_multi_rows(act, xyz, n_frames=n_label, sed_threshold=thr, unify_deg=unify_deg, n_classes=nc)
+            else:
+                r, c = decode_dcase_rows(act, xyz, act.shape[1], act.shape[1], n_frames=n_label, sed_threshold=thr)
+            scorer.merge(score_dcase_rows(r, c, gt_rows[lo:hi], gt_counts[lo:hi], n_frames=n_label, label_rate=rate, n_classes=nc,
+                                          doa_threshold=scorer.doa_threshold, margin=scorer.margin, eval_version='2022',
+                                          average=scorer.average))
+            if return_rows:
+                rows += rows_to_list(r.cpu(), c.cpu(), eval_version='2020')
+        else:
+            for i in range(lo, hi):
+                rows.append(host_rows(act[i - lo], xyz[i - lo], sed_threshold, n_label, nc, fmt, unify_deg))
+                scorer.update(rows[-1], val_gt[i], max_frames=n_label, label_rate=rate)
+        lo = hi
+    return rows
+
+
+def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, combine_method='mean', sed_threshold=None,
+             doa_threshold=20, eval_version='2021', sub_batch=8, return_rows=False, tta=None, unify_deg=15.0, track_merge=None,
+             calibrate=None):
     """One validation pass (models/seld_models.py:96-108 + interfaces.py:163-180): every clip of ``val_bank`` through
     infer_pipelined(Trainer.infer) in test chunks, rows against ``val_gt`` (per clip a list of rows, metrics.load_dcase_csv).  On the
     GPU the rows are decoded and scored on the device (DeviceSeldScore / DeviceSeldScore2020 / DeviceSeldScore2022 by eval_version), on
@@ -52,6 +82,12 @@ def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, comb
     decoded with track unification (infer_pipelined's output_format / unify_deg): whole clips or non-overlapping chunks, no tta --
     unless track_merge='align' (DESIGN.md section 9u), under which overlapping chunks and tta=, alone or together, are merged after
     their tracks are aligned cell by cell.
+    sed_threshold: a scalar or one value per class; None: the trainer's calibrated ``sed_thresholds`` (set by fit(calibrate=) and by
+    resuming its checkpoints), or 0.3 when it has none.
+    calibrate = candidate thresholds, (K,) or (K, n_classes) (eval_version '2022' only): ONE forward pass with
+    infer_pipelined(sweep=), calibrate.ThresholdSweep.best() picks a threshold per class (a class without references keeps
+    sed_threshold), and the KEPT combined outputs are decoded and scored at the chosen vector -- no second forward.  The figures are
+    those of validate(sed_threshold=chosen); 'thresholds' holds the chosen (n_classes,) float32 vector and 'sweep' the accumulator.
     -> dict valER valF1 valLE valLR valSeld (+ the scorer under 'scorer', and 'rows' when asked)."""
     from .infer import infer_pipelined
     from .tta import wrap_forward
@@ -61,6 +97,11 @@ def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, comb
         raise ValueError('Unknown eval_version {}'.format(eval_version))
     device_cls, host_cls = {'2020': (DeviceSeldScore2020, SeldMetrics2020), '2021': (DeviceSeldScore, SeldMetrics),
                             '2022': (DeviceSeldScore2022, SeldMetrics2022)}[eval_version]
+    if calibrate is not None and eval_version != '2022':
+        raise ValueError("calibrate= tunes the class-wise metric: it needs eval_version='2022', not {!r}".format(eval_version))
+    if sed_threshold is None:
+        sed_threshold = getattr(trainer, 'sed_thresholds', None)
+        sed_threshold = 0.3 if sed_threshold is None else sed_threshold
     n = len(val_bank.clip_len)
     if n == 0 or len(val_gt) != n:
         raise ValueError('validation: ground truth of %d clips for a bank of %d' % (len(val_gt), n))
@@ -73,17 +114,27 @@ def validate(trainer, val_bank, val_gt, chunk_len=None, chunk_hop_len=None, comb
     kw = dict(sub_batch=sub_batch, sed_threshold=sed_threshold, n_label_frames=n_label, chunk_len=chunk_len, chunk_hop_len=chunk_hop_len,
               combine_method=combine_method, n_classes=nc, output_format=trainer.output_format, unify_deg=unify_deg,
               track_merge=track_merge, eval_version='2020')       # (the ROW shape only: (frame, class, azimuth, elevation), what SeldMetrics.update reads)
-    if on_gpu:
-        scorer = device_cls(nc, doa_threshold, rate)
-        gt_rows, gt_counts = gt_rows_to_device(val_gt, trainer.device)
+    scorer = device_cls(nc, doa_threshold, rate) if on_gpu else host_cls(nc, doa_threshold)
+    gt_rows, gt_counts = gt_rows_to_device(val_gt, trainer.device) if on_gpu else (None, None)
+    chosen = sweep = None
+    if calibrate is not None:
+        from .calibrate import ThresholdSweep
+        sweep = ThresholdSweep(calibrate, nc, doa_threshold, rate)
+        infer_pipelined(n, val_bank.clip_batch, forward, decode='device' if on_gpu else 'host',
+                        sweep=(gt_rows, gt_counts, sweep) if on_gpu else (val_gt, None, sweep), return_rows=False, **kw)   # (no rows yet: no threshold yet)
+        chosen = sweep.best(default=sed_threshold)[0]
+        rows = _rescore_kept(sweep, scorer, chosen, val_gt, gt_rows, gt_counts, n_label, rate, trainer, unify_deg, on_gpu, return_rows)
+        sweep.outputs = []                                                       # (the outputs have served: a clip's worth of floats each)
+    elif on_gpu:
         rows = infer_pipelined(n, val_bank.clip_batch, forward, decode='device', score=(gt_rows, gt_counts, scorer), **kw)
     else:
-        scorer = host_cls(nc, doa_threshold)
         rows = infer_pipelined(n, val_bank.clip_batch, forward, decode='host', **kw)
         for pred, gt in zip(rows, val_gt):
             scorer.update(pred, gt, max_frames=n_label, label_rate=rate)
     ER, F, LE, LR = (float(v) for v in scorer.scores())
     out = dict(valER=ER, valF1=F, valLE=LE, valLR=LR, valSeld=float(scorer.seld_error()), scorer=scorer)
+    if calibrate is not None:
+        out.update(thresholds=chosen, sweep=sweep)
     if return_rows:
         out['rows'] = rows
     return out
@@ -95,6 +146,7 @@ def _save(path, trainer, loader, epoch, global_step, history, best, val=None):
                 global_step=global_step, history=history, best=best, val=val, loader_seed=loader.seed,
                 output_format=trainer.output_format, n_classes=trainer.n_classes,
                 n_attn_layers=trainer.n_attn_layers, n_attn_heads=trainer.n_attn_heads, **trainer.conformer,
+                **({} if getattr(trainer, 'sed_thresholds', None) is None else {'sed_thresholds': np.asarray(trainer.sed_thresholds, np.float32)}),
                 rng_cpu=torch.get_rng_state(), rng_device=torch.cuda.get_rng_state(dev) if dev.type == 'cuda' else None)
     tmp = path + '.tmp'
     torch.save(ckpt, tmp)
@@ -127,13 +179,15 @@ def _load(path, trainer, loader):
     if ckpt['rng_device'] is not None and trainer.device.type == 'cuda':
         torch.cuda.set_rng_state(ckpt['rng_device'], trainer.device)
     trainer.step_idx = ckpt['global_step']
+    if ckpt.get('sed_thresholds') is not None:                                   # (a checkpoint of a run without calibrate= has no such key)
+        trainer.sed_thresholds = np.asarray(ckpt['sed_thresholds'], dtype=np.float32)
     return ckpt
 
 
 def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, max_epochs=50, epochs=None, milestones=MILESTONES,
         lrs=LRS, moms=MOMS, val_interval=1, train_fraction=1.0, audio_format='foa', feature_type='salsa', augment=True, seed=2021,
         mode='crossval', eval_version='2021', resume=False, chunk_len=None, chunk_hop_len=None, combine_method='mean',
-        sed_threshold=0.3, doa_threshold=20, val_sub_batch=8, loader=None, tta=None, unify_deg=15.0, track_merge=None):
+        sed_threshold=0.3, doa_threshold=20, val_sub_batch=8, loader=None, tta=None, unify_deg=15.0, track_merge=None, calibrate=None):
     """Train ``trainer`` for ``max_epochs`` epochs of ``bank`` (a finalized GpuFeatureBank).  The keywords are the YAML's keys
     (INTEGRATION.md has the table): batch_size = training.train_batch_size; milestones / lrs / moms = training.lr_scheduler.*;
     max_epochs, val_interval = training.*; train_fraction, n_classes (Trainer's) = data.*; eval_version ('2022': valSeld, and with it
@@ -144,6 +198,11 @@ def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, 
     validation pass (validate) and to nothing else: no checkpoint stores them.  The trainer's output_format, n_attn_layers, n_attn_heads and the five Conformer settings are stored in
     every checkpoint and checked on resume; a 'multi_accdoa' trainer takes a bank of trackwise labels (GpuFeatureBank(n_classes=3 C,
     label_format='trackwise')).
+    calibrate = candidate SED thresholds, (K,) or (K, n_classes), eval_version '2022' only (ValueError otherwise): every validation
+    pass calibrates one threshold per class (validate(calibrate=)); the chosen vector is stored in that epoch's history['val'] entry
+    ('thresholds', a list of floats), in ``trainer.sed_thresholds`` and, as 'sed_thresholds', in every checkpoint from then on; valSeld --
+    and with it the best checkpoint -- is the calibrated figure.  Resuming restores ``trainer.sed_thresholds``; a checkpoint without
+    the key resumes as before.  sed_threshold may itself be one value per class.
     -> the history: dict(steps=[epoch, step, lr, mom, loss, sed_loss, doa_loss per step], val=[dict per validated epoch],
     best=dict | None, epoch=epochs finished, global_step)."""
     from ..dataset import BankLoader
@@ -153,6 +212,8 @@ def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, 
         raise ValueError('val_bank and val_gt come together')
     if val_bank is not None and eval_version not in ('2020', '2021', '2022'):     # (what validate refuses, before an epoch is spent)
         raise ValueError('Unknown eval_version {}'.format(eval_version))
+    if calibrate is not None and eval_version != '2022':
+        raise ValueError("calibrate= tunes the class-wise metric: it needs eval_version='2022', not {!r}".format(eval_version))
     if val_bank is not None:
         from .tta import _check_track_merge
         _check_track_merge(track_merge, trainer.output_format)
@@ -188,8 +249,12 @@ def fit(trainer, bank, val_bank=None, val_gt=None, out_dir=None, batch_size=32, 
         val = None
         if val_bank is not None and (epoch + 1) % val_interval == 0:
             val = validate(trainer, val_bank, val_gt, chunk_len, chunk_hop_len, combine_method, sed_threshold, doa_threshold,
-                           eval_version, val_sub_batch, tta=tta, unify_deg=unify_deg, track_merge=track_merge)
+                           eval_version, val_sub_batch, tta=tta, unify_deg=unify_deg, track_merge=track_merge, calibrate=calibrate)
             val.pop('scorer')
+            if calibrate is not None:
+                val.pop('sweep')
+                trainer.sed_thresholds = val['thresholds']
+                val['thresholds'] = [float(t) for t in val['thresholds']]
             val['epoch'] = epoch
             history['val'].append(val)
         improved = val is not None and mode == 'crossval' and (history['best'] is None or val['valSeld'] < history['best']['valSeld'])

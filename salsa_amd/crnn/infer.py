@@ -48,7 +48,7 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
                     chunk_hop_len: Optional[int] = None, decode: str = 'host', combine_method: str = 'mean',
                     eval_version: str = '2021', n_classes: int = 12, chunk_batch: Optional[int] = None,
                     score: Optional[tuple] = None, tta=None, output_format: str = 'reg_xyz', unify_deg: float = 15.0,
-                    track_merge: Optional[str] = None) -> list:
+                    track_merge: Optional[str] = None, sweep: Optional[tuple] = None, return_rows: bool = True) -> list:
     """featurize(lo, hi) -> feature tensor [hi - lo, 7, T, F] of items lo..hi-1 on the model's device; forward(features) ->
     (event probabilities [b, n_label_frames, 12], xyz [b, n_label_frames, 36]).  Returns the DCASE rows of every item, in
     item order.  The device is never idle waiting for the host: up to `depth` sub-batches are in flight.
@@ -88,7 +88,22 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
     not, go through postprocess.combine_chunks_multi (host) or decode.chunk_merge_multi (device, one salsa_nn_chunk_merge_multi
     launch) and then the decoders above; both together compose (the wrapped forward merges per chunk batch, then the chunks are
     combined).  combine_method 'gmean' with overlapping chunks raises ValueError: a geometric mean of signed components is not
-    defined.  With chunk_hop_len == chunk_len, or one chunk, the rows are those of the reshape path."""
+    defined.  With chunk_hop_len == chunk_len, or one chunk, the rows are those of the reshape path.
+
+    sed_threshold: a scalar, or one value per class (REAL class for 'multi_accdoa'), for either decoder (postprocess.class_thresholds).
+
+    sweep = (gt_rows, gt_counts, accumulator), next to score= or without it: a per-class threshold sweep with a
+    calibrate.ThresholdSweep, whose candidates, classes, DOA threshold, label_rate and margin are used.  decode='device': the ground
+    truth on the model's device (score.gt_rows_to_device); each sub-batch's COMBINED file outputs -- behind the chunk combine, tta= and
+    track_merge='align' alike -- are swept by one salsa_nn_seld_sweep launch on the same stream (calibrate.sweep_outputs_async) and
+    merged into the accumulator when the sub-batch is finished.  decode='host': gt_rows is the per-item list of row lists (gt_counts is
+    not read) and calibrate.sweep_host runs on the combined host outputs.  Either way the combined outputs are kept, one (act, xyz)
+    pair per sub-batch, in accumulator.outputs (on the device for decode='device').  The rows returned are unchanged.
+
+    return_rows=False (a pass made for score= or sweep= alone): no rows are copied to the host or built there and the result is a list
+    of None; on the device the row decoding itself is skipped where nothing reads the rows (no score=; for the single-vector formats
+    the salsa_nn_seld_decode launch stays, it is the chunk combine that writes the file outputs).  A per-class sed_threshold is checked
+    here, before the first forward, and uploaded once for all sub-batches."""
     import torch
     assert depth >= 1 and sub_batch >= 1
     if output_format not in ('reg_xyz', 'accdoa', 'multi_accdoa'):
@@ -122,10 +137,20 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
         gt_rows, gt_counts, accumulator = score
         if gt_rows.shape[0] != n_items or gt_counts.shape[0] != n_items:
             raise ValueError('score=: ground truth of %d files for %d items' % (gt_rows.shape[0], n_items))
+    if sweep is not None:
+        sweep_gt, sweep_counts, sweeper = sweep
+        if len(sweep_gt) != n_items or (decode == 'device' and sweep_counts.shape[0] != n_items):
+            raise ValueError('sweep=: ground truth of %d files for %d items' % (len(sweep_gt), n_items))
+        if sweeper.n_classes != n_classes:
+            raise ValueError('sweep=: an accumulator of %d classes for n_classes = %d' % (sweeper.n_classes, n_classes))
+    from .postprocess import class_thresholds
+    class_thresholds(sed_threshold, n_classes)          # (a wrong length: ValueError before any forward or device call)
+    device_threshold = [sed_threshold]                  # a per-class vector is replaced by its device tensor at the first device decode
     if tta is not None:
         from .tta import wrap_forward
         forward = wrap_forward(forward, tta, n_classes, output_format, track_merge) if align else wrap_forward(forward, tta, n_classes)
     results = [None] * n_items
+    on_host = return_rows or (decode == 'host' and sweep is not None)     # is anything of a sub-batch read on the host?
     slots: Dict[int, dict] = {}
     pending = collections.deque()
 
@@ -135,16 +160,26 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
             s['event'].synchronize()                     # this sub-batch's outputs are on the host (nothing else is waited for)
         if s.get('score') is not None:
             accumulator.merge(s.pop('score').result())
-        if decode == 'device':
+        if s.get('sweep') is not None:
+            part = s.pop('sweep').result()
+            part.outputs = [s.pop('kept')]
+            sweeper.merge(part)
+        if not on_host:
+            pass                                         # (return_rows=False: nothing of the sub-batch was copied)
+        elif decode == 'device':
             from .decode import rows_to_list
             results[lo:hi] = rows_to_list(s['rows'][:hi - lo], s['counts'][:hi - lo], eval_version=eval_version, as_array=as_array)
         else:
             p, d = s['p'][:hi - lo].numpy(), s['d'][:hi - lo].numpy()
+            combined = []                                # the file-level outputs the rows are decoded from (sweep= reads them)
             for i in range(lo, hi):
                 if multi:                                # file-level outputs already (chunks were reshaped, not combined) ...
                     pi, di = p[i - lo], d[i - lo]
                     if pi.ndim == 3:                     # ... or, under track_merge='align', a file's chunks: combined here
                         pi, di = combine_chunks_multi(pi, di, lab_len, lab_hop, n_frames=n_label_frames, n_classes=n_classes)
+                    combined.append((pi[:n_label_frames], di[:n_label_frames]))
+                    if not return_rows:
+                        continue
                     results[i] = multi_accdoa_rows(pi, di, sed_threshold=sed_threshold, unify_deg=unify_deg,
                                                    n_classes=n_classes, max_nframes_per_file=n_label_frames, eval_version=eval_version,
                                                    as_array=as_array)
@@ -153,8 +188,16 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
                 pi, di = (p[i - lo], d[i - lo]) if chunk_len is not None else (p[i - lo][None], d[i - lo][None])
                 fp = combine_chunks(pi, lab_len, lab_hop, n_frames=n_label_frames, combine_method=combine_method)
                 fd = combine_chunks(di, lab_len, lab_hop, n_frames=n_label_frames, combine_method=combine_method)
-                results[i] = to_dcase_rows(fp, fd, sed_threshold=sed_threshold, n_classes=n_classes, max_nframes_per_file=n_label_frames,
-                                           eval_version=eval_version, as_array=as_array)
+                combined.append((fp, fd))
+                if return_rows:
+                    results[i] = to_dcase_rows(fp, fd, sed_threshold=sed_threshold, n_classes=n_classes, max_nframes_per_file=n_label_frames,
+                                               eval_version=eval_version, as_array=as_array)
+            if sweep is not None:
+                from .calibrate import sweep_host
+                kept = (np.stack([c[0] for c in combined]), np.stack([c[1] for c in combined]))
+                sweep_host(kept[0], kept[1], sweep_gt[lo:hi], None, n_frames=n_label_frames, output_format=output_format, unify_deg=unify_deg,
+                           accumulator=sweeper)
+                sweeper.outputs.append(kept)
         if stamps is not None:
             stamps.append((lo, hi, t_issue, time.perf_counter()))
 
@@ -186,20 +229,32 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
             if prob.dim() == 3 and (prob.shape[1] < n_label_frames or prob.shape[2] != 3 * n_classes or xyz.shape[2] != 9 * n_classes):
                 raise ValueError("output_format 'multi_accdoa': forward gave %s / %s, expected (b, >= %d, %d) / (.., %d)"
                                  % (tuple(prob.shape), tuple(xyz.shape), n_label_frames, 3 * n_classes, 9 * n_classes))
+        need_rows = return_rows or score is not None
+        if decode == 'device' and np.ndim(device_threshold[0]) > 0 and not torch.is_tensor(device_threshold[0]):
+            from .decode import _device_thresholds
+            device_threshold[0] = _device_thresholds(sed_threshold, n_classes, prob.device)
         if multi and decode == 'device':
             from .decode import decode_multi_rows
-            rows, counts = decode_multi_rows(prob, xyz, n_frames=n_label_frames, sed_threshold=sed_threshold, unify_deg=unify_deg,
-                                             n_classes=n_classes)
-            out = {'rows': rows, 'counts': counts}
+            out, file_outputs = {}, (prob, xyz)
+            if need_rows:
+                rows, counts = decode_multi_rows(prob, xyz, n_frames=n_label_frames, sed_threshold=device_threshold[0], unify_deg=unify_deg,
+                                                 n_classes=n_classes)
+                out = {'rows': rows, 'counts': counts}
         elif decode == 'device':
             from .decode import decode_dcase_rows
             if chunk_len is None:                        # whole clips: one chunk of the forward's length, trimmed to n_label_frames
                 lab_len = lab_hop = prob.shape[1]
-            rows, counts = decode_dcase_rows(prob, xyz, lab_len, lab_hop, n_frames=n_label_frames, sed_threshold=sed_threshold,
-                                             combine_method=combine_method)
+            if sweep is None:
+                rows, counts = decode_dcase_rows(prob, xyz, lab_len, lab_hop, n_frames=n_label_frames, sed_threshold=device_threshold[0],
+                                                 combine_method=combine_method)
+            else:                                        # the same launch also writes the combined file outputs the sweep reads
+                rows, counts, *file_outputs = decode_dcase_rows(prob, xyz, lab_len, lab_hop, n_frames=n_label_frames, sed_threshold=device_threshold[0],
+                                                                combine_method=combine_method, return_file_outputs=True)
             out = {'rows': rows, 'counts': counts}       # 8 bytes per possible row + one count per clip instead of the float outputs
         else:
             out = {'p': prob, 'd': xyz}
+        if not on_host:
+            out = {}                                     # nothing of this sub-batch is read on the host
         s = slots.get(k % depth)
         if s is None or any(s[n].shape[0] < hi - lo for n in out):
             s = slots[k % depth] = {n: torch.empty((hi - lo,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=on_gpu) for n, t in out.items()}
@@ -216,6 +271,13 @@ def infer_pipelined(n_items: int, featurize: Callable[[int, int], 'torch.Tensor'
                                                 label_rate=accumulator.label_rate, n_classes=accumulator.n_classes,
                                                 doa_threshold=accumulator.doa_threshold, margin=accumulator.margin,
                                                 eval_version=version, average=getattr(accumulator, 'average', 'macro'))
+        if sweep is not None and decode == 'device':
+            from .calibrate import sweep_outputs_async
+            s['kept'] = tuple(file_outputs)
+            s['sweep'] = sweep_outputs_async(s['kept'][0], s['kept'][1], sweep_gt[lo:hi], sweep_counts[lo:hi], sweeper.thresholds,
+                                             n_frames=n_label_frames, n_classes=n_classes, doa_threshold=sweeper.doa_threshold,
+                                             label_rate=sweeper.label_rate, margin=sweeper.margin, output_format=output_format,
+                                             unify_deg=unify_deg)
         pending.append((k, lo, hi, t_issue, lab_len, lab_hop))
         while len(pending) >= depth:                     # slot (k + 1) % depth is free again before sub-batch k + 1 is issued
             finish(*pending.popleft())
@@ -230,7 +292,7 @@ def infer_clips_sharded(names: Sequence[str], featurize: Callable[[List[str]], '
                         stamps: Optional[list] = None, chunk_len: Optional[int] = None, chunk_hop_len: Optional[int] = None,
                         decode: str = 'host', combine_method: str = 'mean', eval_version: str = '2021', n_classes: int = 12,
                         chunk_batch: Optional[int] = None, score: Optional[tuple] = None, tta=None, output_format: str = 'reg_xyz',
-                        unify_deg: float = 15.0, track_merge: Optional[str] = None) -> Dict[str, list]:
+                        unify_deg: float = 15.0, track_merge: Optional[str] = None, sweep: Optional[tuple] = None, return_rows: bool = True) -> Dict[str, list]:
     """names: all clip names (any order; sharded over the SORTED list).  featurize(list of names) -> feature tensor
     [b, 7, T, F] on the model's device (e.g. SalsaExtractor.extract of the clips' audio with the scaler attached, cropped
     to 8 * n_label_frames frames); forward(features) -> (event probabilities [b, n_label_frames, 12], xyz [b, .., 36]), e.g.
@@ -238,13 +300,15 @@ def infer_clips_sharded(names: Sequence[str], featurize: Callable[[List[str]], '
     chunk_len, chunk_hop_len, decode, combine_method, eval_version, n_classes, chunk_batch: infer_pipelined's test-chunk and
     device-decoding options, handed through.  score = (gt_rows, gt_counts, accumulator): infer_pipelined's, for THIS rank's shard
     (the ground truth of shard_list(sorted(names), rank, world), in that order); every rank's accumulator holds its shard's score,
-    to be combined with DeviceSeldScore.merge.  tta, output_format, unify_deg, track_merge: infer_pipelined's, handed through."""
+    to be combined with DeviceSeldScore.merge.  tta, output_format, unify_deg, track_merge: infer_pipelined's, handed through; so are
+    a per-class sed_threshold and sweep = (gt_rows, gt_counts, accumulator), the ground truth and the calibrate.ThresholdSweep of THIS
+    rank's shard (combined with ThresholdSweep.merge), and return_rows."""
     mine = shard_list(sorted(names), rank, world)
     rows = infer_pipelined(len(mine), lambda lo, hi: featurize(mine[lo:hi]), forward, sub_batch=sub_batch, depth=depth,
                            sed_threshold=sed_threshold, n_label_frames=n_label_frames, stamps=stamps, chunk_len=chunk_len,
                            chunk_hop_len=chunk_hop_len, decode=decode, combine_method=combine_method, eval_version=eval_version,
                            n_classes=n_classes, chunk_batch=chunk_batch, score=score, tta=tta, output_format=output_format,
-                           unify_deg=unify_deg, track_merge=track_merge)
+                           unify_deg=unify_deg, track_merge=track_merge, sweep=sweep, return_rows=return_rows)
     out = dict(zip(mine, rows))
     if gather and world > 1:
         import torch.distributed as dist

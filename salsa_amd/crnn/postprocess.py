@@ -41,14 +41,30 @@ def sed_from_accdoa(doa: np.ndarray, n_classes: int = 12) -> np.ndarray:
     return np.sqrt(x ** 2 + y ** 2 + z ** 2)
 
 
+def class_thresholds(sed_threshold, n_classes: int):
+    """sed_threshold as every decoder compares it, in float32: a scalar -> np.float32; a sequence of n_classes values (one per class;
+    for 'multi_accdoa' per REAL class, applied to its three tracks) -> a (n_classes,) float32 array.  A sequence of any other length
+    is a ValueError -- raised here, before any device call.  A NaN threshold makes its class inactive (no activity is >= NaN)."""
+    if np.ndim(sed_threshold) == 0:
+        return np.float32(sed_threshold)
+    thr = np.asarray(sed_threshold, dtype=np.float32)
+    if thr.shape != (n_classes,):
+        raise ValueError('sed_threshold: %s values for %d classes (a scalar, or one value per class)' % (thr.shape, n_classes))
+    return thr
+
+
 def to_dcase_rows(event_prob: np.ndarray, doa_xyz: np.ndarray, sed_threshold: float = 0.3, n_classes: int = 12,
                   max_nframes_per_file: int = 600, eval_version: str = '2021', as_array: bool = False):
     """event_prob (T, 12) sigmoid outputs, doa_xyz (T, 36) -> list of [frame, class, (0,) azimuth, elevation] rows, in the
     reference's order (frame ascending, class ascending within a frame: models/interfaces.py:232-258).  The reference walks the
     600 frames in a Python loop; here the active (frame, class) pairs come from one np.nonzero (row-major = the same order) and
     the angles are computed for those pairs only -- 1024 clips per inference step make the loop the bottleneck otherwise.
-    as_array: the rows as one (n, 5 | 4) int64 array instead of a list of lists (bulk inference keeps them that way)."""
-    active = event_prob >= sed_threshold
+    as_array: the rows as one (n, 5 | 4) int64 array instead of a list of lists (bulk inference keeps them that way).
+    sed_threshold: a scalar, or one value per class (class_thresholds: compared in float32, class c against its own value)."""
+    if np.ndim(sed_threshold) == 0:
+        active = event_prob >= sed_threshold
+    else:
+        active = event_prob[:, :n_classes] >= class_thresholds(sed_threshold, n_classes)
     assert active.shape[0] >= max_nframes_per_file, 'n_output_frames of sed < max_nframes_per_file'
     t, c = np.nonzero(active[:max_nframes_per_file, :n_classes])
     x, y, z = doa_xyz[t, c], doa_xyz[t, n_classes + c], doa_xyz[t, 2 * n_classes + c]
@@ -77,7 +93,7 @@ def multi_accdoa_cells(act: np.ndarray, xyz: np.ndarray, sed_threshold: float, c
     act, xyz = np.asarray(act, np.float32), np.asarray(xyz, np.float32)
     T = act.shape[0]
     assert act.shape == (T, 3 * C) and xyz.shape == (T, 9 * C), 'act (T, 3 C) / xyz (T, 9 C)'
-    a = (act.reshape(T, 3, C) >= np.float32(sed_threshold)).transpose(0, 2, 1)         # (T, C, track); NaN is inactive
+    a = (act.reshape(T, 3, C) >= class_thresholds(sed_threshold, C)).transpose(0, 2, 1)   # (T, C, track); NaN is inactive; a (C,) vector: per class
     v = xyz.reshape(T, 3, 3, C).transpose(0, 3, 2, 1)                                  # (T, C, track, axis)
     d = v.astype(np.float64)
 

@@ -70,6 +70,7 @@ class Trainer:
         self.amp_dtype = amp_dtype
         self.total_steps = total_steps
         self.step_idx = 0
+        self.sed_thresholds = None       # per-class SED thresholds calibrated on validation (fit(calibrate=), restored on resume); None: none yet
         self.n_classes = n_classes
         self.n_model_classes = 3 * n_classes if output_format == 'multi_accdoa' else n_classes    # pseudo-classes: track n, class c -> n C + c
         model = SeldCRNN(n_input_channels=n_input_channels, n_classes=self.n_model_classes, decoder_type=decoder_type, freq_pool=freq_pool,

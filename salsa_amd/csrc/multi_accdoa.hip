@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "../../include/salsa_nn.h"
 #include "multi_accdoa.h"
+#include "seld_rows.h" // DcaseRow
 
 namespace {
 
@@ -79,12 +80,14 @@ __global__ __launch_bounds__(64) void adpit_loss_finish_kernel(const double *__r
 
 constexpr int DECODE_THREADS = 256, DECODE_WAVES = DECODE_THREADS / 64;
 
-struct alignas(8) DcaseRow { int16_t frame, cls, azimuth, elevation; };
+using seld_rows::DcaseRow;
 
+// PER_CLASS: the threshold of a cell's three tracks is thresholds[class] (salsa_nn_seld_decode_multi_thr); otherwise the scalar
+template <bool PER_CLASS>
 __global__ __launch_bounds__(DECODE_THREADS) void seld_decode_multi_kernel(const float *__restrict__ act, const float *__restrict__ xyz,
                                                                            int n_in_frames, int n_frames, int C, float sed_threshold,
-                                                                           double cos_unify, DcaseRow *__restrict__ rows,
-                                                                           int *__restrict__ counts)
+                                                                           const float *__restrict__ thresholds, double cos_unify,
+                                                                           DcaseRow *__restrict__ rows, int *__restrict__ counts)
 {
     __shared__ int wave_count[DECODE_WAVES];
     const size_t file = blockIdx.x;
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(DECODE_THREADS) void seld_decode_multi_kernel(const
 #pragma unroll
                 for (int k = 0; k < 3; k++) v[n * 3 + k] = pv[(3 * k + n) * C];
             }
-            n_out = multi_accdoa::unify_cell(a, v, sed_threshold, cos_unify, out, nullptr);
+            n_out = multi_accdoa::unify_cell(a, v, PER_CLASS ? thresholds[cls] : sed_threshold, cos_unify, out, nullptr);
         }
         const unsigned long long bit0 = __ballot(n_out & 1), bit1 = __ballot(n_out & 2), lower = (1ull << lane) - 1ull;
         if (lane == 0) wave_count[wave] = __popcll(bit0) + 2 * __popcll(bit1);
@@ -135,6 +138,25 @@ __global__ __launch_bounds__(DECODE_THREADS) void seld_decode_multi_kernel(const
     if (tid == 0) counts[file] = base;
 }
 
+// both decode exports: the argument checks and the launch, with the scalar or the per-class thresholds [C] on the device
+int launch_decode_multi(const float *act, const float *xyz, int n_files, int n_in_frames, int n_frames, int n_real_classes,
+                        float sed_threshold, const float *d_thresholds, bool per_class, double cos_unify, int16_t *rows, int *counts,
+                        void *hip_stream)
+{
+    if (!act || !xyz || !rows || !counts || ((uintptr_t)rows & 7)) return -1;
+    if (per_class && (!d_thresholds || ((uintptr_t)d_thresholds & 3))) return -1;
+    if (n_files < 1 || n_frames < 1 || n_frames > 32767 || n_in_frames < n_frames || n_real_classes < 1 || n_real_classes > 32767) return -1;
+    if ((int64_t)n_in_frames * 9 * n_real_classes > INT32_MAX / 4) return -1;  // cell indices and 9 C columns stay in int
+    if (!(cos_unify >= -1.0 && cos_unify <= 1.0)) return -1;                   // (NaN fails both comparisons)
+    if (per_class)
+        hipLaunchKernelGGL(seld_decode_multi_kernel<true>, dim3((unsigned)n_files), dim3(DECODE_THREADS), 0, (hipStream_t)hip_stream, act, xyz,
+                           n_in_frames, n_frames, n_real_classes, 0.0f, d_thresholds, cos_unify, (DcaseRow *)rows, counts);
+    else
+        hipLaunchKernelGGL(seld_decode_multi_kernel<false>, dim3((unsigned)n_files), dim3(DECODE_THREADS), 0, (hipStream_t)hip_stream, act, xyz,
+                           n_in_frames, n_frames, n_real_classes, sed_threshold, (const float *)nullptr, cos_unify, (DcaseRow *)rows, counts);
+    return hipGetLastError() == hipSuccess ? 0 : -6;
+}
+
 } // namespace
 
 extern "C" int salsa_nn_adpit_loss(const float *doa, const float *sed_gt, const float *doa_gt, int64_t rows, int n_real_classes,
@@ -155,11 +177,14 @@ extern "C" int salsa_nn_seld_decode_multi(const float *act, const float *xyz, in
                                           int n_real_classes, float sed_threshold, double cos_unify, int16_t *rows, int *counts,
                                           void *hip_stream)
 {
-    if (!act || !xyz || !rows || !counts || ((uintptr_t)rows & 7)) return -1;
-    if (n_files < 1 || n_frames < 1 || n_frames > 32767 || n_in_frames < n_frames || n_real_classes < 1 || n_real_classes > 32767) return -1;
-    if ((int64_t)n_in_frames * 9 * n_real_classes > INT32_MAX / 4) return -1;  // cell indices and 9 C columns stay in int
-    if (!(cos_unify >= -1.0 && cos_unify <= 1.0)) return -1;                   // (NaN fails both comparisons)
-    hipLaunchKernelGGL(seld_decode_multi_kernel, dim3((unsigned)n_files), dim3(DECODE_THREADS), 0, (hipStream_t)hip_stream, act, xyz,
-                       n_in_frames, n_frames, n_real_classes, sed_threshold, cos_unify, (DcaseRow *)rows, counts);
-    return hipGetLastError() == hipSuccess ? 0 : -6;
+    return launch_decode_multi(act, xyz, n_files, n_in_frames, n_frames, n_real_classes, sed_threshold, nullptr, false, cos_unify, rows, counts,
+                               hip_stream);
+}
+
+extern "C" int salsa_nn_seld_decode_multi_thr(const float *act, const float *xyz, int n_files, int n_in_frames, int n_frames,
+                                              int n_real_classes, const float *d_thresholds, double cos_unify, int16_t *rows, int *counts,
+                                              void *hip_stream)
+{
+    return launch_decode_multi(act, xyz, n_files, n_in_frames, n_frames, n_real_classes, 0.0f, d_thresholds, true, cos_unify, rows, counts,
+                               hip_stream);
 }

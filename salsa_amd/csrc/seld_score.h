@@ -122,8 +122,10 @@ SCORE_HD unsigned pair_cell(const int32_t *g, int ng, const int32_t *p, int np, 
 // counts, matched / cell_doubt / cells[].cost what pair_cell left for the cells with both sides present, gfirst the arrival index
 // of a reference cell's first row.  SeldMetrics walks the reference frames in the order they first arrived and keeps the slots in
 // the order they were first matched; sums and averages follow that order so that they round as SeldMetrics' do.
-SCORE_HD void score_class(const Cell *cells, const uint8_t *gcnt, const uint8_t *pcnt, const uint8_t *matched, const uint8_t *cell_doubt,
-                          const int *gfirst, int label_rate, double threshold, double margin, ClassResult *out)
+// sel, when not NULL: frame f's pairing (cells, matched, cell_doubt) is entry sel[f], not f -- the threshold sweep (seld_sweep.h) keeps
+// one pairing per distinct predicted set of a cell and picks per candidate; the counts and gfirst stay per frame.
+SCORE_HD void score_class_sel(const Cell *cells, const uint8_t *gcnt, const uint8_t *pcnt, const uint8_t *matched, const uint8_t *cell_doubt,
+                              const int *gfirst, const uint8_t *sel, int label_rate, double threshold, double margin, ClassResult *out)
 {
 #if defined(__HIPCC__)
 #pragma clang fp contract(off)
@@ -153,11 +155,12 @@ SCORE_HD void score_class(const Cell *cells, const uint8_t *gcnt, const uint8_t 
             if (f < 0) break;
             prev = gfirst[f];
             if (!pcnt[f]) continue;
-            if (cell_doubt[f]) res.flags |= 1;
+            const int e = sel ? sel[f] : f;
+            if (cell_doubt[e]) res.flags |= 1;
             for (int r = 0; r < MAX_DOAS; r++) {
-                if (!(matched[f] >> r & 1)) continue;
+                if (!(matched[e] >> r & 1)) continue;
                 if (!n[r]) order[n_slots++] = r;
-                sum[r] += cells[f].cost[r];
+                sum[r] += cells[e].cost[r];
                 n[r]++;
             }
         }
@@ -199,6 +202,12 @@ SCORE_HD void score_class(const Cell *cells, const uint8_t *gcnt, const uint8_t 
         res.seg_fp += n_p;
     }
     *out = res;
+}
+
+SCORE_HD void score_class(const Cell *cells, const uint8_t *gcnt, const uint8_t *pcnt, const uint8_t *matched, const uint8_t *cell_doubt,
+                          const int *gfirst, int label_rate, double threshold, double margin, ClassResult *out)
+{
+    score_class_sel(cells, gcnt, pcnt, matched, cell_doubt, gfirst, nullptr, label_rate, threshold, margin, out);
 }
 
 // The record of one segment from its classes, in class order: total_DE is ONE running sum over every slot average, as SeldMetrics

@@ -3,7 +3,8 @@
 // SELD 2022 counters of SeldMetrics2022, per (file, segment), on the device.  The statements are seld_score.h's; this file bins the
 // rows, the same way for all three metrics.
 //
-// One workgroup of 256 threads (4 waves) per (file, segment).  Each side's rows are walked in tiles of 256 consecutive rows, one
+// One workgroup of 256 threads (4 waves) per (file, segment).  Each side's rows are binned by seld_rows.h's walk (shared with
+// seld_sweep.hip): in tiles of 256 consecutive rows, one
 // 8-byte load per row; the tile's rows of this segment are compacted in ARRIVAL order (one ballot per wave, the wave counts through
 // LDS, as seld_decode.hip does), and a compacted row's slot in its (class, frame) cell is the cell's count so far plus the number
 // of earlier rows of the tile in the same cell: the cells fill in arrival order with no atomics, so two runs are bit-identical.
@@ -17,73 +18,33 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/salsa_nn.h"
+#include "seld_rows.h"
 #include "seld_score.h"
 
 namespace {
 
 using namespace seld_score;
 
-constexpr int SCORE_THREADS = 256, SCORE_WAVES = SCORE_THREADS / 64;
+using seld_rows::DcaseRow;
 
-struct alignas(8) DcaseRow { int16_t frame, cls, azimuth, elevation; };
+constexpr int SCORE_THREADS = seld_rows::BIN_THREADS;
 
 struct ScoreLds {                                                             // 46 KB
     Cell cells[MAX_CELLS];
     int gfirst[MAX_CELLS];
     uint8_t gcnt[MAX_CELLS], pcnt[MAX_CELLS], matched[MAX_CELLS], cell_doubt[MAX_CELLS];
-    int list_cell[SCORE_THREADS];
-    int32_t list_doa[SCORE_THREADS];
-    int list_row[SCORE_THREADS];
-    int wave_count[SCORE_WAVES];
+    seld_rows::BinScratch bin;
     ClassResult res[MAX_CLASSES];
 };
 
-// the rows of one side of one file into the segment's cells, in arrival order (uniform trip counts: every thread reaches the barriers)
+// the rows of one side of one file into the segment's cells, in arrival order: seld_rows.h's rule (every thread calls it)
 template <bool IS_GT>
 __device__ void bin_rows(ScoreLds &s, const DcaseRow *__restrict__ rows, int count, int seg, int label_rate, int n_classes)
 {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    uint8_t *cnt = IS_GT ? s.gcnt : s.pcnt;
-    for (int tile = 0; tile < count; tile += SCORE_THREADS) {
-        const int i = tile + tid;
-        int cell = -1;
-        DcaseRow r = {0, 0, 0, 0};
-        if (i < count) {                                                       // count <= capacity: checked by the caller
-            r = rows[i];
-            cell = cell_of(r.frame, r.cls, seg, label_rate, n_classes);
-        }
-        const unsigned long long mask = __ballot(cell >= 0);
-        if (lane == 0) s.wave_count[wave] = __popcll(mask);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < SCORE_WAVES; w++) {
-            const int c = s.wave_count[w];
-            if (w < wave) before += c;
-            total += c;
-        }
-        if (cell >= 0) {
-            const int at = before + __popcll(mask & ((1ull << lane) - 1ull));  // < SCORE_THREADS: one entry per row of the tile at most
-            s.list_cell[at] = cell;
-            s.list_doa[at] = pack_doa(r.azimuth, r.elevation);
-            s.list_row[at] = i;
-        }
-        __syncthreads();
-        int my_cell = -1, slot = 0;
-        bool last = true;
-        if (tid < total) {
-            my_cell = s.list_cell[tid];
-            slot = cnt[my_cell];
-            for (int j = 0; j < tid; j++) slot += s.list_cell[j] == my_cell;
-            for (int j = tid + 1; j < total; j++) last = last && s.list_cell[j] != my_cell;
-        }
-        __syncthreads();                                                       // every count of before this tile has been read
-        if (my_cell >= 0) {
-            if (slot < MAX_DOAS) (IS_GT ? s.cells[my_cell].in.g : s.cells[my_cell].in.p)[slot] = s.list_doa[tid];
-            if (IS_GT && slot == 0) s.gfirst[my_cell] = s.list_row[tid];
-            if (last) cnt[my_cell] = (uint8_t)(slot + 1 < COUNT_SAT ? slot + 1 : COUNT_SAT);
-        }
-        __syncthreads();                                                       // the list and wave_count are rewritten by the next tile
-    }
+    seld_rows::bin_rows(s.bin, IS_GT ? s.gcnt : s.pcnt, rows, count, seg, label_rate, n_classes, [&s](int cell, int slot, int32_t doa, int row) {
+        if (slot < MAX_DOAS) (IS_GT ? s.cells[cell].in.g : s.cells[cell].in.p)[slot] = doa;
+        if (IS_GT && slot == 0) s.gfirst[cell] = row;
+    });
 }
 
 // the segment's rows into its cells, the cells paired and every class booked into s.res[0 .. n_classes - 1], valid after the closing
